@@ -5,7 +5,11 @@ config 2: iemocap-cogmen-6 shaped a+t+v features with d_a=100, d_t=768, d_v=512
 (D=1380), B=32 dialogues per GPU, T=110, 6 classes, synthetic data, feature
 block stored in bf16 (``--dtype f32`` runs the fp32 parity path instead).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+K steps are timed after W warm-up steps; the line's ms_per_step is their mean.  Inputs (synthetic batch, parameter
+initialisation, dropout streams) are seeded, so the same arguments give the same inputs on every run; --dump-outputs writes
+what the last timed step computed (see dump_outputs) for comparing two builds output for output.
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU,
 RCCL): dialogues are sharded data-parallel, per-GPU batch fixed (weak scaling),
@@ -286,6 +290,30 @@ def assert_no_skipped_steps(model, what):
         os._exit(4)
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write ``arrays`` (name -> float32 / float64 numpy array) as ``out_dir/<name>.npy``, ``limit`` bytes at most in all.
+    Arrays that fit their share of the limit are written whole; a larger one is written as a sample of its flattened entries
+    at sorted indices drawn from RandomState(seed), the same indices for every array of the same length, so that two runs of
+    one command -- or two builds of the project -- store the same entries.  Returns name -> (entries written, entries held)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written, left = {}, limit - 1024 * len(arrays)     # (room for the .npy headers)
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("dump_outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (a.size, arrays[name].size)
+        left -= a.nbytes
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -304,6 +332,10 @@ def main():
     ap.add_argument("--no_fp32_path", action="store_true",
                     help="COGMEN bf16: skip the second timed run of the same step in --dtype f32 (the 1e-4 parity path)")
     ap.add_argument("--kernel_reps", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32, 64 MB at most): "
+                         "stats = {loss, #correct, weight sum} the step returns, params = the parameters it updated, exp_avg / "
+                         "exp_avg_sq = the optimizer's moments (rank 0)")
     ap.add_argument("--clock_probe", action="store_true", help="diagnostic: append a clock-probe kernel to the step")
     ap.add_argument("--faithful_dead_encoder", action="store_true",
                     help="COGMEN: also run the reference's dead Transformer encoder every step (SURVEY.md 8a C2 (ii))")
@@ -316,6 +348,8 @@ def main():
                     help="launch the ranks, form the process group, count them with one all-reduce and print the line -- no GPU work "
                          "(the launcher's CPU test: --gpus 2 --backend gloo --dry_run)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---------------------------------------------------------------- N > 1 without a launcher: start the N ranks ourselves
     # (the reference gets its ranks from `accelerate launch`, lumo/trainer/trainer.py:62-64,377-384).  The parent never touches
@@ -481,6 +515,15 @@ def main():
         total_utt, rccl_ranks = float(n_utt), 1
     stats = trainer.model._last_ws["stats"].cpu().tolist()
     assert_no_skipped_steps(trainer.model, "timed region (%s, %s)" % (args.module, args.dtype))
+    if args.dump_outputs and rank == 0:
+        # before anything below runs more steps on the same model (dominant-kernel probe, multi-step graph)
+        flat = trainer.model.flat
+        dumped = dump_outputs(args.dump_outputs, {
+            "stats": trainer.model._last_ws["stats"][:3].cpu().numpy(), "params": flat.data.cpu().numpy(),
+            "exp_avg": flat.exp_avg.cpu().numpy(), "exp_avg_sq": flat.exp_avg_sq.cpu().numpy()})
+        print("bench.py: outputs of the last timed step -> %s: %s" % (args.dump_outputs, ", ".join(
+            "%s %d%s" % (k, w, "" if w == n else " (sample of %d)" % n) for k, (w, n) in sorted(dumped.items()))),
+            file=sys.stderr)
 
     # ---------------------------------------------------------------- roofline: dominant kernel (HIP events) + whole step
     roof = None

@@ -1,4 +1,6 @@
-import sys; sys.path.insert(0, "/root/repo")
+import os
+import sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from tests.util_cases import cogmen_case, run_cogmen_parity
 import tests.util_cases as U

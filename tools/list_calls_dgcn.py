@@ -1,5 +1,6 @@
+import os
 import sys
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, importlib
 from erc_amd import capi
 import bench
