@@ -189,6 +189,12 @@ _SIGS = {
     "erc_adam_step_p2p": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _i64, _vp, _vp, _vp]),
     "erc_gcnii_chain_set_spin_limit": (C.c_int, [_i]),
     "erc_dag_attn_sums": (C.c_int, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "erc_cim_meta": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "erc_gru_scan_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _f, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "erc_gru_scan_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _f, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "erc_cim_max_t": (C.c_int, []),
+    "erc_cim_attn_fwd": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp]),
+    "erc_cim_attn_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _f, _vp]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -1108,3 +1114,34 @@ def head_ce_stats_floats(n_rows):
 def head_ce(Z, ldz, F, Cn, n_rows, W, bias, labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats):
     _call("erc_head_ce", Z, ldz, F, Cn, n_rows, W, bias, labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz,
           stats)
+
+
+# --------------------------------------------------------------------------- CIM (csrc/gru.hip, csrc/cim_attn.hip)
+def cim_meta(lengths, B, T, n_cap, node_off, node_row):
+    _dev(lengths, node_off, node_row)
+    _call("erc_cim_meta", lengths, B, T, n_cap, node_off, node_row)
+
+
+def gru_scan_fwd(GX, W_hhT, b_hh, lengths, node_off, B, T, rows, Hout, Hdrop, drop_p, rng, rng_stream, gates, ghn, Hprev):
+    _dev(GX, W_hhT, b_hh, lengths, node_off, Hout, gates, ghn, Hprev)
+    _call("erc_gru_scan_fwd", GX, W_hhT, b_hh, lengths, node_off, B, T, rows, Hout, Hdrop, drop_p, rng, rng_stream, gates, ghn,
+          Hprev)
+
+
+def gru_scan_bwd(W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH):
+    _dev(W_hh, lengths, node_off, gates, ghn, Hprev, dH, dGX, dGH)
+    _call("erc_gru_scan_bwd", W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH)
+
+
+def cim_max_t():
+    return int(lib().erc_cim_max_t())
+
+
+def cim_attn_fwd(merged, node_off, B, T, Pbuf):
+    _dev(merged, node_off, Pbuf)
+    _call("erc_cim_attn_fwd", merged, node_off, B, T, Pbuf)
+
+
+def cim_attn_bwd(merged, dmerged, node_off, B, T, Pbuf, mask_scale):
+    _dev(merged, dmerged, node_off, Pbuf)
+    _call("erc_cim_attn_bwd", merged, dmerged, node_off, B, T, Pbuf, mask_scale)

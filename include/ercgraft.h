@@ -1019,6 +1019,43 @@ int erc_mm_regroup_bwd(const float* dFE, const float* FE, int M, int N, float ke
 int erc_axpy_mask(const float* x, const float* mask, int64_t n, float scale, int accumulate, float* y, void* stream);
 
 
+/* ------------------------------------------------------------------------
+ * CIM (track_mm/cim.py:64-173): bidirectional GRUs (hidden 200) over packed sequences and the six cross-modal
+ * attention ops, on compact rows (row(b,t) = node_off[b] + t, N = sum(lengths) valid positions).
+ *
+ * erc_cim_meta: node_off [B+1] (exclusive prefix sum of lengths, each clamped to T) and node_row [n_cap]
+ * (node -> row b*T+t of the padded [B,T,.] feature block): the compaction of pack_padded_sequence (cim.py:127-132).
+ */
+int erc_cim_meta(const int64_t* lengths, int B, int T, int n_cap, int32_t* node_off, int32_t* node_row, void* stream);
+/* GRU scans (replaces nn.GRU(d_m, 200, bidirectional=True) on packed sequences + pad_packed_sequence, cim.py:73-77,
+ * 136-146), all three modalities x both directions x all dialogues in one launch each.  Gate order r|z|n (torch).
+ *   GX [3][rows][1200]: hoisted x W_ih^T + b_ih per modality (a|v|t in the caller's order), direction d in columns
+ *      [600d, 600d+600)
+ *   forward W_hhT [6][200][600] = erc_transpose_batched(W_hh [6][600][200]); backward W_hh itself; index 2m + d
+ *   b_hh [6][600]; b_hn stays inside r * (W_hn h + b_hn)
+ *   Hout [3][rows][400]; Hdrop (optional) the same with inverted dropout(drop_p) (drop0, cim.py:148-150), mask keyed by
+ *      (rng_state, rng_stream + m, element)
+ *   saved: gates [3][rows][1200] (r|z|n post-activation), ghn [3][rows][400] (W_hn h + b_hn), Hprev [3][rows][400]
+ * Backward: dH = gradient wrt Hout (wrt Hdrop when drop_p > 0).  Writes dGX [3][rows][1200] (d pre-activations of the
+ * input side: dW_ih = dGX^T x, db_ih = colsum) and dGH [3][rows][1200] (the recurrent side, n block scaled by r:
+ * dW_hh[d] = dGH[:,600d:]^T Hprev[:,200d:], db_hh = colsum) -- GEMMs by the caller. */
+int erc_gru_scan_fwd(const float* GX, const float* W_hhT, const float* b_hh, const int64_t* lengths, const int32_t* node_off,
+                     int B, int T, int64_t rows, float* Hout, float* Hdrop, float drop_p, const uint64_t* rng_state,
+                     uint64_t rng_stream, float* gates, float* ghn, float* Hprev, void* stream);
+int erc_gru_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int B, int T, int64_t rows,
+                     const float* gates, const float* ghn, const float* Hprev, const float* dH, float drop_p,
+                     const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH, void* stream);
+/* Cross-modal attention (attention_op, cim.py:108-115, the six calls of :160-172).  merged [N, 900] (16-byte aligned):
+ * columns 600 + 100 m hold dense_m (m = a, v, t); the forward writes pair p of (av, va, ta, tv, at, vt) to columns
+ * [100p, 100p+100) and saves the softmax to Pbuf [6][B][T][T].  The backward reads dmerged[:, 0:600), ADDS the gradient
+ * wrt every dense_m to dmerged[:, 600:900) in a fixed order (no atomics), then multiplies that block by
+ * (dense > 0 ? mask_scale : 0): drop1 and ReLU's backward (cim.py:152-158).  T <= erc_cim_max_t(), else ERC_E_ARG. */
+int erc_cim_max_t(void);
+int erc_cim_attn_fwd(float* merged, const int32_t* node_off, int B, int T, float* Pbuf, void* stream);
+int erc_cim_attn_bwd(const float* merged, float* dmerged, const int32_t* node_off, int B, int T, const float* Pbuf,
+                     float mask_scale, void* stream);
+
+
 /* Test support (not part of the data path): fills the LDS of every CU with NaN bit patterns, so that a persistent
  * kernel that reads LDS it did not initialise fails its parity test deterministically.  sink: one int32, may be NULL. */
 int erc_test_poison_lds(int32_t* sink, void* stream);
