@@ -195,6 +195,12 @@ _SIGS = {
     "erc_cim_max_t": (C.c_int, []),
     "erc_cim_attn_fwd": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp]),
     "erc_cim_attn_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _f, _vp]),
+    "erc_dgcnv2_max_t": (C.c_int, []),
+    "erc_dgcnv2_meta": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "erc_dgcnv2_edge_att_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "erc_dgcnv2_edge_att_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
+    "erc_dgcnv2_nodal_fwd": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "erc_dgcnv2_nodal_bwd": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -1145,3 +1151,34 @@ def cim_attn_fwd(merged, node_off, B, T, Pbuf):
 def cim_attn_bwd(merged, dmerged, node_off, B, T, Pbuf, mask_scale):
     _dev(merged, dmerged, node_off, Pbuf)
     _call("erc_cim_attn_bwd", merged, dmerged, node_off, B, T, Pbuf, mask_scale)
+
+
+# --------------------------------------------------------------------------- conv-emotion DialogueGCN (csrc/dgcnv2_att.hip)
+def dgcnv2_max_t():
+    return int(lib().erc_dgcnv2_max_t())
+
+
+def dgcnv2_meta(onehot, S, lengths, B, T, n_cap, spk, node_row):
+    _dev(onehot, lengths, spk, node_row)
+    _call("erc_dgcnv2_meta", onehot, S, lengths, B, T, n_cap, spk, node_row)
+
+
+def dgcnv2_edge_att_fwd(S, ldS, g, B, T, wp, wf, norm):
+    _dev(S, norm)
+    _call("erc_dgcnv2_edge_att_fwd", S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], norm)
+
+
+def dgcnv2_edge_att_bwd(S, ldS, g, B, T, wp, wf, dnorm, dS, dn_parts=1, dn_stride=0):
+    _dev(S, dnorm, dS)
+    _call("erc_dgcnv2_edge_att_bwd", S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], dnorm,
+          dn_parts, dn_stride, dS)
+
+
+def dgcnv2_nodal_fwd(E, lde, Q, ldq, node_off, B, T, A, lda, P, TH):
+    _dev(E, Q, node_off, A, P, TH)
+    _call("erc_dgcnv2_nodal_fwd", E, lde, Q, ldq, node_off, B, T, A, lda, P, TH)
+
+
+def dgcnv2_nodal_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde):
+    _dev(E, Q, dA, node_off, P, TH, DZ, dQ, dE)
+    _call("erc_dgcnv2_nodal_bwd", E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde)

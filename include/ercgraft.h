@@ -1055,6 +1055,40 @@ int erc_cim_attn_fwd(float* merged, const int32_t* node_off, int B, int T, float
 int erc_cim_attn_bwd(const float* merged, float* dmerged, const int32_t* node_off, int B, int T, const float* Pbuf,
                      float mask_scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * conv-emotion DialogueGCN (track_mm/dgcnv2.py, track_mm/dgcnv2_models.py; csrc/dgcnv2_att.hip).  Batches are time-major
+ * (batch_first=False): padded row t*B + b.  Dialogues of up to erc_dgcnv2_max_t() = 110 utterances (the rows of
+ * MaskedEdgeAttention.scalar, dgcnv2_models.py:529), longer batches give ERC_E_ARG.
+ *
+ * erc_dgcnv2_meta: spk [T*B] int64 = the first index k with onehot[t, b, k] == 1 (0 if none), the speaker lookup of
+ * batch_graphify (dgcnv2_models.py:671-672); node_row [n_cap] = t*B + b of node node_off[b] + t (node_off is the window
+ * graph's).  onehot [T, B, S] fp32. */
+int erc_dgcnv2_max_t(void);
+int erc_dgcnv2_meta(const float* onehot, int S, const int64_t* lengths, int B, int T, int n_cap, int64_t* spk,
+                    int32_t* node_row, void* stream);
+/* Positional edge attention, attn1 of MaskedEdgeAttention.forward (dgcnv2_models.py:533-566).  S [B*T, ldS >= 110] =
+ * M Wscalar^T over every padded row (a GEMM by the caller).  norm[e] of edge j -> i (in-CSR order through out_eid):
+ * exp(S[i, j]) / (sum_{t in win(j)} exp(S[t, j]) + 1e-10 sum_{t < T outside win(j)} exp(S[t, j])), padded positions in
+ * the second sum.  wp / wf: the window (-1 = unbounded).  The backward reads dnorm as dn_parts partial vectors dn_stride
+ * floats apart and writes all of dS [B*T, 110] (columns of absent sources are zero): dWscalar = dS^T M and
+ * dM += dS Wscalar are GEMMs by the caller. */
+int erc_dgcnv2_edge_att_fwd(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                            const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* norm, void* stream);
+int erc_dgcnv2_edge_att_bwd(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                            const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* dnorm,
+                            int dn_parts, int64_t dn_stride, float* dS, void* stream);
+/* Nodal attention, MatchingAttention 'general2' (dgcnv2_models.py:109-148) as attentive_node_features applies it
+ * (:693-720), on compact rows (node_off[b] + t) of E [N, 300] = [features | conv2 output] and Q = E W^T + b (a GEMM by
+ * the caller): A_t = sum_j p_tj E_j, p_tj = softmax_j(tanh(Q_t . E_j)) over the dialogue's valid rows.  P and TH
+ * [B, T, T] save p and tanh for the backward.  The backward writes dQ [N, 300] and dE [N, 300] = P^T dA + dZ^T Q
+ * (the caller adds dQ W), and DZ [B, T, T] (the gradient wrt the pre-tanh scores).  Row pitches >= 300, multiples of 4,
+ * 16-byte aligned.  Every element is summed by one thread in a fixed order. */
+int erc_dgcnv2_nodal_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T, float* A,
+                         int lda, float* P, float* TH, void* stream);
+int erc_dgcnv2_nodal_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
+                         int B, int T, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE, int ldde,
+                         void* stream);
+
 
 /* Test support (not part of the data path): fills the LDS of every CU with NaN bit patterns, so that a persistent
  * kernel that reads LDS it did not initialise fails its parity test deterministically.  sink: one int32, may be NULL. */
