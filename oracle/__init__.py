@@ -25,9 +25,13 @@ Pinning status (see DESIGN.md "Oracle"):
     ``tests/test_oracle_*.py`` / ``test_host_layout.py`` hold the oracle to
     them).
   * torch_geometric ``RGCNConv`` (mean), ``TransformerConv`` (heads=1) and
-    ``GraphConv`` are third-party, unpinned (``requirements.txt:12``) and not
-    installed: restated here from their published formulae ->
-    "parity unpinned" for those three operators.
+    ``GraphConv`` are third-party, unversioned (``requirements.txt:12``) and not
+    installed: restated in ``pyg.py`` from their published formulae.
+    ``RGCNConv`` (mean) and ``GraphConv`` (add) are PINNED by fixtures of the
+    vendored PyG 1.4.2 ``RGCNConv`` set up as each operator
+    (``tests/golden/make_golden_pyg_pin.py``; the per-relation mean itself is
+    PyG's documented definition, encoded in the fixtures' edge_norm).
+    ``TransformerConv`` has no counterpart in the reference: "parity unpinned".
   * COGMEN's bf16 compute mode is checked against the SAME restatement with the
     operands of the products that mode runs on bf16 matrix cores rounded to
     bf16 (``pyg.RoundedLinear`` / ``pyg.RGCNMeanRounded``; their hand-written

@@ -6,8 +6,22 @@ installed here.  These are restated from the published operator definitions
 (PyG 2.x docs) and structurally cross-checked against the vendored 1.4.2
 ``MessagePassing.propagate`` in models/rgcn.py:188-221 (gather
 x[edge_index[0]] -> message -> scatter at edge_index[1] -> update).
-PARITY UNPINNED for these three operators: the reference holds no test or
-golden vector at this boundary.
+Pinning:
+  * ``RGCNConvMean`` (C5) and ``GraphConvAdd`` (D5) are PINNED to an operator
+    the reference ships: the vendored PyG 1.4.2 ``RGCNConv``
+    (models/rgcn.py:264-355, ``sum_e edge_norm_e x_src(e) W_type(e) + x root +
+    bias``) set up as each of them -- num_bases = R, att = I and edge_norm =
+    1 / per-relation in-degree for RGCNConv-mean; R = 1, att = [[1]], no
+    edge_norm for GraphConv-add.  Fixtures ``tests/golden/rgcn_mean_s{2,3}`` /
+    ``graphconv_add*`` (written by tests/golden/make_golden_pyg_pin.py), held
+    by tests/test_oracle_pyg_pin.py here and by tests/test_gpu_ops.py on the
+    kernels.  They pin message direction, relation indexing, the ignored
+    relation ids >= num_relations and the normalisation as edge_norm states it.
+    What they cannot pin: that PyG 2's ``RGCNConv(aggr='mean')`` averages PER
+    RELATION (not over all in-edges) is PyG's documented definition; the
+    fixtures encode it in how edge_norm is built.
+  * ``TransformerConv1`` (C6): PARITY UNPINNED -- the reference has no
+    counterpart of it and holds no test or golden vector at this boundary.
 
 Call sites: track_mm/cogmen.py:65-66,71-72 (RGCNConv, TransformerConv);
 track_mm/dgcn_models.py:42,46 (GraphConv).

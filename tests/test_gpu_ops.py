@@ -670,3 +670,130 @@ def test_gemm_x3_grouped_equals_the_exact_fp32_grouped_product(capi):
             e3 = float((blk[:, :L, :L].sum(0).double() - want).abs().max())
             e32 = float((ref[b * Mo + m, :L, :L].double() - want).abs().max())
             assert e3 <= max(4 * e32, 1e-4), (b, m, e3, e32)
+
+
+# ------------------------------------------------- RGCNConv-mean / GraphConv-add against the vendored PyG RGCNConv (fixtures)
+def _fixture_graph(fx):
+    """the device window graph of the fixture's dialogues; its edge list must be the reference's"""
+    from erc_amd.cogmen import build_graph_tensors
+    gr, ei, et = build_graph_tensors(torch.from_numpy(fx["lengths"]).to(DEV), torch.from_numpy(fx["speakers"]).to(DEV),
+                                     int(fx["wp"]), int(fx["wf"]), int(fx["n_speakers"]))
+    N, E = gr["counts"].cpu().tolist()
+    assert N == fx["x"].shape[0] and E == fx["edge_index"].shape[1]
+    assert torch.equal(ei[:, :E].cpu(), torch.from_numpy(fx["edge_index"]))
+    if "edge_type" in fx.files:
+        assert torch.equal(et[:E].cpu(), torch.from_numpy(fx["edge_type"]))
+    return gr, N
+
+
+@pytest.mark.parametrize("name", ["rgcn_mean_s2", "rgcn_mean_s3"])
+def test_rgcn_mean_kernels_vs_vendored_rgcn(capi, golden, name):
+    """relation-mean aggregation + GEMMs (the recipe of test_rgcn_mean_fwd_bwd) against the vendored PyG RGCNConv set up as
+    RGCNConv-mean (tests/golden/make_golden_pyg_pin.py): output and every gradient.  S = 3: relation ids >= 8 are ignored."""
+    from oracle.pyg import RGCNConvMean
+    from tests.util_cases import fill_params
+    fx = golden(name)
+    T = lambda k: torch.from_numpy(fx[k])
+    gr, N = _fixture_graph(fx)
+    F, R = 100, int(fx["num_relations"])
+    conv = RGCNConvMean(F, F, R)            # parameter holder: the fixture carries the filler's seed
+    fill_params(conv, int(fx["param_seed"]))
+    x, gout = T("x").to(DEV), T("gout").to(DEV)
+    M = torch.zeros(N, (R + 1) * F, device=DEV)
+    inv = torch.zeros(N, R, device=DEV)
+    capi.rgcn_mean_fwd(x, F, F, R, N, gr, M, (R + 1) * F, inv)
+    Wcat = torch.cat([conv.weight.detach().reshape(R * F, F), conv.root.detach()], 0).to(DEV)
+    out = torch.zeros(N, F, device=DEV)
+    capi.gemm_f32(M, (R + 1) * F, 0, None, Wcat, F, 1, None, out, F, N, F, (R + 1) * F, bias=conv.bias.detach().to(DEV))
+    _close(out, T("out"), 1e-4)
+    dM = torch.zeros(N, (R + 1) * F, device=DEV)
+    capi.gemm_f32(gout, F, 0, None, Wcat, F, 0, None, dM, (R + 1) * F, N, (R + 1) * F, F)
+    dx = torch.zeros(N, F, device=DEV)
+    capi.rgcn_mean_bwd(dM, (R + 1) * F, F, R, N, gr, inv, dx, F)
+    _close(dx, T("dx"), 1e-4)
+    dW = torch.zeros((R + 1) * F, F, device=DEV)
+    db = torch.zeros(F, device=DEV)
+    capi.gemm_f32(M, (R + 1) * F, 1, None, gout, F, 1, None, dW, F, (R + 1) * F, F, N, ones_col=2, bias_out=db)
+    _close(dW[:R * F].reshape(R, F, F), T("dweight"), 1e-4)
+    _close(dW[R * F:], T("droot"), 1e-4)
+    _close(db, T("dbias"), 1e-4)
+
+
+def test_split_fused_tile_vs_vendored_rgcn(capi, golden):
+    """The split-mode forward tile kernel (erc_cogmen_fwd_tile_x, three terms: f32x3 / f32x32) on the rgcn_mean_s2 graph: its
+    relation means M against the fixture's edge_norm-weighted sums, its H1 against the vendored RGCNConv's output."""
+    from erc_amd.cogmen import COGMENModule, WP, WF
+    fx = golden("rgcn_mean_s2")
+    T = lambda k: torch.from_numpy(fx[k])
+    F, R = 100, 8
+    assert int(fx["wp"]) == WP and int(fx["wf"]) == WF and int(fx["n_speakers"]) == 2
+    _fixture_graph(fx)
+    m = COGMENModule(48, 100, 17, 2, 6, compute="f32x3").finalize(DEV)
+    assert m.fused_graph
+    from oracle.pyg import RGCNConvMean
+    from tests.util_cases import fill_params
+    conv = RGCNConvMean(F, F, R)
+    fill_params(conv, int(fx["param_seed"]))
+    fp = m.flat
+    fp.w("gcn.conv1.weight").copy_(conv.weight.detach().to(DEV))
+    fp.w("gcn.conv1.root").copy_(conv.root.detach().to(DEV))
+    fp.w("gcn.conv1.bias").copy_(conv.bias.detach().to(DEV))
+    m.refresh_shadows()
+    lengths, spk = T("lengths").to(DEV), T("speakers").to(DEV)
+    B, Tm = spk.shape
+    N = fx["x"].shape[0]
+    ws = m._workspace(B, Tm, N, DEV)
+    g = ws["g"]
+    capi.window_graph_build(lengths, spk, spk.stride(0), spk.stride(1), B, Tm, WP, WF, 2, N, ws["E"], g)
+    x = T("x").to(DEV)
+    bn = m.gcn.bn
+    capi.cogmen_fwd_tile(x, F, N, WP, WF, g, m._sh["catT"], fp.w("gcn.conv1.bias"), m._sh["q"], fp.w("gcn.conv2.lin_query.bias"),
+                         0.1, ws["M"], 9 * F, ws["inv_cnt"], ws["H1"], F, ws["QKVS"], ws["H2"], F, ws["alpha"], bn_fused=0,
+                         running_mean=bn.running_mean, running_var=bn.running_var, momentum=bn.momentum, eps=bn.eps,
+                         saved=ws["bn_saved"], bn_ws=ws["bn_tile_ws"], n_speakers=2, terms=3, catT_plane=m._sh_plane["catT"],
+                         q_plane=m._sh_plane["q"])
+    torch.cuda.synchronize()
+    ei, et, en, xs = T("edge_index"), T("edge_type"), T("edge_norm").double(), T("x").double()
+    M_ref = torch.zeros(N, 9 * F, dtype=torch.float64)
+    for r in range(R):
+        sel = et == r
+        M_ref[:, r * F:(r + 1) * F].index_add_(0, ei[1, sel], xs[ei[0, sel]] * en[sel, None])
+    M_ref[:, R * F:] = xs
+    _close(ws["M"][:, :9 * F], M_ref, 1e-4)
+    _close(ws["H1"], T("out"), 1e-4)
+
+
+@pytest.mark.parametrize("name", ["graphconv_add", "graphconv_add_w2_4"])
+def test_graph_conv_add_kernels_vs_vendored_rgcn(capi, golden, name):
+    """DialogueGCN's unfused GraphConv stage (dgcn.py: erc_csr_sum over in-edges + lin_rel GEMM with bias + lin_root GEMM
+    accumulated; backward: dAGG = dY W_rel summed over out-edges) against the vendored PyG RGCNConv set up as GraphConv-add."""
+    from oracle.pyg import GraphConvAdd
+    from tests.util_cases import fill_params
+    fx = golden(name)
+    T = lambda k: torch.from_numpy(fx[k])
+    gr, N = _fixture_graph(fx)
+    F = 100
+    conv = GraphConvAdd(F, F)
+    fill_params(conv, int(fx["param_seed"]))
+    Wrel, brel = conv.lin_rel.weight.detach().to(DEV), conv.lin_rel.bias.detach().to(DEV)
+    Wroot = conv.lin_root.weight.detach().to(DEV)
+    x, gout = T("x").to(DEV), T("gout").to(DEV)
+    agg = torch.full((N, F), float("nan"), device=DEV)
+    capi.csr_sum(x, F, F, N, gr["in_ptr"], gr["in_src"], agg, F)
+    out = torch.zeros(N, F, device=DEV)
+    capi.gemm_f32(agg, F, 0, None, Wrel, F, 0, None, out, F, N, F, F, bias=brel)
+    capi.gemm_f32(x, F, 0, None, Wroot, F, 0, None, out, F, N, F, F, accumulate=1)
+    _close(out, T("out"), 1e-4)
+    dagg = torch.zeros(N, F, device=DEV)
+    capi.gemm_f32(gout, F, 0, None, Wrel, F, 1, None, dagg, F, N, F, F)
+    dx = torch.zeros(N, F, device=DEV)
+    capi.gemm_f32(gout, F, 0, None, Wroot, F, 1, None, dx, F, N, F, F)
+    capi.csr_sum(dagg, F, F, N, gr["out_ptr"], gr["out_dst"], dx, F, accumulate=1)
+    _close(dx, T("dx"), 1e-4)
+    dWrelT, db = torch.zeros(F, F, device=DEV), torch.zeros(F, device=DEV)
+    capi.gemm_f32(agg, F, 1, None, gout, F, 1, None, dWrelT, F, F, F, N, ones_col=2, bias_out=db)
+    _close(dWrelT.t(), T("dlin_rel_weight"), 1e-4)
+    _close(db, T("dlin_rel_bias"), 1e-4)
+    dWrootT = torch.zeros(F, F, device=DEV)
+    capi.gemm_f32(x, F, 1, None, gout, F, 1, None, dWrootT, F, F, F, N)
+    _close(dWrootT.t(), T("dlin_root_weight"), 1e-4)

@@ -13,6 +13,17 @@ def make_batch(B, dims, n_speakers=2, n_classes=6, min_len=3, max_len=14, seed=1
                batch_first=True, speaker_onehot=False, force_max=False):
     dialogs = make_dialogues(B, dims, n_speakers=n_speakers, n_classes=n_classes, min_len=min_len,
                              max_len=max_len, seed=seed, force_max=force_max)
+    return _collate(dialogs, n_speakers, n_classes, modality, batch_first, speaker_onehot)
+
+
+def make_batch_lengths(lengths, dims, n_speakers=2, n_classes=6, seed=1, modality="atv", batch_first=True, speaker_onehot=False):
+    """A batch of dialogues with exactly the given lengths (node count N = sum(lengths)); dialogue i is drawn with its own seed."""
+    dialogs = [make_dialogues(1, dims, n_speakers=n_speakers, n_classes=n_classes, min_len=int(L), max_len=int(L),
+                              seed=seed * 7919 + i)[0] for i, L in enumerate(lengths)]
+    return _collate(dialogs, n_speakers, n_classes, modality, batch_first, speaker_onehot)
+
+
+def _collate(dialogs, n_speakers, n_classes, modality, batch_first, speaker_onehot):
     p = types.SimpleNamespace(batch_first=batch_first, speaker_onehot=speaker_onehot, n_classes=n_classes,
                               n_speakers=n_speakers, modality=modality)
     batch = ERCCollate(p)([[d] for d in dialogs])
@@ -23,6 +34,13 @@ def make_batch(B, dims, n_speakers=2, n_classes=6, min_len=3, max_len=14, seed=1
 def cogmen_case(B=4, min_len=3, max_len=14, dims=None, seed=3, n_classes=6, n_speakers=2):
     dims = dims or dict(a=12, t=20, v=16)
     return dict(batch=make_batch(B, dims, n_speakers, n_classes, min_len, max_len, seed), D=sum(dims.values()),
+                n_classes=n_classes, n_speakers=n_speakers, seed=seed)
+
+
+def cogmen_case_lengths(lengths, dims=None, seed=3, n_classes=6, n_speakers=2):
+    """cogmen_case with explicit dialogue lengths"""
+    dims = dims or dict(a=12, t=20, v=16)
+    return dict(batch=make_batch_lengths(lengths, dims, n_speakers, n_classes, seed), D=sum(dims.values()),
                 n_classes=n_classes, n_speakers=n_speakers, seed=seed)
 
 
@@ -41,11 +59,14 @@ def rel_err(a, b, floor=1e-5):
 
 
 def run_cogmen_parity(case, device="cuda:0", compute="f32", zero_grad=(), zero_tol=1e-5, ref_rounding=True, kink_aware=False,
-                      kink_tol=2e-5):
+                      kink_tol=2e-5, w1_shadow=False):
     """eval-mode logits and train-mode (dropout p=0) loss/gradients: HIP path vs oracle.
     ``ref_rounding=False`` with compute="bf16": the oracle stays the UNROUNDED fp32 restatement of the reference (fp32
     features, fp32 weights, fp32 products) -- what is measured is the bf16 compute mode's deviation from the reference,
-    quantisation included."""
+    quantisation included.
+    ``w1_shadow=True`` with compute="bf16": the module reads rnn.1.weight through its bf16 shadow, as under a trainer (the
+    shadow is rebuilt from the weights at every forward), so that the projection + graph-build launch can run.
+    Besides the errors, the result records the branch the training step took (``bn_in_tile``, ``fused_graph``)."""
     from oracle.cogmen import COGMENOracle
     from erc_amd.cogmen import COGMENModule
     torch.manual_seed(case["seed"])
@@ -61,6 +82,9 @@ def run_cogmen_parity(case, device="cuda:0", compute="f32", zero_grad=(), zero_t
     mine = COGMENModule(D, 100, 17, S, C, compute=compute)
     mine.load_state_dict(ref.state_dict())
     mine.finalize(device)
+    if w1_shadow:
+        assert compute == "bf16" and mine._shadow_auto
+        mine.w1_shadow = mine._sh["w1"]
     batch = case["batch"]
     dbatch = to_device(batch, device)
     if compute == "bf16":
@@ -91,24 +115,9 @@ def run_cogmen_parity(case, device="cuda:0", compute="f32", zero_grad=(), zero_t
     mine.drop_p = 0.0
     stats = mine.loss_and_grads(dbatch).cpu()
     if kink_aware:
-        # ReLU / LeakyReLU have a derivative JUMP at 0: a unit whose pre-activation lies within the compared path's own
-        # forward deviation of 0 may sit on the other side there, and that one unit's whole gradient contribution appears or
-        # vanishes (measured at config 2: 3e-3 of cls.0.weight's scale per unit, whatever the size of the deviation).  The
-        # oracle's backward is therefore evaluated with the activation PATTERN of the compared path; every unit whose pattern
-        # differs must have an oracle pre-activation below ``kink_tol``.
-        ws = mine._last_ws
-        pat = {"cls": ws["Z"].cpu() > 0, "gcn": ws["H3"].cpu() > 0}
-        flips = []
-
-        def masked(slope, key):
-            def fwd(x):
-                m = pat[key]
-                diff = m != (x > 0)
-                flips.append((key, int(diff.sum()), float(x.detach()[diff].abs().max()) if bool(diff.any()) else 0.0))
-                return torch.where(m, x, x * slope)
-            return fwd
-        ref.cls[1].forward = masked(0.0, "cls")
-        ref.gcn.relu.forward = masked(0.01, "gcn")
+        flips = use_activation_pattern(ref, mine._last_ws)
+    out["bn_in_tile"] = mine._last_ws.get("bn_in_tile")
+    out["fused_graph"] = bool(mine._last_ws.get("fused"))
     logits, _ = ref(**batch)
     loss = F.cross_entropy(logits, batch["label"])
     ref.zero_grad()
@@ -136,6 +145,29 @@ def run_cogmen_parity(case, device="cuda:0", compute="f32", zero_grad=(), zero_t
     dead = [n for n, p in ref.named_parameters() if p.grad is None]
     out["dead_ok"] = all(n.startswith("rnn.0.") for n in dead) and len(dead) > 0
     return out
+
+
+def use_activation_pattern(ref, ws):
+    """Make the COGMEN oracle's next forward take its ReLU / LeakyReLU pattern from the compared path's workspace ``ws`` (fp32 Z / H3).
+
+    ReLU / LeakyReLU have a derivative JUMP at 0: a unit whose pre-activation lies within the compared path's own forward
+    deviation of 0 may sit on the other side there, and that one unit's whole gradient contribution appears or vanishes
+    (measured at config 2: 3e-3 of cls.0.weight's scale per unit, whatever the size of the deviation).  The oracle's backward
+    is therefore evaluated with the activation PATTERN of the compared path.  Returns the list the forward fills with
+    (layer, units whose side differs, largest |oracle pre-activation| among them): the caller bounds the last."""
+    pat = {"cls": ws["Z"].cpu() > 0, "gcn": ws["H3"].cpu() > 0}
+    flips = []
+
+    def masked(slope, key):
+        def fwd(x):
+            m = pat[key]
+            diff = m != (x > 0)
+            flips.append((key, int(diff.sum()), float(x.detach()[diff].abs().max()) if bool(diff.any()) else 0.0))
+            return torch.where(m, x, x * slope)
+        return fwd
+    ref.cls[1].forward = masked(0.0, "cls")
+    ref.gcn.relu.forward = masked(0.01, "gcn")
+    return flips
 
 
 # ----------------------------------------------------------------------------- golden helpers
