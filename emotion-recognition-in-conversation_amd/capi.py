@@ -195,6 +195,7 @@ _SIGS = {
     "erc_cim_max_t": (C.c_int, []),
     "erc_cim_attn_fwd": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp]),
     "erc_cim_attn_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _f, _vp]),
+    "erc_ce_bce_multitask": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _vp, _i, _vp, _vp]),
     "erc_dgcnv2_max_t": (C.c_int, []),
     "erc_dgcnv2_meta": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "erc_dgcnv2_edge_att_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -1151,6 +1152,19 @@ def cim_attn_fwd(merged, node_off, B, T, Pbuf):
 def cim_attn_bwd(merged, dmerged, node_off, B, T, Pbuf, mask_scale):
     _dev(merged, dmerged, node_off, Pbuf)
     _call("erc_cim_attn_bwd", merged, dmerged, node_off, B, T, Pbuf, mask_scale)
+
+
+def ce_bce_multitask(logits, ld, Cn, n_rows, labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats):
+    """cross entropy on logits[:, :Cn] + 7-way BCE on logits[:, Cn:Cn+7] (ercgraft.h erc_ce_bce_multitask)"""
+    _dev(logits, labels, emo_label, dlogits, stats)
+    if labels.dtype != torch.int64 or emo_label.dtype != torch.int64:
+        raise ErcGraftError("ce_bce_multitask: label and emo_label must be int64")
+    if labels.numel() < n_rows or emo_label.dim() != 2 or emo_label.shape[0] < n_rows or emo_label.shape[1] < 7 \
+            or emo_label.stride(1) != 1 or logits.numel() < (n_rows - 1) * ld + Cn + 7:
+        raise ErcGraftError("ce_bce_multitask: operands smaller than %d rows (label %s, emo_label %s)"
+                            % (n_rows, tuple(labels.shape), tuple(emo_label.shape)))
+    _call("erc_ce_bce_multitask", logits, ld, Cn, n_rows, labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl,
+          stats)
 
 
 # --------------------------------------------------------------------------- conv-emotion DialogueGCN (csrc/dgcnv2_att.hip)

@@ -1,7 +1,9 @@
-"""CIM on the MI355X hot path (drop-in for track_mm/cim.py:64-227, non-MOSEI datasets).
+"""CIM on the MI355X hot path (drop-in for track_mm/cim.py:64-227).
 
-``CIMModule`` keeps the reference's constructor, ``state_dict`` keys and shapes (``rnn_adapter.*`` and ``cls7.*`` included,
-which are constructed but never receive a gradient) and ``forward(**batch) -> (logits2 [N, C], logits7 [N, 7])``.
+``CIMModule`` keeps the reference's constructor, ``state_dict`` keys and shapes (``rnn_adapter.*`` included, which is
+constructed but never receives a gradient) and ``forward(**batch) -> (logits2 [N, C], logits7 [N, 7])``.  ``cls7.*``
+trains only with ``multitask=True`` (apply_multi on CMU-MOSEI, cim.py:206-213); otherwise it stays dead as in the
+reference.
 
 Chain, on compact rows (the N = sum(lengths) valid positions, row = node_off[b] + t; csrc/cim_attn.hip erc_cim_meta):
 input projections of the three GRUs (one GEMM per modality, both directions: 1200 columns) -> one GRU scan launch for
@@ -9,6 +11,10 @@ input projections of the three GRUs (one GEMM per modality, both directions: 120
 drop1 in the GEMM epilogue, written straight into the dense block (columns 600..900) of the [N, 900] merged buffer -> the
 six cross-modal attention ops in one launch into columns 0..600 (csrc/cim_attn.hip) -> cls2 -> cross entropy.  The
 backward mirrors it; every weight gradient joins the step's one batched weight-gradient launch (erc_wgrad_table).
+
+Multi-task (``multitask=True``): cls2 and cls7 lie back to back in the flat buffer, one [C + 7, 900] head.  One GEMM
+writes both logit blocks, erc_ce_bce_multitask computes cross entropy + 7-way BCE and their gradient in one launch, one
+GEMM gives dmerged and one deferred weight-gradient record covers both heads: the same launch count as the single task.
 """
 import torch
 from torch import nn
@@ -24,7 +30,8 @@ MERGED = 900
 
 
 class CIMModule(nn.Module):
-    def __init__(self, text_dim, audio_dim, visual_dim, hidden_size, n_classes, drop0=0.3, drop1=0.3, compute="f32", seed=1):
+    def __init__(self, text_dim, audio_dim, visual_dim, hidden_size, n_classes, drop0=0.3, drop1=0.3, compute="f32", seed=1,
+                 multitask=False):
         super().__init__()
         if hidden_size != H:
             raise capi.ErcGraftError("CIM: the GRU scan kernels are built for hidden_size 200 (cim.py:183-184), got %d"
@@ -32,7 +39,7 @@ class CIMModule(nn.Module):
         if compute != "f32":
             raise capi.ErcGraftError("CIM runs in fp32 only (the reference is fp32); --compute=%s is not supported" % compute)
         self.dims = {"t": text_dim, "a": audio_dim, "v": visual_dim}
-        self.n_classes, self.compute = n_classes, compute
+        self.n_classes, self.compute, self.multitask = n_classes, compute, bool(multitask)
         self.p0, self.p1 = float(drop0), float(drop1)
         self.rnn = nn.ModuleDict({m: nn.GRU(self.dims[m], hidden_size=H, bidirectional=True, batch_first=True) for m in "tav"})
         self.rnn_adapter = nn.ModuleDict({m: nn.Linear(self.dims[m], 2 * H) for m in "tav"})
@@ -57,7 +64,11 @@ class CIMModule(nn.Module):
         for m in MODS:
             g.append([("adapter.%s.0.weight" % m, self.adapter[m][0].weight)])
             g.append([("adapter.%s.0.bias" % m, self.adapter[m][0].bias)])
-        g += [[("cls2.weight", self.cls2.weight)], [("cls2.bias", self.cls2.bias)]]
+        if self.multitask:      # one [C + 7, 900] head: cls2 rows, then cls7 rows
+            g += [[("cls2.weight", self.cls2.weight), ("cls7.weight", self.cls7.weight)],
+                  [("cls2.bias", self.cls2.bias), ("cls7.bias", self.cls7.bias)]]
+        else:
+            g += [[("cls2.weight", self.cls2.weight)], [("cls2.bias", self.cls2.bias)]]
         return g
 
     def finalize(self, device):
@@ -92,6 +103,11 @@ class CIMModule(nn.Module):
     def _b_hh6(self):
         return self._span("rnn.a.bias_hh_l0", 1, 6 * 3 * H).view(-1)
 
+    def _head(self):
+        """(weight [C + 7, 900], bias [C + 7]) of cls2 | cls7 (multitask layout)"""
+        C7 = self.n_classes + 7
+        return self._span("cls2.weight", C7, MERGED), self._span("cls2.bias", 1, C7).view(-1)
+
     # ------------------------------------------------------------------ workspace
     def _workspace(self, B, T, N, device):
         return self._ws.get((B, T, N), lambda: self._make_workspace(B, T, N, device))
@@ -101,7 +117,7 @@ class CIMModule(nn.Module):
         # weight-gradient GEMM through a row the step did not touch
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        C = self.n_classes
+        C = self.n_classes + (7 if self.multitask else 0)     # multitask: logits / dlogits hold cls2 | cls7
         ws = dict(node_off=i32(B + 1), node_row=i32(max(N, 1)), GX=f32(3, N, 6 * H), gates=f32(3, N, 6 * H), ghn=f32(3, N, 2 * H),
                   Hprev=f32(3, N, 2 * H), Hout=f32(3, N, 2 * H), Hdrop=f32(3, N, 2 * H), merged=f32(N, MERGED),
                   P=f32(6 * B * T * T), logits=f32(N, C), logits7=f32(N, 7), dlogits=f32(N, C), dmerged=f32(N, MERGED),
@@ -156,9 +172,14 @@ class CIMModule(nn.Module):
                        merged[:, 600 + 100 * i:], MERGED, N, 100, 2 * H, act=3 if p1 > 0 else 1, drop_p=p1,
                        rng=self.rng3[i] if p1 > 0 else None)
         capi.cim_attn_fwd(merged, ws["node_off"], B, T, ws["P"])
-        linear_fwd(pl, merged, MERGED, None, fp.w("cls2.weight"), fp.w("cls2.bias"), ws["logits"], self.n_classes, N,
-                   self.n_classes, MERGED)
-        if logits7:
+        if self.multitask:
+            C7 = self.n_classes + 7
+            w, b = self._head()
+            linear_fwd(pl, merged, MERGED, None, w, b, ws["logits"], C7, N, C7, MERGED)
+        else:
+            linear_fwd(pl, merged, MERGED, None, fp.w("cls2.weight"), fp.w("cls2.bias"), ws["logits"], self.n_classes, N,
+                       self.n_classes, MERGED)
+        if logits7 and not self.multitask:
             linear_fwd(pl, merged, MERGED, None, self.cls7.weight, self.cls7.bias, ws["logits7"], 7, N, 7, MERGED)
         ws["hsrc"], ws["p"] = hsrc, (p0, p1)
         return ws
@@ -173,20 +194,36 @@ class CIMModule(nn.Module):
             raise capi.ErcGraftError("CIM needs all three modalities (--modality=atv): text_feature is missing")
         B, T, N = self._shape(batch, kwargs.get("label"))
         ws = self._forward_impl(batch, B, T, N, self.training, logits7=True)
+        if self.multitask:
+            C = self.n_classes
+            return ws["logits"][:, :C], ws["logits"][:, C:]
         return ws["logits"], ws["logits7"]
 
     # ------------------------------------------------------------------ training step
     def loss_and_grads(self, batch):
-        """F.cross_entropy(logits2, label) (unweighted mean, cim.py:204) and every live gradient into flat.grad."""
+        """F.cross_entropy(logits2, label) (unweighted mean, cim.py:204) -- plus, multitask,
+        F.binary_cross_entropy_with_logits(logits7, emo_label.float()) (cim.py:206-213) -- and every live gradient into
+        flat.grad.  Returns the stats buffer: [0] Lall, [1] #correct, multitask also [2] Lce, [3] Lmulti."""
         ys = batch["label"]
         B, T, N = self._shape(batch, ys)
+        if self.multitask and batch.get("emo_label") is None:
+            raise capi.ErcGraftError("CIM multitask (apply_multi) needs emo_label in the batch (a CMU-MOSEI dataset)")
         ws = self._forward_impl(batch, B, T, N, self.training)
         fp, pl, off = self.flat, ws["planner"], self.flat.offsets
         C, (p0, p1) = self.n_classes, ws["p"]
         merged, dmerged = ws["merged"], ws["dmerged"]
-        capi.cross_entropy(ws["logits"], C, C, N, None, ys, None, 1.0, ws["dlogits"], C, ws["stats"])
-        capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("cls2.weight"), MERGED, 1, None, dmerged, MERGED, N, MERGED, C)
-        linear_wgrad(pl, ws["dlogits"], C, merged, MERGED, None, C, MERGED, N, off["cls2.weight"], off["cls2.bias"], defer=True)
+        if self.multitask:
+            emo = batch["emo_label"]
+            C7 = C + 7
+            capi.ce_bce_multitask(ws["logits"], C7, C, N, ys, emo, emo.stride(0), 1.0, 1.0, 1.0, ws["dlogits"], C7, ws["stats"])
+            capi.gemm_f32(ws["dlogits"], C7, 0, None, self._head()[0], MERGED, 1, None, dmerged, MERGED, N, MERGED, C7)
+            linear_wgrad(pl, ws["dlogits"], C7, merged, MERGED, None, C7, MERGED, N, off["cls2.weight"], off["cls2.bias"],
+                         defer=True)
+        else:
+            capi.cross_entropy(ws["logits"], C, C, N, None, ys, None, 1.0, ws["dlogits"], C, ws["stats"])
+            capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("cls2.weight"), MERGED, 1, None, dmerged, MERGED, N, MERGED, C)
+            linear_wgrad(pl, ws["dlogits"], C, merged, MERGED, None, C, MERGED, N, off["cls2.weight"], off["cls2.bias"],
+                         defer=True)
         # attention backward: + d dense_m into columns 600..900, then through drop1 / ReLU
         capi.cim_attn_bwd(merged, dmerged, ws["node_off"], B, T, ws["P"], 1.0 / (1.0 - p1))
         hsrc = ws["hsrc"]
@@ -209,11 +246,16 @@ class CIMModule(nn.Module):
 
 
 class CIMTrainer:
-    """train_step / to_logits of track_mm/cim.py:180-227 with apply_multi off (every non-MOSEI dataset, cim.py:52-55):
-    unweighted cross entropy on logits2, torch.optim.Adam(lr) without clipping or weight decay."""
+    """train_step / to_logits / to_mosei_multitask_logits of track_mm/cim.py:180-227: unweighted cross entropy on logits2
+    (apply_bin), plus the 7-way BCE on logits7 when apply_multi (CMU-MOSEI only, cim.py:52-53); torch.optim.Adam(lr)
+    without clipping or weight decay.  apply_bin=False is refused: the reference's cls2 would then get neither a gradient
+    nor Adam state, a layout this port does not build."""
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
+        if not params.get("apply_bin", True):
+            raise capi.ErcGraftError("--module=cim: --apply_bin=False is not supported (the cross-entropy term on cls2 is "
+                                     "always trained here)")
         if params.modality != "atv":
             raise ValueError("--module=cim needs all three modalities: the GRUs of cim.py:136-146 run on text, audio and visual "
                              "features (--modality=atv), got --modality=%s" % params.modality)
@@ -221,8 +263,10 @@ class CIMTrainer:
         if compute != "f32":
             raise ValueError("--module=cim runs in fp32 (the reference is fp32); --compute=%s is not supported" % compute)
         torch.manual_seed(params.seed)
+        self.multitask = bool(params.get("apply_multi", False))
         self.model = CIMModule(text_dim=params.hidden_text, audio_dim=params.hidden_audio, visual_dim=params.hidden_visual,
-                               hidden_size=H, n_classes=params.n_classes, seed=params.seed).finalize(self.device)
+                               hidden_size=H, n_classes=params.n_classes, seed=params.seed,
+                               multitask=self.multitask).finalize(self.device)
         o = params.optim
         self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
                                decoupled=(o.name == "AdamW"), seed=params.seed)
@@ -230,6 +274,10 @@ class CIMTrainer:
 
     def to_logits(self, batch):
         return self.model(**batch)[0]
+
+    def to_mosei_multitask_logits(self, batch):
+        """(logits2 [N, C], logits7 [N, 7]) (mmbase.py:144, cim.py:190-191)"""
+        return self.model(**batch)
 
     def prepare_batch(self, batch):
         out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}

@@ -14,6 +14,8 @@ against the reference batch dict runs unchanged:
                                           (:369,418) or float32 one-hot
                                           [B,T,S] when speaker_onehot (:432-433)
   label           int64   [N]            dialogue-major valid utterances (:435)
+  emo_label       int64   [N, 7]         CMU-MOSEI samples only: multi-hot emotions (:422-423,450-451)
+  senti2_label    int64   [N]            CMU-MOSEI samples only: binary sentiment (:424-425,452-453)
   sequence tensors are [T,B,...] when batch_first=False (:427-430,439-442).
 
 Unlike the reference (per-utterance torch.from_numpy + stack), rows are
@@ -78,6 +80,10 @@ class ERCCollate:
         sent = [d["sentence"] for d in dialogs if d.get("sentence") is not None]
         if sent:
             data["utterance_texts"] = sent
+        for key in ("emo_label", "senti2_label"):       # keys of the samples that carry them (no new keys otherwise)
+            parts = [np.asarray(d[key], dtype=np.int64) for d in dialogs if d.get(key) is not None]
+            if parts:
+                data[key] = torch.from_numpy(np.concatenate(parts, 0))
         return data
 
 

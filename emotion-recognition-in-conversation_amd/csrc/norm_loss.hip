@@ -367,6 +367,110 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------ CIM multi-task loss (cross entropy + 7-way BCE)
+// F.cross_entropy(logits[:, :C], label) + F.binary_cross_entropy_with_logits(logits[:, C:C+7], emo_label.float())
+// (track_mm/cim.py:204-216) and their gradient in one launch.  One thread per row; per-thread sums in fp64, a fixed
+// tree per workgroup, and the LAST workgroup to finish combines the per-workgroup partials in workgroup order, as
+// cross_entropy_kernel does: the result does not depend on scheduling.  stats[] layout: [0] Lall = w_ce Lce +
+// w_bce Lmulti, [1] #correct, [2] Lce, [3] Lmulti, [4] (as int) arrival counter (zero between calls),
+// [8 + 3w .. 10 + 3w] partials of workgroup w.
+constexpr int MT_MAXWG = 64;
+constexpr int MT_EMO = 7;
+
+__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(256) void ce_bce_multitask_kernel(const float* __restrict__ logits, int ld, int C,
+                                                               int n_rows, const int64_t* __restrict__ labels,
+                                                               const int64_t* __restrict__ emo, int lde, float w_ce,
+                                                               float w_bce, float grad_scale,
+                                                               float* __restrict__ dlogits, int lddl,
+                                                               float* __restrict__ stats) {
+    __shared__ double red[256];
+    __shared__ int s_last;
+    const int tid = threadIdx.x;
+    const float coef_ce = (float)((double)w_ce / (double)n_rows) * grad_scale;
+    const float coef_bce = (float)((double)w_bce / (7.0 * (double)n_rows)) * grad_scale;
+    double ce_acc = 0.0, bce_acc = 0.0;
+    int hit = 0;
+    for (int i = blockIdx.x * 256 + tid; i < n_rows; i += gridDim.x * 256) {
+        const float* z = logits + (int64_t)i * ld;
+        const int y = (int)labels[i];
+        float mx = z[0], zy = z[0];
+        int am = 0;
+        for (int c = 1; c < C; ++c) {
+            const float v = z[c];
+            if (v > mx) mx = v, am = c;
+            if (c == y) zy = v;   // no logits read through an out-of-range label
+        }
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += expf(z[c] - mx);
+        const float lse = mx + logf(se);
+        ce_acc += (double)(lse - zy);
+        hit += (am == y) ? 1 : 0;
+        const int64_t* e = emo + (int64_t)i * lde;
+        float* d = dlogits ? dlogits + (int64_t)i * lddl : nullptr;
+        if (d) {  // exp(z - max) / sum, not exp(z - lse): lse rounds at the ulp of the largest logit (7.6e-6 at 100)
+            const float inv_se = 1.f / se;
+            for (int c = 0; c < C; ++c) d[c] = coef_ce * (expf(z[c] - mx) * inv_se - (c == y ? 1.f : 0.f));
+        }
+#pragma unroll
+        for (int k = 0; k < MT_EMO; ++k) {
+            const float x = z[C + k], t = (float)e[k];
+            // torch's stable form (1 - t) x + m + log(exp(-m) + exp(-x - m)), m = max(-x, 0), written as
+            // (1 - t) x + m + log1p(exp(-|x|)): the same value for either sign of x, finite for any finite x
+            const float m = fmaxf(-x, 0.f);
+            const float ex = expf(-fabsf(x));
+            bce_acc += (double)((1.f - t) * x + m + log1pf(ex));
+            if (d) {
+                const float sig = x >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);
+                d[C + k] = coef_bce * (sig - t);
+            }
+        }
+    }
+    const double ce_sum = block_sum_fixed(ce_acc, red);
+    const double bce_sum = block_sum_fixed(bce_acc, red);
+    const double hit_sum = block_sum_fixed((double)hit, red);
+    if (tid == 0) {
+        stats[8 + 3 * blockIdx.x] = (float)ce_sum;
+        stats[9 + 3 * blockIdx.x] = (float)hit_sum;
+        stats[10 + 3 * blockIdx.x] = (float)bce_sum;
+        __threadfence();
+        const int prev = atomicAdd(reinterpret_cast<int*>(stats + 4), 1);
+        s_last = (prev == (int)gridDim.x - 1);
+    }
+    __syncthreads();
+    if (s_last) {  // the last workgroup combines the partials: one (parallel) load per thread, fixed-order tree
+        __threadfence();
+        double l = 0.0, h = 0.0, b = 0.0;
+        if (tid < (int)gridDim.x) {
+            l = (double)__hip_atomic_load(stats + 8 + 3 * tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            h = (double)__hip_atomic_load(stats + 9 + 3 * tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            b = (double)__hip_atomic_load(stats + 10 + 3 * tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        const double lsum = block_sum_fixed(l, red);
+        const double hsum = block_sum_fixed(h, red);
+        const double bsum = block_sum_fixed(b, red);
+        if (tid == 0) {
+            const double lce = lsum / (double)n_rows, lmulti = bsum / (7.0 * (double)n_rows);
+            stats[0] = (float)((double)w_ce * lce + (double)w_bce * lmulti);
+            stats[1] = (float)hsum;
+            stats[2] = (float)lce;
+            stats[3] = (float)lmulti;
+            *reinterpret_cast<int*>(stats + 4) = 0;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t erc_head_ce_stats_floats(int n_rows) { return 16 + 2 * HC_MAXWG; }
@@ -439,5 +543,19 @@ extern "C" int erc_cross_entropy(const float* logits, int ld, int C, int n_rows,
     hipLaunchKernelGGL(cross_entropy_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_rows,
                        row_map, labels, weight, grad_scale, dlogits, lddl, stats);
     ERC_LAUNCH_CHECK("cross_entropy");
+    return ERC_OK;
+}
+
+extern "C" int erc_ce_bce_multitask(const float* logits, int ld, int C, int n_rows, const int64_t* labels,
+                                    const int64_t* emo_label, int lde, float w_ce, float w_bce, float grad_scale,
+                                    float* dlogits, int lddl, float* stats, void* stream) {
+    ERC_REQUIRE(logits && labels && emo_label && stats, "ce_bce_multitask: null pointer");
+    ERC_REQUIRE(C > 0 && n_rows > 0 && ld >= C + MT_EMO && lde >= MT_EMO && (!dlogits || lddl >= C + MT_EMO),
+                "ce_bce_multitask: C=%d n_rows=%d ld=%d lde=%d lddl=%d", C, n_rows, ld, lde, lddl);
+    int grid = erc_cdiv(n_rows, 256);
+    if (grid > MT_MAXWG) grid = MT_MAXWG;
+    hipLaunchKernelGGL(ce_bce_multitask_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_rows,
+                       labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats);
+    ERC_LAUNCH_CHECK("ce_bce_multitask");
     return ERC_OK;
 }

@@ -13,6 +13,10 @@ File formats and name table follow the reference (behaviour, not code):
   * dataset names ``{corpus}-{release}[-{text}][-{visual}[-v+]]-{n_classes}`` (mmdatasets/datas/__init__.py:33-69); the
     corpus prefix selects the data root (mmdatasets/const.py:9-10, config.py).
 
+  * CMU-MOSEI (CIM release, ``mosei-cim-2``): ``CIM/{text,audio,video}.npz`` with videos padded to a common length;
+    every video becomes one "dialogue" of a single speaker (``read_mosei_cim``, after
+    mmdatasets/datas/mm/mosei_feature.py:9-126).
+
 Reference quirk kept on purpose: the ``tsnss`` names resolve to ``tsn_vfeat.pkl`` there as well (the 'tsn' substring
 test comes first, iemocap_feature.py:383-386), so they do here.
 
@@ -26,9 +30,9 @@ import pickle
 import numpy as np
 import torch
 
-from .params import DATASETS
+from .params import ALL_DATASETS
 
-ROOT_ENV = {"iemocap": "ERC_IEMOCAP_ROOT", "meld": "ERC_MELD_ROOT"}
+ROOT_ENV = {"iemocap": "ERC_IEMOCAP_ROOT", "meld": "ERC_MELD_ROOT", "mosei": "ERC_MOSEI_ROOT"}
 
 
 def data_root(dataset, roots=None):
@@ -46,8 +50,8 @@ def data_root(dataset, roots=None):
 
 def parse_name(dataset):
     """-> dict(corpus, n_classes, text override or '', visual override or '', concat_visual)."""
-    if dataset not in DATASETS:
-        raise ValueError("dataset %r not in %s" % (dataset, DATASETS))
+    if dataset not in ALL_DATASETS:
+        raise ValueError("dataset %r not in %s" % (dataset, ALL_DATASETS))
     parts = dataset.split("-")
     mid = parts[2:-1]
     text = next((t for t in ("sbert", "robert") if t in mid), "")
@@ -60,10 +64,62 @@ def _load(path):
         return pickle.load(fh)
 
 
+def senti2(a):
+    """binary sentiment of mosei_feature.cmumosei_2: 0 below zero, 1 otherwise (NaN included)"""
+    return np.where(np.asarray(a) < 0, 0, 1).astype(np.int64)
+
+
+def senti7(a):
+    """7 sentiment bins of mosei_feature.cmumosei_7: [-3,-2) (-2 bin edges closed below) ... 0 alone ... (2, 3]"""
+    a = np.asarray(a)
+    out = np.select([a < -2, a < -1, a < 0, a == 0, a <= 1, a <= 2, a > 2], [0, 1, 2, 3, 4, 5, 6], -1).astype(np.int64)
+    if (out < 0).any():
+        raise ValueError("sentiment label %r cannot be binned" % a[out < 0][0])
+    return out
+
+
+def emotion_multi_hot(emo):
+    """mosei_feature.create_emotion_label: [L, 7] int64 with a 1 wherever an emotion intensity is nonzero; a row with no
+    emotion gets column 6"""
+    emo = np.asarray(emo)
+    out = np.zeros((emo.shape[0], 7), dtype=np.int64)
+    out[:, :emo.shape[1]] = emo != 0
+    out[~out.any(1), 6] = 1
+    return out
+
+
+def read_mosei_cim(root, split="train"):
+    """Videos of CIM's CMU-MOSEI release as sample dicts: ``ids, length, speakers ([0]), visual, audio, text`` (cut to the
+    video's length, float32), ``label`` (= ``senti2_label``), ``emo_label`` [L, 7], ``senti2_label``, ``senti7_label``
+    (the binnings of ``*SentiLabel[..., 0]``).  Only 'train' and 'test' exist here: the reference's 'valid' branch takes
+    its ids from ``train_idName`` (mosei_feature.py:84-92), so on the real release it indexes past the validation
+    arrays; that split is refused rather than reproduced."""
+    if split not in ("train", "test"):
+        raise ValueError("mosei-cim-2: split %r is not supported (only 'train' and 'test'; the reference's 'val' split "
+                         "pairs the validation arrays with the training ids)" % (split, ))
+    folder = os.path.join(root, "CIM")
+    text, video, audio = (np.load(os.path.join(folder, f + ".npz")) for f in ("text", "video", "audio"))
+    lengths, emo, sent = text[split + "_length"], text[split + "EmoLabel"], text[split + "SentiLabel"]
+    tdata, vdata, adata, ids = text[split + "_data"], video[split + "_data"], audio[split + "_data"], text[split + "_idName"]
+    out = []
+    for i in range(len(ids)):
+        L = lengths[i]
+        s = sent[i][:L, 0]
+        s2 = senti2(s)
+        out.append({"ids": ids[i], "length": lengths[i], "speakers": [0],
+                    "visual": vdata[i][:L].astype(np.float32), "audio": adata[i][:L].astype(np.float32),
+                    "text": tdata[i][:L].astype(np.float32), "label": s2, "emo_label": emotion_multi_hot(emo[i][:L]),
+                    "senti2_label": s2, "senti7_label": senti7(s)})
+    return out
+
+
 def read_dialogues(dataset, split="train", roots=None):
-    """List of per-dialogue sample dicts of ``split`` ('train' | anything else = the test ids), reference order."""
+    """List of per-dialogue sample dicts of ``split`` ('train' | anything else = the test ids; MOSEI: 'train' | 'test'),
+    reference order."""
     spec = parse_name(dataset)
     root = data_root(dataset, roots)
+    if spec["corpus"] == "mosei":
+        return read_mosei_cim(root, split)
     if spec["corpus"] == "iemocap":
         sub = "cogmen/iemocap" if spec["n_classes"] == 6 else "cogmen/iemocap_4"
         main = "IEMOCAP_features.pkl" if spec["n_classes"] == 6 else "IEMOCAP_features_4.pkl"
@@ -107,9 +163,17 @@ class DeviceDialogueStore:
         cat = lambda key: torch.from_numpy(np.concatenate([np.asarray(d[key], dtype=np.float32) for d in dialogues], 0))
         self.feats = {m: cat(order[m]).to(device=device, dtype=dtype) for m in params.modality}
         self.fused = torch.cat([self.feats[m] for m in params.modality], dim=1)           # column order = --modality
-        spk = np.concatenate([np.asarray(d["speakers"], dtype=np.int64).argmax(-1) for d in dialogues], 0)
+        # a per-dialogue speakers list of one entry ([0], CMU-MOSEI) broadcasts over the utterances, as in the reference collate
+        spk = np.concatenate([np.broadcast_to(np.asarray(d["speakers"], dtype=np.int64).argmax(-1), (n, ))
+                              for d, n in zip(dialogues, lens)], 0)
         self.speaker = torch.from_numpy(spk).to(device)
         self.label = torch.from_numpy(np.concatenate([np.asarray(d["label"], dtype=np.int64) for d in dialogues], 0)).to(device)
+        # CMU-MOSEI extras (mmbase.py:382-383, 422-425, 450-453): carried only when the samples have them
+        self.extra = {}
+        for key in ("emo_label", "senti2_label"):
+            if dialogues and all(d.get(key) is not None for d in dialogues):
+                self.extra[key] = torch.from_numpy(np.concatenate([np.asarray(d[key], dtype=np.int64) for d in dialogues],
+                                                                  0)).to(device)
         self.lengths_dev, self.offsets_dev = self.lengths.to(device), self.offsets.to(device)
 
     def __len__(self):
@@ -126,7 +190,10 @@ class DeviceDialogueStore:
         mask = t[None, :] < lens_d[:, None]                                           # [B, T]
         rows = (self.offsets_dev[idx_d][:, None] + t[None, :]).clamp_(max=self.offsets_dev[-1] - 1)
         pad = lambda src: torch.where(mask[..., None], src[rows], torch.zeros((), dtype=src.dtype, device=dev))
-        out = {"attention_mask": mask.float(), "text_length": lens_d, "label": self.label[rows[mask]]}
+        sel = rows[mask]
+        out = {"attention_mask": mask.float(), "text_length": lens_d, "label": self.label[sel]}
+        for key, v in self.extra.items():
+            out[key] = v[sel]
         spk = torch.where(mask, self.speaker[rows], torch.zeros((), dtype=torch.int64, device=dev))
         if p.speaker_onehot:
             spk = torch.nn.functional.one_hot(spk, p.n_speakers).float()   # padded slots: speaker 0, as ERCCollate

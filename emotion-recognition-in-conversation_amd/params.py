@@ -4,6 +4,11 @@ reference's ``MMBaseParams`` (track_mm/mmbase.py:22-126), ``DataParams``
 (mmdatasets/const.py:35-37), with the ``fire``-style command line of
 lumo/core/params.py:248-270 (``--key=value``, dotted keys for nested groups,
 bare ``--flag`` -> True).  No lumo / fire / omegaconf dependency.
+
+Datasets: the IEMOCAP / MELD feature releases of the conversation-graph track and ``mosei-cim-2`` (CIM's CMU-MOSEI
+release: text 300, audio 74, visual 35, two sentiment classes, and 7-way multi-hot emotion labels that CIM trains on
+as a second task).  ``mosei_metric`` is ``'multiemo'`` on MOSEI -- the test pass then also reports per-emotion metrics
+of the multi-label head -- and ``''`` elsewhere (mmbase.py:49,62-63; CIM also clears it when n_classes != 2).
 """
 import ast
 import sys
@@ -21,11 +26,16 @@ def _names(stem, texts, visuals, ks):
 
 
 # the conversation-graph (IEMOCAP / MELD feature) subset of regist_data,
-# mmdatasets/datas/__init__.py:33-68.  MOSEI / raw-audio tracks are out of scope.
+# mmdatasets/datas/__init__.py:33-68.
 DATASETS = tuple(
     _names("iemocap-cogmen", ("", "sbert", "robert"), ("", "tsn", "tsn-v+"), (6,))
     + _names("iemocap-cogmen", ("", "sbert", "robert"), ("", "tsn", "tsn-v+", "tsnss", "tsnss-v+"), (4,))
     + ["meld-mmgcn-7", "meld-mmgcn-sbert-7"])
+# CIM's CMU-MOSEI release (:81): videos of CIM/{text,audio,video}.npz with binary sentiment and 7-way multi-hot emotion
+# labels, trained by --module=cim only.  The MOSEI.adpated.pkl names (sbert / fbank / is10) and the raw-audio tracks
+# are out of scope.
+MOSEI_DATASETS = ("mosei-cim-2",)
+ALL_DATASETS = DATASETS + MOSEI_DATASETS
 
 
 class Group(dict):
@@ -56,6 +66,7 @@ class ERCParams:
         self.hidden_visual = 100
         self.hidden_all = 300
         self.reimplement = False
+        self.mosei_metric = "multiemo"  # mmbase.py:49; '' for every non-MOSEI dataset (:62-63)
         self.confusion_matrix = True
         self.epoch = 10
         self.device = None
@@ -107,12 +118,14 @@ class ERCParams:
     def iparams(self):
         if self.modality not in MODALITIES:
             raise ValueError("modality %r not in %s" % (self.modality, MODALITIES))
-        if self.dataset not in DATASETS:
-            raise ValueError("dataset %r not in %s" % (self.dataset, DATASETS))
+        if self.dataset not in ALL_DATASETS:
+            raise ValueError("dataset %r not in %s" % (self.dataset, ALL_DATASETS))
         ds = self.dataset
         self.n_classes = round(float(ds.split("-")[-1]))            # const.py:35-37
         if self.debug:                                              # mmbase.py:56-60
             self.train.batch_size = self.test.batch_size = 2
+        if "mosei" not in ds:                                       # mmbase.py:62-63
+            self.mosei_metric = ""
         if "iemocap" in ds:                                         # mmbase.py:65-78
             self.class_names = ["hap", "sad", "neu", "ang"] if self.n_classes == 4 else \
                 ["hap", "sad", "neu", "ang", "exc", "fru"]
@@ -123,6 +136,9 @@ class ERCParams:
             self.n_speakers = 9
             if "mmgcn" in ds:
                 self.hidden_audio, self.hidden_text, self.hidden_visual = 300, 600, 342
+        elif "mosei" in ds:                                         # mmbase.py:89-93
+            self.class_names = ["hap", "sad", "disgust", "fear", "surprise", "ang"]
+            self.hidden_text, self.hidden_audio, self.hidden_visual = 300, 74, 35
         if "sbert" in ds or "robert" in ds:                         # mmbase.py:103-104
             self.hidden_text = 768
         if "tsn" in ds:                                             # mmbase.py:107-115

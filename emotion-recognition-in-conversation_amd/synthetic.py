@@ -36,3 +36,30 @@ def make_dialogues(n, dims, n_speakers=2, n_classes=6, min_len=20, max_len=110, 
             "sentence": ["utt %d.%d" % (i, k) for k in range(L)],
         })
     return out
+
+
+def make_mosei_dialogues(n, dims, min_len=1, max_len=98, seed=1, force_max=False):
+    """CMU-MOSEI-shaped videos (the CIM release, datasets.read_mosei_cim): one speaker (``speakers: [0]``), lengths uniform
+    in [min_len, max_len] (the release pads to 98), binary sentiment ``label`` = ``senti2_label``, and a 7-column
+    multi-hot ``emo_label`` built like the reader's: six emotion columns, and column 6 for a row with none (about one row
+    in five here)."""
+    rng = np.random.RandomState(seed)
+    out = []
+    for i in range(n):
+        L = int(rng.randint(min_len, max_len + 1))
+        if force_max and i == 0:
+            L = max_len
+        emo = np.zeros((L, 7), dtype=np.int64)
+        emo[:, :6] = rng.rand(L, 6) < 0.2
+        emo[~emo.any(1), 6] = 1
+        senti = rng.randint(0, 2, size=L).astype(np.int64)
+        out.append({
+            "speakers": [0],
+            "audio": rng.standard_normal((L, dims["a"])).astype(np.float32),
+            "text": rng.standard_normal((L, dims["t"])).astype(np.float32),
+            "visual": rng.standard_normal((L, dims["v"])).astype(np.float32),
+            "label": senti,
+            "emo_label": emo,
+            "senti2_label": senti,
+        })
+    return out

@@ -5,7 +5,8 @@ lumo/trainer/trainer.py:402-442): build params from the command line, build the
 data loaders (``ERCCollate`` batch layout), loop ``epoch`` times over
 ``train_step``, evaluate with ``test_step`` after every epoch
 (EvalCallback(test_per_epoch=1), mmbase.py:136) and report the sklearn metric
-set of mmbase.py:253-323.  One process per GPU; under torch.distributed the
+set of mmbase.py:253-323 (on CMU-MOSEI with ``mosei_metric='multiemo'``: on the binary sentiment, plus the per-emotion
+block of the multi-label head, ``multiemo_report``).  One process per GPU; under torch.distributed the
 trainers all-reduce the flat gradient buffer (RCCL) once per step.
 
 There are no dataset pickles offline: ``--synthetic`` (default) draws seeded
@@ -25,7 +26,7 @@ from torch.utils.data import DataLoader
 
 from . import capi
 from .collate import ERCCollate
-from .synthetic import make_dialogues
+from .synthetic import make_dialogues, make_mosei_dialogues
 
 
 def fix_seed(seed):
@@ -91,9 +92,12 @@ def load_dialogues(params, rank=0, world=1):
         roots = params.get("data_root", None)
         train = read_dialogues(params.dataset, "train", roots)
         return shard_dialogues(train, rank, world), read_dialogues(params.dataset, "test", roots)
-    meld = "meld" in params.dataset
-    lo, hi = (1, 33) if meld else (20, 110)
+    meld, mosei = "meld" in params.dataset, "mosei" in params.dataset
+    lo, hi = (1, 33) if meld else (1, 98) if mosei else (20, 110)
     lo, hi = int(params.get("syn_min_len", lo)), int(params.get("syn_max_len", hi))     # (tests: equal lengths -> repeating shapes)
+    if mosei:
+        mk = lambda n, seed: make_mosei_dialogues(n, params.dims(), min_len=lo, max_len=hi, seed=seed)
+        return mk(params.n_train, params.seed + 1000 * rank), mk(params.n_test, params.seed + 7)
     mk = lambda n, seed: make_dialogues(n, params.dims(), n_speakers=params.n_speakers, n_classes=params.n_classes,
                                         min_len=lo, max_len=hi, seed=seed)
     return mk(params.n_train, params.seed + 1000 * rank), mk(params.n_test, params.seed + 7)   # every rank draws its own
@@ -412,9 +416,45 @@ def classification_report(true, pred, n_classes):
     }
 
 
+def weighted_accuracy(y_true, y_pred):
+    """mmbase.py:231-251: (TP N / P + TN) / 2N of a binary column -- None where the column has no positives or no
+    negatives (the reference divides by zero there)"""
+    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
+    P = int((y_true == 1).sum())
+    N = len(y_true) - P
+    if P == 0 or N == 0:
+        return None
+    TP = int(((y_true == 1) & (y_pred == 1)).sum())
+    TN = int(((y_true == 0) & (y_pred == 0)).sum())
+    return (1.0 * TP * (N / (1.0 * P)) + TN) / (2.0 * N)
+
+
+def multiemo_report(true_multi, prob_multi, thresh=0.5):
+    """The multi-label block of mmbase.py:280-300 on sigmoid(logits7) > thresh: per emotion column the accuracy, the
+    weighted F1 and the weighted accuracy, and their means.  A column without positives or without negatives reports
+    ``None`` as its weighted accuracy and the mean runs over the defined columns (the reference raises
+    ZeroDivisionError there)."""
+    from sklearn import metrics
+    true_multi, pred = np.asarray(true_multi), (np.asarray(prob_multi) > thresh).astype(int)
+    acc, f1, wa = [], [], []
+    for i in range(true_multi.shape[1]):
+        col = pred[:, i]
+        acc.append(float(metrics.accuracy_score(true_multi[:, i], col)))
+        f1.append(float(metrics.precision_recall_fscore_support(true_multi[:, i], col, average="weighted", zero_division=0)[2]))
+        wa.append(weighted_accuracy(true_multi[:, i], col))
+    defined = [w for w in wa if w is not None]
+    return {"thresh": thresh, "acc": acc, "f1": f1, "wa": wa, "mean_acc": float(np.mean(acc)), "mean_f1": float(np.mean(f1)),
+            "mean_wa": float(np.mean(defined)) if defined else None}
+
+
 def run(trainer_cls, params_cls, argv=None):
     params = params_cls()
     params.from_args(argv)
+    if "mosei" in params.dataset and not hasattr(trainer_cls, "to_mosei_multitask_logits"):
+        # the reference's test_step calls to_mosei_multitask_logits on MOSEI, which only CIM implements
+        # (mmbase.py:144-145,181-182): every other module raises NotImplementedError there
+        raise SystemExit("dataset %s: this module has no multi-task (sentiment + emotion) head; only --module=cim trains on "
+                         "CMU-MOSEI" % params.dataset)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -487,13 +527,26 @@ def run(trainer_cls, params_cls, argv=None):
             dt = time.perf_counter() - t0
         if rank == 0 and params.log_every:
             rows = ring[:len(counts)].cpu().tolist()
+            multitask = getattr(trainer, "multitask", False)
             for i, (row, n_b) in enumerate(zip(rows, counts)):
                 if (i + 1) % params.log_every == 0:
-                    print(json.dumps({"epoch": epoch, "step": i, "Lall": row[0], "Acc": row[1] / max(1, n_b)}), flush=True)
+                    line = {"epoch": epoch, "step": i, "Lall": row[0], "Acc": row[1] / max(1, n_b)}
+                    if multitask:
+                        line.update(Lce=row[2], Lmulti=row[3])
+                    print(json.dumps(line), flush=True)
         # test after every epoch (mmbase.py:136,180-201)
         trainer.model.eval()
         true, pred = [], []
+        multiemo = params.get("mosei_metric", "") == "multiemo"
+        true_multi, prob_multi = [], []
         for batch in test_loader:
+            if multiemo:           # mosei_test_step (mmbase.py:167-178)
+                logits, logits7 = trainer.to_mosei_multitask_logits(trainer.prepare_batch(batch))
+                true_multi.append(batch["emo_label"].cpu().numpy())
+                prob_multi.append(torch.sigmoid(logits7).cpu().numpy())
+                pred.extend(logits.argmax(-1).cpu().tolist())
+                true.extend(batch["senti2_label"].tolist())
+                continue
             logits = trainer.to_logits(trainer.prepare_batch(batch))
             if logits.dim() == 3:
                 logits = logits[batch["attention_mask"].bool().to(logits.device)]
@@ -505,10 +558,13 @@ def run(trainer_cls, params_cls, argv=None):
             rep = classification_report(true, pred, params.n_classes)
             for k in ("acc", "wa", "f1", "mif1", "maf1", "pre", "rec"):
                 best[k] = max(best.get(k, 0.0), rep[k])
-            print(json.dumps({"epoch": epoch, "train_utt_per_s": n_utt / dt, "test": {k: rep[k] for k in rep if k != "cm"},
-                              "best": best, "graph_replays": (resident or graphs).replays if (resident or graphs) else 0,
-                              "eager_steps": (resident or graphs).eager if (resident or graphs) else len(counts),
-                              "graphs_captured": (resident or graphs).captures if (resident or graphs) else 0}), flush=True)
+            line = {"epoch": epoch, "train_utt_per_s": n_utt / dt, "test": {k: rep[k] for k in rep if k != "cm"},
+                    "best": best, "graph_replays": (resident or graphs).replays if (resident or graphs) else 0,
+                    "eager_steps": (resident or graphs).eager if (resident or graphs) else len(counts),
+                    "graphs_captured": (resident or graphs).captures if (resident or graphs) else 0}
+            if multiemo:
+                line["multiemo"] = multiemo_report(np.concatenate(true_multi), np.concatenate(prob_multi))
+            print(json.dumps(line), flush=True)
     if params.get("save") and rank == 0:
         from . import checkpoint
         checkpoint.save(trainer, params.save)

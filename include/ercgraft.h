@@ -1054,6 +1054,20 @@ int erc_cim_max_t(void);
 int erc_cim_attn_fwd(float* merged, const int32_t* node_off, int B, int T, float* Pbuf, void* stream);
 int erc_cim_attn_bwd(const float* merged, float* dmerged, const int32_t* node_off, int B, int T, const float* Pbuf,
                      float mask_scale, void* stream);
+/* Multi-task loss of CIM on CMU-MOSEI (cim.py:204-216): Lce = F.cross_entropy(logits[:, 0:C], label) and
+ * Lmulti = F.binary_cross_entropy_with_logits(logits[:, C:C+7], emo_label.float()), both unweighted means, in one launch.
+ *   logits [n_rows, C + 7] (row pitch ld >= C + 7): cls2 | cls7 outputs of one [C + 7, 900] head GEMM
+ *   label int64 [n_rows]; emo_label int64 [n_rows, 7] (row pitch lde >= 7), read as is (0 / 1 multi-hot)
+ *   w_ce, w_bce: weights of the two terms (apply_bin / apply_multi: 0 or 1)
+ *   dlogits (may be NULL) [n_rows, C + 7] (pitch lddl): (softmax - onehot) w_ce / n_rows in columns 0..C and
+ *     (sigmoid(x) - y) w_bce / (7 n_rows) in columns C..C+7, both times grad_scale
+ *   stats (>= 256 floats, zero-initialised once by the caller): [0] Lall = w_ce Lce + w_bce Lmulti, [1] #rows whose
+ *     argmax over the C sentiment columns equals label, [2] Lce, [3] Lmulti; [4] and [8..) are the arrival counter and
+ *     per-workgroup partials, combined in a fixed order (bit-identical from run to run, no float atomics).
+ * The BCE term uses the stable form of torch, finite for any finite logit. */
+int erc_ce_bce_multitask(const float* logits, int ld, int C, int n_rows, const int64_t* label, const int64_t* emo_label,
+                         int lde, float w_ce, float w_bce, float grad_scale, float* dlogits, int lddl, float* stats,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * conv-emotion DialogueGCN (track_mm/dgcnv2.py, track_mm/dgcnv2_models.py; csrc/dgcnv2_att.hip).  Batches are time-major

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""CIM training step (--module=cim, iemocap-cogmen-6 atv synthetic dialogues of up to 110 utterances) timed as a captured
-HIP graph with device events: warm-up replays, then the median of --replays replays.  Prints one JSON line per batch size
-with ms/step, utterances/s, launches per step, and the same step restated on the CPU (tests/cim_oracle.py, autograd + Adam,
-16 threads) as the baseline.
+"""CIM training step (--module=cim, iemocap-cogmen-6 atv synthetic dialogues of up to 110 utterances, or with --dataset
+mosei-cim-2 synthetic CMU-MOSEI videos of up to 98 utterances and the multi-task loss) timed as a captured HIP graph with
+device events: warm-up replays, then the median of --replays replays.  Prints one JSON line per batch size with ms/step,
+utterances/s, launches per step, and the same step restated on the CPU (tests/cim_oracle.py, tests/cim_mosei_oracle.py
+for MOSEI; autograd + Adam, 16 threads) as the baseline.
 
-    python tools/cim_bench.py [--batch 16,32] [--replays 50] [--cpu_steps 2]
+    python tools/cim_bench.py [--dataset iemocap-cogmen-6|mosei-cim-2] [--batch 16,32] [--replays 50] [--cpu_steps 2]
 """
 import argparse
 import json
@@ -21,9 +22,12 @@ sys.path.insert(0, REPO)
 
 def make_batch(params, B, seed):
     from erc_amd.collate import ERCCollate
-    from erc_amd.synthetic import make_dialogues
-    dialogs = make_dialogues(B, params.dims(), n_speakers=params.n_speakers, n_classes=params.n_classes, min_len=20,
-                             max_len=110, seed=seed, force_max=True)
+    from erc_amd.synthetic import make_dialogues, make_mosei_dialogues
+    if "mosei" in params.dataset:
+        dialogs = make_mosei_dialogues(B, params.dims(), min_len=1, max_len=98, seed=seed, force_max=True)
+    else:
+        dialogs = make_dialogues(B, params.dims(), n_speakers=params.n_speakers, n_classes=params.n_classes, min_len=20,
+                                 max_len=110, seed=seed, force_max=True)
     return ERCCollate(params)([[d] for d in dialogs])
 
 
@@ -36,11 +40,11 @@ def count_launches(tr, b):
     return len(rec) + 1          # + the device add of the drop1 seeds (the only launch that is not a C-ABI call)
 
 
-def gpu_time(B, replays, warmup):
+def gpu_time(dataset, B, replays, warmup):
     from track_mm.cim import CIMParams
     from erc_amd.cim import CIMTrainer
     from erc_amd.engine import GraphedStep
-    params = CIMParams().from_args(["--dataset=iemocap-cogmen-6"])
+    params = CIMParams().from_args(["--dataset=" + dataset])
     tr = CIMTrainer(params, "cuda:0")
     batch = make_batch(params, B, 7)
     n_utt = int(batch["text_length"].sum())
@@ -64,14 +68,24 @@ def gpu_time(B, replays, warmup):
 
 def cpu_time(params, batch, steps):
     from erc_amd.cim import CIMModule
+    from tests.cim_mosei_oracle import cim_mosei_loss_and_grads
     from tests.cim_oracle import cim_forward
     torch.set_num_threads(16)
+    multi = bool(params.apply_multi)
     m = CIMModule(params.hidden_text, params.hidden_audio, params.hidden_visual, 200, params.n_classes)
     P = {k: torch.nn.Parameter(v.detach().clone()) for k, v in m.state_dict().items()}
-    opt = torch.optim.Adam([v for k, v in P.items() if not k.startswith(("rnn_adapter.", "cls7."))], lr=1e-3)
+    dead = ("rnn_adapter.", ) if multi else ("rnn_adapter.", "cls7.")
+    opt = torch.optim.Adam([v for k, v in P.items() if not k.startswith(dead)], lr=1e-3)
     times = []
     for _ in range(steps):
         t0 = time.perf_counter()
+        if multi:           # Lce + Lmulti through the multi-task restatement; its gradients feed the same Adam
+            _, _, _, grads, _ = cim_mosei_loss_and_grads(P, batch)
+            for k, g in grads.items():
+                P[k].grad = g
+            opt.step()
+            times.append((time.perf_counter() - t0) * 1e3)
+            continue
         logits2, _, _ = cim_forward(P, batch)
         loss = torch.nn.functional.cross_entropy(logits2, batch["label"])
         opt.zero_grad()
@@ -83,15 +97,16 @@ def cpu_time(params, batch, steps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dataset", default="iemocap-cogmen-6", choices=("iemocap-cogmen-6", "mosei-cim-2"))
     ap.add_argument("--batch", default="16,32")
     ap.add_argument("--replays", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--cpu_steps", type=int, default=2)
     args = ap.parse_args()
     for B in (int(v) for v in args.batch.split(",")):
-        params, batch, res = gpu_time(B, args.replays, args.warmup)
+        params, batch, res = gpu_time(args.dataset, B, args.replays, args.warmup)
         cpu_ms = cpu_time(params, batch, args.cpu_steps) if args.cpu_steps > 0 else None
-        res.update(module="cim", dataset="iemocap-cogmen-6", modality="atv", B=B, replays=args.replays,
+        res.update(module="cim", dataset=args.dataset, modality="atv", B=B, replays=args.replays,
                    cpu16_ms_per_step=cpu_ms, speedup_vs_cpu16=(cpu_ms / res["ms_per_step"]) if cpu_ms else None)
         print(json.dumps(res), flush=True)
 

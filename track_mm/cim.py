@@ -23,6 +23,8 @@ class CIMParams(ERCParams):
         super().iparams()
         if "mosei" not in self.dataset:                                           # cim.py:52-53
             self.apply_multi = False
+        if self.n_classes != 2:                                                   # cim.py:57-58
+            self.mosei_metric = ""
         return self
 
 
