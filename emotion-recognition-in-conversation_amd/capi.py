@@ -3,9 +3,15 @@
 PyTorch is plumbing here: tensors own device memory, ``data_ptr()`` and the
 current stream handle are passed straight through the C-ABI.  There is NO
 fallback: if the library is missing or a call fails, this raises.
+
+The header is the only place an entry point's types are written down: every
+``erc_*`` prototype is parsed at import (``parse_header``), and ``_call``
+checks each wrapper's arguments against it.  A new entry point is declared in
+the header and gets a wrapper here.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 import torch
@@ -13,198 +19,63 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ERC_LIB_PATH") or os.path.join(_HERE, "lib", "libercgraft.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "ercgraft.h")
 
-_vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
-_SIGS = {
-    "erc_abi_version": (C.c_int, []),
-    "erc_last_error": (C.c_char_p, []),
-    "erc_window_graph_build": (C.c_int, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i] + [_vp] * 13 + [_vp]),
-    "erc_gemm_f32": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _i64,
-                               _vp, _i, _vp, _i, _f, _f, _vp, _i, _vp]),
-    "erc_gemm_f32_stream": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _vp, _i64,
-                                      _vp, _i, _vp, _i, _f, _f, _vp, _i, _vp]),
-    "erc_gemm_bf16a_stream": (C.c_int, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "erc_wgrad_table": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "erc_wgrad_table_x3": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "erc_enc_to_bf16": (C.c_int, [_vp, _i64, _vp, _vp]),
-    "erc_enc_gemm_bf16": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "erc_enc_attention": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "erc_enc_add_layernorm": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp]),
-    "erc_enc_gemm_bf16_ex": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _f, _vp,
-                                       C.c_uint64, _vp]),
-    "erc_enc_attention_train": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _f, _vp, C.c_uint64, _vp, _vp]),
-    "erc_enc_attention_bwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _f, _vp, C.c_uint64, _vp, _vp]),
-    "erc_enc_add_layernorm_train": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _f, _f, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
-                                              _vp]),
-    "erc_enc_layernorm_bwd_blocks": (C.c_int, [_i]),
-    "erc_enc_layernorm_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "erc_enc_transpose_bf16": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
-    "erc_enc_colsum_ws_floats": (_i64, [_i]),
-    "erc_enc_colsum": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "erc_enc_inverse_rows": (C.c_int, [_vp, _i, _vp, _i, _vp]),
-    "erc_wgrad_slab_floats": (C.c_int64, []),
-    "erc_bn_batch_stats_ws_floats": (C.c_int64, [_i]),
-    "erc_bn_batch_stats": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
-    "erc_head_fused_ws_floats": (C.c_int64, [_i]),
-    "erc_head_fused": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp,
-                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
-    "erc_head_fused_bn": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp,
-                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _i,
-                                    _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
-    "erc_wgrad_bf16": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "erc_wgrad_bf16_adam": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp, _vp,
-                                      _i64, _vp, _vp, _vp]),
-    "erc_wgrad_split": (C.c_int, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "erc_wgrad_split_adam": (C.c_int, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp,
-                                       _vp, _i64, _vp, _vp, _vp]),
-    "erc_wgrad_adam_p2p": (C.c_int, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp,
-                                     _vp, _i64, _vp, _vp, _vp]),
-    "erc_wgrad_bf16_set_spin_limit": (C.c_int, [_i]),
-    "erc_wgrad_bf16_wide": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "erc_wgrad_bf16_slab_floats": (C.c_int64, []),
-    "erc_wgrad_bf16_set_stamps": (C.c_int, [_vp, _i]),
-    "erc_wgrad_bf16_max_k_per_split": (C.c_int, []),
-    "erc_bn_bwd_apply": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-    "erc_wgrad_max_k_per_split": (C.c_int, []),
-    "erc_gemm_x3": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i64, _vp]),
-    "erc_gemm_x3_grouped": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp]),
-    "erc_gemm_bf16x": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i64, _i, _vp,
-                                 _i64, _vp]),
-    "erc_slab_reduce": (C.c_int, [_vp, _i, _i64, _vp, _i, _i, _vp, _i, _i64, _vp]),
-    "erc_slab_reduce_batched": (C.c_int, [_vp, _vp, _vp, _i, _i64, _vp]),
-    "erc_rgcn_mean_fwd": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_rgcn_mean_bwd": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "erc_tconv_attn_fwd": (C.c_int, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_tconv_attn_bwd_target": (C.c_int, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp,
-                                            _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_tconv_attn_bwd_source": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_bn_ws_floats": (C.c_int64, [_i]),
-    "erc_bn_lrelu_fwd": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _i, _vp, _vp]),
-    "erc_bn_lrelu_bwd": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "erc_cross_entropy": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp]),
-    "erc_head_ce_stats_floats": (C.c_int64, [_i]),
-    "erc_dgcn_tail_max_rows": (C.c_int, []),
-    "erc_dgcn_tail_set_stamps": (C.c_int, [_vp]),
-    "erc_dgcn_tail_max_window": (C.c_int, []),
-    "erc_dgcn_tail_stats_floats": (C.c_int64, [_i]),
-    "erc_dgcn_tail": (C.c_int, [_vp, _i, _i64, _vp, _vp, _vp, _i] + [_vp] * 9 + [_i, _i, _f, _vp, _vp, _i] + [_vp] * 7 + [_i] + [_vp] * 4),
-    "erc_head_ce": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
-    "erc_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp, _i64, _i64,
-                                _vp, _vp]),
-    "erc_adam_step_tab": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "erc_shadow_refresh": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
-    "erc_cogmen_fwd_tile_ws_doubles": (C.c_int64, [_i]),
-    "erc_cogmen_set_stamps": (C.c_int, [_vp]),
-    "erc_cogmen_project_graph_ok": (C.c_int, [_i, _i, _i, _i, _i]),
-    "erc_cogmen_project_graph": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i]
-                                 + [_vp] * 11 + [_vp, _vp]),
-    "erc_cogmen_project_graph_x": (C.c_int, [_i, _vp, _i, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i,
-                                             _i, _i] + [_vp] * 11 + [_vp, _vp]),
-    "erc_head_set_stamps": (C.c_int, [_vp]),
-    "erc_cogmen_fwd_tile": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _i, _vp,
-                                      _vp, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "erc_cogmen_bwd_tile": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "erc_cogmen_fwd_tile_x": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _f, _vp, _i, _vp, _vp, _i, _vp,
-                                        _vp, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "erc_cogmen_bwd_tile_x": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _vp, _i64, _vp, _i64, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_head_fused_part_floats": (C.c_int, []),
-    "erc_head_rows_occupancy": (C.c_int, []),
-    "erc_head_fused_rows_per_workgroup": (C.c_int, [_i]),
-    "erc_clock_probe": (C.c_int, [_vp, _i, _vp]),
-    "erc_grad_norm": (C.c_int, [_vp, _i64, _f, _vp, _vp, _vp]),
-    "erc_lstm_scan_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _i, _vp, _i, _f, _vp,
-                                    C.c_uint64, _vp, _vp, _vp, _vp]),
-    "erc_lstm_scan_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _i, _f, _vp, C.c_uint64, _vp,
-                                    _vp]),
-    "erc_gather_rows": (C.c_int, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
-    "erc_edge_att_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_edge_att_bwd_parts": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _i, _i,
-                                         _vp, _i, _vp, _vp]),
-    "erc_edge_att_bwd_fused": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _i, _i,
-                                        _vp, _i, _vp, _vp, _i, C.c_int64, _vp, _vp, _vp, _vp, _i, _vp]),
-    "erc_edge_att_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i,
-                                   _vp, _vp]),
-    "erc_brgcn_agg_fwd": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_brgcn_bwd_edges": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_brgcn_bwd_source": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_transpose_batched": (C.c_int, [_vp, _i, _i, _i, _vp, _vp]),
-    "erc_lstm_set_stamps": (C.c_int, [_vp]),
-    "erc_brgcn_fwd_tile_slab_floats": (C.c_int64, [_i]),
-    "erc_brgcn_set_stamps": (C.c_int, [_vp]),
-    "erc_brgcn_fwd_tile_slabs": (C.c_int, []),
-    "erc_brgcn_bwd_edges_tile": (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp,
-                                           C.c_int64, _vp, _vp]),
-    "erc_brgcn_bwd_source_tile": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "erc_brgcn_fwd_tile": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_rrgcn_max_relations": (C.c_int, []),
-    "erc_basis_compose": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "erc_basis_decompose": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "erc_rrgcn_agg_fwd": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "erc_rrgcn_bwd_edges": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "erc_rrgcn_bwd_source": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "erc_csr_sum": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
-    "erc_gemm_f32_grouped": (C.c_int, [_i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f,
-                                       _vp, _i, _i64, _i64, _i, _i64, _vp]),
-    "erc_gemm_f32_planes": (C.c_int, [_vp, _i, _i64, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
-    "erc_mm_meta": (C.c_int, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_mm_flatten": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-    "erc_mm_emb_grad": (C.c_int, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
-    "erc_mm_emb_grad_ws_floats": (_i64, [_i]),
-    "erc_mm_row_normalize": (C.c_int, [_vp, _i, _vp, _vp, _vp]),
-    "erc_mm_row_normalize_bwd": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp]),
-    "erc_mm_adj_finish": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_mm_adj_finish_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "erc_mm_cross_apply": (C.c_int, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
-    "erc_mm_cross_grad": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i64, _i64, _vp]),
-    "erc_gcnii_combine_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _f, _f, _f, _vp, C.c_uint64, _vp, _vp]),
-    "erc_gcnii_combine_bwd": (C.c_int, [_vp, _vp, _i64, _f, _f, _f, _i, _vp, _vp, _vp, _i, _i, _vp]),
-    "erc_gcnii_layer_fwd": (C.c_int, [_vp, _i, _vp, _i, _f, _f, _f, _vp, C.c_uint64, _vp, _i, _i, _i, _vp]),
-    "erc_dropout_fwd": (C.c_int, [_vp, _i64, _f, _vp, C.c_uint64, _vp, _vp]),
-    "erc_mm_regroup_fwd": (C.c_int, [_vp, _vp, _i, _i, _f, _vp, C.c_uint64, _vp, _vp]),
-    "erc_mm_regroup_bwd": (C.c_int, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
-    "erc_axpy_mask": (C.c_int, [_vp, _vp, _i64, _f, _i, _vp, _vp]),
-    "erc_test_poison_lds": (C.c_int, [_vp, _vp]),
-    "erc_gcnii_chain_set_stamps": (C.c_int, [_vp]),
-    "erc_gcnii_chain_prep": (C.c_int, [_vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "erc_gcnii_chain_config": (C.c_int, [_i, _i, _i, _i, _vp, _vp, _vp]),
-    "erc_gcnii_chain_fwd": (C.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp, _i, _vp, _vp,
-                                      _vp, _f, _vp, C.c_uint64, _vp]),
-    "erc_gcnii_chain_bwd": (C.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp,
-                                      _vp, _vp, _f, _vp]),
-    "erc_dag_meta": (C.c_int, [_vp, _vp, _i64, _i64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_dag_rec_config": (C.c_int, [_i, _i, _i, _i, _i, _i, _i, _vp]),
-    "erc_dag_rec_scratch_bytes": (C.c_int64, [_i, _i, _i, _vp]),
-    "erc_dag_rec_set_stamps": (C.c_int, [_vp]),
-    "erc_dag_rec_fwd": (C.c_int, [_vp, _i, _i] + [_vp] * 8 + [_vp, _vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 5 + [_vp, _vp, _vp, _vp, _vp]),
-    "erc_dag_rec_bwd": (C.c_int, [_i, _vp, _i, _vp, _i] + [_vp] * 9 + [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp,
-                                  _vp, _vp, _vp, _vp, _vp]),
-    "erc_health_roll": (C.c_int, [_vp, _vp, _vp]),
-    "erc_p2p_alloc": (C.c_int, [_i64, _vp, _vp]),
-    "erc_p2p_open": (C.c_int, [_vp, _vp]),
-    "erc_p2p_close": (C.c_int, [_vp]),
-    "erc_p2p_free": (C.c_int, [_vp]),
-    "erc_adam_step_p2p": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "erc_gcnii_chain_set_spin_limit": (C.c_int, [_i]),
-    "erc_dag_attn_sums": (C.c_int, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "erc_cim_meta": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "erc_gru_scan_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _f, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "erc_gru_scan_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _f, _vp, C.c_uint64, _vp, _vp, _vp]),
-    "erc_cim_max_t": (C.c_int, []),
-    "erc_cim_attn_fwd": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp]),
-    "erc_cim_attn_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _f, _vp]),
-    "erc_ce_bce_multitask": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _vp, _i, _vp, _vp]),
-    "erc_dgcnv2_max_t": (C.c_int, []),
-    "erc_dgcnv2_meta": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "erc_dgcnv2_edge_att_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "erc_dgcnv2_edge_att_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
-    "erc_dgcnv2_nodal_fwd": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
-    "erc_dgcnv2_nodal_bwd": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-}
+class ErcGraftError(RuntimeError):
+    pass
 
-EXPORTS = tuple(_SIGS)
+
+_CTYPES = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float}
+
+
+def _ctype(decl, proto, ret=False):
+    """ctypes type of a declaration without its name: any pointer is c_void_p, a returned ``const char*`` c_char_p"""
+    t = " ".join(decl.replace("*", " * ").split())
+    if ret and t == "const char *":
+        return C.c_char_p
+    if "*" in t:
+        return C.c_void_p
+    t = re.sub(r"\bconst\b", "", t).strip()
+    if t not in _CTYPES:
+        raise ErcGraftError("%s: type '%s' has no ctypes mapping" % (proto, t))
+    return _CTYPES[t]
+
+
+def parse_header(text):
+    """{name: (restype, argtypes, parameter names)} of every ``erc_*`` prototype in C header ``text``."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)          # preprocessor lines
+    protos = {}
+    for decl in re.split(r"[;{}]", text):
+        m = re.fullmatch(r"\s*(.*?)\b(erc_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        if m is None:
+            continue
+        ret, name, params = m.groups()
+        argtypes, names = [], []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            pm = re.fullmatch(r"\s*(.+?)\b(\w+)\s*", p, flags=re.S)
+            if pm is None:
+                raise ErcGraftError("%s: cannot parse parameter '%s'" % (name, p.strip()))
+            argtypes.append(_ctype(pm.group(1), name))
+            names.append(pm.group(2))
+        protos[name] = (_ctype(ret, name, ret=True), argtypes, tuple(names))
+    return protos
+
+
+with open(HEADER) as _fh:
+    _header = _fh.read()
+PROTOS = parse_header(_header)
+EXPORTS = tuple(PROTOS)
+ERC_ABI_VERSION = int(re.search(r"^\s*#\s*define\s+ERC_ABI_VERSION\s+(\d+)", _header, flags=re.M).group(1))
+del _header
+
+
+def _launches(name):
+    """the entry point enqueues work: its last parameter is the stream"""
+    return PROTOS[name][2][-1:] == ("stream",)
+
+
 _lib = None
 _raw = None
 _record = None     # list of (entry point, argument tuple) while a recording is active (bench.py kernel probes)
@@ -224,13 +95,11 @@ def stop_recording():
 
 
 def replay(entry):
-    """Re-issue a recorded call on the CURRENT stream (the stream handle is every launching entry point's last argument)."""
+    """Re-issue a recorded call, a launching entry point's on the CURRENT stream."""
     name, args = entry
-    _check(getattr(_raw, name)(*(args[:-1] + (stream(),))), name)
-
-
-class ErcGraftError(RuntimeError):
-    pass
+    if _launches(name):
+        args = args[:-1] + (stream(),)
+    _check(getattr(_raw, name)(*args), name)
 
 
 def build(verbose=False):
@@ -257,7 +126,7 @@ def lib():
         class _Recording:          # same attribute surface as the CDLL handle; one global test per call when idle
             pass
         rec = _Recording()
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args, _) in PROTOS.items():
             fn = getattr(handle, name)  # AttributeError = symbol missing: fail loudly
             fn.restype, fn.argtypes = res, args
 
@@ -266,7 +135,7 @@ def lib():
                     _record.append((_name, a))
                 return _fn(*a)
             setattr(rec, name, call)
-        if handle.erc_abi_version() != 3:
+        if handle.erc_abi_version() != ERC_ABI_VERSION:
             raise ErcGraftError("libercgraft ABI version mismatch")
         _raw, _lib = handle, rec
     return _lib
@@ -277,109 +146,93 @@ def _check(code, name):
         raise ErcGraftError("%s failed (%d): %s" % (name, code, lib().erc_last_error().decode()))
 
 
-def ptr(t):
-    if t is None:
-        return None
-    return t.data_ptr()
-
-
 def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _dev(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise ErcGraftError("libercgraft operands must live on the GPU (got a %s tensor)" % t.device)
+def _call(name, *args):
+    """Call status-returning entry point ``name`` with the arguments of its prototype, the stream excluded: a tensor (it
+    must live on the GPU) becomes its data_ptr(), None NULL; ints, floats and ctypes objects pass through.  The current
+    stream is appended when the prototype ends in one; a non-zero status raises."""
+    names, launches = PROTOS[name][2], _launches(name)
+    if len(args) != len(names) - launches:
+        raise ErcGraftError("%s takes %d arguments, got %d" % (name, len(names) - launches, len(args)))
+    conv = []
+    for a, pname in zip(args, names):
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise ErcGraftError("%s: %s must live on the GPU (got a %s tensor)" % (name, pname, a.device))
+            a = a.data_ptr()
+        conv.append(a)
+    if launches:
+        conv.append(stream())
+    _check(getattr(lib(), name)(*conv), name)
 
 
 # --------------------------------------------------------------------------- wrappers
 def window_graph_build(lengths, speakers, spk_sb, spk_st, B, T, wp, wf, S, n_cap, e_cap, g, edge_index=None,
                        edge_type=None):
-    _dev(lengths, speakers)
-    _check(lib().erc_window_graph_build(
-        ptr(lengths), ptr(speakers), spk_sb, spk_st, B, T, wp, wf, S, n_cap, e_cap,
-        ptr(g["node_off"]), ptr(g["node_row"]), ptr(g["node_spk"]), ptr(g["in_ptr"]), ptr(g["in_src"]),
-        ptr(g["in_typ"]), ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_typ"]), ptr(g["out_eid"]),
-        ptr(edge_index), ptr(edge_type), ptr(g["counts"]), stream()), "erc_window_graph_build")
+    _call("erc_window_graph_build", lengths, speakers, spk_sb, spk_st, B, T, wp, wf, S, n_cap, e_cap, g["node_off"],
+          g["node_row"], g["node_spk"], g["in_ptr"], g["in_src"], g["in_typ"], g["out_ptr"], g["out_dst"], g["out_typ"],
+          g["out_eid"], edge_index, edge_type, g["counts"])
 
 
 def gemm_f32(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k=1, c_slab=0,
              ones_col=0, bias_out=None, bias_slab=0, bias=None, act=0, aux=None, ldaux=0, act_scale=1.0,
              drop_p=0.0, rng_state=None, accumulate=0):
-    _dev(A, B, Cmat)
-    _check(lib().erc_gemm_f32(ptr(A), lda, a_kmajor, ptr(a_gather), ptr(B), ldb, b_kmajor, ptr(b_gather),
-                              ptr(Cmat), ldc, M, N, K, split_k, c_slab, ones_col, ptr(bias_out), bias_slab,
-                              ptr(bias), act, ptr(aux), ldaux, act_scale, drop_p, ptr(rng_state), accumulate,
-                              stream()), "erc_gemm_f32")
+    _call("erc_gemm_f32", A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k, c_slab, ones_col,
+          bias_out, bias_slab, bias, act, aux, ldaux, act_scale, drop_p, rng_state, accumulate)
 
 
 def gemm_bf16x(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, x_is_a, Cmat, ldc, M, N, K, split_k=1,
                c_slab=0, ones_col=0, bias_out=None, bias_slab=0):
-    _dev(A, B, Cmat)
-    _check(lib().erc_gemm_bf16x(ptr(A), lda, a_kmajor, ptr(a_gather), ptr(B), ldb, b_kmajor, ptr(b_gather), x_is_a,
-                                ptr(Cmat), ldc, M, N, K, split_k, c_slab, ones_col, ptr(bias_out), bias_slab,
-                                stream()), "erc_gemm_bf16x")
+    _call("erc_gemm_bf16x", A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, x_is_a, Cmat, ldc, M, N, K, split_k, c_slab,
+          ones_col, bias_out, bias_slab)
 
 
 def gemm_x3(A, lda, B, ldb, Cmat, ldc, M, N, K, split_k=1, c_slab=0):
     """C = A B^T (both K-contiguous fp32) on the bf16 matrix cores through a three-term split: fp32-class (ercgraft.h)"""
-    _dev(A, B, Cmat)
-    _check(lib().erc_gemm_x3(ptr(A), lda, ptr(B), ldb, ptr(Cmat), ldc, M, N, K, split_k, c_slab, stream()), "erc_gemm_x3")
+    _call("erc_gemm_x3", A, lda, B, ldb, Cmat, ldc, M, N, K, split_k, c_slab)
 
 
 def gemm_x3_grouped(A, lda, B, ldb, Cmat, pitch, node_off, n_dlg, n_mod, n_nodes, max_rows, K, split_k=1, c_slab=0):
     """per-(dialogue, modality) blocks A_rows B_rows^T with the three-term split (erc_gemm_f32_grouped form 1; ercgraft.h)"""
-    _dev(A, B, Cmat)
-    _check(lib().erc_gemm_x3_grouped(ptr(A), lda, ptr(B), ldb, ptr(Cmat), pitch, ptr(node_off), n_dlg, n_mod, n_nodes, max_rows, K,
-                                     split_k, c_slab, stream()), "erc_gemm_x3_grouped")
+    _call("erc_gemm_x3_grouped", A, lda, B, ldb, Cmat, pitch, node_off, n_dlg, n_mod, n_nodes, max_rows, K, split_k, c_slab)
 
 
 def gemm_bf16a_stream(X, ldx, gather, W, ldw, Cm, ldc, M, N, K, bias=None, act=0):
-    _dev(X, W, Cm)
-    _check(lib().erc_gemm_bf16a_stream(ptr(X), ldx, ptr(gather), ptr(W), ldw, int(W.dtype == torch.bfloat16), ptr(Cm), ldc,
-                                       M, N, K, ptr(bias), act, stream()), "erc_gemm_bf16a_stream")
+    _call("erc_gemm_bf16a_stream", X, ldx, gather, W, ldw, int(W.dtype == torch.bfloat16), Cm, ldc, M, N, K, bias, act)
 
 
 def slab_reduce(slabs, S, stride, bias, n_cols, act, out, numel, ld_out=0):
-    _check(lib().erc_slab_reduce(ptr(slabs), S, stride, ptr(bias), n_cols, act, ptr(out), ld_out, numel, stream()),
-           "erc_slab_reduce")
+    _call("erc_slab_reduce", slabs, S, stride, bias, n_cols, act, out, ld_out, numel)
 
 
 def slab_reduce_batched(ws, dst, jobs, n_jobs, max_numel):
-    _check(lib().erc_slab_reduce_batched(ptr(ws), ptr(dst), ptr(jobs), n_jobs, max_numel, stream()),
-           "erc_slab_reduce_batched")
+    _call("erc_slab_reduce_batched", ws, dst, jobs, n_jobs, max_numel)
 
 
 def rgcn_mean_fwd(x, ldx, F, R, N, g, Mout, ldm, inv_cnt):
-    _check(lib().erc_rgcn_mean_fwd(ptr(x), ldx, F, R, N, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]),
-                                   ptr(Mout), ldm, ptr(inv_cnt), stream()), "erc_rgcn_mean_fwd")
+    _call("erc_rgcn_mean_fwd", x, ldx, F, R, N, g["in_ptr"], g["in_src"], g["in_typ"], Mout, ldm, inv_cnt)
 
 
 def rgcn_mean_bwd(dM, ldm, F, R, N, g, inv_cnt, dx, lddx):
-    _check(lib().erc_rgcn_mean_bwd(ptr(dM), ldm, F, R, N, ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_typ"]),
-                                   ptr(inv_cnt), ptr(dx), lddx, stream()), "erc_rgcn_mean_bwd")
+    _call("erc_rgcn_mean_bwd", dM, ldm, F, R, N, g["out_ptr"], g["out_dst"], g["out_typ"], inv_cnt, dx, lddx)
 
 
 def tconv_attn_fwd(qkvs, ld, F, N, scale, g, out, ldo, alpha):
-    _check(lib().erc_tconv_attn_fwd(ptr(qkvs), ld, F, N, scale, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(out), ldo,
-                                    ptr(alpha), stream()), "erc_tconv_attn_fwd")
+    _call("erc_tconv_attn_fwd", qkvs, ld, F, N, scale, g["in_ptr"], g["in_src"], out, ldo, alpha)
 
 
 def tconv_attn_bwd(qkvs, ld, F, N, scale, g, alpha, dout, lddo, dqkvs, dscore, bn=None):
     """``bn`` = (x, ldx, gamma, saved, bn_bwd, dout_store): ``dout`` is then dY of the BatchNorm behind the layer and the
     layer's own output gradient is derived inside the target pass (and stored in ``dout_store``)."""
     if bn is None:
-        bn_args, dsrc = (None, 0, None, None, None, None), dout
+        bn, dsrc = (None, 0, None, None, None, None), dout
     else:
-        x, ldx, gamma, saved, bn_bwd, dsrc = bn
-        bn_args = (ptr(x), ldx, ptr(gamma), ptr(saved), ptr(bn_bwd), ptr(dsrc))
-    _check(lib().erc_tconv_attn_bwd_target(ptr(qkvs), ld, F, N, scale, ptr(g["in_ptr"]), ptr(g["in_src"]),
-                                           ptr(alpha), ptr(dout), lddo, ptr(dqkvs), ptr(dscore), *bn_args, stream()),
-           "erc_tconv_attn_bwd_target")
-    _check(lib().erc_tconv_attn_bwd_source(ptr(qkvs), ld, F, N, ptr(g["out_ptr"]), ptr(g["out_dst"]),
-                                           ptr(g["out_eid"]), ptr(alpha), ptr(dscore), ptr(dsrc), lddo, ptr(dqkvs),
-                                           stream()), "erc_tconv_attn_bwd_source")
+        dsrc = bn[5]
+    _call("erc_tconv_attn_bwd_target", qkvs, ld, F, N, scale, g["in_ptr"], g["in_src"], alpha, dout, lddo, dqkvs, dscore, *bn)
+    _call("erc_tconv_attn_bwd_source", qkvs, ld, F, N, g["out_ptr"], g["out_dst"], g["out_eid"], alpha, dscore, dsrc, lddo, dqkvs)
 
 
 def bn_ws_floats(F):
@@ -387,26 +240,21 @@ def bn_ws_floats(F):
 
 
 def bn_lrelu_fwd(x, ldx, N, F, gamma, beta, rmean, rvar, momentum, eps, slope, training, saved, y, ldy, ws):
-    _check(lib().erc_bn_lrelu_fwd(ptr(x), ldx, N, F, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), momentum, eps,
-                                  slope, int(training), ptr(saved), ptr(y), ldy, ptr(ws), stream()),
-           "erc_bn_lrelu_fwd")
+    _call("erc_bn_lrelu_fwd", x, ldx, N, F, gamma, beta, rmean, rvar, momentum, eps, slope, int(training), saved, y, ldy, ws)
 
 
 def bn_lrelu_bwd(x, ldx, N, F, gamma, beta, saved, slope, dy, lddy, dx, lddx, dgamma, dbeta, ws):
-    _check(lib().erc_bn_lrelu_bwd(ptr(x), ldx, N, F, ptr(gamma), ptr(beta), ptr(saved), slope, ptr(dy), lddy,
-                                  ptr(dx), lddx, ptr(dgamma), ptr(dbeta), ptr(ws), stream()), "erc_bn_lrelu_bwd")
+    _call("erc_bn_lrelu_bwd", x, ldx, N, F, gamma, beta, saved, slope, dy, lddy, dx, lddx, dgamma, dbeta, ws)
 
 
 def cross_entropy(logits, ld, Cn, n_rows, row_map, labels, weight, grad_scale, dlogits, lddl, stats):
-    _check(lib().erc_cross_entropy(ptr(logits), ld, Cn, n_rows, ptr(row_map), ptr(labels), ptr(weight), grad_scale,
-                                   ptr(dlogits), lddl, ptr(stats), stream()), "erc_cross_entropy")
+    _call("erc_cross_entropy", logits, ld, Cn, n_rows, row_map, labels, weight, grad_scale, dlogits, lddl, stats)
 
 
 def adam_step(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, grad_scale, clip_norm, gnorm, state, shadow=None,
               shadow_off=0, shadow_n=0, skip_flag=None):
-    _check(lib().erc_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), n, lr, b1, b2, eps, wd, int(decoupled), grad_scale,
-                               clip_norm, ptr(gnorm), ptr(state), ptr(shadow), shadow_off, shadow_n, ptr(skip_flag),
-                               stream()), "erc_adam_step")
+    _call("erc_adam_step", p, g, m, v, n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, clip_norm, gnorm, state, shadow,
+          shadow_off, shadow_n, skip_flag)
 
 
 class ShadowTable:
@@ -459,6 +307,11 @@ class ShadowTable:
         return C.addressof(self._packed)
 
 
+def _shadow(table):
+    """(shadow_base, shadow_numel, tab_host) arguments of a ShadowTable, or of none"""
+    return (None, 0, None) if table is None else (table.buf, table.buf.numel(), table.tab_ptr)
+
+
 def mfma_b_fragment_order(W, n_kblocks):
     """Reference packing of a logical B operand W [n][k] (torch tensor) into ErcShadowTab mode 1 order (tests)."""
     n, k = W.shape
@@ -470,9 +323,8 @@ def mfma_b_fragment_order(W, n_kblocks):
 
 
 def adam_step_tab(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, grad_scale, clip_norm, gnorm, state, table, skip_flag=None):
-    _check(lib().erc_adam_step_tab(ptr(p), ptr(g), ptr(m), ptr(v), n, lr, b1, b2, eps, wd, int(decoupled), grad_scale,
-                                   clip_norm, ptr(gnorm), ptr(state), ptr(table.buf), table.buf.numel(), table.tab_ptr, ptr(skip_flag),
-                                   stream()), "erc_adam_step_tab")
+    _call("erc_adam_step_tab", p, g, m, v, n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, clip_norm, gnorm, state,
+          *_shadow(table), skip_flag)
 
 
 class ErcP2P(C.Structure):
@@ -485,45 +337,44 @@ class ErcP2P(C.Structure):
 def p2p_alloc(nbytes):
     """(device pointer, 64-byte IPC handle) of a zero-filled buffer other processes can map"""
     out, handle = C.c_void_p(), C.create_string_buffer(64)
-    _check(lib().erc_p2p_alloc(nbytes, C.addressof(out), C.addressof(handle)), "erc_p2p_alloc")
+    _call("erc_p2p_alloc", nbytes, C.addressof(out), C.addressof(handle))
     return out.value, handle.raw
 
 
 def p2p_open(handle):
     out = C.c_void_p()
-    _check(lib().erc_p2p_open(C.c_char_p(handle), C.addressof(out)), "erc_p2p_open")
+    _call("erc_p2p_open", C.c_char_p(handle), C.addressof(out))
     return out.value
 
 
 def p2p_close(ptr_):
-    _check(lib().erc_p2p_close(C.c_void_p(ptr_)), "erc_p2p_close")
+    _call("erc_p2p_close", C.c_void_p(ptr_))
 
 
 def p2p_free(ptr_):
-    _check(lib().erc_p2p_free(C.c_void_p(ptr_)), "erc_p2p_free")
+    _call("erc_p2p_free", C.c_void_p(ptr_))
 
 
 def adam_step_p2p(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, grad_scale, state, table, x):
     """x: ErcP2P.  table: ShadowTable or None."""
-    _check(lib().erc_adam_step_p2p(ptr(p), ptr(g), ptr(m), ptr(v), n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, ptr(state),
-                                   ptr(table.buf) if table is not None else None, table.buf.numel() if table is not None else 0,
-                                   table.tab_ptr if table is not None else None, C.addressof(x), stream()), "erc_adam_step_p2p")
+    _call("erc_adam_step_p2p", p, g, m, v, n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, state, *_shadow(table),
+          C.addressof(x))
 
 
 def health_roll(health, events):
     """start of a step: a health word still raised becomes one event, the word is cleared (ercgraft.h)"""
-    _check(lib().erc_health_roll(ptr(health), ptr(events), stream()), "erc_health_roll")
+    _call("erc_health_roll", health, events)
 
 
 HEALTH_RAISED = 0x3f800000
 
 
 def gcnii_chain_set_spin_limit(limit):
-    _check(lib().erc_gcnii_chain_set_spin_limit(int(limit)), "erc_gcnii_chain_set_spin_limit")
+    _call("erc_gcnii_chain_set_spin_limit", int(limit))
 
 
 def shadow_refresh(p, n, table):
-    _check(lib().erc_shadow_refresh(ptr(p), n, ptr(table.buf), table.buf.numel(), table.tab_ptr, stream()), "erc_shadow_refresh")
+    _call("erc_shadow_refresh", p, n, *_shadow(table))
 
 
 def cogmen_project_graph_ok(K, n_out, B, ldx, ldw):
@@ -535,37 +386,29 @@ def cogmen_project_graph(x, ldx, W, ldw, bias, H0, ldh0, n_out, K, lengths, spea
     """input projection + window graph in one launch (csrc/cogmen_project.hip); g: the graph dict of window_graph_build.
     desc (int32 [2 B]: lengths | first store rows): resident mode -- x / speakers are a store's [U, ldx] / [U] arrays.
     terms = 2 | 3: split compute mode -- x fp32, W = that many bf16 term planes ``w_plane`` elements apart"""
-    _dev(x)
     sb, st = (0, speakers.stride(0)) if desc is not None else (speakers.stride(0), speakers.stride(1))
     if terms > 1:
         if x.dtype != torch.float32:
             raise ErcGraftError("cogmen_project_graph: split modes take the fp32 feature block")
-        _check(lib().erc_cogmen_project_graph_x(terms, ptr(x), ldx, ptr(W), w_plane, ldw, ptr(bias), ptr(H0), ldh0, n_out, K,
-                                                ptr(lengths), ptr(speakers), sb, st, B, T, wp, wf, n_speakers, n_cap, e_cap,
-                                                ptr(g["node_off"]), ptr(g["node_row"]), ptr(g["node_spk"]), ptr(g["in_ptr"]),
-                                                ptr(g["in_src"]), ptr(g["in_typ"]), ptr(g["out_ptr"]), ptr(g["out_dst"]),
-                                                ptr(g["out_typ"]), ptr(g["out_eid"]), ptr(g["counts"]), ptr(desc), stream()),
-               "erc_cogmen_project_graph_x")
+        _call("erc_cogmen_project_graph_x", terms, x, ldx, W, w_plane, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, sb, st,
+              B, T, wp, wf, n_speakers, n_cap, e_cap, g["node_off"], g["node_row"], g["node_spk"], g["in_ptr"], g["in_src"],
+              g["in_typ"], g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], g["counts"], desc)
         return
-    _check(lib().erc_cogmen_project_graph(ptr(x), ldx, ptr(W), ldw, ptr(bias), ptr(H0), ldh0, n_out, K, ptr(lengths),
-                                          ptr(speakers), sb, st, B, T, wp, wf, n_speakers,
-                                          n_cap, e_cap, ptr(g["node_off"]), ptr(g["node_row"]), ptr(g["node_spk"]),
-                                          ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]), ptr(g["out_ptr"]),
-                                          ptr(g["out_dst"]), ptr(g["out_typ"]), ptr(g["out_eid"]), ptr(g["counts"]), ptr(desc),
-                                          stream()),
-           "erc_cogmen_project_graph")
+    _call("erc_cogmen_project_graph", x, ldx, W, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, sb, st, B, T, wp, wf,
+          n_speakers, n_cap, e_cap, g["node_off"], g["node_row"], g["node_spk"], g["in_ptr"], g["in_src"], g["in_typ"],
+          g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], g["counts"], desc)
 
 
 def cogmen_set_stamps(t):
-    _check(lib().erc_cogmen_set_stamps(ptr(t)), "erc_cogmen_set_stamps")
+    _call("erc_cogmen_set_stamps", t)
 
 
 def lstm_set_stamps(t):
-    _check(lib().erc_lstm_set_stamps(ptr(t)), "erc_lstm_set_stamps")
+    _call("erc_lstm_set_stamps", t)
 
 
 def head_set_stamps(t):
-    _check(lib().erc_head_set_stamps(ptr(t)), "erc_head_set_stamps")
+    _call("erc_head_set_stamps", t)
 
 
 def cogmen_fwd_tile_ws_doubles(n):
@@ -577,19 +420,13 @@ def cogmen_fwd_tile(H0, ldh0, N, wp, wf, g, WcatT, b1, Wq, bq, scale, Mb, ldmb, 
                     n_speakers=2, n_dev=None, health=None, events=None, terms=1, catT_plane=0, q_plane=0):
     """terms = 2 | 3: split compute mode -- WcatT / Wq are term planes, Mb / H1b the FP32 operand buffers (erc_cogmen_fwd_tile_x)"""
     if terms > 1:
-        _check(lib().erc_cogmen_fwd_tile_x(terms, ptr(H0), ldh0, N, wp, wf, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]),
-                                           ptr(WcatT), catT_plane, ptr(b1), ptr(Wq), q_plane, ptr(bq), scale, ptr(Mb), ldmb,
-                                           ptr(inv_cnt), ptr(H1b), ldh1b, ptr(QKVS), ptr(H2), ldh2, ptr(alpha), int(bn_fused),
-                                           ptr(running_mean), ptr(running_var), momentum, eps, ptr(saved), ptr(bn_ws),
-                                           ptr(g["node_spk"]), n_speakers, ptr(n_dev), ptr(health), ptr(events), stream()),
-               "erc_cogmen_fwd_tile_x")
+        _call("erc_cogmen_fwd_tile_x", terms, H0, ldh0, N, wp, wf, g["in_ptr"], g["in_src"], g["in_typ"], WcatT, catT_plane, b1,
+              Wq, q_plane, bq, scale, Mb, ldmb, inv_cnt, H1b, ldh1b, QKVS, H2, ldh2, alpha, int(bn_fused), running_mean,
+              running_var, momentum, eps, saved, bn_ws, g["node_spk"], n_speakers, n_dev, health, events)
         return
-    _check(lib().erc_cogmen_fwd_tile(ptr(H0), ldh0, N, wp, wf, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]),
-                                     ptr(WcatT), ptr(b1), ptr(Wq), ptr(bq), scale, ptr(Mb), ldmb, ptr(inv_cnt), ptr(H1b),
-                                     ldh1b, ptr(QKVS), ptr(H2), ldh2, ptr(alpha), int(bn_fused), ptr(running_mean),
-                                     ptr(running_var), momentum, eps, ptr(saved), ptr(bn_ws), ptr(g["node_spk"]), n_speakers,
-                                     ptr(n_dev), ptr(health), ptr(events), stream()),
-           "erc_cogmen_fwd_tile")
+    _call("erc_cogmen_fwd_tile", H0, ldh0, N, wp, wf, g["in_ptr"], g["in_src"], g["in_typ"], WcatT, b1, Wq, bq, scale, Mb, ldmb,
+          inv_cnt, H1b, ldh1b, QKVS, H2, ldh2, alpha, int(bn_fused), running_mean, running_var, momentum, eps, saved, bn_ws,
+          g["node_spk"], n_speakers, n_dev, health, events)
 
 
 def cogmen_bwd_tile(dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, g, inv_cnt, WqT, Wb, scale, dQKVS, dH1,
@@ -597,60 +434,53 @@ def cogmen_bwd_tile(dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, 
                     lddh1=100, n_dev=None, terms=1, qT_plane=0, wb_plane=0):
     """terms = 2 | 3: split compute mode -- WqT / Wb are term planes, the gradients fp32 (erc_cogmen_bwd_tile_x)"""
     if terms > 1:
-        _check(lib().erc_cogmen_bwd_tile_x(terms, ptr(dY), ptr(H2), ldh2, N, wp, wf, ptr(gamma), ptr(saved), ptr(bn_bwd), ptr(QKVS),
-                                           ptr(alpha), ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["out_ptr"]), ptr(g["out_dst"]),
-                                           ptr(g["out_typ"]), ptr(g["out_eid"]), ptr(inv_cnt), ptr(WqT), qT_plane, ptr(Wb), wb_plane,
-                                           scale, ptr(dQKVS), ptr(dH1), ptr(dH0), lddh0, ptr(g["node_spk"]), n_speakers,
-                                           ptr(head_part), head_parts, head_fused_part_floats() if head_part is not None else 0,
-                                           ptr(dgamma), ptr(dbeta), ptr(stats), lddh1, ptr(n_dev), stream()), "erc_cogmen_bwd_tile_x")
+        _call("erc_cogmen_bwd_tile_x", terms, dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, g["in_ptr"],
+              g["in_src"], g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], inv_cnt, WqT, qT_plane, Wb, wb_plane, scale,
+              dQKVS, dH1, dH0, lddh0, g["node_spk"], n_speakers, head_part, head_parts,
+              head_fused_part_floats() if head_part is not None else 0, dgamma, dbeta, stats, lddh1, n_dev)
         return
-    _check(lib().erc_cogmen_bwd_tile(ptr(dY), ptr(H2), ldh2, N, wp, wf, ptr(gamma), ptr(saved), ptr(bn_bwd), ptr(QKVS),
-                                     ptr(alpha), ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["out_ptr"]), ptr(g["out_dst"]),
-                                     ptr(g["out_typ"]), ptr(g["out_eid"]), ptr(inv_cnt), ptr(WqT), ptr(Wb), scale,
-                                     ptr(dQKVS), ptr(dH1), ptr(dH0), lddh0, ptr(g["node_spk"]), n_speakers, ptr(head_part),
-                                     head_parts, head_fused_part_floats() if head_part is not None else 0, ptr(dgamma),
-                                     ptr(dbeta), ptr(stats), int(grads_bf16), lddh1, ptr(n_dev), stream()), "erc_cogmen_bwd_tile")
+    _call("erc_cogmen_bwd_tile", dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, g["in_ptr"], g["in_src"],
+          g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], inv_cnt, WqT, Wb, scale, dQKVS, dH1, dH0, lddh0, g["node_spk"],
+          n_speakers, head_part, head_parts, head_fused_part_floats() if head_part is not None else 0, dgamma, dbeta, stats,
+          int(grads_bf16), lddh1, n_dev)
 
 
 def grad_norm(g, n, grad_scale, gnorm, ws):
-    _check(lib().erc_grad_norm(ptr(g), n, grad_scale, ptr(gnorm), ptr(ws), stream()), "erc_grad_norm")
+    _call("erc_grad_norm", g, n, grad_scale, gnorm, ws)
 
 
 def gcnii_chain_prep(W, w_stride, lamda, alpha, VT, V, U, UT=None):
-    _check(lib().erc_gcnii_chain_prep(ptr(W), w_stride, lamda, alpha, ptr(VT), ptr(V), ptr(U), ptr(UT), stream()), "erc_gcnii_chain_prep")
+    _call("erc_gcnii_chain_prep", W, w_stride, lamda, alpha, VT, V, U, UT)
 
 
 def gcnii_chain_config(B, T, Mo, P):
     out = (C.c_int * 3)()
-    _check(lib().erc_gcnii_chain_config(B, T, Mo, P, C.addressof(out), C.addressof(out) + 4, C.addressof(out) + 8),
-           "erc_gcnii_chain_config")
+    _call("erc_gcnii_chain_config", B, T, Mo, P, C.addressof(out), C.addressof(out) + 4, C.addressof(out) + 8)
     return int(out[0]), int(out[1]), int(out[2])
 
 
 def gcnii_chain_fwd(ADJ, P, CR, node_off, N, Mo, B, T, cfg, VT, Call, ldc, HD, hd_plane, ZS, lds, ZX, state, drop_p, rng,
                     rng_stream0, health=None):
-    _check(lib().erc_gcnii_chain_fwd(ptr(ADJ), P, ptr(CR), ptr(node_off), N, Mo, B, T, cfg[0], cfg[1], cfg[2], ptr(VT), ptr(Call),
-                                     ldc, ptr(HD), hd_plane, ptr(ZS), lds, ptr(ZX), ptr(state), ptr(health), drop_p, ptr(rng), rng_stream0,
-                                     stream()), "erc_gcnii_chain_fwd")
+    _call("erc_gcnii_chain_fwd", ADJ, P, CR, node_off, N, Mo, B, T, cfg[0], cfg[1], cfg[2], VT, Call, ldc, HD, hd_plane, ZS, lds,
+          ZX, state, health, drop_p, rng, rng_stream0)
 
 
 def gcnii_chain_bwd(ADJ, P, CR, node_off, N, Mo, B, T, cfg, V, HD, hd_plane, dHin, dHout, DG, DZ, lds, ZX, state, drop_p,
                     health=None):
-    _check(lib().erc_gcnii_chain_bwd(ptr(ADJ), P, ptr(CR), ptr(node_off), N, Mo, B, T, cfg[0], cfg[1], cfg[2], ptr(V), ptr(HD),
-                                     hd_plane, ptr(dHin), ptr(dHout), ptr(DG), ptr(DZ), lds, ptr(ZX), ptr(state), ptr(health), drop_p,
-                                     stream()), "erc_gcnii_chain_bwd")
+    _call("erc_gcnii_chain_bwd", ADJ, P, CR, node_off, N, Mo, B, T, cfg[0], cfg[1], cfg[2], V, HD, hd_plane, dHin, dHout, DG, DZ,
+          lds, ZX, state, health, drop_p)
 
 
 def dag_rec_config(direction, B, T, n_layers, epc_hint=0, dg_hint=0, lpl_hint=0):
     """cfg = (epc, dg, groups per launch, layers per launch) of the weight-stationary DAG-ERC recurrence (0 forward,
     1 backward) on the current device, as a ctypes int array the launch wrappers take."""
     cfg = (C.c_int * 4)()
-    _check(lib().erc_dag_rec_config(direction, B, T, n_layers, epc_hint, dg_hint, lpl_hint, C.addressof(cfg)), "erc_dag_rec_config")
+    _call("erc_dag_rec_config", direction, B, T, n_layers, epc_hint, dg_hint, lpl_hint, C.addressof(cfg))
     return cfg
 
 
 def dag_rec_set_stamps(t):
-    _check(lib().erc_dag_rec_set_stamps(ptr(t)), "erc_dag_rec_set_stamps")
+    _call("erc_dag_rec_set_stamps", t)
 
 
 def dag_rec_scratch_bytes(direction, B, T, cfg):
@@ -664,109 +494,90 @@ def ptr_table(tensors):
 
 def dag_rec_fwd(H0, ldh0, n_layers, tables, pred, spk, B, T, ldo, ldgi, cfg, state, scratch, health=None):
     """tables: dict of ptr_table()s -- Wh bh W_hh_c b_hh_c W_ih_p b_ih_p Wr w_k | H1 GI Mseq GH R ks alpha"""
-    _dev(H0)
     t = tables
-    _check(lib().erc_dag_rec_fwd(ptr(H0), ldh0, n_layers, C.addressof(t["Wh"]), C.addressof(t["bh"]), C.addressof(t["W_hh_c"]),
-                                 C.addressof(t["b_hh_c"]), C.addressof(t["W_ih_p"]), C.addressof(t["b_ih_p"]),
-                                 C.addressof(t["Wr"]), C.addressof(t["w_k"]), ptr(pred), ptr(spk), B, T,
-                                 C.addressof(t["H1"]), ldo, C.addressof(t["GI"]), ldgi, C.addressof(t["Mseq"]),
-                                 C.addressof(t["GH"]), C.addressof(t["R"]), C.addressof(t["ks"]), C.addressof(t["alpha"]),
-                                 C.addressof(cfg), ptr(state), ptr(health), ptr(scratch), stream()), "erc_dag_rec_fwd")
+    _call("erc_dag_rec_fwd", H0, ldh0, n_layers, C.addressof(t["Wh"]), C.addressof(t["bh"]), C.addressof(t["W_hh_c"]),
+          C.addressof(t["b_hh_c"]), C.addressof(t["W_ih_p"]), C.addressof(t["b_ih_p"]), C.addressof(t["Wr"]),
+          C.addressof(t["w_k"]), pred, spk, B, T, C.addressof(t["H1"]), ldo, C.addressof(t["GI"]), ldgi, C.addressof(t["Mseq"]),
+          C.addressof(t["GH"]), C.addressof(t["R"]), C.addressof(t["ks"]), C.addressof(t["alpha"]), C.addressof(cfg), state,
+          health, scratch)
 
 
 def dag_rec_bwd(n_layers, tables, ldh, ldgi, pred, spk, B, T, dHall, ldd, lddgi, cfg, state, scratch, health=None):
     """tables: ptr_table()s -- Hl GI GH Mseq R alpha Wh W_hh_c W_ih_p Wr w_k | DGI DGH dM dks"""
-    _dev(dHall)
     t = tables
-    _check(lib().erc_dag_rec_bwd(n_layers, C.addressof(t["Hl"]), ldh, C.addressof(t["GI"]), ldgi, C.addressof(t["GH"]),
-                                 C.addressof(t["Mseq"]), C.addressof(t["R"]), C.addressof(t["alpha"]), C.addressof(t["Wh"]),
-                                 C.addressof(t["W_hh_c"]), C.addressof(t["W_ih_p"]), C.addressof(t["Wr"]),
-                                 C.addressof(t["w_k"]), ptr(pred), ptr(spk), B, T, ptr(dHall), ldd, C.addressof(t["DGI"]),
-                                 lddgi, C.addressof(t["DGH"]), C.addressof(t["dM"]), C.addressof(t["dks"]),
-                                 C.addressof(cfg), ptr(state), ptr(health), ptr(scratch), stream()), "erc_dag_rec_bwd")
+    _call("erc_dag_rec_bwd", n_layers, C.addressof(t["Hl"]), ldh, C.addressof(t["GI"]), ldgi, C.addressof(t["GH"]),
+          C.addressof(t["Mseq"]), C.addressof(t["R"]), C.addressof(t["alpha"]), C.addressof(t["Wh"]), C.addressof(t["W_hh_c"]),
+          C.addressof(t["W_ih_p"]), C.addressof(t["Wr"]), C.addressof(t["w_k"]), pred, spk, B, T, dHall, ldd,
+          C.addressof(t["DGI"]), lddgi, C.addressof(t["DGH"]), C.addressof(t["dM"]), C.addressof(t["dks"]), C.addressof(cfg),
+          state, health, scratch)
 
 
 def dag_attn_sums(alpha, H1, ldo, pred, spk, B, T, A):
-    _check(lib().erc_dag_attn_sums(ptr(alpha), ptr(H1), ldo, ptr(pred), ptr(spk), B, T, ptr(A), stream()), "erc_dag_attn_sums")
+    _call("erc_dag_attn_sums", alpha, H1, ldo, pred, spk, B, T, A)
 
 
 def dag_meta(speaker_onehot, speaker_ids, sb, st, S, lengths, B, T, spk, pred, node_off, node_row):
-    _check(lib().erc_dag_meta(ptr(speaker_onehot), ptr(speaker_ids), sb, st, S, ptr(lengths), B, T, ptr(spk),
-                              ptr(pred), ptr(node_off), ptr(node_row), stream()), "erc_dag_meta")
+    _call("erc_dag_meta", speaker_onehot, speaker_ids, sb, st, S, lengths, B, T, spk, pred, node_off, node_row)
 
 
 def lstm_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
                   rng_stream, gates, Cst, Hprev):
-    _check(lib().erc_lstm_scan_fwd(ptr(GX), ldgx, ptr(W_hh), ptr(b_hh), ptr(lengths), ptr(node_off), sb, st, B, T,
-                                   ptr(Hout), ldh, ptr(Hdrop), ldhd, drop_p, ptr(rng), rng_stream, ptr(gates),
-                                   ptr(Cst), ptr(Hprev), stream()), "erc_lstm_scan_fwd")
+    _call("erc_lstm_scan_fwd", GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
+          rng_stream, gates, Cst, Hprev)
 
 
 def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX):
-    _check(lib().erc_lstm_scan_bwd(ptr(W_hh), ptr(lengths), ptr(node_off), sb, st, B, T, ptr(gates), ptr(Cst),
-                                   ptr(dHout), lddh, drop_p, ptr(rng), rng_stream, ptr(dGX), stream()),
-           "erc_lstm_scan_bwd")
+    _call("erc_lstm_scan_bwd", W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
 
 
 def gather_rows(src, lds, map_, N, F, dst, ldd, scatter=0):
-    _check(lib().erc_gather_rows(ptr(src), lds, ptr(map_), N, F, ptr(dst), ldd, scatter, stream()), "erc_gather_rows")
+    _call("erc_gather_rows", src, lds, map_, N, F, dst, ldd, scatter)
 
 
 def edge_att_fwd(x, ldx, att, lda, F, N, g, norm):
-    _check(lib().erc_edge_att_fwd(ptr(x), ldx, ptr(att), lda, F, N, ptr(g["out_ptr"]), ptr(g["out_dst"]),
-                                  ptr(g["out_eid"]), ptr(norm), stream()), "erc_edge_att_fwd")
+    _call("erc_edge_att_fwd", x, ldx, att, lda, F, N, g["out_ptr"], g["out_dst"], g["out_eid"], norm)
 
 
 def edge_att_bwd(x, ldx, att, lda, F, N, g, norm, dnorm, dx, lddx, accumulate_dx, datt, ldda, dscore, dn_parts=1, dn_stride=0):
     """dn_parts > 1: dnorm holds that many partial vectors, dn_stride floats apart (erc_brgcn_bwd_edges_tile's slabs)"""
-    _check(lib().erc_edge_att_bwd_parts(ptr(x), ldx, ptr(att), lda, F, N, ptr(g["in_ptr"]), ptr(g["in_src"]),
-                                        ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_eid"]), ptr(norm), ptr(dnorm),
-                                        dn_parts, dn_stride, ptr(dx), lddx, accumulate_dx, ptr(datt), ldda, ptr(dscore),
-                                        stream()), "erc_edge_att_bwd_parts")
+    _call("erc_edge_att_bwd_parts", x, ldx, att, lda, F, N, g["in_ptr"], g["in_src"], g["out_ptr"], g["out_dst"], g["out_eid"],
+          norm, dnorm, dn_parts, dn_stride, dx, lddx, accumulate_dx, datt, ldda, dscore)
 
 
 def edge_att_bwd_fused(x, ldx, att, lda, F, N, g, norm, dnorm, dx, lddx, accumulate_dx, datt, ldda, dscore, dn_parts=1, dn_stride=0,
                        dx_slabs=None, n_dx_slabs=0, dx_slab_stride=0, rs_TT=None, rs_datt=None, rs_R=0):
     """edge_att_bwd + (dx_slabs) the slab sum of erc_brgcn_bwd_source_tile into dx + (rs_TT) the relation sums d att of
     erc_brgcn_bwd_edges_tile(datt=None), all inside the source-side launch"""
-    _check(lib().erc_edge_att_bwd_fused(ptr(x), ldx, ptr(att), lda, F, N, ptr(g["in_ptr"]), ptr(g["in_src"]),
-                                        ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_eid"]), ptr(norm), ptr(dnorm),
-                                        dn_parts, dn_stride, ptr(dx), lddx, accumulate_dx, ptr(datt), ldda, ptr(dscore),
-                                        ptr(dx_slabs), n_dx_slabs, int(dx_slab_stride), ptr(rs_TT), ptr(g["in_typ"]),
-                                        ptr(g["counts"]), ptr(rs_datt), rs_R, stream()), "erc_edge_att_bwd_fused")
+    _call("erc_edge_att_bwd_fused", x, ldx, att, lda, F, N, g["in_ptr"], g["in_src"], g["out_ptr"], g["out_dst"], g["out_eid"],
+          norm, dnorm, dn_parts, dn_stride, dx, lddx, accumulate_dx, datt, ldda, dscore, dx_slabs, n_dx_slabs,
+          int(dx_slab_stride), rs_TT, g["in_typ"], g["counts"], rs_datt, rs_R)
 
 
 def brgcn_agg_fwd(x, ldx, F, N, g, norm, att, nb, Z):
-    _check(lib().erc_brgcn_agg_fwd(ptr(x), ldx, F, N, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]), ptr(norm),
-                                   ptr(att), nb, ptr(Z), stream()), "erc_brgcn_agg_fwd")
+    _call("erc_brgcn_agg_fwd", x, ldx, F, N, g["in_ptr"], g["in_src"], g["in_typ"], norm, att, nb, Z)
 
 
 def brgcn_bwd_edges(x, ldx, F, N, R, g, norm, att, nb, dZ, dnorm, TT, datt):
-    _check(lib().erc_brgcn_bwd_edges(ptr(x), ldx, F, N, R, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]),
-                                     ptr(g["counts"]), ptr(norm), ptr(att), nb, ptr(dZ), ptr(dnorm), ptr(TT),
-                                     ptr(datt), stream()), "erc_brgcn_bwd_edges")
+    _call("erc_brgcn_bwd_edges", x, ldx, F, N, R, g["in_ptr"], g["in_src"], g["in_typ"], g["counts"], norm, att, nb, dZ, dnorm,
+          TT, datt)
 
 
 def brgcn_bwd_source(dH, lddh, O, N, g, norm, att, nb, U):
-    _check(lib().erc_brgcn_bwd_source(ptr(dH), lddh, O, N, ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_typ"]),
-                                      ptr(g["out_eid"]), ptr(norm), ptr(att), nb, ptr(U), stream()),
-           "erc_brgcn_bwd_source")
+    _call("erc_brgcn_bwd_source", dH, lddh, O, N, g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], norm, att, nb, U)
 
 
 def brgcn_set_stamps(t):
-    _check(lib().erc_brgcn_set_stamps(ptr(t)), "erc_brgcn_set_stamps")
+    _call("erc_brgcn_set_stamps", t)
 
 
 def brgcn_bwd_source_tile(dH, lddh, F, O, N, g, norm, att, nb, basis, root, slabs):
-    _check(lib().erc_brgcn_bwd_source_tile(ptr(dH), lddh, F, O, N, ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_typ"]),
-                                           ptr(g["out_eid"]), ptr(norm), ptr(att), nb, ptr(basis), ptr(root), ptr(slabs),
-                                           stream()), "erc_brgcn_bwd_source_tile")
+    _call("erc_brgcn_bwd_source_tile", dH, lddh, F, O, N, g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], norm, att, nb,
+          basis, root, slabs)
 
 
 def brgcn_bwd_edges_tile(x, ldx, F, O, N, R, g, norm, att, nb, basis, dH, lddh, TT, dn_slabs, dn_stride, datt):
-    _check(lib().erc_brgcn_bwd_edges_tile(ptr(x), ldx, F, O, N, R, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]),
-                                          ptr(g["counts"]), ptr(norm), ptr(att), nb, ptr(basis), ptr(dH), lddh, ptr(TT),
-                                          ptr(dn_slabs), dn_stride, ptr(datt), stream()), "erc_brgcn_bwd_edges_tile")
+    _call("erc_brgcn_bwd_edges_tile", x, ldx, F, O, N, R, g["in_ptr"], g["in_src"], g["in_typ"], g["counts"], norm, att, nb,
+          basis, dH, lddh, TT, dn_slabs, dn_stride, datt)
 
 
 def brgcn_fwd_tile_slabs():
@@ -778,8 +589,7 @@ def brgcn_fwd_tile_slab_floats(n):
 
 
 def brgcn_fwd_tile(x, ldx, F, O, N, g, norm, att, nb, basis, root, Z, slabs):
-    _check(lib().erc_brgcn_fwd_tile(ptr(x), ldx, F, O, N, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]), ptr(norm),
-                                    ptr(att), nb, ptr(basis), ptr(root), ptr(Z), ptr(slabs), stream()), "erc_brgcn_fwd_tile")
+    _call("erc_brgcn_fwd_tile", x, ldx, F, O, N, g["in_ptr"], g["in_src"], g["in_typ"], norm, att, nb, basis, root, Z, slabs)
 
 
 def rrgcn_max_relations():
@@ -787,61 +597,50 @@ def rrgcn_max_relations():
 
 
 def basis_compose(comp, basis, R, nb, F, O, Wr, WrT):
-    _check(lib().erc_basis_compose(ptr(comp), ptr(basis), R, nb, F, O, ptr(Wr), ptr(WrT), stream()), "erc_basis_compose")
+    _call("erc_basis_compose", comp, basis, R, nb, F, O, Wr, WrT)
 
 
 def basis_decompose(comp, basis, dWr, R, nb, FO, dbasis, dcomp):
-    _check(lib().erc_basis_decompose(ptr(comp), ptr(basis), ptr(dWr), R, nb, FO, ptr(dbasis), ptr(dcomp), stream()),
-           "erc_basis_decompose")
+    _call("erc_basis_decompose", comp, basis, dWr, R, nb, FO, dbasis, dcomp)
 
 
 def rrgcn_agg_fwd(x, ldx, F, N, R, g, norm, Z):
-    _check(lib().erc_rrgcn_agg_fwd(ptr(x), ldx, F, N, R, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]), ptr(norm),
-                                   ptr(Z), stream()), "erc_rrgcn_agg_fwd")
+    _call("erc_rrgcn_agg_fwd", x, ldx, F, N, R, g["in_ptr"], g["in_src"], g["in_typ"], norm, Z)
 
 
 def rrgcn_bwd_edges(x, ldx, F, N, R, g, dZ, dnorm):
-    _check(lib().erc_rrgcn_bwd_edges(ptr(x), ldx, F, N, R, ptr(g["in_ptr"]), ptr(g["in_src"]), ptr(g["in_typ"]), ptr(dZ),
-                                     ptr(dnorm), stream()), "erc_rrgcn_bwd_edges")
+    _call("erc_rrgcn_bwd_edges", x, ldx, F, N, R, g["in_ptr"], g["in_src"], g["in_typ"], dZ, dnorm)
 
 
 def rrgcn_bwd_source(dH, lddh, O, N, R, g, norm, U):
-    _check(lib().erc_rrgcn_bwd_source(ptr(dH), lddh, O, N, R, ptr(g["out_ptr"]), ptr(g["out_dst"]), ptr(g["out_typ"]),
-                                      ptr(g["out_eid"]), ptr(norm), ptr(U), stream()), "erc_rrgcn_bwd_source")
+    _call("erc_rrgcn_bwd_source", dH, lddh, O, N, R, g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], norm, U)
 
 
 def transpose_batched(inp, nb, rows, cols, out):
-    _check(lib().erc_transpose_batched(ptr(inp), nb, rows, cols, ptr(out), stream()), "erc_transpose_batched")
+    _call("erc_transpose_batched", inp, nb, rows, cols, out)
 
 
 def csr_sum(x, ldx, F, N, ptr_, idx, out, ldo, accumulate=0):
-    _check(lib().erc_csr_sum(ptr(x), ldx, F, N, ptr(ptr_), ptr(idx), ptr(out), ldo, accumulate, stream()),
-           "erc_csr_sum")
+    _call("erc_csr_sum", x, ldx, F, N, ptr_, idx, out, ldo, accumulate)
 
 
 def gemm_grouped(form, A, lda, B, ldb, Cm, ldc, n_or_k, node_off, n_dlg, n_mod, n_nodes, max_len, pitch, accumulate=0,
                  act=0, aux=None, ldaux=0, act_scale=1.0, cross=None, planes=1, a_plane=0, b_plane=0, split=1, c_slab=0):
-    _check(lib().erc_gemm_f32_grouped(form, ptr(A), lda, ptr(B), ldb, ptr(Cm), ldc, n_or_k, ptr(node_off), n_dlg, n_mod,
-                                      n_nodes, max_len, pitch, accumulate, act, ptr(aux), ldaux, act_scale, ptr(cross),
-                                      planes, a_plane, b_plane, split, c_slab, stream()),
-           "erc_gemm_f32_grouped")
+    _call("erc_gemm_f32_grouped", form, A, lda, B, ldb, Cm, ldc, n_or_k, node_off, n_dlg, n_mod, n_nodes, max_len, pitch,
+          accumulate, act, aux, ldaux, act_scale, cross, planes, a_plane, b_plane, split, c_slab)
 
 
 def gemm_f32_planes(A, lda, a_plane, B, ldb, b_plane, Cm, ldc, M, N, K, planes, split_k=1, c_slab=0, accumulate=0):
     _call("erc_gemm_f32_planes", A, lda, a_plane, B, ldb, b_plane, Cm, ldc, M, N, K, planes, split_k, c_slab, accumulate)
 
 
-def _call(name, *args):
-    _check(getattr(lib(), name)(*[ptr(a) if torch.is_tensor(a) or a is None else a for a in args], stream()), name)
-
-
 def gcnii_chain_set_stamps(stamps):
-    _check(lib().erc_gcnii_chain_set_stamps(ptr(stamps)), "erc_gcnii_chain_set_stamps")
+    _call("erc_gcnii_chain_set_stamps", stamps)
 
 
 def poison_lds():
     """Test support: NaN bit patterns into the LDS of every CU (see include/ercgraft.h)."""
-    _check(lib().erc_test_poison_lds(None, stream()), "erc_test_poison_lds")
+    _call("erc_test_poison_lds", None)
 
 
 def mm_meta(lengths, qmask, q_st, q_sb, S, B, node_off, node_row, node_dlg, node_spk):
@@ -918,14 +717,12 @@ def clock_probe(out, iters):
 
 def wgrad_table_x3(table, n_desc, item_base, n_items, slabs, counters):
     """erc_wgrad_table with the three-term bf16 split for records of mode 2"""
-    _check(lib().erc_wgrad_table_x3(ptr(table), n_desc, item_base, n_items, ptr(slabs), ptr(counters), stream()),
-           "erc_wgrad_table_x3")
+    _call("erc_wgrad_table_x3", table, n_desc, item_base, n_items, slabs, counters)
 
 
 def wgrad_table(table, n_desc, item_base, n_items, slabs, counters):
     """item_base: ctypes int32 array (host) with the first work item of every descriptor."""
-    _check(lib().erc_wgrad_table(ptr(table), n_desc, item_base, n_items, ptr(slabs), ptr(counters), stream()),
-           "erc_wgrad_table")
+    _call("erc_wgrad_table", table, n_desc, item_base, n_items, slabs, counters)
 
 
 def bn_batch_stats_ws_floats(F):
@@ -1038,43 +835,36 @@ def wgrad_bf16(table, n_desc, item_base, n_items, slabs, counters, terms=1):
     """item_base: ctypes int32 array (host) of the descriptors' first work items (csrc/wgrad_bf16.hip); terms = 2 | 3: the
     records' operands are fp32, expanded into that many bf16 terms in registers (erc_wgrad_split)"""
     if terms > 1:
-        _check(lib().erc_wgrad_split(terms, ptr(table), n_desc, item_base, n_items, ptr(slabs), ptr(counters), stream()), "erc_wgrad_split")
+        _call("erc_wgrad_split", terms, table, n_desc, item_base, n_items, slabs, counters)
         return
-    _check(lib().erc_wgrad_bf16(ptr(table), n_desc, item_base, n_items, ptr(slabs), ptr(counters), stream()), "erc_wgrad_bf16")
+    _call("erc_wgrad_bf16", table, n_desc, item_base, n_items, slabs, counters)
 
 
 def wgrad_bf16_adam(table, n_desc, item_base, n_items, slabs, counters, n_tiles, p, g, m, v, n, lr, b1, b2, eps, wd, decoupled,
                     grad_scale, state, shadow_table, health, terms=1, p2p_desc=None):
     """erc_wgrad_bf16 (terms > 1: erc_wgrad_split) with the optimizer fused in (ercgraft.h); p2p_desc (an ErcP2P): data
     parallel with the gradient exchange inside the launch (erc_wgrad_adam_p2p; health = the descriptor's health word)"""
-    st = shadow_table
+    args = (table, n_desc, item_base, n_items, slabs, counters, int(n_tiles), p, g, m, v, n, lr, b1, b2, eps, wd, int(decoupled),
+            grad_scale, state) + _shadow(shadow_table)
     if p2p_desc is not None:
-        _check(lib().erc_wgrad_adam_p2p(terms, ptr(table), n_desc, item_base, n_items, ptr(slabs), ptr(counters), int(n_tiles), ptr(p),
-                                        ptr(g), ptr(m), ptr(v), n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, ptr(state),
-                                        ptr(st.buf) if st is not None else None, st.buf.numel() if st is not None else 0,
-                                        st.tab_ptr if st is not None else None, C.addressof(p2p_desc), stream()), "erc_wgrad_adam_p2p")
-        return
-    args = (ptr(table), n_desc, item_base, n_items, ptr(slabs), ptr(counters), int(n_tiles), ptr(p), ptr(g),
-            ptr(m), ptr(v), n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, ptr(state),
-            ptr(st.buf) if st is not None else None, st.buf.numel() if st is not None else 0,
-            st.tab_ptr if st is not None else None, ptr(health), stream())
-    if terms > 1:
-        _check(lib().erc_wgrad_split_adam(terms, *args), "erc_wgrad_split_adam")
+        _call("erc_wgrad_adam_p2p", terms, *args, C.addressof(p2p_desc))
+    elif terms > 1:
+        _call("erc_wgrad_split_adam", terms, *args, health)
     else:
-        _check(lib().erc_wgrad_bf16_adam(*args), "erc_wgrad_bf16_adam")
+        _call("erc_wgrad_bf16_adam", *args, health)
 
 
 def wgrad_bf16_wide(table, n_desc, wg_base, n_wgs, slabs, counters):
     """erc_wgrad_bf16 for large K: four neighbouring column tiles per workgroup (ercgraft.h)"""
-    _check(lib().erc_wgrad_bf16_wide(ptr(table), n_desc, wg_base, n_wgs, ptr(slabs), ptr(counters), stream()), "erc_wgrad_bf16_wide")
+    _call("erc_wgrad_bf16_wide", table, n_desc, wg_base, n_wgs, slabs, counters)
 
 
 def wgrad_bf16_set_spin_limit(limit):
-    _check(lib().erc_wgrad_bf16_set_spin_limit(int(limit)), "erc_wgrad_bf16_set_spin_limit")
+    _call("erc_wgrad_bf16_set_spin_limit", int(limit))
 
 
 def wgrad_bf16_set_stamps(t, item=0):
-    _check(lib().erc_wgrad_bf16_set_stamps(ptr(t), int(item)), "erc_wgrad_bf16_set_stamps")
+    _call("erc_wgrad_bf16_set_stamps", t, int(item))
 
 
 def wgrad_bf16_slab_floats():
@@ -1099,7 +889,7 @@ def dgcn_tail_limits():
 
 
 def dgcn_tail_set_stamps(stamps):
-    _check(lib().erc_dgcn_tail_set_stamps(ptr(stamps)), "erc_dgcn_tail_set_stamps")
+    _call("erc_dgcn_tail_set_stamps", stamps)
 
 
 def dgcn_tail_stats_floats(n_rows):
@@ -1125,18 +915,15 @@ def head_ce(Z, ldz, F, Cn, n_rows, W, bias, labels, weight, mask_scale, logits, 
 
 # --------------------------------------------------------------------------- CIM (csrc/gru.hip, csrc/cim_attn.hip)
 def cim_meta(lengths, B, T, n_cap, node_off, node_row):
-    _dev(lengths, node_off, node_row)
     _call("erc_cim_meta", lengths, B, T, n_cap, node_off, node_row)
 
 
 def gru_scan_fwd(GX, W_hhT, b_hh, lengths, node_off, B, T, rows, Hout, Hdrop, drop_p, rng, rng_stream, gates, ghn, Hprev):
-    _dev(GX, W_hhT, b_hh, lengths, node_off, Hout, gates, ghn, Hprev)
     _call("erc_gru_scan_fwd", GX, W_hhT, b_hh, lengths, node_off, B, T, rows, Hout, Hdrop, drop_p, rng, rng_stream, gates, ghn,
           Hprev)
 
 
 def gru_scan_bwd(W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH):
-    _dev(W_hh, lengths, node_off, gates, ghn, Hprev, dH, dGX, dGH)
     _call("erc_gru_scan_bwd", W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH)
 
 
@@ -1145,18 +932,15 @@ def cim_max_t():
 
 
 def cim_attn_fwd(merged, node_off, B, T, Pbuf):
-    _dev(merged, node_off, Pbuf)
     _call("erc_cim_attn_fwd", merged, node_off, B, T, Pbuf)
 
 
 def cim_attn_bwd(merged, dmerged, node_off, B, T, Pbuf, mask_scale):
-    _dev(merged, dmerged, node_off, Pbuf)
     _call("erc_cim_attn_bwd", merged, dmerged, node_off, B, T, Pbuf, mask_scale)
 
 
 def ce_bce_multitask(logits, ld, Cn, n_rows, labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats):
     """cross entropy on logits[:, :Cn] + 7-way BCE on logits[:, Cn:Cn+7] (ercgraft.h erc_ce_bce_multitask)"""
-    _dev(logits, labels, emo_label, dlogits, stats)
     if labels.dtype != torch.int64 or emo_label.dtype != torch.int64:
         raise ErcGraftError("ce_bce_multitask: label and emo_label must be int64")
     if labels.numel() < n_rows or emo_label.dim() != 2 or emo_label.shape[0] < n_rows or emo_label.shape[1] < 7 \
@@ -1173,26 +957,21 @@ def dgcnv2_max_t():
 
 
 def dgcnv2_meta(onehot, S, lengths, B, T, n_cap, spk, node_row):
-    _dev(onehot, lengths, spk, node_row)
     _call("erc_dgcnv2_meta", onehot, S, lengths, B, T, n_cap, spk, node_row)
 
 
 def dgcnv2_edge_att_fwd(S, ldS, g, B, T, wp, wf, norm):
-    _dev(S, norm)
     _call("erc_dgcnv2_edge_att_fwd", S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], norm)
 
 
 def dgcnv2_edge_att_bwd(S, ldS, g, B, T, wp, wf, dnorm, dS, dn_parts=1, dn_stride=0):
-    _dev(S, dnorm, dS)
     _call("erc_dgcnv2_edge_att_bwd", S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], dnorm,
           dn_parts, dn_stride, dS)
 
 
 def dgcnv2_nodal_fwd(E, lde, Q, ldq, node_off, B, T, A, lda, P, TH):
-    _dev(E, Q, node_off, A, P, TH)
     _call("erc_dgcnv2_nodal_fwd", E, lde, Q, ldq, node_off, B, T, A, lda, P, TH)
 
 
 def dgcnv2_nodal_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde):
-    _dev(E, Q, dA, node_off, P, TH, DZ, dQ, dE)
     _call("erc_dgcnv2_nodal_bwd", E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde)
