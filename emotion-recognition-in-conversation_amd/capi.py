@@ -171,10 +171,15 @@ def _call(name, *args):
 
 # --------------------------------------------------------------------------- wrappers
 def window_graph_build(lengths, speakers, spk_sb, spk_st, B, T, wp, wf, S, n_cap, e_cap, g, edge_index=None,
-                       edge_type=None):
-    _call("erc_window_graph_build", lengths, speakers, spk_sb, spk_st, B, T, wp, wf, S, n_cap, e_cap, g["node_off"],
-          g["node_row"], g["node_spk"], g["in_ptr"], g["in_src"], g["in_typ"], g["out_ptr"], g["out_dst"], g["out_typ"],
-          g["out_eid"], edge_index, edge_type, g["counts"])
+                       edge_type=None, desc=None):
+    """``desc`` (int32 [2 B]: lengths | first store rows, or None): resident batch, node_row gets store rows (ercgraft.h)"""
+    args = (lengths, speakers, spk_sb, spk_st, B, T, wp, wf, S, n_cap, e_cap, g["node_off"], g["node_row"], g["node_spk"],
+            g["in_ptr"], g["in_src"], g["in_typ"], g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], edge_index, edge_type,
+            g["counts"])
+    if desc is None:
+        _call("erc_window_graph_build", *args)
+    else:
+        _call("erc_window_graph_build_desc", *args, desc)
 
 
 def gemm_f32(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k=1, c_slab=0,
@@ -526,8 +531,13 @@ def lstm_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, l
           rng_stream, gates, Cst, Hprev)
 
 
-def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX):
-    _call("erc_lstm_scan_bwd", W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
+def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX, zero_to=0):
+    """``zero_to`` > 0 (compact rows): dGX rows [node_off[B], zero_to) are written 0 too (capacity mode)"""
+    args = (W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
+    if zero_to:
+        _call("erc_lstm_scan_bwd_cap", *args, zero_to)
+    else:
+        _call("erc_lstm_scan_bwd", *args)
 
 
 def gather_rows(src, lds, map_, N, F, dst, ldd, scatter=0):
@@ -897,11 +907,16 @@ def dgcn_tail_stats_floats(n_rows):
 
 
 def dgcn_tail(slabs, n_slabs, slab_stride, rgcn_bias, g, window, W_rel, b_rel, W_root, W1, b1, W2, b2, labels, weight, n_classes,
-              n_rows, drop_p, rng, Xc, ldx, Hc, AGG, Zc, logits, dlogits, dZc, dXc, lddx, dAGG, dHc, stats):
-    """DialogueGCN: RGCN slab sum .. GraphConv .. classifier .. cross entropy .. dXc, dAGG, dHc in one launch (include/ercgraft.h)"""
-    _call("erc_dgcn_tail", slabs, n_slabs, int(slab_stride), rgcn_bias, g["in_ptr"], g["in_src"], window, W_rel, b_rel, W_root, W1,
-          b1, W2, b2, labels, weight, n_classes, n_rows, float(drop_p), rng, Xc, ldx, Hc, AGG, Zc, logits, dlogits, dZc, dXc, lddx,
-          dAGG, dHc, stats)
+              n_rows, drop_p, rng, Xc, ldx, Hc, AGG, Zc, logits, dlogits, dZc, dXc, lddx, dAGG, dHc, stats, n_dev=None, label_rows=None):
+    """DialogueGCN: RGCN slab sum .. GraphConv .. classifier .. cross entropy .. dXc, dAGG, dHc in one launch (include/ercgraft.h).
+    ``n_dev`` (device int32, e.g. g["counts"]): capacity mode, n_rows is the capacity; ``label_rows``: resident label map."""
+    args = (slabs, n_slabs, int(slab_stride), rgcn_bias, g["in_ptr"], g["in_src"], window, W_rel, b_rel, W_root, W1, b1, W2, b2,
+            labels, weight, n_classes, n_rows, float(drop_p), rng, Xc, ldx, Hc, AGG, Zc, logits, dlogits, dZc, dXc, lddx, dAGG, dHc,
+            stats)
+    if n_dev is None and label_rows is None:
+        _call("erc_dgcn_tail", *args)
+    else:
+        _call("erc_dgcn_tail_cap", *args, n_dev, label_rows)
 
 
 def head_ce_stats_floats(n_rows):

@@ -44,6 +44,8 @@ struct TailP {
     float* logits; float* dlogits;                            // [N,C] out
     float* dZc; float* dXc; int lddx; float* dAGG; float* dHc;
     float* stats;                                             // [0] loss [1] hits [2] weight sum; [4] arrival; [8 + 2 g] partials
+    const int32_t* n_dev;                                     // capacity mode (or null): the true row count, N above is the capacity
+    const int32_t* label_rows;                                // resident mode (or null): row i's label is labels[label_rows[i]]
     uint64_t* stamps;                                         // diagnostic (erc_dgcn_tail_set_stamps): phase stamps of workgroup 0
 };
 uint64_t* g_tail_stamps = nullptr;
@@ -99,6 +101,82 @@ constexpr int TNTH = 64 * TNW;
 // measured 50 us for the launch with four wavefronts and loads issued per tile, against ~6 us of matrix-core time)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// CAP: the capacity-mode instance of the kernel (n_dev / label_rows may be set); the exact-shape instance compiles without them
+template <bool CAP>
+__device__ __forceinline__ int label_of(const TailP& p, int i) { return (int)p.labels[CAP && p.label_rows ? p.label_rows[i] : i]; }
+
+// the weight sum of the class-weighted mean over the n valid rows (every workgroup: n labels, no exchange); s_red is scratch.
+// ONE implementation for the workgroups that score rows and those past the batch: whichever arrives last writes the loss with
+// its own s_wsum, so the two must be bit-identical.  Its first barrier also orders the LDS writes in front of it; tid 0
+// writes s_wsum / s_invw after the last barrier (readers wait for a later one).
+template <bool CAP>
+__device__ __forceinline__ void weight_sum(const TailP& p, int n, int tid, double* s_red, double& s_wsum, float& s_invw) {
+    if (p.weight) {
+        double wacc = 0.0;
+        for (int i = tid; i < n; i += TNTH) wacc += (double)p.weight[label_of<CAP>(p, i)];
+        s_red[tid] = wacc;
+    }
+    lds_barrier();
+    TAIL_STAMP(2);
+    if (p.weight) {
+        for (int o = TNTH / 2; o > 0; o >>= 1) {
+            if (tid < o) s_red[tid] += s_red[tid + o];
+            lds_barrier();
+            TAIL_STAMP(3);
+        }
+        if (tid == 0) s_wsum = s_red[0], s_invw = (float)(1.0 / s_red[0]);
+    } else if (tid == 0) {
+        s_wsum = (double)n, s_invw = (float)(1.0 / (double)n);
+    }
+}
+
+// capacity mode: gradient rows [lo, hi) past the batch are written 0 (the weight-gradient products run over them)
+__device__ __forceinline__ void zero_grad_rows(const TailP& p, int lo, int hi, int tid) {
+    for (int x = tid; x < (hi - lo) * TX; x += TNTH) {
+        const int64_t row = lo + x / TX;
+        const int c = x % TX;
+        p.dXc[row * p.lddx + c] = 0.f;
+        if (c < TH) p.dZc[row * TH + c] = 0.f, p.dAGG[row * TH + c] = 0.f, p.dHc[row * TH + c] = 0.f;
+        if (c < p.C) p.dlogits[row * p.C + c] = 0.f;
+    }
+}
+
+// loss / accuracy: the last arriver combines the workgroups' parts in workgroup order
+__device__ __forceinline__ void tail_finish(const TailP& p, int ticket, int tid, double* s_red, const double& s_wsum, int& s_last) {
+    if (tid == 64 * (TNW - 1)) s_last = (ticket == (int)gridDim.x - 1);
+    __syncthreads();
+    if (s_last) {
+        __threadfence();
+        double l = 0.0, h = 0.0;
+        for (int g = tid; g < (int)gridDim.x; g += TNTH) {
+            l += (double)__hip_atomic_load(p.stats + 8 + 2 * g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            h += (double)__hip_atomic_load(p.stats + 9 + 2 * g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        s_red[tid] = l;
+        __syncthreads();
+        for (int o = TNTH / 2; o > 0; o >>= 1) {
+            if (tid < o) s_red[tid] += s_red[tid + o];
+            __syncthreads();
+        }
+        const double lsum = s_red[0];
+        __syncthreads();
+        s_red[tid] = h;
+        __syncthreads();
+        for (int o = TNTH / 2; o > 0; o >>= 1) {
+            if (tid < o) s_red[tid] += s_red[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            p.stats[0] = (float)(lsum / s_wsum);
+            p.stats[1] = (float)s_red[0];
+            p.stats[2] = (float)s_wsum;
+            *reinterpret_cast<int*>(p.stats + 4) = 0;
+        }
+    }
+}
+
+template <bool CAP>
 __global__ __launch_bounds__(TNTH) void dgcn_tail_kernel(const TailP p) {
     __shared__ __attribute__((aligned(16))) float sX[TR * PX];      // [features | graph_out | 0]
     __shared__ __attribute__((aligned(16))) float sHw[TW * PH];     // Hc of the window rows
@@ -118,9 +196,23 @@ __global__ __launch_bounds__(TNTH) void dgcn_tail_kernel(const TailP p) {
     __shared__ int s_last;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = p.N, C = p.C;
-    const int r0 = blockIdx.x * TR;
+    const int C = p.C, r0 = blockIdx.x * TR;
+    // capacity mode: the grid covers p.N rows, the batch the first *n_dev of them
+    const int N = CAP && p.n_dev ? __builtin_amdgcn_readfirstlane(min(max(p.n_dev[0], 0), p.N)) : p.N;
     TAIL_STAMP(0);
+    if (CAP && r0 >= N) {      // (uniform) a workgroup past the batch: zero gradient rows, no loss part, but it takes its ticket
+        zero_grad_rows(p, r0, min(r0 + TR, p.N), tid);
+        weight_sum<CAP>(p, N, tid, s_red, s_wsum, s_invw);
+        int ticket = -1;
+        if (tid == 64 * (TNW - 1)) {
+            __hip_atomic_store(p.stats + 8 + 2 * blockIdx.x, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(p.stats + 9 + 2 * blockIdx.x, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __threadfence();
+            ticket = atomicAdd(reinterpret_cast<int*>(p.stats + 4), 1);
+        }
+        tail_finish(p, ticket, tid, s_red, s_wsum, s_last);
+        return;
+    }
     const int w0 = max(0, r0 - THL), w1 = min(N, r0 + TR + THL);
     // the 16-column tile of the 100-wide products this wavefront owns (wavefront 7: none)
     const int n1 = 16 * wave + l15;
@@ -172,7 +264,7 @@ __global__ __launch_bounds__(TNTH) void dgcn_tail_kernel(const TailP p) {
     // cross entropy: wavefront w < 4 scores rows 4 (lane >> 4) + w
     const int ce_row = 4 * kq + min(wave, 3);
     const bool ce_rv = r0 + ce_row < N;
-    const int ce_y = (int)p.labels[min(r0 + ce_row, N - 1)];
+    const int ce_y = label_of<CAP>(p, min(r0 + ce_row, N - 1));
     lds_barrier();
     TAIL_STAMP(1);
     const int e_lo = sPtr[0], n_e = min(sPtr[min(TR, N - r0)] - e_lo, TR * PH);
@@ -216,24 +308,7 @@ __global__ __launch_bounds__(TNTH) void dgcn_tail_kernel(const TailP p) {
     }
     if (tid < n_e) sSrc[tid] = my_src;
     for (int x = tid + TNTH; x < n_e; x += TNTH) sSrc[x] = p.in_src[e_lo + x];
-    // the weight sum of the class-weighted mean (every workgroup: N labels, no exchange)
-    if (p.weight) {
-        double wacc = 0.0;
-        for (int i = tid; i < N; i += TNTH) wacc += (double)p.weight[p.labels[i]];
-        s_red[tid] = wacc;
-    }
-    lds_barrier();
-    TAIL_STAMP(2);
-    if (p.weight) {
-        for (int o = TNTH / 2; o > 0; o >>= 1) {
-            if (tid < o) s_red[tid] += s_red[tid + o];
-            lds_barrier();
-    TAIL_STAMP(3);
-        }
-        if (tid == 0) s_wsum = s_red[0], s_invw = (float)(1.0 / s_red[0]);
-    } else if (tid == 0) {
-        s_wsum = (double)N, s_invw = (float)(1.0 / (double)N);
-    }
+    weight_sum<CAP>(p, N, tid, s_red, s_wsum, s_invw);      // (its first barrier also orders the LDS writes above)
     // ---- AGG_i = sum over the in-edges' source rows (LDS only); the own Hc rows as an A tile
     for (int x = tid; x < TR * (TH / 4); x += TNTH) {
         const int i = x / (TH / 4), c4 = x % (TH / 4);
@@ -440,39 +515,9 @@ __global__ __launch_bounds__(TNTH) void dgcn_tail_kernel(const TailP p) {
         }
     }
 
+    if (CAP && p.n_dev && r0 + TR > N) zero_grad_rows(p, N, min(r0 + TR, p.N), tid);
     TAIL_STAMP(15);
-    // ---- loss / accuracy: the last arriver combines the workgroups' parts in workgroup order
-    if (tid == 64 * (TNW - 1)) s_last = (ticket == (int)gridDim.x - 1);
-    __syncthreads();
-    if (s_last) {
-        __threadfence();
-        double l = 0.0, h = 0.0;
-        for (int g = tid; g < (int)gridDim.x; g += TNTH) {
-            l += (double)__hip_atomic_load(p.stats + 8 + 2 * g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            h += (double)__hip_atomic_load(p.stats + 9 + 2 * g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        s_red[tid] = l;
-        __syncthreads();
-        for (int o = TNTH / 2; o > 0; o >>= 1) {
-            if (tid < o) s_red[tid] += s_red[tid + o];
-            __syncthreads();
-        }
-        const double lsum = s_red[0];
-        __syncthreads();
-        s_red[tid] = h;
-        __syncthreads();
-        for (int o = TNTH / 2; o > 0; o >>= 1) {
-            if (tid < o) s_red[tid] += s_red[tid + o];
-            __syncthreads();
-        }
-        if (tid == 0) {
-            p.stats[0] = (float)(lsum / s_wsum);
-            p.stats[1] = (float)s_red[0];
-            p.stats[2] = (float)s_wsum;
-            *reinterpret_cast<int*>(p.stats + 4) = 0;
-        }
-    }
+    tail_finish(p, ticket, tid, s_red, s_wsum, s_last);
 }
 
 inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
@@ -488,12 +533,13 @@ extern "C" int erc_dgcn_tail_max_rows(void) { return 8192; }
 extern "C" int erc_dgcn_tail_max_window(void) { return THL; }
 extern "C" int64_t erc_dgcn_tail_stats_floats(int n_rows) { return 16 + 2 * (int64_t)erc_cdiv(n_rows, TR); }
 
-extern "C" int erc_dgcn_tail(const float* slabs, int n_slabs, int64_t slab_stride, const float* rgcn_bias, const int32_t* in_ptr,
-                             const int32_t* in_src, int window, const float* W_rel, const float* b_rel, const float* W_root,
-                             const float* W1, const float* b1, const float* W2, const float* b2, const int64_t* labels,
-                             const float* weight, int n_classes, int n_rows, float drop_p, const uint64_t* rng, float* Xc, int ldx,
-                             float* Hc, float* AGG, float* Zc, float* logits, float* dlogits, float* dZc, float* dXc, int lddx,
-                             float* dAGG, float* dHc, float* stats, void* stream) {
+extern "C" int erc_dgcn_tail_cap(const float* slabs, int n_slabs, int64_t slab_stride, const float* rgcn_bias, const int32_t* in_ptr,
+                                 const int32_t* in_src, int window, const float* W_rel, const float* b_rel, const float* W_root,
+                                 const float* W1, const float* b1, const float* W2, const float* b2, const int64_t* labels,
+                                 const float* weight, int n_classes, int n_rows, float drop_p, const uint64_t* rng, float* Xc,
+                                 int ldx, float* Hc, float* AGG, float* Zc, float* logits, float* dlogits, float* dZc, float* dXc,
+                                 int lddx, float* dAGG, float* dHc, float* stats, const int32_t* n_dev, const int32_t* label_rows,
+                                 void* stream) {
     ERC_REQUIRE(slabs && rgcn_bias && in_ptr && in_src && W_rel && b_rel && W_root && W1 && b1 && W2 && b2 && labels && Xc && Hc &&
                     AGG && Zc && logits && dlogits && dZc && dXc && dAGG && dHc && stats, "dgcn_tail: null pointer");
     ERC_REQUIRE(n_rows > 0 && n_rows <= erc_dgcn_tail_max_rows() && n_classes > 0 && n_classes <= TMAXC && n_slabs >= 1,
@@ -509,7 +555,22 @@ extern "C" int erc_dgcn_tail(const float* slabs, int n_slabs, int64_t slab_strid
     p.W_rel = W_rel; p.b_rel = b_rel; p.W_root = W_root; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.labels = labels; p.weight = weight;
     p.rng = rng; p.drop_p = drop_p; p.N = n_rows; p.C = n_classes; p.Xc = Xc; p.ldx = ldx; p.Hc = Hc; p.AGG = AGG; p.Zc = Zc;
     p.logits = logits; p.dlogits = dlogits; p.dZc = dZc; p.dXc = dXc; p.lddx = lddx; p.dAGG = dAGG; p.dHc = dHc; p.stats = stats; p.stamps = g_tail_stamps;
-    hipLaunchKernelGGL(dgcn_tail_kernel, dim3(erc_cdiv(n_rows, TR)), dim3(TNTH), 0, (hipStream_t)stream, p);
+    p.n_dev = n_dev; p.label_rows = label_rows;
+    if (n_dev || label_rows)
+        hipLaunchKernelGGL(dgcn_tail_kernel<true>, dim3(erc_cdiv(n_rows, TR)), dim3(TNTH), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(dgcn_tail_kernel<false>, dim3(erc_cdiv(n_rows, TR)), dim3(TNTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("dgcn_tail");
     return ERC_OK;
+}
+
+extern "C" int erc_dgcn_tail(const float* slabs, int n_slabs, int64_t slab_stride, const float* rgcn_bias, const int32_t* in_ptr,
+                             const int32_t* in_src, int window, const float* W_rel, const float* b_rel, const float* W_root,
+                             const float* W1, const float* b1, const float* W2, const float* b2, const int64_t* labels,
+                             const float* weight, int n_classes, int n_rows, float drop_p, const uint64_t* rng, float* Xc, int ldx,
+                             float* Hc, float* AGG, float* Zc, float* logits, float* dlogits, float* dZc, float* dXc, int lddx,
+                             float* dAGG, float* dHc, float* stats, void* stream) {
+    return erc_dgcn_tail_cap(slabs, n_slabs, slab_stride, rgcn_bias, in_ptr, in_src, window, W_rel, b_rel, W_root, W1, b1, W2, b2,
+                             labels, weight, n_classes, n_rows, drop_p, rng, Xc, ldx, Hc, AGG, Zc, logits, dlogits, dZc, dXc, lddx,
+                             dAGG, dHc, stats, nullptr, nullptr, stream);
 }

@@ -12,6 +12,7 @@ namespace {
 
 __device__ __forceinline__ int window_prefix(int p, int L, int back, int fwd) { return erc_window_prefix(p, L, back, fwd); }
 
+template <bool DESC>     // resident mode (desc != NULL); the padded-batch instance compiles without it
 __global__ __launch_bounds__(256) void window_graph_kernel(
     const int64_t* __restrict__ lengths, const int64_t* __restrict__ speakers, int64_t spk_sb, int64_t spk_st,
     int B, int T, int wp, int wf, int S, int n_cap, int e_cap,
@@ -19,20 +20,23 @@ __global__ __launch_bounds__(256) void window_graph_kernel(
     int32_t* __restrict__ in_ptr, int32_t* __restrict__ in_src, int32_t* __restrict__ in_typ,
     int32_t* __restrict__ out_ptr, int32_t* __restrict__ out_dst, int32_t* __restrict__ out_typ,
     int32_t* __restrict__ out_eid, int64_t* __restrict__ edge_index, int64_t* __restrict__ edge_type,
-    int32_t* __restrict__ counts) {
+    int32_t* __restrict__ counts, const int32_t* __restrict__ desc) {
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
     __shared__ int red_n[4];
     __shared__ int red_e[4];
     extern __shared__ int s_spk[];  // speakers of this dialogue (T entries): one global round trip instead of one per edge
 
-    const int64_t* spk = speakers + (int64_t)b * spk_sb;
-    const int L = (int)lengths[b];
+    // desc (resident mode): slot b holds desc[b] utterances from store row desc[B + b] on (lengths clamped to [0, T])
+    auto len_of = [&](int i) { return DESC ? min(max(desc[i], 0), T) : (int)lengths[i]; };
+    const int64_t base = DESC ? (int64_t)desc[B + b] : (int64_t)b * T;
+    const int64_t* spk = speakers + (DESC ? base * spk_st : (int64_t)b * spk_sb);
+    const int L = len_of(b);
     for (int p = tid; p < min(L, T); p += 256) s_spk[p] = (int)spk[(int64_t)p * spk_st];
     // exclusive prefix of node / edge counts over the dialogues before b
     int acc_n = 0, acc_e = 0;
     for (int i = tid; i < b; i += 256) {
-        int Li = (int)lengths[i];
+        int Li = len_of(i);
         acc_n += Li;
         acc_e += window_prefix(Li, Li, wf, wp);
     }
@@ -56,12 +60,23 @@ __global__ __launch_bounds__(256) void window_graph_kernel(
             }
         }
     }
+    if (b == B - 1 && noff + L <= n_cap) {
+        // capacity rows [N, n_cap): empty CSR ranges and row 0 of the block / store, so that launches sized for n_cap read
+        // nothing past the batch and add nothing for them (no rows when n_cap == N)
+        const int N = noff + L, E = eoff + E_b;
+        for (int n = N + tid; n < n_cap; n += 256) {
+            in_ptr[n + 1] = E;
+            out_ptr[n + 1] = E;
+            node_row[n] = 0;
+            node_spk[n] = 0;
+        }
+    }
     if (noff + L > n_cap || eoff + E_b > e_cap || L > T) return;  // capacity guard (host checks counts)
 
     for (int p = tid; p < L; p += 256) {
         const int n = noff + p;
         const int sp = s_spk[p];
-        node_row[n] = b * T + p;
+        node_row[n] = (int32_t)(base + p);
         node_spk[n] = sp;
 
         // in-edges of target k = p: sources j in [p-wf, p+wp]
@@ -122,23 +137,37 @@ extern "C" int erc_test_poison_lds(int32_t* sink, void* stream) {
     return ERC_OK;
 }
 
-extern "C" int erc_window_graph_build(const int64_t* lengths, const int64_t* speakers, int64_t spk_sb, int64_t spk_st,
-                                      int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
-                                      int32_t* node_off, int32_t* node_row, int32_t* node_spk,
-                                      int32_t* in_ptr, int32_t* in_src, int32_t* in_typ,
-                                      int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
-                                      int64_t* edge_index, int64_t* edge_type, int32_t* counts, void* stream) {
+extern "C" int erc_window_graph_build_desc(const int64_t* lengths, const int64_t* speakers, int64_t spk_sb, int64_t spk_st,
+                                           int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
+                                           int32_t* node_off, int32_t* node_row, int32_t* node_spk,
+                                           int32_t* in_ptr, int32_t* in_src, int32_t* in_typ,
+                                           int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
+                                           int64_t* edge_index, int64_t* edge_type, int32_t* counts, const int32_t* desc,
+                                           void* stream) {
     ERC_REQUIRE(B > 0 && T > 0 && n_speakers > 0, "window_graph_build: bad sizes B=%d T=%d S=%d", B, T, n_speakers);
-    ERC_REQUIRE(lengths && speakers && node_off && node_row && node_spk && in_ptr && in_src && in_typ && out_ptr &&
+    ERC_REQUIRE((lengths || desc) && speakers && node_off && node_row && node_spk && in_ptr && in_src && in_typ && out_ptr &&
                     out_dst && out_typ && out_eid && counts,
                 "window_graph_build: null pointer");
     ERC_REQUIRE(wp >= -1 && wf >= -1, "window_graph_build: window must be >= -1");
     if (wp < 0) wp = T;  // -1 = unbounded past   (cogmen_utils.py:158-163)
     if (wf < 0) wf = T;  // -1 = unbounded future
     ERC_REQUIRE(T <= 12288, "window_graph_build: T=%d exceeds the LDS speaker stage", T);
-    hipLaunchKernelGGL(window_graph_kernel, dim3(B), dim3(256), (size_t)T * sizeof(int), (hipStream_t)stream, lengths, speakers, spk_sb,
+    hipLaunchKernelGGL(desc ? window_graph_kernel<true> : window_graph_kernel<false>, dim3(B), dim3(256), (size_t)T * sizeof(int),
+                       (hipStream_t)stream, lengths, speakers, spk_sb,
                        spk_st, B, T, wp, wf, n_speakers, n_cap, e_cap, node_off, node_row, node_spk, in_ptr, in_src,
-                       in_typ, out_ptr, out_dst, out_typ, out_eid, edge_index, edge_type, counts);
+                       in_typ, out_ptr, out_dst, out_typ, out_eid, edge_index, edge_type, counts, desc);
     ERC_LAUNCH_CHECK("window_graph_build");
     return ERC_OK;
+}
+
+extern "C" int erc_window_graph_build(const int64_t* lengths, const int64_t* speakers, int64_t spk_sb, int64_t spk_st,
+                                      int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
+                                      int32_t* node_off, int32_t* node_row, int32_t* node_spk,
+                                      int32_t* in_ptr, int32_t* in_src, int32_t* in_typ,
+                                      int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
+                                      int64_t* edge_index, int64_t* edge_type, int32_t* counts, void* stream) {
+    ERC_REQUIRE(lengths, "window_graph_build: null lengths");
+    return erc_window_graph_build_desc(lengths, speakers, spk_sb, spk_st, B, T, wp, wf, n_speakers, n_cap, e_cap, node_off, node_row,
+                                       node_spk, in_ptr, in_src, in_typ, out_ptr, out_dst, out_typ, out_eid, edge_index, edge_type,
+                                       counts, nullptr, stream);
 }

@@ -20,7 +20,7 @@ struct LstmP {
     const float* GX; int ldgx;           // hoisted pre-activations, direction d at columns [400d, 400d+400)
     const float* W_hh;                   // [2][400,100]  (forward, reverse)
     const float* b_hh;                   // [2][400]
-    const int64_t* lengths;              // [B] or null (= T for every dialogue: unpacked run)
+    const int64_t* lengths;              // [B] or null: T for every dialogue (unpacked run), or node_off[b+1] - node_off[b] with compact rows
     const int32_t* node_off;             // null: row(b,t) = b*sb + t*st ; else compact rows node_off[b] + t
     int64_t sb, st;
     int B, T;
@@ -34,6 +34,7 @@ struct LstmP {
     // backward only
     const float* dHout; int lddh;        // gradient wrt Hout (or wrt Hdrop when drop_p > 0)
     float* dGX;                          // [rows,800] gradient wrt the gate pre-activations (0 on padded rows)
+    int zero_to;                         // compact rows: rows [node_off[B], zero_to) of dGX are written 0 (capacity rows)
     unsigned long long* stamps;          // diagnostic (erc_lstm_set_stamps): shader-clock stamps of one step of workgroup (0,0)
 };
 unsigned long long* g_lstm_stamps = nullptr;
@@ -53,6 +54,9 @@ struct RowMap {
 };
 __device__ __forceinline__ RowMap rows_of(const LstmP& p, int b) {
     return p.node_off ? RowMap{(int64_t)p.node_off[b], 1} : RowMap{(int64_t)b * p.sb, p.st};
+}
+__device__ __forceinline__ int length_of(const LstmP& p, int b) {
+    return p.lengths ? (int)p.lengths[b] : p.node_off ? p.node_off[b + 1] - p.node_off[b] : p.T;
 }
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -93,7 +97,7 @@ __device__ __forceinline__ float dpp_mov(float v) {
 // others -- h_{t-1} forward, the gate gradients backward -- double-buffered, so a step has ONE barrier.
 __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
-    const int L = p.lengths ? (int)p.lengths[b] : p.T;
+    const int L = length_of(p, b);
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_h[2][HP];
     const int u = tid >> 2, q = tid & 3;
@@ -247,9 +251,10 @@ __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
         }
 }
 
+template <bool ZERO_ROWS>     // capacity mode (zero_to > 0); the other instance compiles without it
 __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
-    const int L = p.lengths ? (int)p.lengths[b] : p.T;
+    const int L = length_of(p, b);
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_dp[2][DPP_];     // gate gradients of the step, entry q*H + j chunked
     const int u = tid >> 2, q = tid & 3;
@@ -385,6 +390,9 @@ __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
         }
     }
     if (L > 0) store_chunk(L - 1 - (L - 1) / SC * SC);
+    if (ZERO_ROWS && p.node_off)      // capacity rows past the batch: the weight-gradient products run over them
+        for (int64_t row = (int64_t)p.node_off[p.B] + b; row < p.zero_to; row += p.B)
+            if (tid < G4) p.dGX[row * 2 * G4 + d * G4 + tid] = 0.f;
     if (!p.node_off)
         for (int t = L; t < p.T; ++t) {
             const int64_t row = rmap(t);
@@ -417,18 +425,30 @@ extern "C" int erc_lstm_scan_fwd(const float* GX, int ldgx, const float* W_hh, c
     return ERC_OK;
 }
 
-extern "C" int erc_lstm_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb,
-                                 int64_t st, int B, int T, const float* gates, const float* Cst, const float* dHout,
-                                 int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX,
-                                 void* stream) {
+extern "C" int erc_lstm_scan_bwd_cap(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb,
+                                     int64_t st, int B, int T, const float* gates, const float* Cst, const float* dHout,
+                                     int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX,
+                                     int zero_to, void* stream) {
     ERC_REQUIRE(W_hh && gates && Cst && dHout && dGX, "lstm_scan_bwd: null pointer");
     ERC_REQUIRE(B > 0 && T > 0, "lstm_scan_bwd: bad sizes B=%d T=%d", B, T);
+    ERC_REQUIRE(zero_to <= 0 || node_off, "lstm_scan_bwd: zero_to needs compact rows (node_off)");
     ERC_REQUIRE(drop_p <= 0.f || rng_state, "lstm_scan_bwd: dropout needs rng_state");
     LstmP p{};
     p.W_hh = W_hh; p.lengths = lengths; p.node_off = node_off; p.sb = sb; p.st = st; p.B = B; p.T = T;
     p.gates = const_cast<float*>(gates); p.Cst = const_cast<float*>(Cst); p.dHout = dHout; p.lddh = lddh;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX;
-    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.zero_to = zero_to;
+    if (zero_to > 0)
+        hipLaunchKernelGGL(lstm_bwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(lstm_bwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("lstm_scan_bwd");
     return ERC_OK;
+}
+
+extern "C" int erc_lstm_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb,
+                                 int64_t st, int B, int T, const float* gates, const float* Cst, const float* dHout,
+                                 int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX,
+                                 void* stream) {
+    return erc_lstm_scan_bwd_cap(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng_state, rng_stream, dGX,
+                                 0, stream);
 }

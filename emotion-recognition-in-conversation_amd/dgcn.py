@@ -94,6 +94,13 @@ class DGCNModule(nn.Module):
         self.fused_tail = True
         # ... and the RGCN backward's slab sum into dXc + its relation sums (d att) inside EdgeAtt's backward launch
         self.fused_edge_bwd = True
+        # CAPACITY MODE (trainer.StepGraphs buckets, trainer.ResidentEpochs): the batch tensors are capacity-sized static
+        # buffers -- B dialogues of which some may have length 0, T the longest dialogue of the split, label [N_cap] -- and
+        # every launch is sized for the capacities.  The graph build writes the true node count to g["counts"][0]; rows
+        # [N, N_cap) get empty CSR ranges, the tail reads N there (loss over the N valid rows, gradient rows past them 0) and
+        # the LSTM backward zeroes its gate-gradient rows past them, so ONE captured HIP graph serves every batch that fits.
+        # Default basis-space path only (supports_capacity).
+        self.dynamic_n = False
         self.drop_p = float(dropout)
         self.rnn = _SeqContext(input_size, hidden_size, dropout)
         self.edge_att = _EdgeAtt(hidden_size)
@@ -159,6 +166,18 @@ class DGCNModule(nn.Module):
         """blocks of the RGCN aggregate Z: relations (relation space) or bases"""
         return self.R if self.relation_space else NB
 
+    def supports_capacity(self, batch=None):
+        """Can a training step run in capacity mode?  Needs the default fused path end to end: basis space, compact LSTM,
+        the RGCN tiles, the fused tail and the fused edge-attention backward."""
+        max_rows, max_win = capi.dgcn_tail_limits()
+        ok = bool(not self.relation_space and self.compact_lstm and self.fused_rgcn_fwd and self.fused_tail and
+                  self.fused_edge_bwd and self.n_classes <= 8 and 0 <= self.wp <= max_win and 0 <= self.wf <= max_win)
+        if ok and batch is not None:
+            x, spk = batch["input_tensor"], batch["speaker_tensor"]
+            ok = (x.dtype == (torch.bfloat16 if self.compute == "bf16" else torch.float32) and x.dim() == 3 and
+                  spk.dim() == 2 and not spk.is_floating_point())
+        return ok
+
     def _shape(self, x, lens, label, n_nodes=None):
         B, T = x.shape[0], x.shape[1]
         N = int(label.shape[0]) if label is not None else (int(n_nodes) if n_nodes is not None else int(lens.sum().item()))
@@ -168,15 +187,24 @@ class DGCNModule(nn.Module):
         max_rows, max_win = capi.dgcn_tail_limits()
         return self.fused_tail and self.n_classes <= 8 and N <= max_rows and 0 <= self.wp <= max_win and 0 <= self.wf <= max_win
 
-    def _forward_impl(self, x, spk, lens, B, T, N, training, with_logits=True, tail=False):
+    def _forward_impl(self, x, spk, lens, B, T, N, training, with_logits=True, tail=False, desc=None):
+        """``desc`` (int32 [2 B]: lengths | first store rows): RESIDENT batch -- x [U, D] / spk [U] are a feature store's
+        arrays, B / T / N are capacities (capacity mode is implied), no padded block exists."""
         fp = self.flat
+        if (self.dynamic_n or desc is not None) and not (self.dynamic_n and tail and self.supports_capacity()):
+            raise capi.ErcGraftError("DialogueGCN capacity mode needs the default fused training path (supports_capacity) "
+                                     "with N_cap <= %d" % capi.dgcn_tail_limits()[0])
         ws = self._workspace(B, T, N, x.device)
         g, pl = ws["g"], ws["planner"]
         pl.reset()
         D, C, BT, XW = self.input_size, self.n_classes, B * T, G_DIM + H1
         x_bf16 = x.dtype == torch.bfloat16
-        capi.window_graph_build(lens, spk, spk.stride(0), spk.stride(1), B, T, self.wp, self.wf, self.n_speakers, N,
-                                ws["E"], g)
+        if desc is not None:
+            capi.window_graph_build(None, spk, 0, spk.stride(0), B, T, self.wp, self.wf, self.n_speakers, N, ws["E"], g,
+                                    desc=desc)
+        else:
+            capi.window_graph_build(lens, spk, spk.stride(0), spk.stride(1), B, T, self.wp, self.wf, self.n_speakers, N,
+                                    ws["E"], g)
         Xc = ws["Xc"]
         if self.compact_lstm:
             # the BiLSTM on the N valid positions in node order (row = node_off[b] + t), written next to the graph output
@@ -242,15 +270,17 @@ class DGCNModule(nn.Module):
 
     def loss_and_grads(self, batch, class_weight=None):
         x, spk, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
-        B, T, N = self._shape(x, lens, ys)
+        desc = batch.get("desc")          # resident batch (trainer.ResidentEpochs): store arrays + 2 B int32 of batch description
+        B, T, N = batch["caps"] if desc is not None else self._shape(x, lens, ys)
         training = self.training
         fused_tail = self.n_classes <= 8
         tail = self._tail_ok(N)
-        ws = self._forward_impl(x, spk, lens, B, T, N, training, with_logits=not fused_tail, tail=tail)
+        ws = self._forward_impl(x, spk, lens, B, T, N, training, with_logits=not fused_tail, tail=tail, desc=desc)
         fp, g, pl, off = self.flat, ws["g"], ws["planner"], self.flat.offsets
         C, BT, XW = self.n_classes, B * T, G_DIM + H1
         Xc, dXc = ws["Xc"], ws["dXc"]
         p = self.drop_p if training else 0.0
+        nd = g["counts"] if self.dynamic_n else None      # capacity mode: N above is the capacity, the batch's count is here
         # classifier
         if tail:
             slabs, n_slabs, stride = ws["tail_src"]
@@ -258,7 +288,8 @@ class DGCNModule(nn.Module):
                            fp.w("gcn.conv2.lin_rel.weight"), fp.w("gcn.conv2.lin_rel.bias"), fp.w("gcn.conv2.lin_root.weight"),
                            fp.w("clf.lin1.weight"), fp.w("clf.lin1.bias"), fp.w("clf.lin2.weight"), fp.w("clf.lin2.bias"), ys,
                            class_weight, C, N, p, self.rng_state, Xc, XW, ws["Hc"], ws["AGG"], ws["Zc"], ws["logits"], ws["dlogits"],
-                           ws["dZc"], dXc, XW, ws["dAGG"], ws["dHc"], ws["stats"])
+                           ws["dZc"], dXc, XW, ws["dAGG"], ws["dHc"], ws["stats"], n_dev=nd,
+                           label_rows=g["node_row"] if desc is not None else None)
         elif fused_tail:
             # lin2 + cross entropy + their backward through the ReLU / dropout mask in one launch (dgcn_models.py:163-170)
             capi.head_ce(ws["Zc"], 100, 100, C, N, fp.w("clf.lin2.weight"), fp.w("clf.lin2.bias"), ys, class_weight,
@@ -337,7 +368,7 @@ class DGCNModule(nn.Module):
                 pl.flush_wgrads(ws, tag="_early")
         # back to the padded rows and through the BiLSTM
         if self.compact_lstm:
-            self.lstm.backward(pl, dXc, XW)
+            self.lstm.backward(pl, dXc, XW, zero_to=N if self.dynamic_n else 0)
         else:
             ws["drnn"].zero_()
             capi.gather_rows(dXc, XW, g["node_row"], N, G_DIM, ws["drnn"], G_DIM, scatter=1)
@@ -362,6 +393,12 @@ class DGCNTrainer:
         self.model = DGCNModule(input_size=params.hidden_all, hidden_size=200, n_speakers=params.n_speakers,
                                 n_classes=params.n_classes, compute=params.get("compute", "f32"),
                                 seed=params.seed).finalize(self.device)
+        rs = params.get("relation_space")      # DGCNParams.relation_space: None = the module's choice
+        if rs is not None:
+            if rs and self.model.R > capi.rrgcn_max_relations():
+                raise ValueError("--relation_space=True: %d relations, the relation-space kernels hold at most %d"
+                                 % (self.model.R, capi.rrgcn_max_relations()))
+            self.model.relation_space = bool(rs)
         o = params.optim
         self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
                                decoupled=(o.name == "AdamW"), seed=params.seed)
@@ -384,6 +421,84 @@ class DGCNTrainer:
         if self.model.compute == "bf16":
             out["input_tensor"] = out["input_tensor"].to(torch.bfloat16)
         return out
+
+    N_BUCKET = 128     # capacity buckets: node counts rounded up to a multiple of this (the launches scale with N_cap)
+
+    def _p2p(self):
+        """the opt-in peer-to-peer gradient exchange (ERC_DP_P2P=1): capacity buckets stay off there"""
+        import os
+        return getattr(self.model.flat, "p2p", None) is not None or os.environ.get("ERC_DP_P2P", "0") == "1"
+
+    def _capacity_ok(self, N_cap, batch=None):
+        return (self.model.supports_capacity(batch) and not self._p2p() and 0 < N_cap <= capi.dgcn_tail_limits()[0])
+
+    def _caps(self, batch):
+        B, T = batch["input_tensor"].shape[:2]
+        return max(B, int(self.params.train.batch_size)), max(T, int(getattr(self, "t_cap", 0)))
+
+    def _n_cap(self, N, B_cap, T_cap):
+        return min(-(-N // self.N_BUCKET) * self.N_BUCKET, B_cap * T_cap)
+
+    def _bucket(self, like, B_cap, T_cap, N_cap):
+        x, spk, dev, D = like["input_tensor"], like["speaker_tensor"], self.device, like["input_tensor"].shape[2]
+
+        def make():
+            return dict(input_tensor=torch.zeros(B_cap, T_cap, D, dtype=x.dtype, device=dev),
+                        speaker_tensor=torch.zeros(B_cap, T_cap, dtype=spk.dtype, device=dev),
+                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
+                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev))
+
+        def fill(static, b):
+            Bb, Tb = b["input_tensor"].shape[:2]
+            static["input_tensor"][:Bb, :Tb].copy_(b["input_tensor"], non_blocking=True)
+            static["speaker_tensor"][:Bb, :Tb].copy_(b["speaker_tensor"], non_blocking=True)
+            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
+            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
+            static["label"][:b["label"].shape[0]].copy_(b["label"], non_blocking=True)
+
+        return ("capacity", B_cap, T_cap, N_cap), make, fill
+
+    def capacity_bucket(self, batch):
+        """trainer.StepGraphs: (key, make_static, fill) of the capacity bucket that holds ``batch`` (a prepared device batch),
+        or None when the step cannot run in capacity mode (relation space or an unfused path, N_cap above the fused tail's
+        row limit, the peer-to-peer exchange): the exact-shape path runs then.  So does a batch that already has its
+        bucket's shape (B, T, N = B_cap, T_cap, N_cap): there is nothing to pad."""
+        B_cap, T_cap = self._caps(batch)
+        N = int(batch["label"].shape[0])
+        N_cap = self._n_cap(N, B_cap, T_cap)
+        if not self._capacity_ok(N_cap, batch) or tuple(batch["input_tensor"].shape[:2]) + (N, ) == (B_cap, T_cap, N_cap):
+            return None
+        return self._bucket(batch, B_cap, T_cap, N_cap)
+
+    def all_capacity_buckets(self, batch):
+        """Every bucket a batch of this loader can fall into, smallest first, each with a synthetic filler (all B_cap
+        dialogues present, lengths adding up to the capacity, each <= T_cap): data parallel runs capture all of them up front,
+        in the same order on every rank.  The list depends only on what every rank shares -- the module's path, B_cap =
+        train.batch_size, T_cap (trainer.bucket_t_cap) -- never on the probe batch's own N or shape."""
+        if not self._capacity_ok(self.N_BUCKET, batch):
+            return []
+        B_cap, T_cap = self._caps(batch)
+        top = min(B_cap * T_cap, capi.dgcn_tail_limits()[0])
+        out = []
+        for N_cap in sorted({min(n, top) for n in range(self.N_BUCKET, top + self.N_BUCKET, self.N_BUCKET)}):
+            key, make, fill = self._bucket(batch, B_cap, T_cap, N_cap)
+
+            def synth(static, n=N_cap):
+                lens = torch.full((B_cap, ), n // B_cap, dtype=torch.int64)
+                lens[:n - int(lens.sum())] += 1                        # lengths add up to n, each <= T_cap
+                static["text_length"].copy_(lens)
+            out.append((key, make, fill, synth))
+        return out
+
+    def resident_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
+        """trainer.ResidentEpochs: the "batch" of a step whose dialogues stay in the HBM-resident store -- the store's arrays,
+        the 2 B_cap int32 the host rewrites per step (lengths | first store rows of the batch's dialogue slots) and the
+        capacities the launches are sized for.  None when the step cannot run that way."""
+        want = torch.bfloat16 if self.model.compute == "bf16" else torch.float32
+        if store.fused.dtype != want or store.fused.shape[1] != self.model.input_size or not self._capacity_ok(N_cap):
+            return None
+        return dict(input_tensor=store.fused, speaker_tensor=store.speaker, text_length=None, label=store.label, desc=cur_desc,
+                    caps=(B_cap, T_cap, N_cap))
 
     def train_step(self, batch):
         self.model.train()

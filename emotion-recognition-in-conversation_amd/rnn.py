@@ -74,9 +74,10 @@ class BiLSTM2:
                            B, T, out, ldo, None, 0, 0.0, None, 0, ws["gates"][1], ws["Cst"][1], ws["Hprev"][1])
         self._last = (x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store)
 
-    def backward(self, pl, dout, lddo, dx=None, lddx=0):
+    def backward(self, pl, dout, lddo, dx=None, lddx=0, zero_to=0):
         """dout = gradient wrt the layer-1 output.  Registers all weight-gradient jobs; optionally writes
-        dx [rows, d_in] (needed when the LSTM input is itself trainable, MMGCN)."""
+        dx [rows, d_in] (needed when the LSTM input is itself trainable, MMGCN).  ``zero_to`` (compact rows, capacity mode):
+        the gate gradients of rows [node_off[B], zero_to) are written 0, so the weight gradients may run over all rows."""
         x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store = self._last
         ws = self._buf(rows, dout.device, store)
         # one gate-gradient buffer per layer: every weight gradient of the LSTM then joins the step's ONE batched
@@ -85,11 +86,11 @@ class BiLSTM2:
             dGX = ws["dGX"][k]
             if k == 1:
                 capi.lstm_scan_bwd(self._w("weight_hh_l1"), lengths, node_off, sb, st, B, T, ws["gates"][1], ws["Cst"][1],
-                                   dout, lddo, 0.0, None, 0, dGX)
+                                   dout, lddo, 0.0, None, 0, dGX, zero_to=zero_to)
                 xin, ldin, d_in, bf, gat = ws["H0d"], 2 * H, 2 * H, False, None
             else:
                 capi.lstm_scan_bwd(self._w("weight_hh_l0"), lengths, node_off, sb, st, B, T, ws["gates"][0], ws["Cst"][0],
-                                   ws["dH0d"], 2 * H, p, rng, 0x5EED0, dGX)
+                                   ws["dH0d"], 2 * H, p, rng, 0x5EED0, dGX, zero_to=zero_to)
                 xin, ldin, d_in, bf, gat = x, ldx, self.d_in, x_bf16, node_row
             # W_ih (both directions stacked [800, d_in]) and b_ih
             linear_wgrad(pl, dGX, 8 * H, xin, ldin, gat, 8 * H, d_in, rows, self._off("weight_ih_l%d" % k),

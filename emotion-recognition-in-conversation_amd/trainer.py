@@ -120,10 +120,23 @@ def make_loaders(params, rank=0, world=1, device=None):
 
 
 def longest_dialogue(loader):
-    """longest training dialogue of this rank's split (the T capacity of the buckets)"""
+    """longest training dialogue of this rank's split"""
     if isinstance(loader, StoreLoader):
         return int(loader.store.lengths.max())
     return max(len(d["label"]) for d in loader.dataset.dialogs)
+
+
+def bucket_t_cap(loader, world, device):
+    """The T capacity of the capacity buckets: the longest training dialogue of ALL ranks.  Under data parallelism every
+    rank precaptures the same bucket list (StepGraphs.precapture), and that list depends on T_cap; with each rank's own
+    longest dialogue the ranks would run different numbers of warm-up collectives.  (A collective: every rank calls it.)"""
+    t = longest_dialogue(loader)
+    if world > 1:
+        import torch.distributed as dist
+        v = torch.tensor([t], dtype=torch.int64, device=device)
+        dist.all_reduce(v, op=dist.ReduceOp.MAX)
+        t = int(v.item())
+    return t
 
 
 def first_batch(loader):
@@ -156,10 +169,12 @@ class FixedBatches:
 class StepGraphs:
     """Captured HIP graphs of the whole training step, least-recently-used eviction.
 
-    * CAPACITY BUCKETS (trainers that offer ``capacity_bucket``: COGMEN in the bf16 compute mode).  The reference reshuffles
+    * CAPACITY BUCKETS (trainers that offer ``capacity_bucket``: COGMEN in the bf16 compute mode, DialogueGCN on its default
+      path).  The reference reshuffles
       the dialogues every epoch and its last batch is smaller (lumo/trainer/trainer.py:429-442, mmbase.py:468), so (B, T, N)
       almost never repeats.  A bucket is a set of static capacity-sized input buffers -- ``batch_size`` dialogues (missing
-      ones get length 0), the longest dialogue of the split, N rounded up to a multiple of 256 -- plus one graph captured
+      ones get length 0), the longest training dialogue of every rank, N rounded up to the trainer's N_BUCKET (COGMEN 256,
+      DialogueGCN 128) -- plus one graph captured
       over them; the step's kernels read the true node count from the device (COGMENModule.dynamic_n), so every batch
       that fits replays that graph: a reshuffled epoch hits a handful of graphs.
     * otherwise one graph per exact batch shape, captured when the shape shows up the SECOND time (under shuffling most
@@ -479,7 +494,7 @@ def run(trainer_cls, params_cls, argv=None):
     # every capture must happen at the same point on every rank: buckets are captured up front, in one order
     # (StepGraphs.precapture); a trainer without buckets keeps the eager step there.
     if hasattr(trainer, "capacity_bucket"):
-        trainer.t_cap = longest_dialogue(train_loader)
+        trainer.t_cap = bucket_t_cap(train_loader, world, device)
     graphs = StepGraphs(trainer, capture=params.get("graph_capture", True)) if params.get("graph_replay", True) else None
     fixed = FixedBatches(train_loader, trainer, params.seed + rank) if params.get("fixed_batches", False) else None
     if graphs is not None and world > 1 and fixed is None:
@@ -494,11 +509,11 @@ def run(trainer_cls, params_cls, argv=None):
     resident, acc_prev = None, [0.0] * 4
     if params.get("resident", False):
         if world > 1 or not isinstance(train_loader, StoreLoader) or not hasattr(trainer, "resident_batch"):
-            raise SystemExit("--resident needs --device_collate, one rank and a trainer with resident batches (cogmen, --compute=bf16)")
+            raise SystemExit("--resident needs --device_collate, one rank and a trainer with resident batches (capacity mode)")
         resident = ResidentEpochs(trainer, train_loader.store, params.train.batch_size, params.seed + rank,
                                   capture=params.get("graph_capture", True))
         if not resident.supported():
-            raise SystemExit("--resident: this configuration cannot run the fused bf16 step in capacity mode")
+            raise SystemExit("--resident: this configuration cannot run its step in capacity mode")
         resident.plan(params.epoch)
     for epoch in range(params.epoch):
         trainer.model.train()

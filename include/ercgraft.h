@@ -62,7 +62,9 @@ const char* erc_last_error(void);
  *   edge_index int64 [2, e_cap] (row 0 = source j, row 1 = target k) and
  *   edge_type  int64 [e_cap]: the reference's tensors; either may be NULL
  *   counts    int32 [2] = {N, E}
- * Entries beyond N / E are left untouched.
+ * Capacity rows: when N < n_cap, rows [N, n_cap) get empty CSR ranges (in_ptr / out_ptr [N, n_cap] = E) and node_row =
+ * node_spk = 0, so that launches sized for n_cap add nothing for them and gather only row 0.  Entries beyond E are left
+ * untouched.
  */
 int erc_window_graph_build(const int64_t* lengths, const int64_t* speakers, int64_t spk_sb, int64_t spk_st,
                            int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
@@ -70,6 +72,15 @@ int erc_window_graph_build(const int64_t* lengths, const int64_t* speakers, int6
                            int32_t* in_ptr, int32_t* in_src, int32_t* in_typ,
                            int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
                            int64_t* edge_index, int64_t* edge_type, int32_t* counts, void* stream);
+/* The same with desc (int32 [2B], or NULL = erc_window_graph_build): RESIDENT mode.  desc[b] = length of dialogue slot b
+ * (0 = empty, clamped to [0, T]), desc[B + b] = its first row in a feature store; lengths is unused (may be NULL), speakers
+ * are the store's [U] ids (element stride spk_st; spk_sb unused) and node_row receives STORE rows desc[B + b] + t. */
+int erc_window_graph_build_desc(const int64_t* lengths, const int64_t* speakers, int64_t spk_sb, int64_t spk_st,
+                                int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
+                                int32_t* node_off, int32_t* node_row, int32_t* node_spk,
+                                int32_t* in_ptr, int32_t* in_src, int32_t* in_typ,
+                                int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
+                                int64_t* edge_index, int64_t* edge_type, int32_t* counts, const int32_t* desc, void* stream);
 
 /* ------------------------------------------------------------------------
  * K2  dense fp32 GEMM on the matrix cores (v_mfma_f32_16x16x4_f32: exact
@@ -797,7 +808,7 @@ int erc_lstm_set_stamps(unsigned long long* stamps);
  *   GX [rows, >=800]: hoisted x W_ih^T + b_ih, direction d in columns [400d, 400d+400)  (one GEMM by the caller)
  *   W_hh [2][400,100], b_hh [2][400]: weight_hh_l{k}, weight_hh_l{k}_reverse and their biases
  *   lengths: int64 [B] (packed: dialogue b runs L_b steps, the reverse direction starts at L_b-1; positions
- *            >= L_b produce zeros) or NULL (every dialogue runs T steps)
+ *            >= L_b produce zeros) or NULL (every dialogue runs T steps; with node_off: node_off[b+1] - node_off[b] steps)
  *   rows: row(b,t) = b*sb + t*st (in rows), or node_off[b] + t when node_off != NULL
  *   Hout [rows, ldh] columns [100d,100d+100); Hdrop (optional): the same with inverted dropout(drop_p)
  *   applied -- the inter-layer dropout of nn.LSTM; mask keyed by (rng_state, rng_stream, element)
@@ -805,6 +816,8 @@ int erc_lstm_set_stamps(unsigned long long* stamps);
  *   scan order: dW_hh[d] = dGX[:,400d:]^T Hprev[:,100d:])
  * Backward: dHout = gradient wrt Hout (wrt Hdrop when drop_p > 0); writes dGX [rows,800] (zero on padded
  * rows); dW_ih = dGX^T x, db = colsum(dGX), dx = dGX W_ih are GEMMs by the caller.
+ * erc_lstm_scan_bwd_cap with zero_to > 0 (compact rows only): capacity mode -- rows [node_off[B], zero_to) of dGX are
+ * written 0 as well, so those GEMMs may run over zero_to rows (zero_to = 0: erc_lstm_scan_bwd).
  */
 int erc_lstm_scan_fwd(const float* GX, int ldgx, const float* W_hh, const float* b_hh, const int64_t* lengths,
                       const int32_t* node_off, int64_t sb, int64_t st, int B, int T,
@@ -813,6 +826,9 @@ int erc_lstm_scan_fwd(const float* GX, int ldgx, const float* W_hh, const float*
 int erc_lstm_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st,
                       int B, int T, const float* gates, const float* Cst, const float* dHout, int lddh,
                       float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, void* stream);
+int erc_lstm_scan_bwd_cap(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st,
+                          int B, int T, const float* gates, const float* Cst, const float* dHout, int lddh,
+                          float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, int zero_to, void* stream);
 
 /* ------------------------------------------------------------------------
  * DialogueGCN graph operators (track_mm/dgcn_models.py:36-152, models/rgcn.py:264-355) over the CSRs of K1.
@@ -926,7 +942,13 @@ int erc_csr_sum(const float* x, int ldx, int F, int N, const int32_t* ptr, const
  * Replaces erc_slab_reduce + erc_csr_sum + 3 forward GEMMs + erc_head_ce + 3 backward GEMMs.  The in-CSR's sources of a row lie
  * within `window` <= erc_dgcn_tail_max_window() rows of it; n_rows <= erc_dgcn_tail_max_rows(); n_classes <= 8; dropout draws
  * erc_uniform(seed, offset, row * 100 + column) like erc_gemm_f32_stream's act 3.  stats: >= erc_dgcn_tail_stats_floats(n_rows)
- * floats, zero-initialised once.  Exact fp32 products (v_mfma_f32_16x16x4_f32). */
+ * floats, zero-initialised once.  Exact fp32 products (v_mfma_f32_16x16x4_f32).
+ * erc_dgcn_tail_cap adds two arguments (NULL / NULL = erc_dgcn_tail).
+ * n_dev (int32 on the device, or NULL): CAPACITY mode -- the launch is sized for n_rows, the batch is the first N = *n_dev
+ * rows (erc_window_graph_build's counts[0]).  Loss, #correct and the weight sum run over those N rows only (labels of rows
+ * >= N are never read) and the gradient rows [N, n_rows) of dlogits, dZc, dXc, dAGG and dHc are written 0; the forward
+ * outputs of those rows are not written.  label_rows (int32 [N] or NULL): RESIDENT mode -- row i's label is
+ * labels[label_rows[i]] (node_row of a store-resident batch). */
 int erc_dgcn_tail_max_rows(void);
 int erc_dgcn_tail_set_stamps(uint64_t* stamps);   /* diagnostic: 16 x uint64 phase stamps (10 ns ticks) of workgroup 0; NULL = off */
 int erc_dgcn_tail_max_window(void);
@@ -937,6 +959,12 @@ int erc_dgcn_tail(const float* slabs, int n_slabs, int64_t slab_stride, const fl
                   const float* weight, int n_classes, int n_rows, float drop_p, const uint64_t* rng, float* Xc, int ldx,
                   float* Hc, float* AGG, float* Zc, float* logits, float* dlogits, float* dZc, float* dXc, int lddx,
                   float* dAGG, float* dHc, float* stats, void* stream);
+int erc_dgcn_tail_cap(const float* slabs, int n_slabs, int64_t slab_stride, const float* rgcn_bias, const int32_t* in_ptr,
+                      const int32_t* in_src, int window, const float* W_rel, const float* b_rel, const float* W_root,
+                      const float* W1, const float* b1, const float* W2, const float* b2, const int64_t* labels,
+                      const float* weight, int n_classes, int n_rows, float drop_p, const uint64_t* rng, float* Xc, int ldx,
+                      float* Hc, float* AGG, float* Zc, float* logits, float* dlogits, float* dZc, float* dXc, int lddx,
+                      float* dAGG, float* dHc, float* stats, const int32_t* n_dev, const int32_t* label_rows, void* stream);
 
 /* ------------------------------------------------------------------------
  * MMGCN (track_mm/mmgcn.py:56-123, track_mm/mmgcn_models.py:8-39,344-394,493-646).  Node rows are

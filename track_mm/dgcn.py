@@ -14,6 +14,9 @@ class DGCNParams(ERCParams):
         self.dataset = "iemocap-cogmen-6"
         self.epoch = 55
         self.optim = Group(name="Adam", lr=0.0003, weight_decay=0)                # dgcn.py:41
+        # RGCNConv in relation space (True) or basis space (False); None = relation space when the library's relation-space
+        # kernels hold the relations (two speakers).  Capacity buckets and --resident need basis space.
+        self.relation_space = None
 
 
 ParamsType = DGCNParams
