@@ -62,7 +62,7 @@ def sim_block(x):
 def big_adjacency(feats, dia_len):
     """create_big_adj (mmgcn_models.py:582-646); modality order is the order of ``feats``."""
     M, N = len(feats), feats[0].shape[0]
-    adj = torch.zeros(M * N, M * N)
+    adj = torch.zeros(M * N, M * N, dtype=feats[0].dtype)
     start = 0
     for L in dia_len:
         L = int(L)
