@@ -131,7 +131,14 @@ __device__ __forceinline__ const float* gate_row(const float* W_hh_c, const floa
     return gate < 3 ? W_hh_c + (int64_t)(gate * HID + e) * HID : W_ih_p + (int64_t)((gate - 3) * HID + e) * HID;
 }
 
-constexpr int MAX_T = 1022;
+// The one limit on the padded length T, shared by erc_dag_meta, erc_dag_rec_config and both recurrence entry points.
+// A launch's tags are epoch * 1024 + k with k in [1, 1023]: k = 0 is what an unused record half carries (tag 0 marks
+// "no value" in the backward's reduce-scatter records, and epoch * 1024 wraps to 0 when the epoch reaches 2^22), and
+// k = 1024 would be the next epoch's.  The forward uses k <= T.  The backward tags step i with i + 1, hands step i + 1 to
+// the layer below as k = i + 2 <= T and closes with the flush round at k = T + 2, so T + 2 <= 1023.
+constexpr int TAG_SPAN = 1024;
+constexpr int MAX_T = TAG_SPAN - 1 - 2;      // 1021
+static_assert(MAX_T + 2 < TAG_SPAN && MAX_T <= 1024, "flush tag inside the epoch; dag_meta's speaker table holds 1024");
 
 // ----------------------------------------------------------------------------- meta
 // speaker ids, DAG predecessor, valid-row map.  One workgroup per dialogue.
@@ -623,7 +630,9 @@ __global__ __launch_bounds__(NTH) void dag_rec_bwd_kernel(RecBwd p) {
         float suma = 0.f, sumb = 0.f;
         if (tid < S) {
             int spins = 0;
-            if (tid < total) {   // sentinel: wait for this thread's first record before requesting the others (see poll_operand)
+            // sentinel: wait for this thread's first record before requesting the others (see poll_operand).  T = 1 has a
+            // round with neither product (step 0 is also step T - 1): its records carry tag 0 and nobody waits for them
+            if (tid < total && (do_a || do_b)) {
                 const u64* sp = do_a ? blka + 2 * tid : blkb + 2 * tid;
                 u64 v0 = ld64(sp);
                 while ((unsigned)(v0 >> 32) != tag) {
@@ -992,7 +1001,7 @@ extern "C" int erc_dag_meta(const float* speaker_onehot, const int64_t* speaker_
 
 // cfg[4] = {elements per workgroup, dialogues per group, groups per launch, layers per launch}
 extern "C" int erc_dag_rec_config(int dir, int B, int T, int n_layers, int epc_hint, int dg_hint, int lpl_hint, int* cfg) {
-    ERC_REQUIRE(B > 0 && T > 0 && T < 1023 && n_layers > 0 && cfg, "dag_rec_config: B=%d T=%d layers=%d", B, T, n_layers);
+    ERC_REQUIRE(B > 0 && T > 0 && T <= MAX_T && n_layers > 0 && cfg, "dag_rec_config: B=%d T=%d layers=%d (T <= %d)", B, T, n_layers, MAX_T);
     const int cand[3] = {5, 4, 2};
     double best = 1e30;
     cfg[0] = 0;
@@ -1056,8 +1065,8 @@ extern "C" int erc_dag_rec_fwd(const float* H0, int ldh0, int n_layers, const fl
     ERC_REQUIRE(H0 && Wh && bh && W_hh_c && b_hh_c && W_ih_p && b_ih_p && Wr && w_k && pred && spk && H1 && GI && Mseq && GH &&
                     R && ks && alpha && state && scratch,
                 "dag_rec_fwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && T < 1023 && n_layers > 0 && ldh0 >= HID && ldo >= HID && ldgi > 6 * HID,
-                "dag_rec_fwd: bad sizes B=%d T=%d layers=%d", B, T, n_layers);
+    ERC_REQUIRE(B > 0 && T > 0 && T <= MAX_T && n_layers > 0 && ldh0 >= HID && ldo >= HID && ldgi > 6 * HID,
+                "dag_rec_fwd: bad sizes B=%d T=%d layers=%d (T <= %d)", B, T, n_layers, MAX_T);
     ERC_REQUIRE(cfg_ok(cfg) && ((uintptr_t)scratch & 7) == 0, "dag_rec_fwd: bad configuration (use erc_dag_rec_config)");
     const int dg = cfg[1], gpl = cfg[2], lpl = cfg[3];
     const int lds = lds_fwd(cfg[0], dg, T);
@@ -1102,9 +1111,9 @@ extern "C" int erc_dag_rec_bwd(int n_layers, const float* const* Hl, int ldh, co
     ERC_REQUIRE(Hl && GI && GH && Mseq && R && alpha && Wh && W_hh_c && W_ih_p && Wr && w_k && pred && spk && dHall && DGI && DGH &&
                     dM && dks && state && scratch,
                 "dag_rec_bwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && T < 1021 && n_layers > 0 && ldh >= HID && ldgi > 6 * HID && lddgi > 6 * HID &&
+    ERC_REQUIRE(B > 0 && T > 0 && T <= MAX_T && n_layers > 0 && ldh >= HID && ldgi > 6 * HID && lddgi > 6 * HID &&
                     ldd >= HID * (n_layers + 1),
-                "dag_rec_bwd: bad sizes B=%d T=%d layers=%d", B, T, n_layers);
+                "dag_rec_bwd: bad sizes B=%d T=%d layers=%d (T <= %d)", B, T, n_layers, MAX_T);
     ERC_REQUIRE(cfg_ok(cfg) && ((uintptr_t)scratch & 7) == 0, "dag_rec_bwd: bad configuration (use erc_dag_rec_config)");
     const int dg = cfg[1], gpl = cfg[2], lpl = cfg[3];
     const int lds = lds_bwd(cfg[0], dg, T);

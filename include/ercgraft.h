@@ -773,7 +773,10 @@ int erc_dag_meta(const float* speaker_onehot, const int64_t* speaker_ids, int64_
  *     invalid; pass it to erc_adam_step as skip_flag) unless `health` names another word (erc_health_roll), then one
  *     launch epoch per group (shared by both directions).
  *   scratch: erc_dag_rec_scratch_bytes(dir, B, T, cfg) bytes per direction, 8-byte aligned, zero-filled ONCE.
- * T <= 1022 and the per-workgroup LDS (histories of the slice: grows with dg * T) <= 160 KB. */
+ *     A scratch buffer holds records tagged with its groups' epochs: keep it with the state it was first used with.
+ * T <= 1021 in erc_dag_meta, erc_dag_rec_config and both directions alike (a launch's record tags are epoch * 1024 + k,
+ * 1 <= k <= 1023, and the backward closes with k = T + 2), and the per-workgroup LDS (histories of the slice: grows with
+ * dg * T) <= 160 KB; anything beyond is refused before a launch. */
 int erc_dag_rec_config(int dir, int B, int T, int n_layers, int epc_hint, int dg_hint, int lpl_hint, int* cfg);
 int64_t erc_dag_rec_scratch_bytes(int dir, int B, int T, const int* cfg);
 /* diagnostic: while set, the recurrence kernels store shader-clock stamps of workgroup 0 per step and phase into

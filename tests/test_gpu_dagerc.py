@@ -56,18 +56,22 @@ def test_dagerc_matches_reference_golden(golden, name):
     print("worst relative gradient error", worst)
 
 
-@pytest.mark.parametrize("B,lens,dims,S,C", [(16, (20, 110), dict(a=100, t=100, v=512), 2, 6),
-                                             (5, (1, 40), dict(a=30, t=60, v=34), 9, 7)])
-def test_dagerc_parity_vs_oracle_large(B, lens, dims, S, C, monkeypatch):
-    """BASELINE config-4 shape (B=16, T=110, D=712) and a multi-speaker ragged case vs the (reference-pinned) oracle."""
+@pytest.mark.parametrize("B,lens,dims,S,C,L", [
+    pytest.param(16, (20, 110), dict(a=100, t=100, v=512), 2, 6, 4, id="16-lens0-dims0-2-6"),
+    pytest.param(5, (1, 40), dict(a=30, t=60, v=34), 9, 7, 4, id="5-lens1-dims1-9-7"),
+    pytest.param(6, (2, 37), dict(a=30, t=60, v=34), 3, 5, 5, id="layers5"),
+    pytest.param(2, (50, 300), dict(a=30, t=60, v=34), 2, 6, 4, id="t300-b2")])
+def test_dagerc_parity_vs_oracle_large(B, lens, dims, S, C, L, monkeypatch):
+    """BASELINE config-4 shape (B=16, T=110, D=712), a multi-speaker ragged case, five layers (more than one launch holds:
+    the directions chunk them differently) and T = 300 vs the (reference-pinned) oracle."""
     from oracle.dagerc import DAGERCOracle, dagerc_loss
     from erc_amd.dagerc import DAGERCModule
     batch = make_batch(B, dims, n_speakers=S, n_classes=C, min_len=lens[0], max_len=lens[1], seed=8,
                        speaker_onehot=True, force_max=True)
     D = sum(dims.values())
     torch.manual_seed(5)
-    ref = DAGERCOracle(emb_dim=D, dropout=0.0, n_classes=C, gnn_layers=4)
-    mine = DAGERCModule(emb_dim=D, dropout=0.0, n_classes=C, gnn_layers=4)
+    ref = DAGERCOracle(emb_dim=D, dropout=0.0, n_classes=C, gnn_layers=L)
+    mine = DAGERCModule(emb_dim=D, dropout=0.0, n_classes=C, gnn_layers=L)
     mine.load_state_dict(ref.state_dict())
     mine.finalize(DEV)
     ref.train(), mine.train()
@@ -87,6 +91,66 @@ def test_dagerc_parity_vs_oracle_large(B, lens, dims, S, C, monkeypatch):
     for n in mine.flat.params:
         assert rel_err(mine.flat.g(n).cpu(), refp[n].grad) < 2e-3, n
     mine.check_cluster()      # no member of a cluster-mode recurrence kernel timed out
+
+
+def test_dagerc_alternating_shapes_share_the_epoch_words(monkeypatch):
+    """one module, training steps on shapes A, B, A, B (other B and T: other workspaces, record scratch and dialogues per
+    group, but ONE rec_state, whose epoch words then serve different groups in turn): every step against the oracle"""
+    from oracle.dagerc import DAGERCOracle, dagerc_loss
+    from erc_amd.dagerc import DAGERCModule
+    dims, C = dict(a=30, t=60, v=34), 6
+    shapes = [make_batch(9, dims, n_speakers=2, n_classes=C, min_len=3, max_len=70, seed=21, speaker_onehot=True, force_max=True),
+              make_batch(3, dims, n_speakers=3, n_classes=C, min_len=1, max_len=12, seed=22, speaker_onehot=True, force_max=True)]
+    D = sum(dims.values())
+    torch.manual_seed(11)
+    ref = DAGERCOracle(emb_dim=D, dropout=0.0, n_classes=C, gnn_layers=4)
+    mine = DAGERCModule(emb_dim=D, dropout=0.0, n_classes=C, gnn_layers=4)
+    mine.load_state_dict(ref.state_dict())
+    mine.finalize(DEV)
+    ref.train(), mine.train()
+    torch.set_num_threads(8)
+    poison_lds_before(monkeypatch, "dag_rec_fwd", "dag_rec_bwd")
+    want = []
+    for batch in shapes:
+        ref.zero_grad()
+        loss, _ = dagerc_loss(ref, batch)
+        loss.backward()
+        want.append((float(loss), ref(**batch)[0].detach(), {n: p.grad.clone() for n, p in ref.named_parameters() if p.grad is not None}))
+    cfgs = set()
+    for step in range(4):
+        batch, (loss, logits, grads) = shapes[step % 2], want[step % 2]
+        stats = mine.loss_and_grads(to_device(batch, DEV)).cpu()
+        B, T = batch["input_tensor"].shape[:2]
+        got = mine._last_ws["logits"].view(B, T, -1).cpu()
+        cfgs.add(mine._last_ws["cfg"])
+        assert float((got - logits).abs().max()) < 1e-4, step
+        assert abs(float(stats[0]) - loss) < 1e-5, step
+        for n in mine.flat.params:
+            assert rel_err(mine.flat.g(n).cpu(), grads[n]) < 2e-3, (step, n)
+    assert len(cfgs) == 2 and len({cf[1][1] for cf in cfgs}) == 2       # two workspaces, other dialogues per group
+    assert int(mine.rec_state[1]) > 0
+    mine.check_cluster()
+
+
+def test_dagerc_refuses_a_dialogue_longer_than_the_recurrence_admits():
+    """one utterance more than the recurrence's maximum T: ErcGraftError from the forward, before any recurrence launch"""
+    from erc_amd import capi
+    from erc_amd.dagerc import DAGERCModule
+    from tests.dag_rec_ref import MAX_T
+    from tests.util_cases import make_batch_lengths
+    dims = dict(a=4, t=4, v=4)
+    mine = DAGERCModule(emb_dim=12, dropout=0.0, n_classes=4, gnn_layers=2).finalize(DEV)
+    mine.train()
+    batch = to_device(make_batch_lengths([MAX_T + 1], dims, n_classes=4, speaker_onehot=True), DEV)
+    assert batch["input_tensor"].shape[1] == MAX_T + 1
+    with pytest.raises(capi.ErcGraftError):
+        mine.loss_and_grads(batch)
+    with pytest.raises(capi.ErcGraftError):
+        mine(**batch)
+    torch.cuda.synchronize()
+    assert int(mine.rec_state.abs().sum()) == 0           # no launch advanced an epoch
+    mine.loss_and_grads(to_device(make_batch_lengths([MAX_T], dims, n_classes=4, speaker_onehot=True), DEV))
+    mine.check_cluster()                                  # the maximum itself trains: forward and backward
 
 
 def test_recurrence_configurations_agree(monkeypatch):
