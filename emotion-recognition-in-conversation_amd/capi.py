@@ -990,3 +990,74 @@ def dgcnv2_nodal_fwd(E, lde, Q, ldq, node_off, B, T, A, lda, P, TH):
 
 def dgcnv2_nodal_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde):
     _call("erc_dgcnv2_nodal_bwd", E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde)
+
+
+# --------------------------------------------------------------------------- DialogueRNN (csrc/dialogrnn.hip)
+DIALOGRNN_SAVE = {"gates_g": (0, 450), "ghn_g": (450, 150), "g_prev": (600, 150), "g": (750, 150), "g_drop": (900, 150),
+                  "c": (1050, 150), "gates_p": (1200, 450), "ghn_p": (1650, 150), "q_prev": (1800, 150), "q": (1950, 150),
+                  "q_drop": (2100, 150), "gates_e": (2250, 300), "ghn_e": (2550, 100), "e_prev": (2650, 100), "e": (2750, 100),
+                  "e_drop": (2850, 100)}
+DIALOGRNN_DREC = {"dgh_g": (0, 450), "dgh_p": (450, 450), "dgi_e": (900, 300), "dgh_e": (1200, 300)}
+DIALOGRNN_DREC_ROW = 1500
+DIALOGRNN_GXW = 1050
+
+
+def dialogrnn_max_t():
+    return int(lib().erc_dialogrnn_max_t())
+
+
+def dialogrnn_wt_floats():
+    return int(lib().erc_dialogrnn_wt_floats())
+
+
+def dialogrnn_save_floats(N, B, T):
+    return int(lib().erc_dialogrnn_save_floats(N, B, T))
+
+
+def dialogrnn_planes(buf, N, layout):
+    """{name: [2, N, w] view} of the planes of a save / dREC buffer (ercgraft.h)"""
+    return {k: buf[o * 2 * N:(o + w) * 2 * N].view(2, N, w) for k, (o, w) in layout.items()}
+
+
+def dialogrnn_alpha(save, N, B, T):
+    o = 2950 * 2 * N
+    return save[o:o + 2 * B * T * T].view(2, B, T, T)
+
+
+def dialogrnn_offsets(offs):
+    """host int64[20] of the parameter offsets erc_dialogrnn_* take"""
+    if len(offs) != 20:
+        raise ErcGraftError("dialogrnn: 20 parameter offsets expected, got %d" % len(offs))
+    return (C.c_int64 * 20)(*[int(o) for o in offs])
+
+
+def dialogrnn_meta(onehot, S, lengths, B, T, n_cap, node_off, node_row, node_spk):
+    _call("erc_dialogrnn_meta", onehot, S, lengths, B, T, n_cap, node_off, node_row, node_spk)
+
+
+def dialogrnn_pack(params, offs, D_m, WT):
+    _call("erc_dialogrnn_pack", params, C.addressof(offs), D_m, WT)
+
+
+def dialogrnn_scan_fwd(GX, ldgx, WT, params, offs, D_m, node_off, node_spk, B, T, S, N, drop_p, drop_rec, rng, rng_stream,
+                       emotions, lde, save):
+    _call("erc_dialogrnn_scan_fwd", GX, ldgx, WT, params, C.addressof(offs), D_m, node_off, node_spk, B, T, S, N, float(drop_p),
+          float(drop_rec), rng, rng_stream, emotions, lde, save)
+
+
+def dialogrnn_scan_bwd(GX, ldgx, WT, params, offs, D_m, node_off, node_spk, B, T, S, N, drop_p, drop_rec, rng, rng_stream, save,
+                       dEmo, ldde, dGX, lddgx, dREC):
+    _call("erc_dialogrnn_scan_bwd", GX, ldgx, WT, params, C.addressof(offs), D_m, node_off, node_spk, B, T, S, N, float(drop_p),
+          float(drop_rec), rng, rng_stream, save, dEmo, ldde, dGX, lddgx, dREC)
+
+
+def match_att_fwd(E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH):
+    _call("erc_match_att_fwd", E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH)
+
+
+def match_att_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde):
+    _call("erc_match_att_bwd", E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde)
+
+
+def log_softmax_rows(x, ldx, Cn, n_rows, y, ldy):
+    _call("erc_log_softmax_rows", x, ldx, Cn, n_rows, y, ldy)

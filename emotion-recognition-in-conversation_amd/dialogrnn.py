@@ -1,0 +1,294 @@
+"""DialogueRNN on the MI355X hot path (drop-in for DialogRNNModel, track_mm/dgcnv2_models.py:428-487 over :235-347, with
+MaskedNLLLoss :13-33).
+
+``DialogRNNModule`` keeps the reference's constructor signature, its ``state_dict`` key for key and shape for shape
+(``dialog_rnn_{f,r}.dialogue_cell.{g_cell,p_cell,e_cell}.*``, ``...attention.transform.weight``, ``matchatt.transform.*``,
+``linear.*``, ``smax_fc.*``; all 32 parameters are live) and ``forward(**batch) -> (log_prob [N, C], emotions [N, 2 D_e])``
+on the valid rows, dialogue-major.  Built: context_attention='general', listener_state=False, D_g = D_p = 150,
+D_e = D_h = 100, fp32, up to 9 speakers and 110 utterances; anything else raises ``ErcGraftError`` naming the argument.
+
+Batches are time-major (batch_first=False, one-hot speakers): padded row t*B + b.  Chain: batch tables (node_off, node_row,
+speaker per node) -> the u-side products W_ih^g[:, :D] u, W_ih^p[:, :D] u (one GEMM per direction: the two weights are
+neighbours in the flat buffer) and W_a u over the N valid rows, gathered straight from the padded batch -> the two scans of
+all dialogues in one launch (csrc/dialogrnn.hip: padded steps are not run, only the speaker's party cell is evaluated,
+dropout_rec' on the emotions in the same launch) -> Q = E W^T + b (GEMM) -> matching attention 'general2' per dialogue
+(200 wide) -> ReLU(Linear(200, 100)) + dropout in the GEMM epilogue -> smax_fc + class-weighted NLL in one launch.  The
+backward mirrors it; every weight gradient (hoisted products, head, and the recurrent blocks as GEMMs over the per-step gate
+gradients and saved states the backward scan writes) joins the step's batched weight-gradient launch (erc_wgrad_table).
+"""
+import torch
+from torch import nn
+
+from . import capi
+from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
+from .dgcnv2 import IEMOCAP6_WEIGHTS
+
+D_G, D_E, D_HID, EW, MAX_T, MAX_S = 150, 100, 100, 200, 110, 9
+GXW = capi.DIALOGRNN_GXW
+DIRS = ("dialog_rnn_f", "dialog_rnn_r")
+RNG_STREAM = 0x5d10
+
+
+class _Attention(nn.Module):          # MatchingAttention(D_g, D_m, att_type='general'): Linear(D_m, D_g, bias=False)
+    def __init__(self, d_m, d_g):
+        super().__init__()
+        self.transform = nn.Linear(d_m, d_g, bias=False)
+
+
+class _Transform(nn.Module):          # MatchingAttention('general2'): its one parameterised layer
+    def __init__(self, d):
+        super().__init__()
+        self.transform = nn.Linear(d, d, bias=True)
+
+
+class _Cell(nn.Module):
+    def __init__(self, D_m, D_g, D_p, D_e):
+        super().__init__()
+        self.g_cell = nn.GRUCell(D_m + D_p, D_g)
+        self.p_cell = nn.GRUCell(D_m + D_g, D_p)
+        self.e_cell = nn.GRUCell(D_p, D_e)
+        self.attention = _Attention(D_m, D_g)
+
+
+class _DialogueRNN(nn.Module):
+    def __init__(self, D_m, D_g, D_p, D_e):
+        super().__init__()
+        self.dialogue_cell = _Cell(D_m, D_g, D_p, D_e)
+
+
+class DialogRNNModule(nn.Module):
+    def __init__(self, D_m, D_g, D_p, D_e, D_h, D_a=100, n_classes=7, listener_state=False, context_attention="simple",
+                 dropout_rec=0.5, dropout=0.5, compute="f32", seed=1):
+        super().__init__()
+        if listener_state:
+            raise capi.ErcGraftError("dialogrnn: listener_state=True is not built (the reference default, False, is)")
+        if context_attention != "general":
+            raise capi.ErcGraftError("dialogrnn: context_attention=%r is not built ('general' is)" % (context_attention,))
+        for name, got, want in (("D_g", D_g, D_G), ("D_p", D_p, D_G), ("D_e", D_e, D_E), ("D_h", D_h, D_HID)):
+            if got != want:
+                raise capi.ErcGraftError("dialogrnn: the kernels are built for %s=%d (dgcnv2.py:71-77), got %r" % (name, want, got))
+        if int(D_m) < 1:
+            raise capi.ErcGraftError("dialogrnn: D_m=%r" % (D_m,))
+        if compute != "f32":
+            raise capi.ErcGraftError("dialogrnn runs in fp32 only (the reference is fp32); --compute=%s is not supported" % compute)
+        for name, p in (("dropout_rec", dropout_rec), ("dropout", dropout)):
+            if not 0.0 <= p + (0.15 if name == "dropout" else 0.0) < 1.0:
+                raise capi.ErcGraftError("dialogrnn: %s=%r out of range" % (name, p))
+        self.D_m, self.n_classes, self.compute = int(D_m), n_classes, compute
+        self.drop_cell, self.drop_emo, self.drop_p = float(dropout_rec), float(dropout) + 0.15, float(dropout)   # :436-438
+        self.dialog_rnn_f = _DialogueRNN(D_m, D_g, D_p, D_e)
+        self.dialog_rnn_r = _DialogueRNN(D_m, D_g, D_p, D_e)
+        self.matchatt = _Transform(2 * D_e)
+        self.linear = nn.Linear(2 * D_e, D_h)
+        self.smax_fc = nn.Linear(D_h, n_classes)
+        self.flat, self._ws, self._seed = None, WorkspaceCache(), seed
+
+    def live_groups(self):
+        groups = []
+        for d in DIRS:
+            c = getattr(self, d).dialogue_cell
+            n = d + ".dialogue_cell."
+            # the two input-side weights (and their biases) are neighbours: [900, D_m + 150], one hoisted GEMM per direction
+            groups += [[(n + "g_cell.weight_ih", c.g_cell.weight_ih), (n + "p_cell.weight_ih", c.p_cell.weight_ih)],
+                       [(n + "g_cell.bias_ih", c.g_cell.bias_ih), (n + "p_cell.bias_ih", c.p_cell.bias_ih)]]
+            groups += [[(n + "%s.%s" % (cell, k), getattr(getattr(c, cell), k))]
+                       for cell, k in (("g_cell", "weight_hh"), ("g_cell", "bias_hh"), ("p_cell", "weight_hh"), ("p_cell", "bias_hh"),
+                                       ("e_cell", "weight_ih"), ("e_cell", "weight_hh"), ("e_cell", "bias_ih"), ("e_cell", "bias_hh"))]
+            groups.append([(n + "attention.transform.weight", c.attention.transform.weight)])
+        return groups + [[("matchatt.transform.weight", self.matchatt.transform.weight)],
+                         [("matchatt.transform.bias", self.matchatt.transform.bias)],
+                         [("linear.weight", self.linear.weight)], [("linear.bias", self.linear.bias)],
+                         [("smax_fc.weight", self.smax_fc.weight)], [("smax_fc.bias", self.smax_fc.bias)]]
+
+    def finalize(self, device):
+        self.to(device)
+        self.flat = FlatParams(self.live_groups(), device)
+        off = self.flat.offsets
+        self.offs = capi.dialogrnn_offsets([off[d + ".dialogue_cell." + k] for d in DIRS for k in (
+            "g_cell.weight_ih", "g_cell.weight_hh", "g_cell.bias_hh", "p_cell.weight_ih", "p_cell.weight_hh", "p_cell.bias_hh",
+            "e_cell.weight_ih", "e_cell.weight_hh", "e_cell.bias_ih", "e_cell.bias_hh")])
+        if self.flat.device.type == "cuda":
+            self.WT = torch.zeros(capi.dialogrnn_wt_floats(), dtype=torch.float32, device=device)
+        self.rng_state = torch.tensor([0, self._seed], dtype=torch.int64, device=device)
+        return self
+
+    @property
+    def _last_ws(self):
+        """workspace of the most recent forward (tests / bench read results out of it)"""
+        return self._ws.last
+
+    def _workspace(self, B, T, N, device):
+        return self._ws.get((B, T, N), lambda: self._make_workspace(B, T, N, device))
+
+    def _make_workspace(self, B, T, N, device):
+        # zeros, not empty: a stale NaN must never reach a weight-gradient GEMM through a row the step did not touch
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        C = self.n_classes
+        ws = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), GX=f32(N, 2 * GXW), E=f32(N, EW),
+                  save=f32(capi.dialogrnn_save_floats(N, B, T)), Q=f32(N, EW), A=f32(N, EW), P=f32(B * T * T), TH=f32(B * T * T),
+                  Zc=f32(N, D_HID), logits=f32(N, C), logp=f32(N, C), stats=f32(max(256, capi.head_ce_stats_floats(N))),
+                  dlogits=f32(N, C), dZc=f32(N, D_HID), dA=f32(N, EW), DZ=f32(B * T * T), dQ=f32(N, EW), dE=f32(N, EW),
+                  dGX=f32(N, 2 * GXW), dREC=f32(2 * N * capi.DIALOGRNN_DREC_ROW))
+        ws["sv"] = capi.dialogrnn_planes(ws["save"], N, capi.DIALOGRNN_SAVE)
+        ws["dr"] = capi.dialogrnn_planes(ws["dREC"], N, capi.DIALOGRNN_DREC)
+        ws["alpha"] = capi.dialogrnn_alpha(ws["save"], N, B, T)
+        ws["planner"] = GemmPlanner(device, 1 << 21, grad=self.flat.grad)
+        ws["jobs"] = None
+        return ws
+
+    def _shape(self, x, lens, label, n_nodes=None):
+        T, B = int(x.shape[0]), int(x.shape[1])
+        N = int(label.shape[0]) if label is not None else (int(n_nodes) if n_nodes is not None else int(lens.sum().item()))
+        return B, T, N
+
+    def _check(self, x, onehot, T):
+        if T > MAX_T:
+            raise capi.ErcGraftError("dialogrnn: the scan keeps the history of the global state in LDS, dialogues of up to %d "
+                                     "utterances are supported (batch T=%d)" % (MAX_T, T))
+        if int(onehot.shape[-1]) > MAX_S:
+            raise capi.ErcGraftError("dialogrnn: n_speakers=%d (up to %d party states are built)" % (int(onehot.shape[-1]), MAX_S))
+        if int(x.shape[-1]) != self.D_m:
+            raise capi.ErcGraftError("dialogrnn: input_tensor has %d features, D_m=%d" % (int(x.shape[-1]), self.D_m))
+        if x.dtype != torch.float32 or onehot.dtype != torch.float32:
+            raise capi.ErcGraftError("dialogrnn: input_tensor and speaker_tensor must be fp32 (one-hot speakers)")
+
+    def _drops(self, training):
+        return (self.drop_cell, self.drop_emo, self.drop_p) if training else (0.0, 0.0, 0.0)
+
+    def _forward_impl(self, x, onehot, lens, B, T, N, training, with_logits=True):
+        self._check(x, onehot, T)
+        fp = self.flat
+        ws = self._workspace(B, T, N, x.device)
+        pl = ws["planner"]
+        pl.reset()
+        D, C, S = self.D_m, self.n_classes, int(onehot.shape[-1])
+        x, onehot = x.contiguous(), onehot.contiguous()
+        capi.dialogrnn_meta(onehot, S, lens, B, T, N, ws["node_off"], ws["node_row"], ws["node_spk"])
+        capi.dialogrnn_pack(fp.data, self.offs, D, self.WT)
+        GX = ws["GX"]
+        for d, name in enumerate(DIRS):
+            c = name + ".dialogue_cell."
+            # [g_cell.weight_ih ; p_cell.weight_ih][:, :D] u + [b_ih^g ; b_ih^p], and W_a u, over the gathered valid rows
+            linear_fwd(pl, x, D, ws["node_row"], fp.w(c + "g_cell.weight_ih"), fp.w(c + "g_cell.bias_ih"), GX[:, d * GXW:], 2 * GXW,
+                       N, 900, D, ldw=D + D_G)
+            linear_fwd(pl, x, D, ws["node_row"], fp.w(c + "attention.transform.weight"), None, GX[:, d * GXW + 900:], 2 * GXW,
+                       N, D_G, D)
+        p_cell, p_emo, p_clf = self._drops(training)
+        capi.dialogrnn_scan_fwd(GX, 2 * GXW, self.WT, fp.data, self.offs, D, ws["node_off"], ws["node_spk"], B, T, S, N, p_cell, p_emo,
+                                self.rng_state, RNG_STREAM, ws["E"], EW, ws["save"])
+        E = ws["E"]
+        linear_fwd(pl, E, EW, None, fp.w("matchatt.transform.weight"), fp.w("matchatt.transform.bias"), ws["Q"], EW, N, EW, EW)
+        capi.match_att_fwd(E, EW, ws["Q"], EW, ws["node_off"], B, T, EW, ws["A"], EW, ws["P"], ws["TH"])
+        linear_fwd(pl, ws["A"], EW, None, fp.w("linear.weight"), fp.w("linear.bias"), ws["Zc"], D_HID, N, D_HID, EW,
+                   act=3 if p_clf > 0 else 1, drop_p=p_clf, rng=self.rng_state)
+        if with_logits:
+            linear_fwd(pl, ws["Zc"], D_HID, None, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ws["logits"], C, N, C, D_HID)
+        ws["x"], ws["S"] = x, S
+        return ws
+
+    def forward(self, input_tensor, speaker_tensor, attention_mask=None, text_length=None, label=None, **kwargs):
+        if self.flat is None:
+            raise capi.ErcGraftError("call DialogRNNModule.finalize(device) before forward")
+        B, T, N = self._shape(input_tensor, text_length, label, kwargs.get("n_nodes"))
+        ws = self._forward_impl(input_tensor, speaker_tensor, text_length, B, T, N, self.training)
+        capi.log_softmax_rows(ws["logits"], self.n_classes, self.n_classes, N, ws["logp"], self.n_classes)
+        return ws["logp"], ws["E"]
+
+    def loss_and_grads(self, batch, class_weight=None):
+        """MaskedNLLLoss(weight) of the log-probabilities (= class-weighted cross entropy of the valid rows' logits) and every
+        gradient into flat.grad"""
+        x, onehot, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
+        B, T, N = self._shape(x, lens, ys)
+        head = self.n_classes <= 8
+        ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=not head)
+        fp, pl, off = self.flat, ws["planner"], self.flat.offsets
+        C, D, S = self.n_classes, self.D_m, ws["S"]
+        E, dE, sv, dr = ws["E"], ws["dE"], ws["sv"], ws["dr"]
+        p_cell, p_emo, p_clf = self._drops(self.training)
+        # smax_fc + NLL of the log-softmax + their backward through the dropout / ReLU mask
+        if head:
+            capi.head_ce(ws["Zc"], D_HID, D_HID, C, N, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ys, class_weight,
+                         1.0 / (1.0 - p_clf), ws["logits"], C, ws["dlogits"], C, ws["dZc"], D_HID, ws["stats"])
+        else:
+            capi.cross_entropy(ws["logits"], C, C, N, None, ys, class_weight, 1.0, ws["dlogits"], C, ws["stats"])
+            capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("smax_fc.weight"), D_HID, 1, None, ws["dZc"], D_HID, N, D_HID, C,
+                          act=2, aux=ws["Zc"], ldaux=D_HID, act_scale=1.0 / (1.0 - p_clf))
+        linear_wgrad(pl, ws["dlogits"], C, ws["Zc"], D_HID, None, C, D_HID, N, off["smax_fc.weight"], off["smax_fc.bias"], defer=True)
+        capi.gemm_f32(ws["dZc"], D_HID, 0, None, fp.w("linear.weight"), EW, 1, None, ws["dA"], EW, N, EW, D_HID)
+        linear_wgrad(pl, ws["dZc"], D_HID, ws["A"], EW, None, D_HID, EW, N, off["linear.weight"], off["linear.bias"], defer=True)
+        # matching attention: dQ and dE (key side + score side); E is also the query transform's input
+        capi.match_att_bwd(E, EW, ws["Q"], EW, ws["dA"], EW, ws["node_off"], B, T, EW, ws["P"], ws["TH"], ws["DZ"], ws["dQ"], EW, dE, EW)
+        linear_wgrad(pl, ws["dQ"], EW, E, EW, None, EW, EW, N, off["matchatt.transform.weight"], off["matchatt.transform.bias"],
+                     defer=True)
+        capi.gemm_f32(ws["dQ"], EW, 0, None, fp.w("matchatt.transform.weight"), EW, 1, None, dE, EW, N, EW, EW, accumulate=1)
+        # both scans backwards in one launch
+        GX, dGX = ws["GX"], ws["dGX"]
+        capi.dialogrnn_scan_bwd(GX, 2 * GXW, self.WT, fp.data, self.offs, D, ws["node_off"], ws["node_spk"], B, T, S, N, p_cell, p_emo,
+                                self.rng_state, RNG_STREAM, ws["save"], dE, EW, dGX, 2 * GXW, ws["dREC"])
+        ldi = D + D_G
+        for d, name in enumerate(DIRS):
+            c = name + ".dialogue_cell."
+            g0 = d * GXW
+            # hoisted products: [d W_ih^g ; d W_ih^p][:, :D] and both input biases in one record, then d W_a
+            linear_wgrad(pl, dGX[:, g0:], 2 * GXW, ws["x"], D, ws["node_row"], 900, D, N, off[c + "g_cell.weight_ih"],
+                         off[c + "g_cell.bias_ih"], ld_w=ldi, defer=True)
+            linear_wgrad(pl, dGX[:, g0 + 900:], 2 * GXW, ws["x"], D, ws["node_row"], D_G, D, N, off[c + "attention.transform.weight"],
+                         None, defer=True)
+            # recurrent blocks: the state columns of the input-side weights, then the hidden-side weights
+            linear_wgrad(pl, dGX[:, g0:], 2 * GXW, sv["q_prev"][d], D_G, None, 450, D_G, N, off[c + "g_cell.weight_ih"], None,
+                         ld_w=ldi, col_off=D, defer=True)
+            linear_wgrad(pl, dGX[:, g0 + 450:], 2 * GXW, sv["c"][d], D_G, None, 450, D_G, N, off[c + "p_cell.weight_ih"], None,
+                         ld_w=ldi, col_off=D, defer=True)
+            linear_wgrad(pl, dr["dgh_g"][d], 450, sv["g_prev"][d], D_G, None, 450, D_G, N, off[c + "g_cell.weight_hh"],
+                         off[c + "g_cell.bias_hh"], defer=True)
+            linear_wgrad(pl, dr["dgh_p"][d], 450, sv["q_prev"][d], D_G, None, 450, D_G, N, off[c + "p_cell.weight_hh"],
+                         off[c + "p_cell.bias_hh"], defer=True)
+            linear_wgrad(pl, dr["dgi_e"][d], 300, sv["q_drop"][d], D_G, None, 300, D_G, N, off[c + "e_cell.weight_ih"],
+                         off[c + "e_cell.bias_ih"], defer=True)
+            linear_wgrad(pl, dr["dgh_e"][d], 300, sv["e_prev"][d], D_E, None, 300, D_E, N, off[c + "e_cell.weight_hh"],
+                         off[c + "e_cell.bias_hh"], defer=True)
+        pl.reduce_into(ws, fp.grad)
+        return ws["stats"]
+
+
+class DialogRNNTrainer:
+    """train_step / to_logits for ``--module=dialogrnn``: class-weighted MaskedNLLLoss, Adam lr 3e-4, no weight decay (the
+    defaults of the sibling plugin, track_mm/dgcnv2.py:22-48,184-219)."""
+
+    def __init__(self, params, device):
+        self.params, self.device = params, torch.device(device)
+        compute = params.get("compute", "f32")
+        if compute != "f32":
+            raise capi.ErcGraftError("--module=dialogrnn runs in fp32 (the reference is fp32); --compute=%s is not supported" % compute)
+        self.class_weight = None
+        if params.get("loss_weights", True):
+            if params.n_classes != 6:
+                raise capi.ErcGraftError("--loss_weights uses the six hard-coded IEMOCAP-6 inverse frequencies "
+                                         "(dgcnv2.py:213-214); run %d-class datasets with --loss_weights=False" % params.n_classes)
+            self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
+        torch.manual_seed(params.seed)
+        self.model = DialogRNNModule(params.hidden_all, D_G, D_G, D_E, D_HID, n_classes=params.n_classes, context_attention="general",
+                                     dropout_rec=params.get("dropout_rec", 0.5), dropout=params.get("dropout", 0.5),
+                                     compute=compute, seed=params.seed).finalize(self.device)
+        o = params.optim
+        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
+                               decoupled=(o.name == "AdamW"), seed=params.seed)
+        self.model.rng_state = self.optim.rng_state
+
+    def to_logits(self, batch):
+        return self.model(**batch)[0]
+
+    def prepare_batch(self, batch):
+        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+        tl = batch.get("text_length")
+        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
+            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
+        return out
+
+    def train_step(self, batch):
+        self.model.train()
+        stats = self.model.loss_and_grads(batch, self.class_weight)
+        scale = all_reduce_grads(self.model.flat)
+        self.optim.step(grad_scale=scale)
+        return stats

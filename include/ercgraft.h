@@ -1135,6 +1135,70 @@ int erc_dgcnv2_nodal_bwd(const float* E, int lde, const float* Q, int ldq, const
                          void* stream);
 
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * DialogueRNN (track_mm/dgcnv2_models.py:235-347 DialogueRNNCell / DialogueRNN, :428-487 DialogRNNModel;
+ * csrc/dialogrnn.hip), built for context_attention='general', listener_state=False, D_g = D_p = 150, D_e = 100, any D_m,
+ * fp32, n_speakers <= 9, dialogues of up to erc_dialogrnn_max_t() = 110 utterances (longer batches give ERC_E_ARG before
+ * anything is launched).  Rows are compact: node node_off[b] + t of the N = sum(lengths) valid utterances.
+ *
+ * erc_dialogrnn_meta: node_off [B+1], node_row [n_cap] = t*B + b (row of the time-major batch) and node_spk [n_cap] =
+ * argmax of the node's one-hot speaker row (first index of the maximum: torch.argmax, :275).  onehot [T, B, S] fp32.
+ *
+ * Parameters are addressed as `params` + offs_host[10 d + i] floats (d = 0 dialog_rnn_f, 1 dialog_rnn_r; a host array of
+ * 20 int64), i = 0 g_cell.weight_ih [450, D_m+150], 1 g_cell.weight_hh [450, 150], 2 g_cell.bias_hh, 3 p_cell.weight_ih
+ * [450, D_m+150], 4 p_cell.weight_hh [450, 150], 5 p_cell.bias_hh, 6 e_cell.weight_ih [300, 150], 7 e_cell.weight_hh
+ * [300, 100], 8 e_cell.bias_ih, 9 e_cell.bias_hh.  erc_dialogrnn_pack writes the copies of the recurrent blocks the scans
+ * stream, WT [4][345000] (erc_dialogrnn_wt_floats()): WT[d] = W_ih^g[:, D_m:]^T | W_hh^g^T | W_ih^p[:, D_m:]^T | W_hh^p^T |
+ * W_ih^e^T | W_hh^e^T (forward), WT[2 + d] = the same six blocks row-major and contiguous (backward); once per step,
+ * after the optimizer has changed the parameters.
+ *
+ * GX [N, ldgx >= 2100]: the hoisted u-side products, direction d in columns [1050 d, 1050 d + 1050):
+ *   W_ih^g[:, :D_m] u + b_ih^g (450) | W_ih^p[:, :D_m] u + b_ih^p (450) | W_a u (150, attention.transform, no bias)
+ *
+ * erc_dialogrnn_scan_fwd (replaces the Python loop of DialogueRNN.forward :340-345 with DialogueRNNCell.forward :267-309,
+ * _select_parties :260-265, MatchingAttention 'general' :123-126,147, _reverse_seq :445-457 and dropout_rec :465,470):
+ * both directions of all dialogues in one launch, one workgroup per (dialogue, direction); padded steps are not run and
+ * only the speaker's party cell is evaluated.  emotions [N, lde >= 200] = dropout(drop_rec)(e') with direction d in
+ * columns [100 d, 100 d + 100).  Dropout(drop_p) on g, q[p], e with masks keyed by (rng_state, rng_stream + d, element).
+ * save (erc_dialogrnn_save_floats(N, B, T) floats): planes [2][N][w] at float offset o * 2N, (o, w) =
+ *   gates_g (0, 450) r|z|n   ghn_g (450, 150)   g'_{s-1} (600, 150)   g (750, 150)   g' (900, 150)   c (1050, 150)
+ *   gates_p (1200, 450)      ghn_p (1650, 150)  q[p] before (1800, 150)  q (1950, 150)  q' (2100, 150)
+ *   gates_e (2250, 300)      ghn_e (2550, 100)  e'_{s-1} (2650, 100)  e (2750, 100)  e' (2850, 100)
+ * followed at 2950 * 2N by the attention weights alpha [2][B][T][T] (scan step s, history index j < s).
+ *
+ * erc_dialogrnn_scan_bwd: BPTT of the same from dEmo [N, ldde] (gradient wrt emotions).  Writes dGX [N, lddgx >= 2100]
+ * (gradient wrt GX: d W_ih[:, :D_m] = dGX^T u, d b_ih = colsum, d W_a likewise) and dREC, planes [2][N][w] at o * 2N:
+ *   dgh_g (0, 450)   dgh_p (450, 450)   dgi_e (900, 300)   dgh_e (1200, 300)     (n block of the dgh scaled by r)
+ * so that d W_hh^g = dgh_g^T g'_{s-1}, d W_ih^g[:, D_m:] = dGX[:, 0:450]^T q[p] before, d W_hh^p = dgh_p^T q[p] before,
+ * d W_ih^p[:, D_m:] = dGX[:, 450:900]^T c, d W_ih^e = dgi_e^T q', d W_hh^e = dgh_e^T e'_{s-1} and the bias gradients
+ * (column sums) are GEMMs by the caller.  The gradient of g'_j collects from the next global step and from the attention
+ * of every later step in a fixed order, one owner thread per element, no float atomics: a second run is bit-identical. */
+int erc_dialogrnn_max_t(void);
+int64_t erc_dialogrnn_wt_floats(void);
+int64_t erc_dialogrnn_save_floats(int64_t N, int B, int T);
+int erc_dialogrnn_meta(const float* onehot, int S, const int64_t* lengths, int B, int T, int n_cap, int32_t* node_off,
+                       int32_t* node_row, int32_t* node_spk, void* stream);
+int erc_dialogrnn_pack(const float* params, const int64_t* offs_host, int D_m, float* WT, void* stream);
+int erc_dialogrnn_scan_fwd(const float* GX, int ldgx, const float* WT, const float* params, const int64_t* offs_host, int D_m,
+                           const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N, float drop_p,
+                           float drop_rec, const uint64_t* rng_state, uint64_t rng_stream, float* emotions, int lde,
+                           float* save, void* stream);
+int erc_dialogrnn_scan_bwd(const float* GX, int ldgx, const float* WT, const float* params, const int64_t* offs_host, int D_m,
+                           const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N, float drop_p,
+                           float drop_rec, const uint64_t* rng_state, uint64_t rng_stream, const float* save,
+                           const float* dEmo, int ldde, float* dGX, int lddgx, float* dREC, void* stream);
+/* MatchingAttention 'general2' (dgcnv2_models.py:127-138,147) as DialogRNNModel.forward applies it to every time step
+ * (:473-480), per dialogue over its valid rows, for row width F (built: F = 200 = 2 D_e).  Operands, saved buffers and
+ * gradients as erc_dgcnv2_nodal_fwd / _bwd, which stay the 300-wide form. */
+int erc_match_att_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T, int F, float* A,
+                      int lda, float* P, float* TH, void* stream);
+int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
+                      int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE, int ldde,
+                      void* stream);
+/* y[r, :C] = x[r, :C] - logsumexp(x[r, :C]): F.log_softmax of the classifier (dgcnv2_models.py:486) */
+int erc_log_softmax_rows(const float* x, int ldx, int C, int n_rows, float* y, int ldy, void* stream);
+
+
 /* Test support (not part of the data path): fills the LDS of every CU with NaN bit patterns, so that a persistent
  * kernel that reads LDS it did not initialise fails its parity test deterministically.  sink: one int32, may be NULL. */
 int erc_test_poison_lds(int32_t* sink, void* stream);
