@@ -540,6 +540,18 @@ def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh
         _call("erc_lstm_scan_bwd", *args)
 
 
+def gru100_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
+                    rng_stream, gates, ghn, Hprev):
+    """hidden-100 weight-stationary GRU scan, one layer x both directions (csrc/gru100.hip; ercgraft.h)"""
+    _call("erc_gru100_scan_fwd", GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
+          rng_stream, gates, ghn, Hprev)
+
+
+def gru100_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX, dGH):
+    _call("erc_gru100_scan_bwd", W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream,
+          dGX, dGH)
+
+
 def gather_rows(src, lds, map_, N, F, dst, ldd, scatter=0):
     _call("erc_gather_rows", src, lds, map_, N, F, dst, ldd, scatter)
 

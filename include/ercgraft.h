@@ -834,6 +834,34 @@ int erc_lstm_scan_bwd_cap(const float* W_hh, const int64_t* lengths, const int32
                           float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, int zero_to, void* stream);
 
 /* ------------------------------------------------------------------------
+ * (Bi)GRU recurrence, hidden 100 per direction, torch.nn.GRU semantics (gate order r|z|n, h0 = 0; csrc/gru100.hip): the
+ * sequence encoder of conv-emotion's bc-GRU baseline, GRUModel (track_mm/dgcnv2_models.py:350-386: the nn.GRU of :358 as
+ * :368 runs it, unpacked over the padded length).  One layer, both directions per call, one workgroup per (dialogue,
+ * direction), the direction's W_hh in registers for the whole scan.  Arguments as erc_lstm_scan_fwd / _bwd:
+ *   GX [rows, >=600]: hoisted x W_ih^T + b_ih, direction d in columns [300d, 300d+300)  (one GEMM by the caller)
+ *   W_hh [2][300,100], b_hh [2][300]: weight_hh_l{k}, weight_hh_l{k}_reverse and their biases; b_hn stays inside
+ *            r * (W_hn h + b_hn)
+ *   lengths: int64 [B] (packed: dialogue b runs L_b steps, the reverse direction starts at L_b-1; positions
+ *            >= L_b produce zeros) or NULL (every dialogue runs T steps; with node_off: node_off[b+1] - node_off[b] steps)
+ *   rows: row(b,t) = b*sb + t*st (in rows), or node_off[b] + t when node_off != NULL
+ *   Hout [rows, ldh] columns [100d,100d+100); Hdrop (optional): the same with inverted dropout(drop_p) applied -- the
+ *   inter-layer dropout of nn.GRU; mask keyed by (rng_state, rng_stream, element)
+ *   saved for the backward: gates [rows,600] (post-activation r|z|n), ghn [rows,200] (W_hn h + b_hn), Hprev [rows,200]
+ *   (h_{t-1} in scan order); rows of padded positions are not written
+ * Backward: dHout = gradient wrt Hout (wrt Hdrop when drop_p > 0).  Writes dGX [rows,600] (d pre-activations of the input
+ * side: dW_ih = dGX^T x, db_ih = colsum) and dGH [rows,600] (the recurrent side, n block scaled by r:
+ * dW_hh[d] = dGH[:,300d:]^T Hprev[:,100d:], db_hh = colsum), both zero on padded rows -- GEMMs by the caller.  Every element
+ * is written by one thread, sums run in a fixed order: a second run is bit-identical.  No limit on T.
+ */
+int erc_gru100_scan_fwd(const float* GX, int ldgx, const float* W_hh, const float* b_hh, const int64_t* lengths,
+                        const int32_t* node_off, int64_t sb, int64_t st, int B, int T,
+                        float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p, const uint64_t* rng_state,
+                        uint64_t rng_stream, float* gates, float* ghn, float* Hprev, void* stream);
+int erc_gru100_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st,
+                        int B, int T, const float* gates, const float* ghn, const float* Hprev, const float* dHout, int lddh,
+                        float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH, void* stream);
+
+/* ------------------------------------------------------------------------
  * DialogueGCN graph operators (track_mm/dgcn_models.py:36-152, models/rgcn.py:264-355) over the CSRs of K1.
  */
 /* dst[i,:] = src[map[i],:] (scatter = 0) or dst[map[i],:] = src[i,:] (scatter = 1): compaction of the valid rows of
