@@ -15,6 +15,10 @@ valid rows -> Q = E W^T + b (GEMM) -> matching attention 'general2' per dialogue
 ReLU(Linear(200, 100)) + dropout in the GEMM epilogue -> smax_fc + class-weighted NLL in one launch.  The backward mirrors
 it; every weight gradient joins the step's batched weight-gradient launch (erc_wgrad_table).  One ``dropout`` value drives the
 RNN's inter-layer dropout and the classifier's (:357-358, :396-397).
+
+Capacity mode (``--capacity_buckets=True``, ``--resident``; off by default): the same chain with every launch sized for a
+bucket (B_cap, T_cap, N_cap) and the batch's node count and longest dialogue read from the device -- ``_forward_cap``,
+``BcRnnTrainer.capacity_bucket`` / ``all_capacity_buckets`` / ``resident_batch``; DESIGN.md section 8e.
 """
 import torch
 from torch import nn
@@ -55,6 +59,12 @@ class _BcRnnModule(nn.Module):
         self.matchatt = _Transform(2 * D_e)
         self.linear = nn.Linear(2 * D_e, D_h)
         self.smax_fc = nn.Linear(D_h, n_classes)
+        # CAPACITY MODE (trainer.StepGraphs buckets, trainer.ResidentEpochs): the batch tensors are capacity-sized static
+        # buffers -- B dialogue slots of which some may have length 0, T the longest dialogue of the split, label [N_cap] -- and
+        # every launch is sized for the capacities.  erc_bcrnn_meta_cap writes the batch's node count and its longest dialogue
+        # to the device (ws["counts"]): the scans run that many steps, the loss covers that many rows, and the kernels that own
+        # a gradient buffer zero its rows past them, so ONE captured HIP graph serves every batch that fits.
+        self.dynamic_n = False
         self.flat, self._ws, self._seed = None, WorkspaceCache(), seed
 
     def live_groups(self):
@@ -76,10 +86,12 @@ class _BcRnnModule(nn.Module):
         """workspace of the most recent forward (tests / bench read results out of it)"""
         return self._ws.last
 
-    def _workspace(self, B, T, N, device):
+    def _workspace(self, B, T, N, device, cap=False):
+        if cap:
+            return self._ws.get((B, T, N, "capacity"), lambda: self._make_workspace(B, T, N, device, cap=True))
         return self._ws.get((B, T, N), lambda: self._make_workspace(B, T, N, device))
 
-    def _make_workspace(self, B, T, N, device):
+    def _make_workspace(self, B, T, N, device, cap=False):
         # zeros, not empty: a stale NaN must never reach a weight-gradient GEMM through a row the step did not touch
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
@@ -88,6 +100,11 @@ class _BcRnnModule(nn.Module):
                   P=f32(B * T * T), TH=f32(B * T * T), Zc=f32(N, D_HID), logits=f32(N, C), logp=f32(N, C),
                   stats=f32(max(256, capi.head_ce_stats_floats(N))), dlogits=f32(N, C), dZc=f32(N, D_HID), dA=f32(N, EW),
                   DZ=f32(B * T * T), dQ=f32(N, EW), dE=f32(N, EW), dM=f32(BT, EW))
+        if cap:
+            # one more row behind the padded RNN output and behind the node gradient, never written by anything: the zero row
+            # that node_row (capacity nodes) and pad_node (padded positions) point at
+            ws.update(M=f32(BT + 1, EW), dE=f32(N + 1, EW), pad_node=i32(BT), x_row=i32(BT), counts=i32(2),
+                      label=torch.zeros(N, dtype=torch.int64, device=device))
         ws["planner"] = GemmPlanner(device, 4 * BT * 800 + 10 * (800 * D + 800 * 200) + (1 << 21), grad=self.flat.grad)
         ws["jobs"] = None
         return ws
@@ -106,9 +123,53 @@ class _BcRnnModule(nn.Module):
         if x.dtype != torch.float32 or onehot.dtype != torch.float32:
             raise capi.ErcGraftError("bc%s: input_tensor and speaker_tensor must be fp32 (one-hot speakers)" % self.CELL)
 
+    def _forward_cap(self, x, lens, B, T, N, training, desc=None, store_label=None):
+        """The forward in CAPACITY mode: B, T, N are capacities, the batch's own node count and longest dialogue are on the
+        device (ws["counts"] = [n_dev, t_dev]).  ``desc`` (int32 [2 B]: lengths | first store rows): RESIDENT batch -- x is the
+        feature store [U + 1, D] whose last row is zero, read through ws["x_row"]; labels are gathered into ws["label"].
+
+        Rows past the batch: the RNN's rows t >= *t_dev are not run (outputs written 0, gate gradients written 0 by the
+        backward scans); node rows i >= N gather the zero row of M, so E is 0 there; A / Zc of those rows are whatever an
+        earlier batch left (finite) and meet a zero gradient row in every weight-gradient product (dZc, dlogits: head_ce_cap;
+        dQ, dE: match_att_bwd_cap; dA = dZc W).  Dialogue slots the batch does not fill (length 0) run the RNN over zero
+        input; no valid node reads their rows, so the gradient wrt their outputs (pad_node -> the zero row of dE) and with it
+        every gate gradient of theirs is exactly 0."""
+        if T > MAX_T:
+            raise capi.ErcGraftError("bc%s: the 200-wide matching attention (erc_match_att_fwd) is built for dialogues of up to %d "
+                                     "utterances (T_cap=%d)" % (self.CELL, MAX_T, T))
+        if x.dtype != torch.float32 or int(x.shape[-1]) != self.D_m:
+            raise capi.ErcGraftError("bc%s: capacity mode needs fp32 features of width D_m=%d" % (self.CELL, self.D_m))
+        if desc is None and lens.dtype != torch.int64:
+            raise capi.ErcGraftError("bc%s: capacity mode needs int64 text_length" % self.CELL)
+        fp = self.flat
+        ws = self._workspace(B, T, N, x.device, cap=True)
+        pl = ws["planner"]
+        pl.reset()
+        D, BT = self.D_m, B * T
+        x = x.contiguous()
+        if desc is not None:
+            capi.bcrnn_meta_cap(None, desc, store_label, int(x.shape[0]) - 1, B, T, N, ws["node_off"], ws["node_row"], ws["pad_node"],
+                                ws["x_row"], ws["label"], ws["counts"])
+        else:
+            capi.bcrnn_meta_cap(lens, None, None, 0, B, T, N, ws["node_off"], ws["node_row"], ws["pad_node"], None, None,
+                                ws["counts"])
+        self.enc.forward(pl, x, D, BT, B, T, 1, B, None, training, self.rng_state, ws["M"], EW, store=ws,
+                         node_row=ws["x_row"] if desc is not None else None, t_dev=ws["counts"][1:])
+        E = ws["E"]
+        capi.gather_rows(ws["M"], EW, ws["node_row"], N, EW, E, EW)
+        linear_fwd(pl, E, EW, None, fp.w("matchatt.transform.weight"), fp.w("matchatt.transform.bias"), ws["Q"], EW, N, EW, EW)
+        capi.match_att_fwd(E, EW, ws["Q"], EW, ws["node_off"], B, T, EW, ws["A"], EW, ws["P"], ws["TH"])
+        p = self.drop_p if training else 0.0
+        linear_fwd(pl, ws["A"], EW, None, fp.w("linear.weight"), fp.w("linear.bias"), ws["Zc"], D_HID, N, D_HID, EW,
+                   act=3 if p > 0 else 1, drop_p=p, rng=self.rng_state)
+        ws["x"] = x
+        return ws
+
     def _forward_impl(self, x, onehot, lens, B, T, N, training, with_logits=True, att2=True):
         if not att2:
             raise capi.ErcGraftError("bc%s: att2=False is not built (the reference default, True, is)" % self.CELL)
+        if self.dynamic_n:
+            raise capi.ErcGraftError("bc%s: capacity mode (dynamic_n) is the training step's (loss_and_grads)" % self.CELL)
         self._check(x, onehot, T)
         fp = self.flat
         ws = self._workspace(B, T, N, x.device)
@@ -144,9 +205,19 @@ class _BcRnnModule(nn.Module):
         """MaskedNLLLoss(weight) of the log-probabilities (= class-weighted cross entropy of the valid rows' logits) and every
         gradient into flat.grad"""
         x, onehot, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
-        B, T, N = self._shape(x, lens, ys)
+        desc = batch.get("desc")          # resident batch (trainer.ResidentEpochs): the store + 2 B int32 of batch description
+        cap = self.dynamic_n or desc is not None
         head = self.n_classes <= 8
-        ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=not head)
+        if cap:
+            if not (self.dynamic_n and head):
+                raise capi.ErcGraftError("bc%s: capacity mode needs dynamic_n and at most 8 classes (erc_head_ce_cap)" % self.CELL)
+            B, T, N = batch["caps"] if desc is not None else self._shape(x, lens, ys)
+            ws = self._forward_cap(x, lens, B, T, N, self.training, desc=desc, store_label=ys if desc is not None else None)
+            if desc is not None:
+                ys = ws["label"]
+        else:
+            B, T, N = self._shape(x, lens, ys)
+            ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=not head)
         fp, pl, off = self.flat, ws["planner"], self.flat.offsets
         C = self.n_classes
         E, dE = ws["E"], ws["dE"]
@@ -154,7 +225,8 @@ class _BcRnnModule(nn.Module):
         # smax_fc + NLL of the log-softmax + their backward through the dropout / ReLU mask
         if head:
             capi.head_ce(ws["Zc"], D_HID, D_HID, C, N, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ys, class_weight,
-                         1.0 / (1.0 - p), ws["logits"], C, ws["dlogits"], C, ws["dZc"], D_HID, ws["stats"])
+                         1.0 / (1.0 - p), ws["logits"], C, ws["dlogits"], C, ws["dZc"], D_HID, ws["stats"],
+                         n_dev=ws["counts"] if cap else None)
         else:
             capi.cross_entropy(ws["logits"], C, C, N, None, ys, class_weight, 1.0, ws["dlogits"], C, ws["stats"])
             capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("smax_fc.weight"), D_HID, 1, None, ws["dZc"], D_HID, N, D_HID, C,
@@ -163,14 +235,19 @@ class _BcRnnModule(nn.Module):
         capi.gemm_f32(ws["dZc"], D_HID, 0, None, fp.w("linear.weight"), EW, 1, None, ws["dA"], EW, N, EW, D_HID)
         linear_wgrad(pl, ws["dZc"], D_HID, ws["A"], EW, None, D_HID, EW, N, off["linear.weight"], off["linear.bias"], defer=True)
         # matching attention: dQ and dE (key side + score side); E is also the query transform's input
-        capi.match_att_bwd(E, EW, ws["Q"], EW, ws["dA"], EW, ws["node_off"], B, T, EW, ws["P"], ws["TH"], ws["DZ"], ws["dQ"], EW, dE, EW)
+        capi.match_att_bwd(E, EW, ws["Q"], EW, ws["dA"], EW, ws["node_off"], B, T, EW, ws["P"], ws["TH"], ws["DZ"], ws["dQ"], EW, dE, EW,
+                           n_cap=N if cap else 0)
         linear_wgrad(pl, ws["dQ"], EW, E, EW, None, EW, EW, N, off["matchatt.transform.weight"], off["matchatt.transform.bias"],
                      defer=True)
         capi.gemm_f32(ws["dQ"], EW, 0, None, fp.w("matchatt.transform.weight"), EW, 1, None, dE, EW, N, EW, EW, accumulate=1)
         # back to the padded rows (zero on the padding: nothing downstream reads the RNN's output there), then the RNN
         dM = ws["dM"]
-        dM.zero_()
-        capi.gather_rows(dE, EW, ws["node_row"], N, EW, dM, EW, scatter=1)
+        if cap:
+            # every padded row fetches its node's gradient, or the zero row behind dE: no whole-buffer zero_() per step
+            capi.gather_rows(dE, EW, ws["pad_node"], B * T, EW, dM, EW)
+        else:
+            dM.zero_()
+            capi.gather_rows(dE, EW, ws["node_row"], N, EW, dM, EW, scatter=1)
         self.enc.backward(pl, dM, EW)
         pl.reduce_into(ws, fp.grad)
         return ws["stats"]
@@ -210,6 +287,112 @@ class BcRnnTrainer:
         self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
                                decoupled=(o.name == "AdamW"), seed=params.seed)
         self.model.rng_state = self.optim.rng_state
+        # capacity buckets are opt-in (--capacity_buckets=True; --resident implies them): the default stays the exact-shape
+        # step, whose dropout masks (keyed by the element index, so by B) a captured exact-shape graph must reproduce
+        self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
+        self._store_ext = None
+
+    N_BUCKET = 128     # capacity buckets: node counts rounded up to a multiple of this (the node launches scale with N_cap)
+
+    def _p2p(self):
+        """the opt-in peer-to-peer gradient exchange (ERC_DP_P2P=1): capacity buckets stay off there"""
+        import os
+        return getattr(self.model.flat, "p2p", None) is not None or os.environ.get("ERC_DP_P2P", "0") == "1"
+
+    def _capacity_ok(self, T_cap, batch=None):
+        ok = self.capacity and not self._p2p() and 0 < T_cap <= MAX_T and self.model.n_classes <= 8
+        if ok and batch is not None:
+            x, spk = batch["input_tensor"], batch["speaker_tensor"]
+            ok = (x.dtype == torch.float32 and x.dim() == 3 and int(x.shape[2]) == self.model.D_m and spk.dim() == 3 and
+                  batch["text_length"].dtype == torch.int64)
+        return bool(ok)
+
+    def _caps(self, batch):
+        T, B = batch["input_tensor"].shape[:2]            # time-major
+        return max(int(B), int(self.params.train.batch_size)), max(int(T), int(getattr(self, "t_cap", 0)))
+
+    def _n_cap(self, N, B_cap, T_cap):
+        return min(-(-N // self.N_BUCKET) * self.N_BUCKET, B_cap * T_cap)
+
+    def _bucket(self, like, B_cap, T_cap, N_cap):
+        x, spk, dev = like["input_tensor"], like["speaker_tensor"], self.device
+        D, S = int(x.shape[2]), int(spk.shape[2])
+
+        def make():
+            # "extent" (host side): the [T, B, N] block the last batch occupied -- all that fill has to clear
+            return dict(input_tensor=torch.zeros(T_cap, B_cap, D, dtype=x.dtype, device=dev),
+                        speaker_tensor=torch.zeros(T_cap, B_cap, S, dtype=spk.dtype, device=dev),
+                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
+                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev), extent=[0, 0, 0])
+
+        def fill(static, b):
+            # the RNN is unpacked: it READS the padded rows t < T_eff of every dialogue slot, so they must be zero, not stale.
+            # Only what the previous batch occupied and this one does not cover is cleared (never the whole capacity buffer).
+            Tb, Bb = (int(v) for v in b["input_tensor"].shape[:2])
+            Nb = int(b["label"].shape[0])
+            Tp, Bp, Np = static["extent"]
+            for k in ("input_tensor", "speaker_tensor"):
+                static[k][:Tb, :Bb].copy_(b[k], non_blocking=True)
+                if Tp > Tb:
+                    static[k][Tb:Tp, :Bp].zero_()
+                if Bp > Bb:
+                    static[k][:min(Tb, Tp), Bb:Bp].zero_()
+            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
+            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
+            static["label"][:Nb].copy_(b["label"], non_blocking=True)
+            if Np > Nb:
+                static["label"][Nb:Np].zero_()
+            static["extent"][:] = [Tb, Bb, Nb]
+
+        return ("capacity", B_cap, T_cap, N_cap), make, fill
+
+    def capacity_bucket(self, batch):
+        """trainer.StepGraphs: (key, make_static, fill) of the capacity bucket that holds ``batch`` (a prepared device batch),
+        or None: capacity buckets are off (the default), the peer-to-peer exchange is on, T_cap is above the matching
+        attention's limit, or the batch already has its bucket's shape (nothing to pad).  The exact-shape path runs then."""
+        if not self.capacity:
+            return None
+        B_cap, T_cap = self._caps(batch)
+        N = int(batch["label"].shape[0])
+        N_cap = self._n_cap(N, B_cap, T_cap)
+        T, B = batch["input_tensor"].shape[:2]
+        if not self._capacity_ok(T_cap, batch) or (int(B), int(T), N) == (B_cap, T_cap, N_cap):
+            return None
+        return self._bucket(batch, B_cap, T_cap, N_cap)
+
+    def all_capacity_buckets(self, batch):
+        """Every bucket a batch of this loader can fall into, smallest first, each with a synthetic filler (all B_cap
+        dialogues present, lengths adding up to the capacity, each <= T_cap): data parallel runs capture all of them up front,
+        in the same order on every rank.  The list depends only on what every rank shares -- B_cap = train.batch_size and T_cap
+        (trainer.bucket_t_cap) -- never on the probe batch's own N or shape."""
+        B_cap, T_cap = int(self.params.train.batch_size), int(getattr(self, "t_cap", 0))
+        if not self._capacity_ok(T_cap, batch):
+            return []
+        top = B_cap * T_cap
+        out = []
+        for N_cap in sorted({min(n, top) for n in range(self.N_BUCKET, top + self.N_BUCKET, self.N_BUCKET)}):
+            key, make, fill = self._bucket(batch, B_cap, T_cap, N_cap)
+
+            def synth(static, n=N_cap):
+                lens = torch.full((B_cap, ), n // B_cap, dtype=torch.int64)
+                lens[:n - int(lens.sum())] += 1                        # lengths add up to n, each <= T_cap
+                static["text_length"].copy_(lens)
+            out.append((key, make, fill, synth))
+        return out
+
+    def resident_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
+        """trainer.ResidentEpochs: the "batch" of a step whose dialogues stay in the HBM-resident store -- the feature rows, the
+        2 B_cap int32 the host rewrites per step (lengths | first store rows of the batch's dialogue slots) and the capacities
+        the launches are sized for.  The layer-0 projection reads the store's rows through the step's row map; padded
+        positions read a zero row, which the store does not have, so the features are kept once with one appended.  None
+        when the step cannot run that way (dtype or width of the store, T_cap above the attention's limit)."""
+        if store.fused.dtype != torch.float32 or int(store.fused.shape[1]) != self.model.D_m or not self._capacity_ok(T_cap):
+            return None
+        if self._store_ext is None or self._store_ext[0] is not store:
+            self._store_ext = (store, torch.cat([store.fused, torch.zeros(1, self.model.D_m, dtype=torch.float32,
+                                                                            device=store.fused.device)]))
+        return dict(input_tensor=self._store_ext[1], speaker_tensor=None, text_length=None, label=store.label, desc=cur_desc,
+                    caps=(B_cap, T_cap, N_cap))
 
     def to_logits(self, batch):
         return self.model(**batch)[0]

@@ -525,29 +525,58 @@ def dag_meta(speaker_onehot, speaker_ids, sb, st, S, lengths, B, T, spk, pred, n
     _call("erc_dag_meta", speaker_onehot, speaker_ids, sb, st, S, lengths, B, T, spk, pred, node_off, node_row)
 
 
+def _tcap_only(name, lengths, node_off):
+    if lengths is not None or node_off is not None:
+        raise ErcGraftError("%s: t_dev is the unpacked padded-row form (lengths=None, node_off=None)" % name)
+
+
 def lstm_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
-                  rng_stream, gates, Cst, Hprev):
+                  rng_stream, gates, Cst, Hprev, t_dev=None):
+    """``t_dev`` (device int32; unpacked padded rows): T is a capacity, *t_dev steps run (erc_lstm_scan_fwd_tcap, ercgraft.h)"""
+    if t_dev is not None:
+        _tcap_only("lstm_scan_fwd", lengths, node_off)
+        _call("erc_lstm_scan_fwd_tcap", GX, ldgx, W_hh, b_hh, sb, st, B, T, t_dev, Hout, ldh, Hdrop, ldhd, drop_p, rng, rng_stream,
+              gates, Cst, Hprev)
+        return
     _call("erc_lstm_scan_fwd", GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
           rng_stream, gates, Cst, Hprev)
 
 
-def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX, zero_to=0):
-    """``zero_to`` > 0 (compact rows): dGX rows [node_off[B], zero_to) are written 0 too (capacity mode)"""
+def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX, zero_to=0,
+                  t_dev=None):
+    """``zero_to`` > 0 (compact rows): dGX rows [node_off[B], zero_to) are written 0 too (capacity mode); ``t_dev`` (unpacked
+    padded rows): *t_dev steps run, dGX rows t >= *t_dev are written 0 (erc_lstm_scan_bwd_tcap)"""
     args = (W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
-    if zero_to:
+    if t_dev is not None:
+        _tcap_only("lstm_scan_bwd", lengths, node_off)
+        _call("erc_lstm_scan_bwd_tcap", W_hh, sb, st, B, T, t_dev, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
+    elif zero_to:
         _call("erc_lstm_scan_bwd_cap", *args, zero_to)
     else:
         _call("erc_lstm_scan_bwd", *args)
 
 
 def gru100_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
-                    rng_stream, gates, ghn, Hprev):
-    """hidden-100 weight-stationary GRU scan, one layer x both directions (csrc/gru100.hip; ercgraft.h)"""
+                    rng_stream, gates, ghn, Hprev, t_dev=None):
+    """hidden-100 weight-stationary GRU scan, one layer x both directions (csrc/gru100.hip; ercgraft.h); ``t_dev`` as
+    lstm_scan_fwd (erc_gru100_scan_fwd_tcap)"""
+    if t_dev is not None:
+        _tcap_only("gru100_scan_fwd", lengths, node_off)
+        _call("erc_gru100_scan_fwd_tcap", GX, ldgx, W_hh, b_hh, sb, st, B, T, t_dev, Hout, ldh, Hdrop, ldhd, drop_p, rng, rng_stream,
+              gates, ghn, Hprev)
+        return
     _call("erc_gru100_scan_fwd", GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
           rng_stream, gates, ghn, Hprev)
 
 
-def gru100_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX, dGH):
+def gru100_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX, dGH,
+                    t_dev=None):
+    """``t_dev`` as lstm_scan_bwd: dGX / dGH rows t >= *t_dev are written 0 (erc_gru100_scan_bwd_tcap)"""
+    if t_dev is not None:
+        _tcap_only("gru100_scan_bwd", lengths, node_off)
+        _call("erc_gru100_scan_bwd_tcap", W_hh, sb, st, B, T, t_dev, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX,
+              dGH)
+        return
     _call("erc_gru100_scan_bwd", W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream,
           dGX, dGH)
 
@@ -935,9 +964,13 @@ def head_ce_stats_floats(n_rows):
     return int(lib().erc_head_ce_stats_floats(n_rows))
 
 
-def head_ce(Z, ldz, F, Cn, n_rows, W, bias, labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats):
-    _call("erc_head_ce", Z, ldz, F, Cn, n_rows, W, bias, labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz,
-          stats)
+def head_ce(Z, ldz, F, Cn, n_rows, W, bias, labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats, n_dev=None):
+    """``n_dev`` (device int32): capacity mode, n_rows is the capacity and the batch its first *n_dev rows (ercgraft.h)"""
+    args = (Z, ldz, F, Cn, n_rows, W, bias, labels, weight, float(mask_scale), logits, ldl, dlogits, lddl, dZ, lddz, stats)
+    if n_dev is None:
+        _call("erc_head_ce", *args)
+    else:
+        _call("erc_head_ce_cap", *args, n_dev)
 
 
 # --------------------------------------------------------------------------- CIM (csrc/gru.hip, csrc/cim_attn.hip)
@@ -1067,8 +1100,19 @@ def match_att_fwd(E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH):
     _call("erc_match_att_fwd", E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH)
 
 
-def match_att_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde):
-    _call("erc_match_att_bwd", E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde)
+def match_att_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde, n_cap=0):
+    """``n_cap`` > 0: capacity mode, rows [node_off[B], n_cap) of dQ and dE are written 0 (ercgraft.h)"""
+    args = (E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde)
+    if n_cap:
+        _call("erc_match_att_bwd_cap", *args, n_cap)
+    else:
+        _call("erc_match_att_bwd", *args)
+
+
+def bcrnn_meta_cap(lengths, desc, store_label, zero_store_row, B, T, n_cap, node_off, node_row, pad_node, x_row, label_out, counts):
+    """index tables of a bc-LSTM / bc-GRU step in capacity mode; counts = [n_dev, t_dev] (ercgraft.h)"""
+    _call("erc_bcrnn_meta_cap", lengths, desc, store_label, zero_store_row, B, T, n_cap, node_off, node_row, pad_node, x_row,
+          label_out, counts)
 
 
 def log_softmax_rows(x, ldx, Cn, n_rows, y, ldy):

@@ -515,6 +515,46 @@ __global__ void drnn_meta_kernel(const float* onehot, int S, const int64_t* leng
     }
 }
 
+// bc-LSTM / bc-GRU in capacity mode (bcrnn.py): the index tables of a step whose launches are sized for (B, T, n_cap) while the
+// batch's own counts live on the device.  lengths [B] (int64) or desc [2 B] (int32: lengths | first store rows; RESIDENT).
+__global__ void bcrnn_meta_kernel(const int64_t* lengths, const int32_t* desc, const int64_t* store_label, int zero_store_row,
+                                  int B, int T, int n_cap, int32_t* node_off, int32_t* node_row, int32_t* pad_node, int32_t* x_row,
+                                  int64_t* label_out, int32_t* counts) {
+    __shared__ int s_off[1025];
+    if (threadIdx.x == 0) {
+        int acc = 0, tmax = 0;
+        for (int b = 0; b < B; ++b) {
+            s_off[b] = acc;
+            const int L = (int)min(max(desc ? (int64_t)desc[b] : lengths[b], (int64_t)0), (int64_t)T);
+            const int Lc = min(L, n_cap - acc);       // never past the capacity (the host sizes n_cap >= sum(lengths))
+            acc += Lc;
+            tmax = max(tmax, Lc);
+        }
+        s_off[B] = acc;
+        counts[0] = acc;       // n_dev
+        counts[1] = tmax;      // t_dev
+    }
+    __syncthreads();
+    const int N = s_off[B];
+    for (int b = threadIdx.x; b <= B; b += blockDim.x) node_off[b] = s_off[b];
+    // padded row t*B + b -> its node (n_cap: the zero row behind the node buffers) and, resident, its store row
+    for (int i = threadIdx.x; i < B * T; i += blockDim.x) {
+        const int t = i / B, b = i % B;
+        const int o = s_off[b], L = s_off[b + 1] - o;
+        pad_node[i] = t < L ? o + t : n_cap;
+        if (x_row) x_row[i] = t < L ? desc[B + b] + t : zero_store_row;
+        if (t < L) {
+            node_row[o + t] = i;
+            if (label_out && store_label) label_out[o + t] = store_label[desc[B + b] + t];
+        }
+    }
+    // capacity nodes: the zero row behind the padded buffers, label 0
+    for (int i = N + threadIdx.x; i < n_cap; i += blockDim.x) {
+        node_row[i] = B * T;
+        if (label_out && store_label) label_out[i] = 0;
+    }
+}
+
 __global__ void log_softmax_kernel(const float* x, int ldx, int C, int n_rows, float* y, int ldy) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
@@ -631,17 +671,27 @@ __global__ __launch_bounds__(MT) void match_fwd_kernel(const float* __restrict__
     M::store_tile(acc, A, lda, base, q0, L);
 }
 
+// capacity rows [n, n_cap) of a gradient the attention backward owns: written 0 by the whole grid, a row per workgroup and
+// round (no row has a dialogue, so no tile writes there; the caller's weight-gradient products run over all n_cap rows)
 template <int F>
+__device__ __forceinline__ void zero_tail_rows(float* __restrict__ out, int ld, int n, int n_cap) {
+    const int nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;
+    for (int row = max(n, 0) + wg; row < n_cap; row += nwg)
+        if (threadIdx.x < F) out[(int64_t)row * ld + threadIdx.x] = 0.f;
+}
+
+template <int F, bool CAP>
 __global__ __launch_bounds__(MT) void match_bwd_q_kernel(const float* __restrict__ E, int lde, const float* __restrict__ dA, int ldda,
                                                          const int32_t* __restrict__ node_off, int T, const float* __restrict__ Pg,
                                                          const float* __restrict__ THg, float* __restrict__ DZg,
-                                                         float* __restrict__ dQ, int lddq) {
+                                                         float* __restrict__ dQ, int lddq, int B, int n_cap) {
     using M = Att<F>;
     __shared__ __attribute__((aligned(16))) float sG[TILE * F];
     __shared__ __attribute__((aligned(16))) float sC[TILE * F];
     __shared__ float sS[TILE * TPAD];
     const int b = blockIdx.y, q0 = blockIdx.x * TILE;
     const int base = node_off[b], L = min(node_off[b + 1] - base, T);
+    if (CAP) zero_tail_rows<F>(dQ, lddq, node_off[B], n_cap);
     if (q0 >= L) return;
     M::load_tile(sG, dA, ldda, base, q0, L);
     M::tile_dots(sS, sG, E, lde, base, L, q0, sC, false);          // dp
@@ -668,10 +718,11 @@ __global__ __launch_bounds__(MT) void match_bwd_q_kernel(const float* __restrict
     M::store_tile(acc, dQ, lddq, base, q0, L);
 }
 
-template <int F>
+template <int F, bool CAP>
 __global__ __launch_bounds__(MT) void match_bwd_k_kernel(const float* __restrict__ Q, int ldq, const float* __restrict__ dA, int ldda,
                                                          const int32_t* __restrict__ node_off, int T, const float* __restrict__ Pg,
-                                                         const float* __restrict__ DZg, float* __restrict__ dE, int ldde) {
+                                                         const float* __restrict__ DZg, float* __restrict__ dE, int ldde, int B,
+                                                         int n_cap) {
     using M = Att<F>;
     __shared__ __attribute__((aligned(16))) float sG[TILE * F];
     __shared__ __attribute__((aligned(16))) float sQ[TILE * F];
@@ -679,6 +730,7 @@ __global__ __launch_bounds__(MT) void match_bwd_k_kernel(const float* __restrict
     __shared__ float sZ[TILE * TILE];
     const int b = blockIdx.y, k0 = blockIdx.x * TILE;
     const int base = node_off[b], L = min(node_off[b + 1] - base, T);
+    if (CAP) zero_tail_rows<F>(dE, ldde, node_off[B], n_cap);
     if (k0 >= L) return;
     f4 acc[M::PER];
 #pragma unroll
@@ -741,6 +793,19 @@ extern "C" int erc_dialogrnn_meta(const float* onehot, int S, const int64_t* len
     hipLaunchKernelGGL(drnn_meta_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, onehot, S, lengths, B, T, n_cap, node_off,
                        node_row, node_spk);
     ERC_LAUNCH_CHECK("dialogrnn_meta");
+    return ERC_OK;
+}
+
+extern "C" int erc_bcrnn_meta_cap(const int64_t* lengths, const int32_t* desc, const int64_t* store_label, int zero_store_row,
+                                  int B, int T, int n_cap, int32_t* node_off, int32_t* node_row, int32_t* pad_node, int32_t* x_row,
+                                  int64_t* label_out, int32_t* counts, void* stream) {
+    ERC_REQUIRE((lengths || desc) && node_off && node_row && pad_node && counts, "bcrnn_meta_cap: null pointer");
+    ERC_REQUIRE(!x_row || desc, "bcrnn_meta_cap: x_row needs the resident descriptor");
+    ERC_REQUIRE(!store_label || (desc && label_out), "bcrnn_meta_cap: store_label needs desc and label_out");
+    ERC_REQUIRE(B > 0 && B <= 1024 && T > 0 && n_cap > 0, "bcrnn_meta_cap: bad sizes B=%d T=%d n_cap=%d", B, T, n_cap);
+    hipLaunchKernelGGL(bcrnn_meta_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, lengths, desc, store_label, zero_store_row, B,
+                       T, n_cap, node_off, node_row, pad_node, x_row, label_out, counts);
+    ERC_LAUNCH_CHECK("bcrnn_meta_cap");
     return ERC_OK;
 }
 
@@ -819,9 +884,9 @@ extern "C" int erc_match_att_fwd(const float* E, int lde, const float* Q, int ld
     return ERC_OK;
 }
 
-extern "C" int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
-                                 int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE,
-                                 int ldde, void* stream) {
+extern "C" int erc_match_att_bwd_cap(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda,
+                                     const int32_t* node_off, int B, int T, int F, const float* P, const float* TH, float* DZ,
+                                     float* dQ, int lddq, float* dE, int ldde, int n_cap, void* stream) {
     ERC_REQUIRE(E && Q && dA && node_off && P && TH && DZ && dQ && dE, "match_att_bwd: null pointer");
     ERC_REQUIRE(F == 200, "match_att_bwd: built for row width 200 (2 D_e), got %d", F);
     ERC_REQUIRE(B > 0 && T > 0 && T <= MAXT, "match_att_bwd: bad sizes B=%d T=%d (T <= %d)", B, T, MAXT);
@@ -830,12 +895,27 @@ extern "C" int erc_match_att_bwd(const float* E, int lde, const float* Q, int ld
     ERC_REQUIRE(lde >= F && ldq >= F && ldda >= F && lddq >= F && ldde >= F, "match_att_bwd: row pitches below %d", F);
     ERC_REQUIRE(dE != E && dE != Q && dE != dA && dQ != E && dQ != dA, "match_att_bwd: outputs must not alias inputs");
     const dim3 grid(erc_cdiv(T, TILE), B);
-    hipLaunchKernelGGL(match_bwd_q_kernel<200>, grid, dim3(MT), 0, (hipStream_t)stream, E, lde, dA, ldda, node_off, T, P, TH, DZ, dQ,
-                       lddq);
-    ERC_LAUNCH_CHECK("match_att_bwd_q");
-    hipLaunchKernelGGL(match_bwd_k_kernel<200>, grid, dim3(MT), 0, (hipStream_t)stream, Q, ldq, dA, ldda, node_off, T, P, DZ, dE, ldde);
+    if (n_cap > 0) {
+        hipLaunchKernelGGL((match_bwd_q_kernel<200, true>), grid, dim3(MT), 0, (hipStream_t)stream, E, lde, dA, ldda, node_off, T, P,
+                           TH, DZ, dQ, lddq, B, n_cap);
+        ERC_LAUNCH_CHECK("match_att_bwd_q");
+        hipLaunchKernelGGL((match_bwd_k_kernel<200, true>), grid, dim3(MT), 0, (hipStream_t)stream, Q, ldq, dA, ldda, node_off, T, P,
+                           DZ, dE, ldde, B, n_cap);
+    } else {
+        hipLaunchKernelGGL((match_bwd_q_kernel<200, false>), grid, dim3(MT), 0, (hipStream_t)stream, E, lde, dA, ldda, node_off, T, P,
+                           TH, DZ, dQ, lddq, B, n_cap);
+        ERC_LAUNCH_CHECK("match_att_bwd_q");
+        hipLaunchKernelGGL((match_bwd_k_kernel<200, false>), grid, dim3(MT), 0, (hipStream_t)stream, Q, ldq, dA, ldda, node_off, T, P,
+                           DZ, dE, ldde, B, n_cap);
+    }
     ERC_LAUNCH_CHECK("match_att_bwd_k");
     return ERC_OK;
+}
+
+extern "C" int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
+                                 int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE,
+                                 int ldde, void* stream) {
+    return erc_match_att_bwd_cap(E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde, 0, stream);
 }
 
 extern "C" int erc_log_softmax_rows(const float* x, int ldx, int C, int n_rows, float* y, int ldy, void* stream) {

@@ -44,6 +44,7 @@ struct GruP {
     const float* dHout; int lddh;        // gradient wrt Hout (or wrt Hdrop when drop_p > 0)
     float* dGX;                          // [rows,600] gradient wrt the input-side pre-activations (0 on padded rows)
     float* dGH;                          // [rows,600] the recurrent side: the n block scaled by r  (0 on padded rows)
+    const int32_t* t_dev;                // *_tcap entry points (padded rows, unpacked): every dialogue runs *t_dev <= T steps
 };
 
 // rows of a dialogue: row(t) = base + t * step
@@ -57,6 +58,13 @@ __device__ __forceinline__ RowMap rows_of(const GruP& p, int b) {
 __device__ __forceinline__ int length_of(const GruP& p, int b) {
     if (p.node_off) return p.lengths ? (int)p.lengths[b] : p.node_off[b + 1] - p.node_off[b];
     return p.lengths ? min((int)p.lengths[b], p.T) : p.T;      // padded rows: never past the T rows of the dialogue
+}
+// T capacity (TDEV): the launch is sized for T = T_cap, the batch's own longest dialogue is read from the device.  Everything
+// below depends on the step count through L alone, so a (dialogue, direction) computes exactly what a launch with T = *t_dev
+// computes, in the same order, and the rows t >= *t_dev fall to the padded-position tails (zero outputs / gate gradients).
+template <bool TDEV>
+__device__ __forceinline__ int steps_of(const GruP& p, int b) {
+    return TDEV ? min(max(*p.t_dev, 0), p.T) : length_of(p, b);
 }
 typedef float f2 __attribute__((ext_vector_type(2)));
 // barrier that orders LDS traffic only: __syncthreads() fences global memory too, and so would wait for the chunk's loads
@@ -88,9 +96,10 @@ __device__ __forceinline__ int chunk_pos(int k) { return (k / CHK) * CHP + k % C
 // Thread layout of both scans: quad u = tid / 4 (< 100 live) owns hidden unit u.  Forward: lane q of the quad multiplies the
 // unit's THREE gate rows by h[25q .. 25q+25) (75 weights in registers, 25 LDS values a step), the quad sums by DPP and every
 // lane of it evaluates the cell (the same bits in the four lanes); lane q < 3 owns column q*100 + u of GX / gates.
+template <bool TDEV>
 __global__ __launch_bounds__(NTH) void gru100_fwd_kernel(GruP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
-    const int L = length_of(p, b);
+    const int L = steps_of<TDEV>(p, b);
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_h[2][HP];
     const int u = tid >> 2, q = tid & 3;
@@ -208,9 +217,10 @@ __global__ __launch_bounds__(NTH) void gru100_fwd_kernel(GruP p) {
 // The recurrent product (W_hh^T dGH)[u]: a DPP row of 16 lanes = 4 units; lane `part` < 12 of the row multiplies entries
 // [25 part, 25 part + 25) of the 300 gate gradients into each of the row's 4 units (100 weights in registers, 25 LDS values a
 // step; lanes 12 .. 15 hold zeros), the row sums by DPP in a fixed order.  The elementwise part keeps the quad layout.
+template <bool TDEV>
 __global__ __launch_bounds__(NTH) void gru100_bwd_kernel(GruP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
-    const int L = length_of(p, b);
+    const int L = steps_of<TDEV>(p, b);
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_dp[2][DGP];
     const int u = tid >> 2, q = tid & 3;
@@ -354,7 +364,7 @@ extern "C" int erc_gru100_scan_fwd(const float* GX, int ldgx, const float* W_hh,
     p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.lengths = lengths; p.node_off = node_off;
     p.sb = sb; p.st = st; p.B = B; p.T = T; p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
     p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.ghn = ghn; p.Hprev = Hprev;
-    hipLaunchKernelGGL(gru100_fwd_kernel, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(gru100_fwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru100_scan_fwd");
     return ERC_OK;
 }
@@ -371,7 +381,44 @@ extern "C" int erc_gru100_scan_bwd(const float* W_hh, const int64_t* lengths, co
     p.W_hh = W_hh; p.lengths = lengths; p.node_off = node_off; p.sb = sb; p.st = st; p.B = B; p.T = T;
     p.gates = const_cast<float*>(gates); p.ghn = const_cast<float*>(ghn); p.Hprev = const_cast<float*>(Hprev);
     p.dHout = dHout; p.lddh = lddh; p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.dGH = dGH;
-    hipLaunchKernelGGL(gru100_bwd_kernel, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(gru100_bwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru100_scan_bwd");
+    return ERC_OK;
+}
+
+// T capacity: the unpacked padded-row form (lengths = NULL, node_off = NULL) with the step count read from the device
+extern "C" int erc_gru100_scan_fwd_tcap(const float* GX, int ldgx, const float* W_hh, const float* b_hh, int64_t sb, int64_t st,
+                                        int B, int T, const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd,
+                                        float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* gates, float* ghn,
+                                        float* Hprev, void* stream) {
+    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && ghn && Hprev && t_dev, "gru100_scan_fwd_tcap: null pointer");
+    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G3 && ldh >= 2 * H, "gru100_scan_fwd_tcap: bad sizes B=%d T=%d ldgx=%d ldh=%d", B, T,
+                ldgx, ldh);
+    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "gru100_scan_fwd_tcap: ldhd=%d < 200", ldhd);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru100_scan_fwd_tcap: drop_p=%g outside [0, 1)", (double)drop_p);
+    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "gru100_scan_fwd_tcap: dropout needs rng_state");
+    GruP p{};
+    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
+    p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.ghn = ghn; p.Hprev = Hprev;
+    hipLaunchKernelGGL(gru100_fwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK("gru100_scan_fwd_tcap");
+    return ERC_OK;
+}
+
+extern "C" int erc_gru100_scan_bwd_tcap(const float* W_hh, int64_t sb, int64_t st, int B, int T, const int32_t* t_dev,
+                                        const float* gates, const float* ghn, const float* Hprev, const float* dHout, int lddh,
+                                        float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH,
+                                        void* stream) {
+    ERC_REQUIRE(W_hh && gates && ghn && Hprev && dHout && dGX && dGH && t_dev, "gru100_scan_bwd_tcap: null pointer");
+    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "gru100_scan_bwd_tcap: bad sizes B=%d T=%d lddh=%d", B, T, lddh);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru100_scan_bwd_tcap: drop_p=%g outside [0, 1)", (double)drop_p);
+    ERC_REQUIRE(drop_p <= 0.f || rng_state, "gru100_scan_bwd_tcap: dropout needs rng_state");
+    GruP p{};
+    p.W_hh = W_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
+    p.gates = const_cast<float*>(gates); p.ghn = const_cast<float*>(ghn); p.Hprev = const_cast<float*>(Hprev);
+    p.dHout = dHout; p.lddh = lddh; p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.dGH = dGH;
+    hipLaunchKernelGGL(gru100_bwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK("gru100_scan_bwd_tcap");
     return ERC_OK;
 }

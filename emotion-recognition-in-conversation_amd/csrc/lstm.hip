@@ -35,6 +35,7 @@ struct LstmP {
     const float* dHout; int lddh;        // gradient wrt Hout (or wrt Hdrop when drop_p > 0)
     float* dGX;                          // [rows,800] gradient wrt the gate pre-activations (0 on padded rows)
     int zero_to;                         // compact rows: rows [node_off[B], zero_to) of dGX are written 0 (capacity rows)
+    const int32_t* t_dev;                // *_tcap entry points (padded rows, unpacked): every dialogue runs *t_dev <= T steps
     unsigned long long* stamps;          // diagnostic (erc_lstm_set_stamps): shader-clock stamps of one step of workgroup (0,0)
 };
 unsigned long long* g_lstm_stamps = nullptr;
@@ -57,6 +58,13 @@ __device__ __forceinline__ RowMap rows_of(const LstmP& p, int b) {
 }
 __device__ __forceinline__ int length_of(const LstmP& p, int b) {
     return p.lengths ? (int)p.lengths[b] : p.node_off ? p.node_off[b + 1] - p.node_off[b] : p.T;
+}
+// T capacity (TDEV): the launch is sized for T = T_cap, the batch's own longest dialogue is read from the device.  Everything
+// below depends on the step count through L alone, so a (dialogue, direction) computes exactly what a launch with T = *t_dev
+// computes, in the same order, and the rows t >= *t_dev fall to the padded-position tails (zero outputs / gate gradients).
+template <bool TDEV>
+__device__ __forceinline__ int steps_of(const LstmP& p, int b) {
+    return TDEV ? min(max(*p.t_dev, 0), p.T) : length_of(p, b);
 }
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -95,9 +103,10 @@ __device__ __forceinline__ float dpp_mov(float v) {
 // (i|f|g|o).  The four gates of a unit meet through DPP moves inside the quad, the cell state / the recurrent gradients
 // live in registers (the same value in the 4 lanes), and the only LDS traffic is the vector every thread needs from all
 // others -- h_{t-1} forward, the gate gradients backward -- double-buffered, so a step has ONE barrier.
+template <bool TDEV>
 __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
-    const int L = length_of(p, b);
+    const int L = steps_of<TDEV>(p, b);
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_h[2][HP];
     const int u = tid >> 2, q = tid & 3;
@@ -251,10 +260,10 @@ __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
         }
 }
 
-template <bool ZERO_ROWS>     // capacity mode (zero_to > 0); the other instance compiles without it
+template <bool ZERO_ROWS, bool TDEV>     // capacity modes (zero_to > 0 | t_dev); the plain instance compiles without them
 __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
-    const int L = length_of(p, b);
+    const int L = steps_of<TDEV>(p, b);
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_dp[2][DPP_];     // gate gradients of the step, entry q*H + j chunked
     const int u = tid >> 2, q = tid & 3;
@@ -420,7 +429,7 @@ extern "C" int erc_lstm_scan_fwd(const float* GX, int ldgx, const float* W_hh, c
     p.sb = sb; p.st = st; p.B = B; p.T = T; p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
     p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.Cst = Cst; p.Hprev = Hprev;
     p.stamps = g_lstm_stamps;
-    hipLaunchKernelGGL(lstm_fwd_kernel, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(lstm_fwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("lstm_scan_fwd");
     return ERC_OK;
 }
@@ -438,9 +447,9 @@ extern "C" int erc_lstm_scan_bwd_cap(const float* W_hh, const int64_t* lengths, 
     p.gates = const_cast<float*>(gates); p.Cst = const_cast<float*>(Cst); p.dHout = dHout; p.lddh = lddh;
     p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.zero_to = zero_to;
     if (zero_to > 0)
-        hipLaunchKernelGGL(lstm_bwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL((lstm_bwd_kernel<true, false>), dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     else
-        hipLaunchKernelGGL(lstm_bwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL((lstm_bwd_kernel<false, false>), dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("lstm_scan_bwd");
     return ERC_OK;
 }
@@ -451,4 +460,37 @@ extern "C" int erc_lstm_scan_bwd(const float* W_hh, const int64_t* lengths, cons
                                  void* stream) {
     return erc_lstm_scan_bwd_cap(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng_state, rng_stream, dGX,
                                  0, stream);
+}
+
+// T capacity: the unpacked padded-row form (lengths = NULL, node_off = NULL) with the step count read from the device
+extern "C" int erc_lstm_scan_fwd_tcap(const float* GX, int ldgx, const float* W_hh, const float* b_hh, int64_t sb, int64_t st, int B,
+                                      int T, const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p,
+                                      const uint64_t* rng_state, uint64_t rng_stream, float* gates, float* Cst, float* Hprev,
+                                      void* stream) {
+    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && Cst && Hprev && t_dev, "lstm_scan_fwd_tcap: null pointer");
+    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G4 && ldh >= 2 * H, "lstm_scan_fwd_tcap: bad sizes B=%d T=%d", B, T);
+    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "lstm_scan_fwd_tcap: ldhd=%d < 200", ldhd);
+    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "lstm_scan_fwd_tcap: dropout needs rng_state");
+    LstmP p{};
+    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
+    p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.Cst = Cst; p.Hprev = Hprev;
+    hipLaunchKernelGGL(lstm_fwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK("lstm_scan_fwd_tcap");
+    return ERC_OK;
+}
+
+extern "C" int erc_lstm_scan_bwd_tcap(const float* W_hh, int64_t sb, int64_t st, int B, int T, const int32_t* t_dev,
+                                      const float* gates, const float* Cst, const float* dHout, int lddh, float drop_p,
+                                      const uint64_t* rng_state, uint64_t rng_stream, float* dGX, void* stream) {
+    ERC_REQUIRE(W_hh && gates && Cst && dHout && dGX && t_dev, "lstm_scan_bwd_tcap: null pointer");
+    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "lstm_scan_bwd_tcap: bad sizes B=%d T=%d lddh=%d", B, T, lddh);
+    ERC_REQUIRE(drop_p <= 0.f || rng_state, "lstm_scan_bwd_tcap: dropout needs rng_state");
+    LstmP p{};
+    p.W_hh = W_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
+    p.gates = const_cast<float*>(gates); p.Cst = const_cast<float*>(Cst); p.dHout = dHout; p.lddh = lddh;
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX;
+    hipLaunchKernelGGL((lstm_bwd_kernel<false, true>), dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK("lstm_scan_bwd_tcap");
+    return ERC_OK;
 }

@@ -245,21 +245,27 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
 constexpr int HC_MAXC = 8;
 constexpr int HC_MAXWG = 256;  // workgroups (one arrival atomic each)
 
+// CAP (erc_head_ce_cap): the launch is sized for n_rows = the capacity, the batch is the first *n_dev rows.  Rows past them
+// add nothing to the loss, the correct count or the weight sum, and their dlogits / dZ rows are written 0 (the weight-gradient
+// products of the caller run over all n_rows rows).
+template <bool CAP>
 __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ Z, int ldz, int F, int C, int n_rows,
                                                       const float* __restrict__ W, const float* __restrict__ bias,
                                                       const int64_t* __restrict__ labels,
                                                       const float* __restrict__ weight, float mask_scale,
                                                       float* __restrict__ logits, int ldl, float* __restrict__ dlogits,
                                                       int lddl, float* __restrict__ dZ, int lddz,
-                                                      float* __restrict__ stats, int rows_per_wg) {
+                                                      float* __restrict__ stats, int rows_per_wg,
+                                                      const int32_t* __restrict__ n_dev) {
     __shared__ double s_red[256];
     __shared__ double s_wsum;
     __shared__ float s_part[4][2];
     __shared__ int s_last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_valid = CAP ? min(max(*n_dev, 0), n_rows) : n_rows;
     if (weight) {
         double wacc = 0.0;
-        for (int i = tid; i < n_rows; i += 256) wacc += (double)weight[labels[i]];
+        for (int i = tid; i < n_valid; i += 256) wacc += (double)weight[labels[i]];
         s_red[tid] = wacc;
         __syncthreads();
         for (int o = 128; o > 0; o >>= 1) {
@@ -268,11 +274,12 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
         }
         if (tid == 0) s_wsum = s_red[0];
     } else if (tid == 0) {
-        s_wsum = (double)n_rows;
+        s_wsum = (double)n_valid;
     }
     __syncthreads();
     const double wsum = s_wsum;
-    const float inv_w = (float)(1.0 / wsum);
+    // an empty capacity batch (*n_dev = 0) has no row to weigh: every gradient row is written 0 and the loss reads 0, not 0 / 0
+    const float inv_w = CAP && !(wsum > 0.0) ? 0.f : (float)(1.0 / wsum);
     const bool h0 = lane < F, h1 = lane + 64 < F;
     const int c0 = min(lane, F - 1), c1 = min(lane + 64, F - 1);
     // unconditional clamped loads, masked afterwards (a guarded load costs a full round trip each)
@@ -289,6 +296,12 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
     for (int rr = wave; rr < rows_per_wg; rr += 4) {
         const int row = blockIdx.x * rows_per_wg + rr;
         if (row >= n_rows) break;
+        if (CAP && row >= n_valid) {      // wave-uniform: a capacity row
+            if (lane < C) logits[(int64_t)row * ldl + lane] = 0.f, dlogits[(int64_t)row * lddl + lane] = 0.f;
+            if (h0) dZ[(int64_t)row * lddz + lane] = 0.f;
+            if (h1) dZ[(int64_t)row * lddz + lane + 64] = 0.f;
+            continue;
+        }
         const float z0 = Z[(int64_t)row * ldz + c0], z1 = Z[(int64_t)row * ldz + c1];
         const int y = (int)labels[row];
         float lg[HC_MAXC];
@@ -359,7 +372,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
             __syncthreads();
         }
         if (tid == 0) {
-            stats[0] = (float)(lsum / wsum);
+            stats[0] = CAP && !(wsum > 0.0) ? 0.f : (float)(lsum / wsum);
             stats[1] = (float)s_red[0];
             stats[2] = (float)wsum;
             *reinterpret_cast<int*>(stats + 4) = 0;
@@ -475,19 +488,30 @@ __global__ __launch_bounds__(256) void ce_bce_multitask_kernel(const float* __re
 
 extern "C" int64_t erc_head_ce_stats_floats(int n_rows) { return 16 + 2 * HC_MAXWG; }
 
-extern "C" int erc_head_ce(const float* Z, int ldz, int F, int C, int n_rows, const float* W, const float* bias,
-                           const int64_t* labels, const float* weight, float mask_scale, float* logits, int ldl,
-                           float* dlogits, int lddl, float* dZ, int lddz, float* stats, void* stream) {
+extern "C" int erc_head_ce_cap(const float* Z, int ldz, int F, int C, int n_rows, const float* W, const float* bias,
+                               const int64_t* labels, const float* weight, float mask_scale, float* logits, int ldl,
+                               float* dlogits, int lddl, float* dZ, int lddz, float* stats, const int32_t* n_dev, void* stream) {
     ERC_REQUIRE(Z && W && bias && labels && logits && dlogits && dZ && stats, "head_ce: null pointer");
     ERC_REQUIRE(F > 0 && F <= 128 && C > 0 && C <= HC_MAXC && n_rows > 0, "head_ce: F=%d C=%d n_rows=%d unsupported", F, C, n_rows);
     int grid = erc_cdiv(n_rows, 16);
     if (grid > HC_MAXWG) grid = HC_MAXWG;
     const int rows_per_wg = erc_cdiv(n_rows, grid);
     grid = erc_cdiv(n_rows, rows_per_wg);
-    hipLaunchKernelGGL(head_ce_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, Z, ldz, F, C, n_rows, W, bias,
-                       labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats, rows_per_wg);
+    if (n_dev)
+        hipLaunchKernelGGL(head_ce_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, Z, ldz, F, C, n_rows, W, bias,
+                           labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats, rows_per_wg, n_dev);
+    else
+        hipLaunchKernelGGL(head_ce_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, Z, ldz, F, C, n_rows, W, bias,
+                           labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats, rows_per_wg, n_dev);
     ERC_LAUNCH_CHECK("head_ce");
     return ERC_OK;
+}
+
+extern "C" int erc_head_ce(const float* Z, int ldz, int F, int C, int n_rows, const float* W, const float* bias,
+                           const int64_t* labels, const float* weight, float mask_scale, float* logits, int ldl,
+                           float* dlogits, int lddl, float* dZ, int lddz, float* stats, void* stream) {
+    return erc_head_ce_cap(Z, ldz, F, C, n_rows, W, bias, labels, weight, mask_scale, logits, ldl, dlogits, lddl, dZ, lddz, stats,
+                           nullptr, stream);
 }
 
 extern "C" int64_t erc_bn_ws_floats(int F) { return (int64_t)BN_G * 2 * F * 2 + 16; }

@@ -56,8 +56,10 @@ class BiLSTM2:
         return ws
 
     def forward(self, pl, x, ldx, rows, B, T, sb, st, lengths, training, rng, out, ldo, x_bf16=False, node_off=None,
-                node_row=None, store=None):
+                node_row=None, store=None, t_dev=None):
         """x [*, d_in] -> out [rows, 200] (row pitch ldo).  Padded rows: row(b,t) = b*sb + t*st of x and of every buffer.
+        ``t_dev`` (device int32; unpacked padded rows only, ``lengths`` and ``node_off`` None): T is a capacity and every
+        dialogue runs *t_dev steps (erc_lstm_scan_fwd_tcap); ``node_row`` [rows] then only maps the rows of x.
         Compact rows (``node_off`` [B+1] and ``node_row`` [rows] given, packed sequences only): every buffer holds the
         ``rows`` = sum(lengths) valid positions in dialogue order (row = node_off[b] + t), x is read through node_row --
         the input projections, the saved state and the weight gradients shrink from B*T to sum(lengths) rows and the
@@ -68,18 +70,19 @@ class BiLSTM2:
                    self.d_in, x_bf16=x_bf16)
         capi.lstm_scan_fwd(ws["GX"][0], 8 * H, self._w("weight_hh_l0"), self._w("bias_hh_l0"), lengths, node_off, sb, st,
                            B, T, ws["H0"], 2 * H, ws["H0d"], 2 * H, p, rng, 0x5EED0, ws["gates"][0], ws["Cst"][0],
-                           ws["Hprev"][0])
+                           ws["Hprev"][0], t_dev=t_dev)
         linear_fwd(pl, ws["H0d"], 2 * H, None, self._w("weight_ih_l1"), self._w("bias_ih_l1"), ws["GX"][1], 8 * H, rows,
                    8 * H, 2 * H)
         capi.lstm_scan_fwd(ws["GX"][1], 8 * H, self._w("weight_hh_l1"), self._w("bias_hh_l1"), lengths, node_off, sb, st,
-                           B, T, out, ldo, None, 0, 0.0, None, 0, ws["gates"][1], ws["Cst"][1], ws["Hprev"][1])
-        self._last = (x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store)
+                           B, T, out, ldo, None, 0, 0.0, None, 0, ws["gates"][1], ws["Cst"][1], ws["Hprev"][1], t_dev=t_dev)
+        self._last = (x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store, t_dev)
 
     def backward(self, pl, dout, lddo, dx=None, lddx=0, zero_to=0):
         """dout = gradient wrt the layer-1 output.  Registers all weight-gradient jobs; optionally writes
         dx [rows, d_in] (needed when the LSTM input is itself trainable, MMGCN).  ``zero_to`` (compact rows, capacity mode):
-        the gate gradients of rows [node_off[B], zero_to) are written 0, so the weight gradients may run over all rows."""
-        x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store = self._last
+        the gate gradients of rows [node_off[B], zero_to) are written 0, so the weight gradients may run over all rows; after a
+        forward with ``t_dev`` the scans write those of rows t >= *t_dev 0 (ercgraft.h)."""
+        x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store, t_dev = self._last
         ws = self._buf(rows, dout.device, store)
         # one gate-gradient buffer per layer: every weight gradient of the LSTM then joins the step's ONE batched
         # weight-gradient launch (erc_wgrad_table) instead of 6 split-K GEMMs + a slab reduce per layer pair
@@ -87,11 +90,11 @@ class BiLSTM2:
             dGX = ws["dGX"][k]
             if k == 1:
                 capi.lstm_scan_bwd(self._w("weight_hh_l1"), lengths, node_off, sb, st, B, T, ws["gates"][1], ws["Cst"][1],
-                                   dout, lddo, 0.0, None, 0, dGX, zero_to=zero_to)
+                                   dout, lddo, 0.0, None, 0, dGX, zero_to=zero_to, t_dev=t_dev)
                 xin, ldin, d_in, bf, gat = ws["H0d"], 2 * H, 2 * H, False, None
             else:
                 capi.lstm_scan_bwd(self._w("weight_hh_l0"), lengths, node_off, sb, st, B, T, ws["gates"][0], ws["Cst"][0],
-                                   ws["dH0d"], 2 * H, p, rng, 0x5EED0, dGX, zero_to=zero_to)
+                                   ws["dH0d"], 2 * H, p, rng, 0x5EED0, dGX, zero_to=zero_to, t_dev=t_dev)
                 xin, ldin, d_in, bf, gat = x, ldx, self.d_in, x_bf16, node_row
             # W_ih (both directions stacked [800, d_in]) and b_ih
             linear_wgrad(pl, dGX, 8 * H, xin, ldin, gat, 8 * H, d_in, rows, self._off("weight_ih_l%d" % k),
@@ -152,34 +155,34 @@ class BiGRU2:
         return ws
 
     def forward(self, pl, x, ldx, rows, B, T, sb, st, lengths, training, rng, out, ldo, x_bf16=False, node_off=None,
-                node_row=None, store=None):
-        """x [*, d_in] -> out [rows, 200] (row pitch ldo); rows, lengths, node_off / node_row as BiLSTM2.forward"""
+                node_row=None, store=None, t_dev=None):
+        """x [*, d_in] -> out [rows, 200] (row pitch ldo); rows, lengths, node_off / node_row, t_dev as BiLSTM2.forward"""
         ws = self._buf(rows, out.device, store)
         p = self.drop_p if training else 0.0
         linear_fwd(pl, x, ldx, node_row, self._w("weight_ih_l0"), self._w("bias_ih_l0"), ws["GX"][0], 6 * H, rows, 6 * H,
                    self.d_in, x_bf16=x_bf16)
         capi.gru100_scan_fwd(ws["GX"][0], 6 * H, self._w("weight_hh_l0"), self._w("bias_hh_l0"), lengths, node_off, sb, st,
                              B, T, ws["H0"], 2 * H, ws["H0d"], 2 * H, p, rng, 0x6EED0, ws["gates"][0], ws["ghn"][0],
-                             ws["Hprev"][0])
+                             ws["Hprev"][0], t_dev=t_dev)
         linear_fwd(pl, ws["H0d"], 2 * H, None, self._w("weight_ih_l1"), self._w("bias_ih_l1"), ws["GX"][1], 6 * H, rows,
                    6 * H, 2 * H)
         capi.gru100_scan_fwd(ws["GX"][1], 6 * H, self._w("weight_hh_l1"), self._w("bias_hh_l1"), lengths, node_off, sb, st,
-                             B, T, out, ldo, None, 0, 0.0, None, 0, ws["gates"][1], ws["ghn"][1], ws["Hprev"][1])
-        self._last = (x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store)
+                             B, T, out, ldo, None, 0, 0.0, None, 0, ws["gates"][1], ws["ghn"][1], ws["Hprev"][1], t_dev=t_dev)
+        self._last = (x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store, t_dev)
 
     def backward(self, pl, dout, lddo, dx=None, lddx=0):
         """dout = gradient wrt the layer-1 output.  Registers all weight-gradient jobs; optionally writes dx [rows, d_in]."""
-        x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store = self._last
+        x, ldx, rows, B, T, sb, st, lengths, p, rng, x_bf16, node_off, node_row, store, t_dev = self._last
         ws = self._buf(rows, dout.device, store)
         for k in (1, 0):
             dGX, dGH = ws["dGX"][k], ws["dGH"][k]
             if k == 1:
                 capi.gru100_scan_bwd(self._w("weight_hh_l1"), lengths, node_off, sb, st, B, T, ws["gates"][1], ws["ghn"][1],
-                                     ws["Hprev"][1], dout, lddo, 0.0, None, 0, dGX, dGH)
+                                     ws["Hprev"][1], dout, lddo, 0.0, None, 0, dGX, dGH, t_dev=t_dev)
                 xin, ldin, d_in, bf, gat = ws["H0d"], 2 * H, 2 * H, False, None
             else:
                 capi.gru100_scan_bwd(self._w("weight_hh_l0"), lengths, node_off, sb, st, B, T, ws["gates"][0], ws["ghn"][0],
-                                     ws["Hprev"][0], ws["dH0d"], 2 * H, p, rng, 0x6EED0, dGX, dGH)
+                                     ws["Hprev"][0], ws["dH0d"], 2 * H, p, rng, 0x6EED0, dGX, dGH, t_dev=t_dev)
                 xin, ldin, d_in, bf, gat = x, ldx, self.d_in, x_bf16, node_row
             # W_ih (both directions stacked [600, d_in]) and b_ih = the column sums of dGX
             linear_wgrad(pl, dGX, 6 * H, xin, ldin, gat, 6 * H, d_in, rows, self._off("weight_ih_l%d" % k),

@@ -170,12 +170,13 @@ class StepGraphs:
     """Captured HIP graphs of the whole training step, least-recently-used eviction.
 
     * CAPACITY BUCKETS (trainers that offer ``capacity_bucket``: COGMEN in the bf16 compute mode, DialogueGCN on its default
-      path).  The reference reshuffles
+      path, bc-LSTM / bc-GRU with ``--capacity_buckets=True`` or ``--resident``).  The reference reshuffles
       the dialogues every epoch and its last batch is smaller (lumo/trainer/trainer.py:429-442, mmbase.py:468), so (B, T, N)
       almost never repeats.  A bucket is a set of static capacity-sized input buffers -- ``batch_size`` dialogues (missing
       ones get length 0), the longest training dialogue of every rank, N rounded up to the trainer's N_BUCKET (COGMEN 256,
-      DialogueGCN 128) -- plus one graph captured
-      over them; the step's kernels read the true node count from the device (COGMENModule.dynamic_n), so every batch
+      DialogueGCN and bc-LSTM / bc-GRU 128) -- plus one graph captured
+      over them; the step's kernels read the true node count from the device (COGMENModule.dynamic_n; the bc-RNN scans also
+      the batch's longest dialogue), so every batch
       that fits replays that graph: a reshuffled epoch hits a handful of graphs.
     * otherwise one graph per exact batch shape, captured when the shape shows up the SECOND time (under shuffling most
       shapes never repeat: capturing each one would cost a synchronisation + instantiation per step and pin a workspace).
@@ -332,7 +333,9 @@ class ResidentEpochs:
     semantics: every dialogue once, a smaller last batch) and uploads ONE int32 table [steps, 2 B] (lengths | first store
     rows of every batch's dialogues); per step it copies that step's 2 B int32 into the fixed descriptor buffer and replays
     the bucket's captured graph -- the projection launch reads feature rows, speakers and labels straight from the store
-    (csrc/cogmen_project.hip, resident mode).  Host work per step: one 256-byte device copy + one graph launch."""
+    (csrc/cogmen_project.hip, resident mode).  Host work per step: one 256-byte device copy + one graph launch.
+    Trainers with ``resident_batch``: COGMEN, DialogueGCN, bc-LSTM / bc-GRU (their layer-0 input projection reads the store
+    through the row map of erc_bcrnn_meta_cap)."""
 
     N_BUCKET = 128
 

@@ -433,6 +433,14 @@ int64_t erc_head_ce_stats_floats(int n_rows);
 int erc_head_ce(const float* Z, int ldz, int F, int C, int n_rows, const float* W, const float* bias,
                 const int64_t* labels, const float* weight, float mask_scale, float* logits, int ldl,
                 float* dlogits, int lddl, float* dZ, int lddz, float* stats, void* stream);
+/* erc_head_ce_cap: CAPACITY mode of the same (n_dev = NULL: erc_head_ce).  The launch is sized for n_rows, the batch is the
+ * first N = *n_dev rows (int32 on the device): rows >= N add nothing to the loss, the correct count or the weight sum, and
+ * their logits / dlogits / dZ rows are written 0, so weight-gradient products may run over all n_rows rows; N = 0 (or a zero
+ * weight sum) gives loss 0 and all-zero gradient rows, not 0 / 0 (the classifier of
+ * bc-LSTM / bc-GRU under bucketed graph replay, dgcnv2_models.py:384-386,423-425). */
+int erc_head_ce_cap(const float* Z, int ldz, int F, int C, int n_rows, const float* W, const float* bias,
+                    const int64_t* labels, const float* weight, float mask_scale, float* logits, int ldl,
+                    float* dlogits, int lddl, float* dZ, int lddz, float* stats, const int32_t* n_dev, void* stream);
 
 /* ------------------------------------------------------------------------
  * S4  optimizer over the flat live-parameter buffer (torch.optim.Adam /
@@ -832,6 +840,21 @@ int erc_lstm_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* 
 int erc_lstm_scan_bwd_cap(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st,
                           int B, int T, const float* gates, const float* Cst, const float* dHout, int lddh,
                           float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, int zero_to, void* stream);
+/* T CAPACITY (erc_lstm_scan_fwd_tcap / _bwd_tcap; "_bwd_cap" is the compact-row form above): the unpacked padded-row form
+ * (lengths = NULL, node_off = NULL, row = b*sb + t*st) of a launch sized for T = T_cap whose batch is only *t_dev <= T steps
+ * long (int32 on the device: the batch's longest dialogue) -- conv-emotion's bc-LSTM runs nn.LSTM on the padded tensor, so the
+ * reverse direction starts at the batch's last row, inside the padding of the shorter dialogues (dgcnv2_models.py:413-415).
+ * Both directions run exactly *t_dev steps, the reverse one from row t = *t_dev - 1; arithmetic and order of a (dialogue,
+ * direction) are those of erc_lstm_scan_fwd / _bwd launched with T = *t_dev, bit for bit, and so is the time (one workgroup
+ * per (dialogue, direction) whose loop runs *t_dev steps).  Rows t >= *t_dev: Hout and Hdrop are WRITTEN 0, the saved state
+ * (gates, Cst, Hprev) is left untouched, and the backward WRITES dGX = 0 there whatever an earlier, longer batch left, so
+ * the caller's weight-gradient products may run over all B * T rows. */
+int erc_lstm_scan_fwd_tcap(const float* GX, int ldgx, const float* W_hh, const float* b_hh, int64_t sb, int64_t st, int B, int T,
+                           const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p,
+                           const uint64_t* rng_state, uint64_t rng_stream, float* gates, float* Cst, float* Hprev, void* stream);
+int erc_lstm_scan_bwd_tcap(const float* W_hh, int64_t sb, int64_t st, int B, int T, const int32_t* t_dev, const float* gates,
+                           const float* Cst, const float* dHout, int lddh, float drop_p, const uint64_t* rng_state,
+                           uint64_t rng_stream, float* dGX, void* stream);
 
 /* ------------------------------------------------------------------------
  * (Bi)GRU recurrence, hidden 100 per direction, torch.nn.GRU semantics (gate order r|z|n, h0 = 0; csrc/gru100.hip): the
@@ -860,6 +883,17 @@ int erc_gru100_scan_fwd(const float* GX, int ldgx, const float* W_hh, const floa
 int erc_gru100_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st,
                         int B, int T, const float* gates, const float* ghn, const float* Hprev, const float* dHout, int lddh,
                         float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH, void* stream);
+/* T CAPACITY of the same (as erc_lstm_scan_fwd_tcap / _bwd_tcap; bc-GRU, dgcnv2_models.py:374-376): unpacked padded rows, the
+ * launch sized for T = T_cap, both directions run *t_dev <= T steps (int32 on the device), the reverse one from row
+ * t = *t_dev - 1, bit-identical to a launch with T = *t_dev.  Rows t >= *t_dev: Hout / Hdrop are WRITTEN 0, the saved state is
+ * left untouched, the backward WRITES dGX = dGH = 0. */
+int erc_gru100_scan_fwd_tcap(const float* GX, int ldgx, const float* W_hh, const float* b_hh, int64_t sb, int64_t st, int B, int T,
+                             const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p,
+                             const uint64_t* rng_state, uint64_t rng_stream, float* gates, float* ghn, float* Hprev,
+                             void* stream);
+int erc_gru100_scan_bwd_tcap(const float* W_hh, int64_t sb, int64_t st, int B, int T, const int32_t* t_dev, const float* gates,
+                             const float* ghn, const float* Hprev, const float* dHout, int lddh, float drop_p,
+                             const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH, void* stream);
 
 /* ------------------------------------------------------------------------
  * DialogueGCN graph operators (track_mm/dgcn_models.py:36-152, models/rgcn.py:264-355) over the CSRs of K1.
@@ -1223,6 +1257,23 @@ int erc_match_att_fwd(const float* E, int lde, const float* Q, int ldq, const in
 int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
                       int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE, int ldde,
                       void* stream);
+/* erc_match_att_bwd_cap (n_cap = 0: erc_match_att_bwd): CAPACITY mode -- dQ and dE hold n_cap rows of which the batch uses
+ * the first node_off[B]; the rows [node_off[B], n_cap) of both are written 0 by the same two launches, so the caller's
+ * weight-gradient products may run over all n_cap rows whatever a larger batch left there. */
+int erc_match_att_bwd_cap(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
+                          int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE,
+                          int ldde, int n_cap, void* stream);
+/* bc-LSTM / bc-GRU (LSTMModel / GRUModel, dgcnv2_models.py:389-425 / :350-386) in CAPACITY mode: the index tables of a step
+ * whose launches are sized for B dialogue slots (missing ones: length 0), T = T_cap and n_cap nodes, from lengths [B] (int64)
+ * or, RESIDENT, from desc [2 B] (int32: lengths | first store rows).  Rows are time-major (t*B + b, batch_first=False).
+ *   node_off [B+1]; node_row [n_cap] = t*B + b of node node_off[b] + t, and B*T for the capacity nodes i >= N (a row the
+ *   caller keeps zero behind its padded buffers); pad_node [B*T] = the node of padded row t*B + b, and n_cap where t >=
+ *   length (a row the caller keeps zero behind its node buffers); counts[0] = N = sum(lengths) (n_dev), counts[1] = the
+ *   longest dialogue (t_dev).  Resident only (NULL otherwise): x_row [B*T] = store row first[b] + t of padded row t*B + b,
+ *   zero_store_row where t >= length; label_out [n_cap] = store_label of the node's store row, 0 for i >= N. */
+int erc_bcrnn_meta_cap(const int64_t* lengths, const int32_t* desc, const int64_t* store_label, int zero_store_row, int B, int T,
+                       int n_cap, int32_t* node_off, int32_t* node_row, int32_t* pad_node, int32_t* x_row, int64_t* label_out,
+                       int32_t* counts, void* stream);
 /* y[r, :C] = x[r, :C] - logsumexp(x[r, :C]): F.log_softmax of the classifier (dgcnv2_models.py:486) */
 int erc_log_softmax_rows(const float* x, int ldx, int C, int n_rows, float* y, int ldy, void* stream);
 
