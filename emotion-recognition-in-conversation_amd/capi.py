@@ -808,6 +808,15 @@ def head_fused_bn(H2, ldh, n_rows, F, C, gamma, beta, saved, slope, W0, b0, W3, 
           label_rows, int(lddl))
 
 
+def head_eval(H2, ldh, n_rows, F, C, gamma, beta, running_mean, running_var, eps, slope, W0, b0, W3, b3, labels, cm, logits=None,
+              n_dev=None, label_rows=None):
+    """eval-mode head scored on the device: cm int64 [C, C] (true x predicted) is added to (erc_head_eval, ercgraft.h)"""
+    if cm.dtype != torch.int64 or cm.numel() != C * C or not cm.is_contiguous():
+        raise ErcGraftError("head_eval: cm must be a contiguous int64 [%d, %d] tensor" % (C, C))
+    _call("erc_head_eval", H2, ldh, n_rows, F, C, gamma, beta, running_mean, running_var, float(eps), float(slope), W0, b0, W3, b3,
+          labels, label_rows, n_dev, cm, logits)
+
+
 def head_fused_rows_per_workgroup(n_rows):
     return int(lib().erc_head_fused_rows_per_workgroup(int(n_rows)))
 

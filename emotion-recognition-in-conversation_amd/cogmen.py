@@ -117,6 +117,7 @@ class COGMENModule(nn.Module):
         self.fused_optim = None
         self.flat = None
         self._ws = WorkspaceCache()
+        self._eval_ws = {}             # (B, T, N) capacities -> buffers of the forward-only step (eval_scores)
         self._seed = seed
 
     # ------------------------------------------------------------------ setup
@@ -386,6 +387,70 @@ class COGMENModule(nn.Module):
         linear_fwd(pl, ws["H3"], F, None, fp.w("cls.0.weight"), fp.w("cls.0.bias"), ws["Z"], F, N, F, F,
                    act=3 if p > 0 else 1, drop_p=p, rng=self.rng_state)
         linear_fwd(pl, ws["Z"], F, None, fp.w("cls.3.weight"), fp.w("cls.3.bias"), ws["logits"], C, N, C, F)
+        return ws
+
+    # ------------------------------------------------------------- evaluation
+    def _eval_workspace(self, B, T, N, device):
+        """The forward-only step's own buffers, keyed by capacity: a training bucket of the same (B, T, N) also carries host-side
+        flags of the step in flight (bn_in_tile, head_deferred) and the weight-gradient table -- nothing of that is shared."""
+        ws = self._eval_ws.get((B, T, N))
+        if ws is not None:
+            return ws
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
+        z32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        bf = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=device)
+        E, F = N * (WP + WF + 1), F_HID
+        g = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), in_ptr=i32(N + 1), in_src=i32(E),
+                 in_typ=i32(E), out_ptr=i32(N + 1), out_dst=i32(E), out_typ=i32(E), out_eid=i32(E), counts=i32(2))
+        ws = dict(g=g, E=E, H0=f32(N, F), inv_cnt=f32(N, N_REL), QKVS=f32(N, 4 * F), alpha=f32(E), H2=f32(N, F),
+                  logits=z32(N, self.n_classes))
+        if self.terms > 1:
+            ws.update(M=z32(N, 9 * F), H1=z32(N, F))
+        else:
+            ws.update(Mb=bf(N, PM), H1b=bf(N, PA))
+        self._eval_ws[(B, T, N)] = ws
+        return ws
+
+    def eval_scores(self, batch, cm):
+        """Forward-only step in capacity form, scored on the device: the project-and-graph launch, the forward tile kernel
+        (node count from the device, no BatchNorm tile sums, no health roll) and the evaluation head (csrc/head.hip,
+        erc_head_eval), which ADDS the batch's confusion matrix to ``cm`` (int64 [C, C], true x predicted).  Three launches, no
+        host synchronisation, capturable.  ``batch``: a resident batch (``desc`` + ``caps``, as loss_and_grads takes) or a
+        capacity-sized static one (B dialogue slots of which some may have length 0, label [N_cap]).  Returns the workspace
+        (``logits`` [N_cap, C]: rows below the device count are valid).  Touches no training state."""
+        if self.flat is None:
+            raise capi.ErcGraftError("call COGMENModule.finalize(device) before eval_scores")
+        x, spk, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
+        desc = batch.get("desc")
+        B, T, N = batch["caps"] if desc is not None else (x.shape[0], x.shape[1], int(ys.shape[0]))
+        F, C, D = F_HID, self.n_classes, self.input_size
+        split = self.terms > 1
+        ok = (self.fused_graph and self.fuse_project_graph and self.w1_shadow is not None and self.enc_train is None
+              and x.dtype == (torch.float32 if split else torch.bfloat16) and spk.dim() == (1 if desc is not None else 2)
+              and x.is_contiguous() and C <= 8 and N <= self.BN_FUSED_MAX_N and capi.cogmen_project_graph_ok(D, F, B, D, D))
+        if not ok:
+            raise capi.ErcGraftError("COGMEN eval_scores needs the fused bf16 / split path in capacity mode (supports_capacity)")
+        fp, bn = self.flat, self.gcn.bn
+        ws = self._eval_workspace(B, T, N, x.device)
+        g = ws["g"]
+        if self._shadow_auto:      # nobody keeps the bf16 weight copies in sync (no optimizer attached)
+            self.refresh_shadows()
+        capi.cogmen_project_graph(x, D, self.w1_shadow, D, fp.w("rnn.1.bias"), ws["H0"], F, F, D, lens, spk, B, T, WP, WF,
+                                  self.n_speakers, N, ws["E"], g, desc=desc, terms=self.terms, w_plane=self._sh_plane["w1"])
+        tile_kw = dict(bn_fused=0, n_speakers=self.n_speakers, n_dev=g["counts"])
+        if split:
+            capi.cogmen_fwd_tile(ws["H0"], F, N, WP, WF, g, self._sh["catT"], fp.w("gcn.conv1.bias"), self._sh["q"],
+                                 fp.w("gcn.conv2.lin_query.bias"), 1.0 / math.sqrt(F), ws["M"], 9 * F, ws["inv_cnt"],
+                                 ws["H1"], F, ws["QKVS"], ws["H2"], F, ws["alpha"], terms=self.terms,
+                                 catT_plane=self._sh_plane["catT"], q_plane=self._sh_plane["q"], **tile_kw)
+        else:
+            capi.cogmen_fwd_tile(ws["H0"], F, N, WP, WF, g, self._sh["catT"], fp.w("gcn.conv1.bias"), self._sh["q"],
+                                 fp.w("gcn.conv2.lin_query.bias"), 1.0 / math.sqrt(F), ws["Mb"], PM, ws["inv_cnt"],
+                                 ws["H1b"], PA, ws["QKVS"], ws["H2"], F, ws["alpha"], **tile_kw)
+        capi.head_eval(ws["H2"], F, N, F, C, fp.w("gcn.bn.weight"), fp.w("gcn.bn.bias"), bn.running_mean, bn.running_var, bn.eps,
+                       0.01, fp.w("cls.0.weight"), fp.w("cls.0.bias"), fp.w("cls.3.weight"), fp.w("cls.3.bias"), ys, cm,
+                       logits=ws["logits"], n_dev=g["counts"], label_rows=g["node_row"] if desc is not None else None)
         return ws
 
     def check_cluster(self):
@@ -770,6 +835,16 @@ class COGMENTrainer:
             return None
         return dict(input_tensor=store.fused, speaker_tensor=store.speaker, text_length=None, label=store.label, desc=cur_desc,
                     caps=(B_cap, T_cap, N_cap))
+
+    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
+        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
+        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
+        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
+
+    def resident_eval_step(self, batch, cm):
+        """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
+        sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
+        return self.model.eval_scores(batch, cm)
 
     def all_capacity_buckets(self, batch):
         """Every bucket a batch of this loader can fall into, smallest first, each with a synthetic filler (all B_cap

@@ -970,9 +970,183 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// EVALUATION HEAD: H2 -> confusion matrix (the forward half of head_fused_kernel<false, 1> in eval mode; trainer.ResidentEval).
+//   H3 = LeakyReLU(BatchNorm(H2; running statistics))   Z = ReLU(H3 W0^T + b0)   logits = Z W3^T + b3
+//   pred = first index of the maximum (torch.argmax)    cm[label][pred] += 1
+// Same tiling: a workgroup of 8 wavefronts takes 16 rows, wavefront w the column tile w of the 7 (the eighth adds zeros), W0
+// staged once per workgroup with pitch HF_S, the 100 -> C product on the VALU from the accumulator layout, the class space
+// exchanged through LDS.  Counts are integers: a [8][8] histogram per workgroup in LDS, then one vector atomic add per
+// non-empty cell -- order-independent, hence deterministic.  Rows at or beyond the count are neither read nor counted (a
+// workgroup without rows returns before it loads anything); nothing of the training state is written.
+struct HeadEvalP {
+    const float* H2;
+    const float* gamma;
+    const float* beta;
+    const float* rmean;
+    const float* rvar;
+    const float* W0;
+    const float* b0;
+    const float* W3;
+    const float* b3;
+    const int64_t* labels;
+    const int32_t* label_rows;
+    const int32_t* n_dev;
+    long long* cm;       // [C][C] true class x predicted class, added to
+    float* logits;       // [n_rows][C] or null
+    float slope, eps;
+    int ldh, N, F, C;
+};
+
+__global__ __launch_bounds__(512) void head_eval_kernel(const HeadEvalP p) {
+    __shared__ __attribute__((aligned(16))) float sW[HF_MAXF * HF_S];      // W0, row pitch HF_S
+    __shared__ __attribute__((aligned(16))) float sPar[4][112];            // mean | rstd | gamma | beta of the columns
+    __shared__ float sLg[8][16][8];                                        // [column tile][row][class] partial logits
+    __shared__ int sCm[HF_MAXC * HF_MAXC];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int F = p.F, C = p.C, N = p.n_dev ? min(max(*p.n_dev, 0), p.N) : p.N;
+    const int m0 = (int)blockIdx.x * 16;
+    if (m0 >= N) return;      // (uniform) no row of this tile counts: nothing is read
+    const int mrc = min(m0 + r, N - 1);
+    f32x4 xh[HF_NT];
+#pragma unroll
+    for (int kb = 0; kb < HF_NT; ++kb) {
+        const int k0 = 16 * kb + 4 * g;
+        xh[kb] = *reinterpret_cast<const f32x4*>(p.H2 + (int64_t)mrc * p.ldh + (k0 < F ? k0 : 0));
+    }
+    {   // W0 (F x F) -> LDS: F*F/4 <= 2500 float4 over 512 threads, all loads in flight
+        const int nq = F * F / 4, per_row = F / 4;
+        f32x4 v[5];
+        int dst[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const int i = min(j * 512 + tid, nq - 1);
+            const int row = i / per_row, q = i - row * per_row;
+            v[j] = *reinterpret_cast<const f32x4*>(p.W0 + (int64_t)row * F + 4 * q);
+            dst[j] = row * HF_S + 4 * q;
+        }
+        if (tid < 112) {
+            const int cc = min(tid, F - 1);
+            sPar[0][tid] = p.rmean[cc], sPar[1][tid] = 1.f / sqrtf(p.rvar[cc] + p.eps);
+            sPar[2][tid] = p.gamma[cc], sPar[3][tid] = p.beta[cc];
+        }
+        if (tid < HF_MAXC * HF_MAXC) sCm[tid] = 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            if (j * 512 + tid < nq) *reinterpret_cast<f32x4*>(sW + dst[j]) = v[j];
+    }
+    // operands of the later phases, requested before the barrier
+    const int col = 16 * w + r, colc = min(col, F - 1);
+    const float cmk = col < F ? 1.f : 0.f;
+    const float b0c = p.b0[colc];
+    float w3[HF_MAXC];
+#pragma unroll
+    for (int c = 0; c < HF_MAXC; ++c) w3[c] = p.W3[(int64_t)min(c, C - 1) * F + colc] * cmk * (c < C ? 1.f : 0.f);
+    const int cr = r & 7;
+    const float b3c = p.b3[min(cr, C - 1)];
+    int ylab[4] = {0, 0, 0, 0};
+    if (w == 0) {      // (the wavefront that scores)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int rr = min(m0 + 4 * g + q, N - 1);
+            ylab[q] = (int)p.labels[p.label_rows ? p.label_rows[rr] : rr];
+        }
+    }
+    __syncthreads();  // sW, sPar, sCm complete
+
+    // ---- A fragments of H3 = lrelu(bn(H2)); lane (r,g): row m0 + r, k = 16 kb + 4 g + t
+    float a1[HF_NT][4];
+#pragma unroll
+    for (int kb = 0; kb < HF_NT; ++kb) {
+        const int k0 = 16 * kb + 4 * g;
+        const int k0c = k0 < F ? k0 : 0;
+        const float km = k0 < F ? 1.f : 0.f;
+        const f32x4 x = xh[kb];
+        const f32x4 mu = *reinterpret_cast<const f32x4*>(&sPar[0][k0c]), rs = *reinterpret_cast<const f32x4*>(&sPar[1][k0c]);
+        const f32x4 ga = *reinterpret_cast<const f32x4*>(&sPar[2][k0c]), be = *reinterpret_cast<const f32x4*>(&sPar[3][k0c]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float z = (x[t] - mu[t]) * rs[t] * ga[t] + be[t];
+            a1[kb][t] = (z > 0.f ? z : z * p.slope) * km;
+        }
+    }
+    // ---- Z = relu(H3 W0^T + b0) for this wavefront's column tile; rows m0 + 4g + q, column 16 w + r
+    float zreg[4] = {0.f, 0.f, 0.f, 0.f};
+    if (w < HF_NT) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kb = 0; kb < HF_NT; ++kb) {
+            const int k0 = 16 * kb + 4 * g;
+            const int k0c = k0 < F ? k0 : 0;
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(sW + colc * HF_S + k0c);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[kb][t], wv[t], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) zreg[q] = fmaxf(acc[q] + b0c, 0.f) * cmk;
+    }
+    // ---- this wavefront's share of the logits: dot products over its columns, summed over the 16 lanes r
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float mine = 0.f;
+#pragma unroll
+        for (int c = 0; c < HF_MAXC; ++c) {
+            // (the product is rounded on its own: fused into the first exchange step, fma(z, w, neighbour's product), lanes r
+            //  and r ^ 1 would round differently and two classes with equal weights would not score bit-equal)
+            float zw = zreg[q] * w3[c];
+            asm volatile("" : "+v"(zw));
+            const float s = row16_sum(zw);
+            if (c == cr) mine = s;
+        }
+        if (r < 8) sLg[w][4 * g + q][cr] = mine;
+    }
+    __syncthreads();
+    // ---- wavefront 0: logits with one class per lane (lanes r and r + 8 duplicate), argmax, histogram; rows 4g + q
+    if (w == 0) {
+        const bool cv = cr < C;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = m0 + 4 * g + q;
+            const bool rv = row < N;
+            float v = b3c;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v += sLg[j][4 * g + q][cr];
+            const float mx = row8_max(cv ? v : -3.0e38f);
+            const int pred = (int)row8_min((cv && v == mx) ? (float)cr : 99.f);      // the lowest index among equal maxima
+            if (rv && r < C && p.logits) p.logits[(int64_t)row * C + r] = v;
+            const int y = ylab[q];
+            if (rv && r == 0 && y >= 0 && y < C && pred < C) atomicAdd(&sCm[y * HF_MAXC + pred], 1);
+        }
+    }
+    __syncthreads();
+    if (tid < HF_MAXC * HF_MAXC) {
+        const int y = tid >> 3, c = tid & 7, cnt = sCm[tid];
+        if (cnt > 0 && y < C && c < C) atomicAdd(reinterpret_cast<unsigned long long*>(p.cm + y * C + c), (unsigned long long)cnt);
+    }
+}
+
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
+
+extern "C" int erc_head_eval(const float* H2, int ldh, int n_rows, int F, int C, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, float slope, const float* W0,
+                             const float* b0, const float* W3, const float* b3, const int64_t* labels,
+                             const int32_t* label_rows, const int32_t* n_dev, int64_t* cm, float* logits, void* stream) {
+    ERC_REQUIRE(H2 && gamma && beta && running_mean && running_var && W0 && b0 && W3 && b3 && labels && cm, "head_eval: null pointer");
+    ERC_REQUIRE(n_rows > 0 && F >= 4 && F <= HF_MAXF && F % 4 == 0 && C > 0 && C <= HF_MAXC && ldh >= F && ldh % 4 == 0,
+                "head_eval: n_rows=%d F=%d C=%d ldh=%d unsupported (F <= %d, F %% 4 == 0, C <= %d)", n_rows, F, C, ldh,
+                HF_MAXF, HF_MAXC);
+    ERC_REQUIRE(al16(H2) && al16(W0) && ((uintptr_t)cm & 7) == 0, "head_eval: 16-byte alignment (H2, W0), 8-byte (cm)");
+    HeadEvalP p{};
+    p.H2 = H2, p.gamma = gamma, p.beta = beta, p.rmean = running_mean, p.rvar = running_var, p.W0 = W0, p.b0 = b0, p.W3 = W3, p.b3 = b3;
+    p.labels = labels, p.label_rows = label_rows, p.n_dev = n_dev, p.cm = reinterpret_cast<long long*>(cm), p.logits = logits;
+    p.slope = slope, p.eps = eps, p.ldh = ldh, p.N = n_rows, p.F = F, p.C = C;
+    hipLaunchKernelGGL(head_eval_kernel, dim3(erc_cdiv(n_rows, 16)), dim3(512), 0, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK("head_eval");
+    return ERC_OK;
+}
 
 extern "C" int64_t erc_bn_batch_stats_ws_floats(int F) { return (int64_t)BS_G * 2 * F * 2 + 16; }
 

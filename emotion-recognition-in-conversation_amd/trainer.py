@@ -14,6 +14,8 @@ IEMOCAP-/MELD-shaped dialogues (synthetic.py); ``--synthetic=False --data_root=<
 (or $ERC_IEMOCAP_ROOT / $ERC_MELD_ROOT) reads the reference's feature pickles
 (datasets.py).  ``--device_collate`` keeps the dialogues resident in HBM and builds
 every batch on the device (datasets.DeviceDialogueStore) instead of in a DataLoader.
+``--resident`` runs the training epochs from that store (ResidentEpochs); ``--resident_eval`` the test epochs too,
+scored on the device (ResidentEval, report_from_cm).
 """
 import json
 import os
@@ -419,6 +421,101 @@ class ResidentEpochs:
         return sum(counts), steps
 
 
+class ResidentEval:
+    """``--resident_eval``: the test epoch from HBM, scored on the device.  The test dialogues stay in their
+    DeviceDialogueStore; the test order is fixed (sequential batches of ``batch_size`` dialogues, the last one padded with
+    zero-length slots: DataLoader(shuffle=False) semantics), so the whole int32 table [steps, 2 B] (lengths | first store
+    rows) is uploaded ONCE, here.  T is the TEST store's own longest dialogue; a step's node capacity is its node count rounded
+    up to N_BUCKET, at most B * T (buckets as in ResidentEpochs).  The first visit of a bucket runs the trainer's
+    ``resident_eval_step`` eagerly and captures it; from then on a test epoch is
+
+        cm.zero_() ; per step: copy 2 B int32, replay ; one cm.cpu() at the end
+
+    and every metric of the epoch line is a function of that confusion matrix (``report_from_cm``)."""
+
+    N_BUCKET = 128
+
+    def __init__(self, trainer, store, batch_size, capture=True, n_classes=None):
+        self.trainer, self.store, self.B = trainer, store, int(batch_size)
+        B, n = self.B, len(store)
+        self.steps = -(-n // B)
+        self.T = int(store.lengths.max())
+        flat_l, flat_o = np.zeros(self.steps * B, dtype=np.int32), np.zeros(self.steps * B, dtype=np.int32)
+        flat_l[:n], flat_o[:n] = store.lengths.to(torch.int32).numpy(), store.offsets[:-1].to(torch.int32).numpy()
+        self.table = np.concatenate([flat_l.reshape(self.steps, B), flat_o.reshape(self.steps, B)], axis=1)
+        self.counts = self.table[:, :B].sum(1).tolist()
+        self.caps = [min(-(-c // self.N_BUCKET) * self.N_BUCKET, B * self.T) for c in self.counts]
+        dev = store.device
+        self.table_dev = torch.from_numpy(self.table).to(dev)
+        self.cur_desc = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+        C = int(n_classes if n_classes is not None else trainer.params.n_classes)
+        self.cm = torch.zeros(C, C, dtype=torch.int64, device=dev)
+        self.graphs, self.capture = {}, capture      # node capacity -> (graph or None, batch, workspace kept alive)
+        self.replays = self.eager = self.captures = 0
+
+    def _capture(self, fn):
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        return g
+
+    def supported(self):
+        """Can EVERY step of the test epoch run from the resident store?  (asked once, before the first epoch)"""
+        return all(self.trainer.resident_eval_batch(self.store, self.cur_desc, self.B, self.T, cap) is not None
+                   for cap in sorted(set(self.caps)))
+
+    def epoch(self):
+        """one pass over the test store; returns its confusion matrix (host int64 [C, C], true x predicted)"""
+        tr = self.trainer
+        self.cm.zero_()
+        for s in range(self.steps):
+            self.cur_desc.copy_(self.table_dev[s], non_blocking=True)
+            cap = self.caps[s]
+            ent = self.graphs.get(cap)
+            if ent is not None and ent[0] is not None:
+                ent[0].replay()
+                self.replays += 1
+                continue
+            batch = ent[1] if ent is not None else tr.resident_eval_batch(self.store, self.cur_desc, self.B, self.T, cap)
+            if batch is None:
+                raise capi.ErcGraftError("ResidentEval: the trainer offers no resident test batch of capacity %d" % cap)
+            ws = tr.resident_eval_step(batch, self.cm)            # a real step; allocates the bucket's buffers
+            self.eager += 1
+            graph = None
+            if self.capture:
+                graph = self._capture(lambda: tr.resident_eval_step(batch, self.cm))
+                self.captures += 1
+            self.graphs[cap] = (graph, batch, ws)      # (the graph holds raw pointers into ws: kept alive with it)
+        return self.cm.cpu()
+
+
+def report_from_cm(cm):
+    """``classification_report``'s dict from the confusion matrix alone (rows = true class, columns = predicted): every one
+    of these metrics is a function of it.  Per class: recall = tp / support, precision = tp / predicted, f1 = 2 tp /
+    (support + predicted), 0 where undefined (zero_division=0).  ``wa`` (balanced accuracy) is the mean recall over the classes
+    that occur in the labels; ``pre`` / ``rec`` / ``f1`` are weighted by support; ``maf1`` is the mean f1 over the classes
+    that occur in the labels or the predictions (sklearn's default label set); ``mif1`` = ``acc``."""
+    cm = np.asarray(cm, dtype=np.int64)
+    n = int(cm.sum())
+    tp, sup, prd = np.diag(cm).astype(np.float64), cm.sum(1).astype(np.float64), cm.sum(0).astype(np.float64)
+    div = lambda a, b: np.divide(a, b, out=np.zeros_like(a), where=b > 0)
+    rec, pre, f1 = div(tp, sup), div(tp, prd), div(2.0 * tp, sup + prd)
+    weighted = lambda v: float((v * sup).sum() / n) if n else 0.0
+    acc = float(tp.sum() / n) if n else 0.0
+    seen = (sup > 0) | (prd > 0)
+    return {
+        "cm": cm.tolist(),
+        "acc": acc,
+        "wa": float(rec[sup > 0].mean()) if n else 0.0,
+        "pre": weighted(pre),
+        "rec": weighted(rec),
+        "f1": weighted(f1),
+        "mif1": acc,
+        "maf1": float(f1[seen].mean()) if n else 0.0,
+    }
+
+
 def classification_report(true, pred, n_classes):
     """The metric set of mmbase.py:259-275."""
     from sklearn import metrics
@@ -518,6 +615,18 @@ def run(trainer_cls, params_cls, argv=None):
         if not resident.supported():
             raise SystemExit("--resident: this configuration cannot run its step in capacity mode")
         resident.plan(params.epoch)
+    res_eval = None
+    if params.get("resident_eval", False):      # the test epoch from HBM too, scored on the device (ResidentEval)
+        if resident is None:
+            raise SystemExit("--resident_eval needs --resident (the test epoch then runs from the HBM-resident test store)")
+        if not hasattr(trainer, "resident_eval_step"):
+            raise SystemExit("--resident_eval: this module's trainer has no resident_eval_step (--module=cogmen has one)")
+        if params.get("mosei_metric", "") == "multiemo":
+            raise SystemExit("--resident_eval: mosei_metric=multiemo reports multi-label metrics, which are no function of the "
+                             "confusion matrix the device returns")
+        res_eval = ResidentEval(trainer, test_loader.store, params.test.batch_size, capture=params.get("graph_capture", True))
+        if not res_eval.supported():
+            raise SystemExit("--resident_eval: this configuration cannot run its test step in capacity mode")
     for epoch in range(params.epoch):
         trainer.model.train()
         t0, n_utt, counts = time.perf_counter(), 0, []
@@ -557,7 +666,13 @@ def run(trainer_cls, params_cls, argv=None):
         true, pred = [], []
         multiemo = params.get("mosei_metric", "") == "multiemo"
         true_multi, prob_multi = [], []
-        for batch in test_loader:
+        cm_host, test_s = None, None
+        if res_eval is not None:       # graph replays over the resident test store, one device -> host copy (the training
+            t1 = time.perf_counter()   # epoch above ended with a synchronisation)
+            cm_host = res_eval.epoch()
+            torch.cuda.synchronize()
+            test_s = time.perf_counter() - t1
+        for batch in (test_loader if res_eval is None else ()):
             if multiemo:           # mosei_test_step (mmbase.py:167-178)
                 logits, logits7 = trainer.to_mosei_multitask_logits(trainer.prepare_batch(batch))
                 true_multi.append(batch["emo_label"].cpu().numpy())
@@ -573,13 +688,15 @@ def run(trainer_cls, params_cls, argv=None):
         if hasattr(trainer.model, "check_cluster"):
             trainer.model.check_cluster()      # a timeout inside to_logits would make the metrics below meaningless
         if rank == 0:
-            rep = classification_report(true, pred, params.n_classes)
+            rep = classification_report(true, pred, params.n_classes) if cm_host is None else report_from_cm(cm_host.numpy())
             for k in ("acc", "wa", "f1", "mif1", "maf1", "pre", "rec"):
                 best[k] = max(best.get(k, 0.0), rep[k])
             line = {"epoch": epoch, "train_utt_per_s": n_utt / dt, "test": {k: rep[k] for k in rep if k != "cm"},
                     "best": best, "graph_replays": (resident or graphs).replays if (resident or graphs) else 0,
                     "eager_steps": (resident or graphs).eager if (resident or graphs) else len(counts),
                     "graphs_captured": (resident or graphs).captures if (resident or graphs) else 0}
+            if test_s is not None:
+                line["test_s"] = test_s
             if multiemo:
                 line["multiemo"] = multiemo_report(np.concatenate(true_multi), np.concatenate(prob_multi))
             print(json.dumps(line), flush=True)

@@ -417,6 +417,22 @@ int erc_head_rows_occupancy(void);
  * ceil(n_rows / this) records */
 int erc_head_fused_rows_per_workgroup(int n_rows);
 
+/* COGMEN classifier head in EVAL mode, scored on the device (track_mm/cogmen.py:67-68,72-73 BatchNorm1d in eval() +
+ * leaky_relu; :116-122 cls without dropout; mmbase.py:180-201 test_step's argmax): per row of H2 [n_rows, ldh]
+ *   H3 = lrelu((H2 - running_mean) * gamma / sqrt(running_var + eps) + beta, slope);  Z = relu(H3 W0^T + b0)
+ *   logits = Z W3^T + b3;  pred = the first index of the maximum (torch.argmax);  cm[label * C + pred] += 1
+ * cm: int64 [C, C] (true class x predicted class), ADDED TO -- the caller zeroes it before the first launch of a test epoch;
+ * integer counts (a histogram per workgroup, one atomic add per non-empty cell): the result does not depend on the order.
+ * logits [n_rows, C] (or NULL): the scores, written for the counted rows only.
+ * n_rows, n_dev, labels, label_rows as in erc_head_fused; rows at or beyond the count (*n_dev clamped to [0, n_rows], 0
+ * allowed) are neither read nor counted, a row whose label lies outside [0, C) is not counted.  Writes nothing but cm and
+ * logits: running statistics, gradients, health word and RNG state stay as they are.
+ * F <= 100, F % 4 == 0, C <= 8, ldh % 4 == 0, H2 / W0 16-byte aligned, cm 8-byte aligned. */
+int erc_head_eval(const float* H2, int ldh, int n_rows, int F, int C, const float* gamma, const float* beta,
+                  const float* running_mean, const float* running_var, float eps, float slope, const float* W0,
+                  const float* b0, const float* W3, const float* b3, const int64_t* labels, const int32_t* label_rows,
+                  const int32_t* n_dev, int64_t* cm, float* logits, void* stream);
+
 /* diagnostic: 8 x uint64 phase stamps (10 ns ticks) of the middle workgroup of the following erc_head_fused[_bn] launches;
  * NULL switches them off (tools/cogmen_stamps.py) */
 int erc_head_set_stamps(uint64_t* stamps);
