@@ -24,8 +24,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
-from .dgcnv2 import IEMOCAP6_WEIGHTS
+from .capacity import IEMOCAP6_WEIGHTS, CapacityBuckets, TrainerBase, bucket_sizes
+from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, linear_fwd, linear_wgrad
 from .rnn import BiGRU2, BiLSTM2, gru_groups, lstm_groups
 
 D_E, D_HID, EW, MAX_T = 100, 100, 200, 110
@@ -263,7 +263,7 @@ class GRUModule(_BcRnnModule):
     CELL = "gru"
 
 
-class BcRnnTrainer:
+class BcRnnTrainer(CapacityBuckets, TrainerBase):
     """train_step / to_logits for ``--module=bclstm`` and ``--module=bcgru``: class-weighted MaskedNLLLoss, Adam lr 3e-4, no
     weight decay (the defaults of the sibling plugin, track_mm/dgcnv2.py:22-48,184-219).  ``MODULE`` picks the cell."""
     MODULE, NAME = None, None
@@ -292,27 +292,19 @@ class BcRnnTrainer:
         self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
         self._store_ext = None
 
-    N_BUCKET = 128     # capacity buckets: node counts rounded up to a multiple of this (the node launches scale with N_cap)
+    # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  N_BUCKET 128 and "a batch of exactly its
+    #    bucket's shape stays exact" are the mixin's defaults; ``self.capacity`` (set above) makes the buckets opt-in
+    TIME_MAJOR = True          # [T, B, D] features, [T, B, S] one-hot speakers
 
-    def _p2p(self):
-        """the opt-in peer-to-peer gradient exchange (ERC_DP_P2P=1): capacity buckets stay off there"""
-        import os
-        return getattr(self.model.flat, "p2p", None) is not None or os.environ.get("ERC_DP_P2P", "0") == "1"
-
-    def _capacity_ok(self, T_cap, batch=None):
+    def _capacity_ok(self, B_cap, T_cap, N_cap, batch=None):
+        """no bucket with the flag off, with the peer-to-peer exchange, above the matching attention's T or the head's classes,
+        or for a batch of other dtypes / ranks (the gate is on T_cap: the node launches take any N_cap)"""
         ok = self.capacity and not self._p2p() and 0 < T_cap <= MAX_T and self.model.n_classes <= 8
         if ok and batch is not None:
             x, spk = batch["input_tensor"], batch["speaker_tensor"]
             ok = (x.dtype == torch.float32 and x.dim() == 3 and int(x.shape[2]) == self.model.D_m and spk.dim() == 3 and
                   batch["text_length"].dtype == torch.int64)
         return bool(ok)
-
-    def _caps(self, batch):
-        T, B = batch["input_tensor"].shape[:2]            # time-major
-        return max(int(B), int(self.params.train.batch_size)), max(int(T), int(getattr(self, "t_cap", 0)))
-
-    def _n_cap(self, N, B_cap, T_cap):
-        return min(-(-N // self.N_BUCKET) * self.N_BUCKET, B_cap * T_cap)
 
     def _bucket(self, like, B_cap, T_cap, N_cap):
         x, spk, dev = like["input_tensor"], like["speaker_tensor"], self.device
@@ -346,70 +338,24 @@ class BcRnnTrainer:
 
         return ("capacity", B_cap, T_cap, N_cap), make, fill
 
-    def capacity_bucket(self, batch):
-        """trainer.StepGraphs: (key, make_static, fill) of the capacity bucket that holds ``batch`` (a prepared device batch),
-        or None: capacity buckets are off (the default), the peer-to-peer exchange is on, T_cap is above the matching
-        attention's limit, or the batch already has its bucket's shape (nothing to pad).  The exact-shape path runs then."""
-        if not self.capacity:
-            return None
-        B_cap, T_cap = self._caps(batch)
-        N = int(batch["label"].shape[0])
-        N_cap = self._n_cap(N, B_cap, T_cap)
-        T, B = batch["input_tensor"].shape[:2]
-        if not self._capacity_ok(T_cap, batch) or (int(B), int(T), N) == (B_cap, T_cap, N_cap):
-            return None
-        return self._bucket(batch, B_cap, T_cap, N_cap)
-
-    def all_capacity_buckets(self, batch):
-        """Every bucket a batch of this loader can fall into, smallest first, each with a synthetic filler (all B_cap
-        dialogues present, lengths adding up to the capacity, each <= T_cap): data parallel runs capture all of them up front,
-        in the same order on every rank.  The list depends only on what every rank shares -- B_cap = train.batch_size and T_cap
-        (trainer.bucket_t_cap) -- never on the probe batch's own N or shape."""
+    def _precapture_caps(self, batch):
+        # built from train.batch_size and T_cap (trainer.bucket_t_cap) ALONE, never from the probe batch's shape (the other two
+        # trainers go through the probe); the list includes the clipped top bucket B_cap * T_cap
         B_cap, T_cap = int(self.params.train.batch_size), int(getattr(self, "t_cap", 0))
-        if not self._capacity_ok(T_cap, batch):
-            return []
-        top = B_cap * T_cap
-        out = []
-        for N_cap in sorted({min(n, top) for n in range(self.N_BUCKET, top + self.N_BUCKET, self.N_BUCKET)}):
-            key, make, fill = self._bucket(batch, B_cap, T_cap, N_cap)
-
-            def synth(static, n=N_cap):
-                lens = torch.full((B_cap, ), n // B_cap, dtype=torch.int64)
-                lens[:n - int(lens.sum())] += 1                        # lengths add up to n, each <= T_cap
-                static["text_length"].copy_(lens)
-            out.append((key, make, fill, synth))
-        return out
-
-    def resident_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEpochs: the "batch" of a step whose dialogues stay in the HBM-resident store -- the feature rows, the
-        2 B_cap int32 the host rewrites per step (lengths | first store rows of the batch's dialogue slots) and the capacities
-        the launches are sized for.  The layer-0 projection reads the store's rows through the step's row map; padded
-        positions read a zero row, which the store does not have, so the features are kept once with one appended.  None
-        when the step cannot run that way (dtype or width of the store, T_cap above the attention's limit)."""
-        if store.fused.dtype != torch.float32 or int(store.fused.shape[1]) != self.model.D_m or not self._capacity_ok(T_cap):
+        if not self._capacity_ok(B_cap, T_cap, self.N_BUCKET, batch):
             return None
+        return B_cap, T_cap, bucket_sizes(self.N_BUCKET, B_cap * T_cap)
+
+    def _resident_ok(self, store, B_cap, T_cap, N_cap):
+        return store.fused.dtype == torch.float32 and int(store.fused.shape[1]) == self.model.D_m and self._capacity_ok(B_cap, T_cap, N_cap)
+
+    def _resident_inputs(self, store):
+        """The layer-0 projection reads the store's rows through the step's row map; padded positions read a zero row, which
+        the store does not have, so the features are kept once per store with one appended.  No speakers: the model reads none."""
         if self._store_ext is None or self._store_ext[0] is not store:
             self._store_ext = (store, torch.cat([store.fused, torch.zeros(1, self.model.D_m, dtype=torch.float32,
                                                                             device=store.fused.device)]))
-        return dict(input_tensor=self._store_ext[1], speaker_tensor=None, text_length=None, label=store.label, desc=cur_desc,
-                    caps=(B_cap, T_cap, N_cap))
-
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        return out
-
-    def train_step(self, batch):
-        self.model.train()
-        stats = self.model.loss_and_grads(batch, self.class_weight)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats
+        return self._store_ext[1], None
 
 
 class BcLstmTrainer(BcRnnTrainer):

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import capi
+from .capacity import TrainerBase
 from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
 
 H = 200
@@ -245,7 +246,7 @@ class CIMModule(nn.Module):
         return ws["stats"]
 
 
-class CIMTrainer:
+class CIMTrainer(TrainerBase):
     """train_step / to_logits / to_mosei_multitask_logits of track_mm/cim.py:180-227: unweighted cross entropy on logits2
     (apply_bin), plus the 7-way BCE on logits7 when apply_multi (CMU-MOSEI only, cim.py:52-53); torch.optim.Adam(lr)
     without clipping or weight decay.  apply_bin=False is refused: the reference's cls2 would then get neither a gradient
@@ -272,21 +273,11 @@ class CIMTrainer:
                                decoupled=(o.name == "AdamW"), seed=params.seed)
         self.model.rng_state = self.optim.rng_state
 
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
     def to_mosei_multitask_logits(self, batch):
         """(logits2 [N, C], logits7 [N, 7]) (mmbase.py:144, cim.py:190-191)"""
         return self.model(**batch)
 
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        return out
-
-    def train_step(self, batch):
+    def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
         self.model.train()
         stats = self.model.loss_and_grads(batch)
         scale = all_reduce_grads(self.model.flat)

@@ -26,6 +26,7 @@ import torch
 from torch import nn
 
 from . import capi
+from .capacity import CapacityBuckets, TrainerBase
 from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, all_reduce_grads, linear_fwd, linear_wgrad, \
     matmul_wgrad_io
 
@@ -740,8 +741,9 @@ def build_graph_tensors(text_length, speaker_tensor, wp, wf, n_speakers, n_nodes
     return g, ei, et
 
 
-class COGMENTrainer:
+class COGMENTrainer(CapacityBuckets, TrainerBase):
     """train_step / to_logits of track_mm/cogmen.py:163-195 without lumo."""
+    BF16_INPUT = True
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -775,66 +777,33 @@ class COGMENTrainer:
             self.encoder.forward(batch["input_tensor"])
         return self.model(**batch)[0]
 
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        if self.model.compute == "bf16":
-            out["input_tensor"] = out["input_tensor"].to(torch.bfloat16)
-        return out
+    # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets)
+    N_BUCKET = 256               # StepGraphs rounds to 256 here; ResidentEpochs / ResidentEval round to their own 128
+    EXACT_SHAPE_STAYS = False    # a batch of exactly its bucket's shape still gets a bucket (the other trainers return None)
 
-    N_BUCKET = 256     # capacity buckets: node counts rounded up to a multiple of this
+    def _capacity_ok(self, B_cap, T_cap, N_cap, batch):
+        """no bucket on the fp32 parity path, in the chained / faithful-cost encoder modes, above the fused path's node limit"""
+        D = batch["input_tensor"].shape[2]
+        return (self.encoder is None and self.model.supports_capacity(batch) and N_cap <= self.model.BN_FUSED_MAX_N and
+                capi.cogmen_project_graph_ok(D, F_HID, B_cap, D, D))
 
-    def _bucket(self, like, B_cap, T_cap, N_cap):
-        x, dev, D = like["input_tensor"], self.device, like["input_tensor"].shape[2]
-
-        def make():
-            return dict(input_tensor=torch.zeros(B_cap, T_cap, D, dtype=x.dtype, device=dev),
-                        speaker_tensor=torch.zeros(B_cap, T_cap, dtype=like["speaker_tensor"].dtype, device=dev),
-                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
-                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev))
-
-        def fill(static, b):
-            Bb, Tb = b["input_tensor"].shape[:2]
-            static["input_tensor"][:Bb, :Tb].copy_(b["input_tensor"], non_blocking=True)
-            static["speaker_tensor"][:Bb, :Tb].copy_(b["speaker_tensor"], non_blocking=True)
-            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
-            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
-            static["label"][:b["label"].shape[0]].copy_(b["label"], non_blocking=True)
-
-        return ("capacity", B_cap, T_cap, N_cap), make, fill
-
-    def _caps(self, batch):
-        B, T, D = batch["input_tensor"].shape
-        B_cap = max(B, int(self.params.train.batch_size))
-        return B_cap, max(T, int(getattr(self, "t_cap", 0))), D
-
-    def capacity_bucket(self, batch):
-        """trainer.StepGraphs: (key, make_static, fill) of the capacity bucket that holds ``batch`` (a prepared device batch),
-        or None when the step cannot run in capacity mode (fp32 parity path, chained / faithful-cost encoder modes)."""
-        if self.encoder is not None or not self.model.supports_capacity(batch):
+    def _precapture_caps(self, batch):
+        # the gate is asked for the probe's OWN bucket; the list holds the multiples of N_BUCKET only: the clipped top bucket
+        # (B_cap * T_cap, where that is no multiple) is NOT in it -- under data parallelism its batches run eagerly
+        if self.capacity_bucket(batch) is None:
             return None
-        B_cap, T_cap, D = self._caps(batch)
-        N = int(batch["label"].shape[0])
-        N_cap = min(-(-N // self.N_BUCKET) * self.N_BUCKET, B_cap * T_cap)
-        if N_cap > self.model.BN_FUSED_MAX_N or not capi.cogmen_project_graph_ok(D, F_HID, B_cap, D, D):
-            return None
-        return self._bucket(batch, B_cap, T_cap, N_cap)
+        B_cap, T_cap = self._caps(batch)
+        return B_cap, T_cap, range(self.N_BUCKET, min(B_cap * T_cap, self.model.BN_FUSED_MAX_N) + 1, self.N_BUCKET)
 
-    def resident_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEpochs: the "batch" of a step whose dialogues stay in the HBM-resident store -- the store's arrays,
-        the 2 B_cap int32 the host rewrites per step (lengths | first store rows of the batch's dialogue slots) and the
-        capacities the launches are sized for.  None when the step cannot run that way."""
-        probe = dict(input_tensor=store.fused[None, :1], speaker_tensor=store.speaker[None, :1])
+    def _synth_lengths(self, B_cap, T_cap, n):
+        return super()._synth_lengths(B_cap, T_cap, n).clamp_(max=T_cap)      # COGMEN alone clamps (a no-op for the list above)
+
+    def _resident_ok(self, store, B_cap, T_cap, N_cap):
+        # the store's dtype follows ``terms``: the split modes (terms > 1) read the fp32 features, the bf16 mode bf16 ones
         D = int(store.fused.shape[1])
-        if self.encoder is not None or store.fused.dtype != (torch.float32 if self.model.terms > 1 else torch.bfloat16) or \
-                not self.model.supports_capacity(
-                dict(probe, input_tensor=store.fused.view(1, -1, D))) or N_cap > self.model.BN_FUSED_MAX_N or \
-                not capi.cogmen_project_graph_ok(D, F_HID, B_cap, D, D):
-            return None
-        return dict(input_tensor=store.fused, speaker_tensor=store.speaker, text_length=None, label=store.label, desc=cur_desc,
-                    caps=(B_cap, T_cap, N_cap))
+        probe = dict(input_tensor=store.fused.view(1, -1, D), speaker_tensor=store.speaker[None, :1])
+        return (store.fused.dtype == (torch.float32 if self.model.terms > 1 else torch.bfloat16) and
+                self._capacity_ok(B_cap, T_cap, N_cap, probe))
 
     def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
         """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
@@ -845,24 +814,6 @@ class COGMENTrainer:
         """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
         sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
         return self.model.eval_scores(batch, cm)
-
-    def all_capacity_buckets(self, batch):
-        """Every bucket a batch of this loader can fall into, smallest first, each with a synthetic filler (all B_cap
-        dialogues present, lengths adding up to the capacity): data parallel runs capture all of them up front, in the
-        same order on every rank (a captured step holds a collective: ranks must not capture at different times)."""
-        if self.capacity_bucket(batch) is None:
-            return []
-        B_cap, T_cap, D = self._caps(batch)
-        out = []
-        for N_cap in range(self.N_BUCKET, min(B_cap * T_cap, self.model.BN_FUSED_MAX_N) + 1, self.N_BUCKET):
-            key, make, fill = self._bucket(batch, B_cap, T_cap, N_cap)
-
-            def synth(static, n=N_cap):
-                lens = torch.full((B_cap, ), n // B_cap, dtype=torch.int64)
-                lens[:n - int(lens.sum())] += 1                        # lengths add up to n, each <= T_cap
-                static["text_length"].copy_(lens.clamp_(max=T_cap))
-            out.append((key, make, fill, synth))
-        return out
 
     def train_step(self, batch):
         """forward + CE + backward + (DP all-reduce) + Adam.  Returns the device stats tensor."""

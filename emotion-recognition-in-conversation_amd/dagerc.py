@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from . import capi
+from .capacity import TrainerBase
 from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
 
 HID = 300
@@ -276,8 +277,9 @@ class DAGERCModule(nn.Module):
         return ws["stats"]
 
 
-class DAGERCTrainer:
+class DAGERCTrainer(TrainerBase):
     """train_step / to_logits of track_mm/dagerc.py:201-237 (masked CE, clip_grad_norm_ 5, AdamW)."""
+    BF16_INPUT = True
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -291,19 +293,7 @@ class DAGERCTrainer:
         self.model.rng_state = self.optim.rng_state
         self.optim.skip_flag = self.model.flat.health    # a recurrence exchange timed out (on any rank) -> the update is skipped
 
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        if self.model.compute == "bf16":
-            out["input_tensor"] = out["input_tensor"].to(torch.bfloat16)
-        return out
-
-    def train_step(self, batch):
+    def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
         self.model.train()
         stats = self.model.loss_and_grads(batch)
         scale = all_reduce_grads(self.model.flat)

@@ -12,7 +12,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, all_reduce_grads, linear_fwd, linear_wgrad, \
+from .capacity import IEMOCAP6_WEIGHTS, CapacityBuckets, TrainerBase, bucket_sizes
+from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, linear_fwd, linear_wgrad, \
     matmul_wgrad_io
 from .rnn import BiLSTM2, lstm_groups
 
@@ -381,11 +382,9 @@ class DGCNModule(nn.Module):
         return ws["stats"]
 
 
-IEMOCAP6_WEIGHTS = [1 / 0.086747, 1 / 0.144406, 1 / 0.227883, 1 / 0.160585, 1 / 0.127711, 1 / 0.252668]  # dgcn.py:109-110
-
-
-class DGCNTrainer:
+class DGCNTrainer(CapacityBuckets, TrainerBase):
     """train_step / to_logits of track_mm/dgcn.py:96-134 (class-weighted CE, Adam lr 3e-4)."""
+    BF16_INPUT = True
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -410,99 +409,21 @@ class DGCNTrainer:
                                  "(dgcn.py:109-110); run %d-class datasets with --loss_weights=False" % params.n_classes)
             self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
 
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        if self.model.compute == "bf16":
-            out["input_tensor"] = out["input_tensor"].to(torch.bfloat16)
-        return out
-
-    N_BUCKET = 128     # capacity buckets: node counts rounded up to a multiple of this (the launches scale with N_cap)
-
-    def _p2p(self):
-        """the opt-in peer-to-peer gradient exchange (ERC_DP_P2P=1): capacity buckets stay off there"""
-        import os
-        return getattr(self.model.flat, "p2p", None) is not None or os.environ.get("ERC_DP_P2P", "0") == "1"
-
-    def _capacity_ok(self, N_cap, batch=None):
+    # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  N_BUCKET 128, batch-first, a batch of
+    #    exactly its bucket's shape stays on the exact-shape path: the mixin's defaults
+    def _capacity_ok(self, B_cap, T_cap, N_cap, batch=None):
+        """no bucket in relation space or on an unfused path, above the fused tail's row limit, with the peer-to-peer exchange"""
         return (self.model.supports_capacity(batch) and not self._p2p() and 0 < N_cap <= capi.dgcn_tail_limits()[0])
 
-    def _caps(self, batch):
-        B, T = batch["input_tensor"].shape[:2]
-        return max(B, int(self.params.train.batch_size)), max(T, int(getattr(self, "t_cap", 0)))
-
-    def _n_cap(self, N, B_cap, T_cap):
-        return min(-(-N // self.N_BUCKET) * self.N_BUCKET, B_cap * T_cap)
-
-    def _bucket(self, like, B_cap, T_cap, N_cap):
-        x, spk, dev, D = like["input_tensor"], like["speaker_tensor"], self.device, like["input_tensor"].shape[2]
-
-        def make():
-            return dict(input_tensor=torch.zeros(B_cap, T_cap, D, dtype=x.dtype, device=dev),
-                        speaker_tensor=torch.zeros(B_cap, T_cap, dtype=spk.dtype, device=dev),
-                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
-                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev))
-
-        def fill(static, b):
-            Bb, Tb = b["input_tensor"].shape[:2]
-            static["input_tensor"][:Bb, :Tb].copy_(b["input_tensor"], non_blocking=True)
-            static["speaker_tensor"][:Bb, :Tb].copy_(b["speaker_tensor"], non_blocking=True)
-            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
-            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
-            static["label"][:b["label"].shape[0]].copy_(b["label"], non_blocking=True)
-
-        return ("capacity", B_cap, T_cap, N_cap), make, fill
-
-    def capacity_bucket(self, batch):
-        """trainer.StepGraphs: (key, make_static, fill) of the capacity bucket that holds ``batch`` (a prepared device batch),
-        or None when the step cannot run in capacity mode (relation space or an unfused path, N_cap above the fused tail's
-        row limit, the peer-to-peer exchange): the exact-shape path runs then.  So does a batch that already has its
-        bucket's shape (B, T, N = B_cap, T_cap, N_cap): there is nothing to pad."""
+    def _precapture_caps(self, batch):
+        # the gate is asked for the smallest bucket; the list includes the clipped top bucket (B_cap * T_cap or the tail's row
+        # limit).  It depends only on what every rank shares -- the module's path, B_cap = train.batch_size, T_cap
+        # (trainer.bucket_t_cap) -- never on the probe batch's own N
         B_cap, T_cap = self._caps(batch)
-        N = int(batch["label"].shape[0])
-        N_cap = self._n_cap(N, B_cap, T_cap)
-        if not self._capacity_ok(N_cap, batch) or tuple(batch["input_tensor"].shape[:2]) + (N, ) == (B_cap, T_cap, N_cap):
+        if not self._capacity_ok(B_cap, T_cap, self.N_BUCKET, batch):
             return None
-        return self._bucket(batch, B_cap, T_cap, N_cap)
+        return B_cap, T_cap, bucket_sizes(self.N_BUCKET, min(B_cap * T_cap, capi.dgcn_tail_limits()[0]))
 
-    def all_capacity_buckets(self, batch):
-        """Every bucket a batch of this loader can fall into, smallest first, each with a synthetic filler (all B_cap
-        dialogues present, lengths adding up to the capacity, each <= T_cap): data parallel runs capture all of them up front,
-        in the same order on every rank.  The list depends only on what every rank shares -- the module's path, B_cap =
-        train.batch_size, T_cap (trainer.bucket_t_cap) -- never on the probe batch's own N or shape."""
-        if not self._capacity_ok(self.N_BUCKET, batch):
-            return []
-        B_cap, T_cap = self._caps(batch)
-        top = min(B_cap * T_cap, capi.dgcn_tail_limits()[0])
-        out = []
-        for N_cap in sorted({min(n, top) for n in range(self.N_BUCKET, top + self.N_BUCKET, self.N_BUCKET)}):
-            key, make, fill = self._bucket(batch, B_cap, T_cap, N_cap)
-
-            def synth(static, n=N_cap):
-                lens = torch.full((B_cap, ), n // B_cap, dtype=torch.int64)
-                lens[:n - int(lens.sum())] += 1                        # lengths add up to n, each <= T_cap
-                static["text_length"].copy_(lens)
-            out.append((key, make, fill, synth))
-        return out
-
-    def resident_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEpochs: the "batch" of a step whose dialogues stay in the HBM-resident store -- the store's arrays,
-        the 2 B_cap int32 the host rewrites per step (lengths | first store rows of the batch's dialogue slots) and the
-        capacities the launches are sized for.  None when the step cannot run that way."""
+    def _resident_ok(self, store, B_cap, T_cap, N_cap):
         want = torch.bfloat16 if self.model.compute == "bf16" else torch.float32
-        if store.fused.dtype != want or store.fused.shape[1] != self.model.input_size or not self._capacity_ok(N_cap):
-            return None
-        return dict(input_tensor=store.fused, speaker_tensor=store.speaker, text_length=None, label=store.label, desc=cur_desc,
-                    caps=(B_cap, T_cap, N_cap))
-
-    def train_step(self, batch):
-        self.model.train()
-        stats = self.model.loss_and_grads(batch, self.class_weight)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats
+        return store.fused.dtype == want and store.fused.shape[1] == self.model.input_size and self._capacity_ok(B_cap, T_cap, N_cap)

@@ -17,13 +17,13 @@ import torch
 from torch import nn
 
 from . import capi
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad, matmul_wgrad_io
+from .capacity import IEMOCAP6_WEIGHTS, TrainerBase
+from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, linear_fwd, linear_wgrad, matmul_wgrad_io
 from .rnn import BiLSTM2, lstm_groups
 
 G_DIM, H1, NB, NSCAL = 200, 100, 30, 110
 EW = G_DIM + H1            # row width of E = [features | conv2 output]
 DEAD = ("att_model.matchatt.", "att_model.simpleatt.", "att_model.att.")
-IEMOCAP6_WEIGHTS = [1 / 0.086747, 1 / 0.144406, 1 / 0.227883, 1 / 0.160585, 1 / 0.127711, 1 / 0.252668]  # dgcnv2.py:213-214
 
 
 class _Transform(nn.Module):          # MatchingAttention('general2'): its one parameterised layer
@@ -299,7 +299,7 @@ class DGCNModule(nn.Module):
         return ws["stats"]
 
 
-class DGCNv2Trainer:
+class DGCNv2Trainer(TrainerBase):
     """train_step / to_logits of track_mm/dgcnv2.py:184-219 (class-weighted CE, Adam lr 3e-4, no weight decay)."""
 
     def __init__(self, params, device):
@@ -323,20 +323,3 @@ class DGCNv2Trainer:
         self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
                                decoupled=(o.name == "AdamW"), seed=params.seed)
         self.model.rng_state = self.optim.rng_state
-
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        return out
-
-    def train_step(self, batch):
-        self.model.train()
-        stats = self.model.loss_and_grads(batch, self.class_weight)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats

@@ -20,8 +20,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
-from .dgcnv2 import IEMOCAP6_WEIGHTS
+from .capacity import IEMOCAP6_WEIGHTS, TrainerBase
+from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, linear_fwd, linear_wgrad
 
 D_G, D_E, D_HID, EW, MAX_T, MAX_S = 150, 100, 100, 200, 110, 9
 GXW = capi.DIALOGRNN_GXW
@@ -252,7 +252,7 @@ class DialogRNNModule(nn.Module):
         return ws["stats"]
 
 
-class DialogRNNTrainer:
+class DialogRNNTrainer(TrainerBase):
     """train_step / to_logits for ``--module=dialogrnn``: class-weighted MaskedNLLLoss, Adam lr 3e-4, no weight decay (the
     defaults of the sibling plugin, track_mm/dgcnv2.py:22-48,184-219)."""
 
@@ -275,20 +275,3 @@ class DialogRNNTrainer:
         self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
                                decoupled=(o.name == "AdamW"), seed=params.seed)
         self.model.rng_state = self.optim.rng_state
-
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        return out
-
-    def train_step(self, batch):
-        self.model.train()
-        stats = self.model.loss_and_grads(batch, self.class_weight)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats

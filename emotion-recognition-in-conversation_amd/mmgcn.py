@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from . import capi
+from .capacity import TrainerBase
 from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, all_reduce_grads, linear_fwd, linear_wgrad, \
     matmul_wgrad_io
 from .rnn import BiLSTM2, lstm_groups
@@ -425,7 +426,7 @@ class MMGCNModule(nn.Module):
         return ws["stats"]
 
 
-class MMGCNTrainer:
+class MMGCNTrainer(TrainerBase):
     """train_step / to_logits of track_mm/mmgcn.py:126-157 (CE, Adam lr 3e-4 wd 3e-5)."""
 
     def __init__(self, params, device):
@@ -440,17 +441,7 @@ class MMGCNTrainer:
         self.model.rng_state = self.optim.rng_state
         self.optim.skip_flag = self.model.flat.health    # a chain exchange timed out (on any rank) -> the update is skipped
 
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
-
-    def prepare_batch(self, batch):
-        out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        tl = batch.get("text_length")
-        if "n_nodes" not in out and torch.is_tensor(tl) and not tl.is_cuda:
-            out["n_nodes"] = int(tl.sum())      # host tensor: no device sync when a batch carries no labels
-        return out
-
-    def train_step(self, batch):
+    def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
         self.model.train()
         stats = self.model.loss_and_grads(batch)
         scale = all_reduce_grads(self.model.flat)

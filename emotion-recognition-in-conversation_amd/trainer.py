@@ -17,6 +17,8 @@ every batch on the device (datasets.DeviceDialogueStore) instead of in a DataLoa
 ``--resident`` runs the training epochs from that store (ResidentEpochs); ``--resident_eval`` the test epochs too,
 scored on the device (ResidentEval, report_from_cm).
 """
+import contextlib
+import dataclasses
 import json
 import os
 import sys
@@ -27,6 +29,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import capi
+from .capacity import node_capacity
 from .collate import ERCCollate
 from .synthetic import make_dialogues, make_mosei_dialogues
 
@@ -168,10 +171,46 @@ class FixedBatches:
             yield i, self.batches[i]
 
 
+def batch_table(lengths, offsets, order, B):
+    """The int32 table [steps, 2 B] of an epoch that visits the store's dialogues in ``order``, B per step: a row holds the
+    lengths, then the first store rows of its batch's dialogues; 0 in the empty slots of a smaller last batch.
+    ``lengths`` / ``offsets``: int32 arrays, one entry per dialogue."""
+    n = len(order)
+    steps = -(-n // B)
+    flat = np.zeros((2, steps * B), dtype=np.int32)
+    flat[0, :n], flat[1, :n] = lengths[order], offsets[order]
+    return np.concatenate([flat[0].reshape(steps, B), flat[1].reshape(steps, B)], axis=1)
+
+
+@contextlib.contextmanager
+def dynamic_n(model, on=True):
+    """capacity mode inside the block: the module's launches are sized for the capacities and read the batch's true node
+    count from the device (``model.dynamic_n``); off again afterwards, whatever the block raised"""
+    if on:
+        model.dynamic_n = True
+    try:
+        yield
+    finally:
+        if on:
+            model.dynamic_n = False
+
+
+@dataclasses.dataclass
+class GraphEntry:
+    """what StepGraphs keeps per key"""
+    static: dict               # the static input buffers the step runs on
+    fill: object               # fill(static, batch) copies a batch in; None: the batch IS the static buffers (FixedBatches)
+    capacity: bool             # a capacity bucket (the step runs under dynamic_n) or an exact batch shape
+    seen: int = 0              # how many times the key has occurred
+    graph: object = None       # the captured step, once there is one
+    out: object = None         # the captured step's output (the device stats tensor)
+    workspace: object = None   # the module's workspace of this key: the graph holds raw pointers into it
+
+
 class StepGraphs:
     """Captured HIP graphs of the whole training step, least-recently-used eviction.
 
-    * CAPACITY BUCKETS (trainers that offer ``capacity_bucket``: COGMEN in the bf16 compute mode, DialogueGCN on its default
+    * CAPACITY BUCKETS (trainers with capacity.CapacityBuckets: COGMEN in the bf16 compute mode, DialogueGCN on its default
       path, bc-LSTM / bc-GRU with ``--capacity_buckets=True`` or ``--resident``).  The reference reshuffles
       the dialogues every epoch and its last batch is smaller (lumo/trainer/trainer.py:429-442, mmbase.py:468), so (B, T, N)
       almost never repeats.  A bucket is a set of static capacity-sized input buffers -- ``batch_size`` dialogues (missing
@@ -183,15 +222,16 @@ class StepGraphs:
     * otherwise one graph per exact batch shape, captured when the shape shows up the SECOND time (under shuffling most
       shapes never repeat: capturing each one would cost a synchronisation + instantiation per step and pin a workspace).
 
-    Whatever the key, the first step of a key is a real training step run EAGERLY ON THE GRAPH'S OWN STATIC BUFFERS (the
-    batch is copied in first): every pointer the later capture sees -- inputs, workspace, weight-gradient table -- already
-    exists, so nothing is allocated or uploaded while capturing.  Losses are those of the eager loop."""
+    Whatever the key, its entry is a ``GraphEntry`` and its first step is a real training step run EAGERLY ON THE GRAPH'S OWN
+    STATIC BUFFERS (the batch is copied in first): every pointer the later capture sees -- inputs, workspace, weight-gradient
+    table -- already exists, so nothing is allocated or uploaded while capturing (``_eager_then_capture``, which ``step`` and
+    ``precapture`` share).  Losses are those of the eager loop."""
 
     def __init__(self, trainer, maxsize=16, capture=True):
         import collections
         self.trainer, self.maxsize = trainer, maxsize
         self.capture = capture     # False (--graph_capture=False): same buckets and static buffers, every step eager
-        self.cache = collections.OrderedDict()     # key -> [static, graph or None, out, workspace, fill, dynamic]
+        self.cache = collections.OrderedDict()     # key -> GraphEntry
         self.replays = self.eager = self.captures = 0
         self.capture_failed = False
         self.lazy = True           # False (data parallel): only precaptured graphs, everything else eager
@@ -219,19 +259,27 @@ class StepGraphs:
             if torch.is_tensor(v):
                 static[k].copy_(v, non_blocking=True)
 
-    def _run(self, ent, eager):
-        static, graph, out, dynamic = ent[0], ent[1], ent[2], ent[5]
-        model = self.trainer.model
-        if dynamic:
-            model.dynamic_n = True
-        try:
-            if eager:
-                return self.trainer.train_step(static)
-            graph.replay()
-            return out
-        finally:
-            if dynamic:
-                model.dynamic_n = False
+    def _eager_then_capture(self, ent, capture=True, must=False):
+        """A real step on the entry's static buffers, then (``capture``) the same step captured over them.  A step that cannot
+        be captured stays eager, here and for every later key; ``must``: the failure is raised instead."""
+        tr = self.trainer
+        with dynamic_n(tr.model, ent.capacity):
+            stats = tr.train_step(ent.static)
+            if not capture:
+                return stats
+            try:
+                ent.graph, ent.out = self._capture(lambda: tr.train_step(ent.static))
+            except Exception as exc:
+                if must:
+                    raise
+                print(json.dumps({"graph_replay": "capture failed, staying eager", "error": str(exc)[:200]}), file=sys.stderr)
+                self.capture_failed = True
+                return stats
+        # the graph holds raw pointers into this key's workspace: keep the workspace object alive with the graph, whatever
+        # the module's own LRU cache does with it (evaluation batches of other shapes come in between)
+        ent.workspace = getattr(tr.model, "_last_ws", None)
+        self.captures += 1
+        return stats
 
     def precapture(self, probe):
         """Data parallel: capture every capacity bucket NOW, in the same order on every rank.  A captured step contains the
@@ -252,17 +300,9 @@ class StepGraphs:
         if getattr(flat, "p2p", None) is not None:
             snap.append((flat.p2p.epoch, flat.p2p.epoch.clone()))
         for key, make, fill, synth in tr.all_capacity_buckets(probe):
-            static = make()
-            synth(static)
-            ent = self.cache[key] = [static, None, None, None, fill, True, 1]
-            self._run(ent, eager=True)
-            model.dynamic_n = True
-            try:
-                g, out = self._capture(lambda: tr.train_step(static))
-            finally:
-                model.dynamic_n = False
-            ent[1], ent[2], ent[3] = g, out, getattr(model, "_last_ws", None)
-            self.captures += 1
+            ent = self.cache[key] = GraphEntry(make(), fill, True, seen=1)
+            synth(ent.static)
+            self._eager_then_capture(ent, must=True)
         self._sync()
         with torch.no_grad():
             for t, keep in snap:
@@ -294,165 +334,41 @@ class StepGraphs:
             else:
                 static = batch if resident else {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
                 fill = None if resident else self._copy_in
-            ent = self.cache[key] = [static, None, None, None, fill, bucket is not None]
-            ent.append(0)            # occurrences
+            ent = self.cache[key] = GraphEntry(static, fill, bucket is not None)
             while len(self.cache) > self.maxsize:
                 self.cache.popitem(last=False)
         else:
             self.cache.move_to_end(key)
-        static, graph, fill = ent[0], ent[1], ent[4]
-        ent[6] += 1
-        if fill is not None and (graph is not None or ent[6] > 1 or ent[5]):
-            fill(static, batch)          # (a plain first occurrence was cloned above: already in place)
-        if graph is not None:
+        ent.seen += 1
+        if ent.fill is not None and (ent.graph is not None or ent.seen > 1 or ent.capacity):
+            ent.fill(ent.static, batch)          # (a plain first occurrence was cloned above: already in place)
+        if ent.graph is not None:
             self.replays += 1
-            return self._run(ent, eager=False)
-        stats = self._run(ent, eager=True)                  # a real step, on the static buffers
+            ent.graph.replay()
+            return ent.out
         self.eager += 1
-        if self.capture_failed or not self.capture or not (ent[5] or ent[6] >= 2 or resident):
-            return stats                                    # plain shapes are captured on their second occurrence
-        try:
-            if ent[5]:
-                self.trainer.model.dynamic_n = True
-            g, out = self._capture(lambda: self.trainer.train_step(static))
-        except Exception as exc:                               # a step that cannot be captured stays eager
-            print(json.dumps({"graph_replay": "capture failed, staying eager", "error": str(exc)[:200]}), file=sys.stderr)
-            self.capture_failed = True
-            return stats
-        finally:
-            if ent[5]:
-                self.trainer.model.dynamic_n = False
-        # the graph holds raw pointers into this key's workspace: keep the workspace object alive with the graph, whatever
-        # the module's own LRU cache does with it (evaluation batches of other shapes come in between)
-        ent[1], ent[2], ent[3] = g, out, getattr(self.trainer.model, "_last_ws", None)
-        self.captures += 1
-        return stats
+        # plain shapes are captured on their second occurrence
+        return self._eager_then_capture(ent, capture=self.capture and not self.capture_failed and
+                                        (ent.capacity or ent.seen >= 2 or resident))
 
 
-class ResidentEpochs:
-    """``--resident``: the training dialogues live in HBM (datasets.DeviceDialogueStore, 288 GB per GPU: IEMOCAP's features are
-    16 MB) and a step's batch is never materialised.  Per epoch the host draws the permutation (DataLoader(shuffle=True)
-    semantics: every dialogue once, a smaller last batch) and uploads ONE int32 table [steps, 2 B] (lengths | first store
-    rows of every batch's dialogues); per step it copies that step's 2 B int32 into the fixed descriptor buffer and replays
-    the bucket's captured graph -- the projection launch reads feature rows, speakers and labels straight from the store
-    (csrc/cogmen_project.hip, resident mode).  Host work per step: one 256-byte device copy + one graph launch.
-    Trainers with ``resident_batch``: COGMEN, DialogueGCN, bc-LSTM / bc-GRU (their layer-0 input projection reads the store
-    through the row map of erc_bcrnn_meta_cap)."""
+class ResidentLoop:
+    """What ``--resident`` and ``--resident_eval`` share: the dialogues stay in a DeviceDialogueStore and a step's batch is
+    never materialised.  A step is 2 B int32 (a row of ``batch_table``) copied into the fixed descriptor ``cur_desc`` plus its
+    node capacity -- the batch's node count rounded up to N_BUCKET, at most B * T, T the store's own longest dialogue.  The
+    first visit of a capacity runs the subclass's ``_step`` eagerly on the trainer's resident batch of that capacity and then
+    captures it; every later step of that capacity is one copy, one dict lookup, one replay."""
 
     N_BUCKET = 128
 
-    def __init__(self, trainer, store, batch_size, seed, capture=True):
+    def __init__(self, trainer, store, batch_size, capture=True):
         self.trainer, self.store, self.B = trainer, store, int(batch_size)
-        self.gen = torch.Generator().manual_seed(seed)
         self.T = int(store.lengths.max())
-        dev = store.device
-        self.cur_desc = torch.zeros(2 * self.B, dtype=torch.int32, device=dev)
-        self.acc = torch.zeros(4, dtype=torch.float64, device=dev)      # sums of the steps' {loss, #correct, weight, -}
-        self.graphs, self.capture = {}, capture
-        self.replays = self.eager = self.captures = 0
-        self._lens32, self._offs32 = store.lengths.to(torch.int32), store.offsets[:-1].to(torch.int32)
-        self._ahead = []           # (node counts per step, device table) of the epochs planned ahead
-
-    def plan(self, n_epochs):
-        """Draw the permutations of the next ``n_epochs`` epochs (sequential randperm draws: the same epochs as drawing them
-        one by one) and upload their batch tables -- int32 [steps, 2 B]: lengths | first store rows, 0 for the empty slots of
-        a smaller last batch -- in one copy: nothing but the step loop is left inside an epoch."""
-        import numpy as np
-        st, B = self.store, self.B
-        n = len(st)
-        steps = -(-n // B)
-        lens, offs = self._lens32.numpy(), self._offs32.numpy()
-        tabs = np.zeros((n_epochs, steps, 2 * B), dtype=np.int32)
-        for e in range(n_epochs):
-            order = torch.randperm(n, generator=self.gen).numpy()
-            flat_l, flat_o = np.zeros(steps * B, dtype=np.int32), np.zeros(steps * B, dtype=np.int32)
-            flat_l[:n], flat_o[:n] = lens[order], offs[order]
-            tabs[e, :, :B], tabs[e, :, B:] = flat_l.reshape(steps, B), flat_o.reshape(steps, B)
-        dev = torch.from_numpy(tabs).to(st.device)
-        for e in range(n_epochs):
-            self._ahead.append((tabs[e, :, :B].sum(1).tolist(), dev[e]))
-
-    def supported(self):
-        """Can EVERY step of an epoch run from the resident store?  Probed with the smallest bucket and with the largest a batch
-        of this store can need (batch_size of its longest dialogues: above the fused path's node limit `resident_batch` returns
-        None -- found here, before the first epoch, not by a step in the middle of one)."""
-        lens = sorted((int(v) for v in self.store.lengths.tolist()), reverse=True)
-        worst = min(-(-sum(lens[:self.B]) // self.N_BUCKET) * self.N_BUCKET, self.B * self.T)
-        return all(self.trainer.resident_batch(self.store, self.cur_desc, self.B, self.T, cap) is not None
-                   for cap in sorted({self.N_BUCKET, max(worst, self.N_BUCKET)}))
-
-    def _step_fn(self, batch):
-        stats = self.trainer.train_step(batch)
-        self.acc.add_(stats[:4])
-        return stats
-
-    def epoch(self):
-        """one pass over the store; returns (#utterances, #steps)"""
-        st, B = self.store, self.B
-        n = len(st)
-        steps = -(-n // B)
-        if not self._ahead:
-            self.plan(1)
-        counts, table_dev = self._ahead.pop(0)
-        model = self.trainer.model
-        model.dynamic_n = True
-        try:
-            for s in range(steps):
-                self.cur_desc.copy_(table_dev[s], non_blocking=True)
-                n_cap = min(-(-counts[s] // self.N_BUCKET) * self.N_BUCKET, B * self.T)
-                ent = self.graphs.get(n_cap)
-                if ent is not None and ent[0] is not None:
-                    ent[0].replay()
-                    self.replays += 1
-                    continue
-                batch = self.trainer.resident_batch(st, self.cur_desc, B, self.T, n_cap)
-                self._step_fn(batch)                    # a real step; allocates the bucket's workspace
-                self.eager += 1
-                if not self.capture:
-                    continue
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._step_fn(batch)
-                self.graphs[n_cap] = (g, batch, getattr(model, "_last_ws", None))
-                self.captures += 1
-        finally:
-            model.dynamic_n = False
-        return sum(counts), steps
-
-
-class ResidentEval:
-    """``--resident_eval``: the test epoch from HBM, scored on the device.  The test dialogues stay in their
-    DeviceDialogueStore; the test order is fixed (sequential batches of ``batch_size`` dialogues, the last one padded with
-    zero-length slots: DataLoader(shuffle=False) semantics), so the whole int32 table [steps, 2 B] (lengths | first store
-    rows) is uploaded ONCE, here.  T is the TEST store's own longest dialogue; a step's node capacity is its node count rounded
-    up to N_BUCKET, at most B * T (buckets as in ResidentEpochs).  The first visit of a bucket runs the trainer's
-    ``resident_eval_step`` eagerly and captures it; from then on a test epoch is
-
-        cm.zero_() ; per step: copy 2 B int32, replay ; one cm.cpu() at the end
-
-    and every metric of the epoch line is a function of that confusion matrix (``report_from_cm``)."""
-
-    N_BUCKET = 128
-
-    def __init__(self, trainer, store, batch_size, capture=True, n_classes=None):
-        self.trainer, self.store, self.B = trainer, store, int(batch_size)
-        B, n = self.B, len(store)
-        self.steps = -(-n // B)
-        self.T = int(store.lengths.max())
-        flat_l, flat_o = np.zeros(self.steps * B, dtype=np.int32), np.zeros(self.steps * B, dtype=np.int32)
-        flat_l[:n], flat_o[:n] = store.lengths.to(torch.int32).numpy(), store.offsets[:-1].to(torch.int32).numpy()
-        self.table = np.concatenate([flat_l.reshape(self.steps, B), flat_o.reshape(self.steps, B)], axis=1)
-        self.counts = self.table[:, :B].sum(1).tolist()
-        self.caps = [min(-(-c // self.N_BUCKET) * self.N_BUCKET, B * self.T) for c in self.counts]
-        dev = store.device
-        self.table_dev = torch.from_numpy(self.table).to(dev)
-        self.cur_desc = torch.zeros(2 * B, dtype=torch.int32, device=dev)
-        C = int(n_classes if n_classes is not None else trainer.params.n_classes)
-        self.cm = torch.zeros(C, C, dtype=torch.int64, device=dev)
+        self.cur_desc = torch.zeros(2 * self.B, dtype=torch.int32, device=store.device)
         self.graphs, self.capture = {}, capture      # node capacity -> (graph or None, batch, workspace kept alive)
         self.replays = self.eager = self.captures = 0
 
+    # -- the one place that touches the HIP runtime (a test replaces it with a recorder that does not execute what it records)
     def _capture(self, fn):
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -460,33 +376,124 @@ class ResidentEval:
             fn()
         return g
 
-    def supported(self):
-        """Can EVERY step of the test epoch run from the resident store?  (asked once, before the first epoch)"""
-        return all(self.trainer.resident_eval_batch(self.store, self.cur_desc, self.B, self.T, cap) is not None
-                   for cap in sorted(set(self.caps)))
+    def _caps_of(self, counts):
+        return [node_capacity(c, self.N_BUCKET, self.B * self.T) for c in counts]
 
-    def epoch(self):
-        """one pass over the test store; returns its confusion matrix (host int64 [C, C], true x predicted)"""
-        tr = self.trainer
-        self.cm.zero_()
-        for s in range(self.steps):
-            self.cur_desc.copy_(self.table_dev[s], non_blocking=True)
-            cap = self.caps[s]
-            ent = self.graphs.get(cap)
+    def _visit(self, cap):
+        """a capacity without a graph: a real step (it allocates the bucket's buffers), then the capture"""
+        ent = self.graphs.get(cap)
+        batch = ent[1] if ent is not None else self._batch(cap)
+        if batch is None:
+            raise capi.ErcGraftError("%s: the trainer offers no resident batch of capacity %d" % (type(self).__name__, cap))
+        ws = self._step(batch)
+        self.eager += 1
+        graph = None
+        if self.capture:
+            graph = self._capture(lambda: self._step(batch))
+            self.captures += 1
+        self.graphs[cap] = (graph, batch, ws)      # (the graph holds raw pointers into ws: kept alive with it)
+
+    def _steps(self, table_dev, caps):
+        cur_desc, graphs = self.cur_desc, self.graphs
+        for s, cap in enumerate(caps):
+            cur_desc.copy_(table_dev[s], non_blocking=True)
+            ent = graphs.get(cap)
             if ent is not None and ent[0] is not None:
                 ent[0].replay()
                 self.replays += 1
                 continue
-            batch = ent[1] if ent is not None else tr.resident_eval_batch(self.store, self.cur_desc, self.B, self.T, cap)
-            if batch is None:
-                raise capi.ErcGraftError("ResidentEval: the trainer offers no resident test batch of capacity %d" % cap)
-            ws = tr.resident_eval_step(batch, self.cm)            # a real step; allocates the bucket's buffers
-            self.eager += 1
-            graph = None
-            if self.capture:
-                graph = self._capture(lambda: tr.resident_eval_step(batch, self.cm))
-                self.captures += 1
-            self.graphs[cap] = (graph, batch, ws)      # (the graph holds raw pointers into ws: kept alive with it)
+            self._visit(cap)
+
+
+class ResidentEpochs(ResidentLoop):
+    """``--resident``: the training dialogues live in HBM (datasets.DeviceDialogueStore, 288 GB per GPU: IEMOCAP's features are
+    16 MB).  Per epoch the host draws the permutation (DataLoader(shuffle=True) semantics: every dialogue once, a smaller last
+    batch) and uploads ONE int32 table [steps, 2 B] (``batch_table``); per step it copies that step's 2 B int32 into the fixed
+    descriptor buffer and replays the bucket's captured graph -- the projection launch reads feature rows, speakers and labels
+    straight from the store (csrc/cogmen_project.hip, resident mode).  Host work per step: one 256-byte device copy + one
+    graph launch.  Trainers with ``resident_batch``: COGMEN, DialogueGCN, bc-LSTM / bc-GRU (their layer-0 input projection
+    reads the store through the row map of erc_bcrnn_meta_cap)."""
+
+    def __init__(self, trainer, store, batch_size, seed, capture=True):
+        super().__init__(trainer, store, batch_size, capture)
+        self.gen = torch.Generator().manual_seed(seed)
+        self.acc = torch.zeros(4, dtype=torch.float64, device=store.device)      # sums of the steps' {loss, #correct, weight, -}
+        self._lens32, self._offs32 = store.lengths.to(torch.int32).numpy(), store.offsets[:-1].to(torch.int32).numpy()
+        self._ahead = []           # (#utterances, node capacity per step, device table) of the epochs planned ahead
+
+    def plan(self, n_epochs):
+        """Draw the permutations of the next ``n_epochs`` epochs (sequential randperm draws: the same epochs as drawing them
+        one by one) and upload their batch tables in one copy: nothing but the step loop is left inside an epoch."""
+        n, B = len(self.store), self.B
+        tabs = np.zeros((n_epochs, -(-n // B), 2 * B), dtype=np.int32)
+        for e in range(n_epochs):
+            tabs[e] = batch_table(self._lens32, self._offs32, torch.randperm(n, generator=self.gen).numpy(), B)
+        dev = torch.from_numpy(tabs).to(self.store.device)
+        for e in range(n_epochs):
+            counts = tabs[e, :, :B].sum(1).tolist()
+            self._ahead.append((sum(counts), self._caps_of(counts), dev[e]))
+
+    def supported(self):
+        """Can EVERY step of an epoch run from the resident store?  Probed with the smallest bucket and with the largest a batch
+        of this store can need (batch_size of its longest dialogues: above the fused path's node limit `resident_batch` returns
+        None -- found here, before the first epoch, not by a step in the middle of one)."""
+        lens = sorted((int(v) for v in self.store.lengths.tolist()), reverse=True)
+        worst = self._caps_of([sum(lens[:self.B])])[0]
+        return all(self._batch(cap) is not None for cap in sorted({self.N_BUCKET, max(worst, self.N_BUCKET)}))
+
+    def _batch(self, cap):
+        return self.trainer.resident_batch(self.store, self.cur_desc, self.B, self.T, cap)
+
+    def _step(self, batch):
+        self.acc.add_(self.trainer.train_step(batch)[:4])
+        return getattr(self.trainer.model, "_last_ws", None)
+
+    def epoch(self):
+        """one pass over the store; returns (#utterances, #steps)"""
+        if not self._ahead:
+            self.plan(1)
+        n_utt, caps, table_dev = self._ahead.pop(0)
+        with dynamic_n(self.trainer.model):
+            self._steps(table_dev, caps)
+        return n_utt, len(caps)
+
+
+class ResidentEval(ResidentLoop):
+    """``--resident_eval``: the test epoch from HBM, scored on the device.  The test dialogues stay in their
+    DeviceDialogueStore; the test order is fixed (sequential batches of ``batch_size`` dialogues, the last one padded with
+    zero-length slots: DataLoader(shuffle=False) semantics), so the whole int32 table [steps, 2 B] (``batch_table``) is
+    uploaded ONCE, here.  T is the TEST store's own longest dialogue.  The first visit of a bucket runs the trainer's
+    ``resident_eval_step`` eagerly and captures it; from then on a test epoch is
+
+        cm.zero_() ; per step: copy 2 B int32, replay ; one cm.cpu() at the end
+
+    and every metric of the epoch line is a function of that confusion matrix (``report_from_cm``)."""
+
+    def __init__(self, trainer, store, batch_size, capture=True, n_classes=None):
+        super().__init__(trainer, store, batch_size, capture)
+        self.table = batch_table(store.lengths.to(torch.int32).numpy(), store.offsets[:-1].to(torch.int32).numpy(),
+                                 np.arange(len(store)), self.B)
+        self.steps = len(self.table)
+        self.counts = self.table[:, :self.B].sum(1).tolist()
+        self.caps = self._caps_of(self.counts)
+        self.table_dev = torch.from_numpy(self.table).to(store.device)
+        C = int(n_classes if n_classes is not None else trainer.params.n_classes)
+        self.cm = torch.zeros(C, C, dtype=torch.int64, device=store.device)
+
+    def supported(self):
+        """Can EVERY step of the test epoch run from the resident store?  (asked once, before the first epoch)"""
+        return all(self._batch(cap) is not None for cap in sorted(set(self.caps)))
+
+    def _batch(self, cap):
+        return self.trainer.resident_eval_batch(self.store, self.cur_desc, self.B, self.T, cap)
+
+    def _step(self, batch):
+        return self.trainer.resident_eval_step(batch, self.cm)
+
+    def epoch(self):
+        """one pass over the test store; returns its confusion matrix (host int64 [C, C], true x predicted)"""
+        self.cm.zero_()
+        self._steps(self.table_dev, self.caps)
         return self.cm.cpu()
 
 
@@ -562,6 +569,137 @@ def multiemo_report(true_multi, prob_multi, thresh=0.5):
             "mean_wa": float(np.mean(defined)) if defined else None}
 
 
+def _setup_graphs(params, trainer, train_loader, rank, world, device):
+    """(StepGraphs or None, FixedBatches or None).  Captured whole-step graphs: capacity buckets where the trainer offers
+    them, exact shapes otherwise.  Under data parallelism the captured step is the same one -- forward, backward, the RCCL
+    all-reduce, the optimizer -- but every capture must happen at the same point on every rank: buckets are captured up
+    front, in one order (StepGraphs.precapture); a trainer without buckets keeps the eager step there."""
+    if hasattr(trainer, "capacity_bucket"):
+        trainer.t_cap = bucket_t_cap(train_loader, world, device)
+    graphs = StepGraphs(trainer, capture=params.get("graph_capture", True)) if params.get("graph_replay", True) else None
+    fixed = FixedBatches(train_loader, trainer, params.seed + rank) if params.get("fixed_batches", False) else None
+    if graphs is not None and world > 1 and fixed is None:
+        probe = trainer.prepare_batch(first_batch(train_loader))
+        if hasattr(trainer, "all_capacity_buckets") and trainer.all_capacity_buckets(probe):
+            graphs.precapture(probe)
+            graphs.lazy = False         # a batch outside every bucket runs eagerly (same collectives, no capture)
+        else:
+            graphs = None
+    return graphs, fixed
+
+
+def _setup_resident(params, trainer, train_loader, test_loader, rank, world):
+    """(ResidentEpochs or None, ResidentEval or None) of ``--resident`` / ``--resident_eval``; a configuration that cannot
+    run that way exits here, before the first epoch"""
+    resident = res_eval = None
+    if params.get("resident", False):
+        if world > 1 or not isinstance(train_loader, StoreLoader) or not hasattr(trainer, "resident_batch"):
+            raise SystemExit("--resident needs --device_collate, one rank and a trainer with resident batches (capacity mode)")
+        resident = ResidentEpochs(trainer, train_loader.store, params.train.batch_size, params.seed + rank,
+                                  capture=params.get("graph_capture", True))
+        if not resident.supported():
+            raise SystemExit("--resident: this configuration cannot run its step in capacity mode")
+        resident.plan(params.epoch)
+    if params.get("resident_eval", False):      # the test epoch from HBM too, scored on the device (ResidentEval)
+        if resident is None:
+            raise SystemExit("--resident_eval needs --resident (the test epoch then runs from the HBM-resident test store)")
+        if not hasattr(trainer, "resident_eval_step"):
+            raise SystemExit("--resident_eval: this module's trainer has no resident_eval_step (--module=cogmen has one)")
+        if params.get("mosei_metric", "") == "multiemo":
+            raise SystemExit("--resident_eval: mosei_metric=multiemo reports multi-label metrics, which are no function of the "
+                             "confusion matrix the device returns")
+        res_eval = ResidentEval(trainer, test_loader.store, params.test.batch_size, capture=params.get("graph_capture", True))
+        if not res_eval.supported():
+            raise SystemExit("--resident_eval: this configuration cannot run its test step in capacity mode")
+    return resident, res_eval
+
+
+# -- one training epoch, in three forms.  The step forms return the batches' utterance counts; a step's stats go into its row
+#    of ``ring`` (no device->host synchronisation inside the epoch)
+def _train_epoch_resident(resident, t0, acc_prev, epoch, log):
+    """--resident: returns (#utterances, seconds, the running totals); prints the epoch's mean loss / accuracy"""
+    n_utt, n_st = resident.epoch()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    tot = resident.acc.cpu().tolist()                           # running totals: this epoch = the difference
+    acc = [a - b for a, b in zip(tot, acc_prev)]
+    if log:
+        print(json.dumps({"epoch": epoch, "steps": n_st, "Lall": acc[0] / n_st, "Acc": acc[1] / max(1, n_utt)}), flush=True)
+    return n_utt, dt, tot
+
+
+def _train_epoch_fixed(fixed, graphs, trainer, ring):
+    """--fixed_batches: the device batches collated once, in a fresh order; each one's graph binds to its own buffers"""
+    counts = []
+    for i, (bid, (n_b, dev_batch)) in enumerate(fixed):
+        stats = graphs.step(dev_batch, key=bid, resident=True) if graphs is not None else trainer.train_step(dev_batch)
+        ring[i].copy_(stats[:4], non_blocking=True)
+        counts.append(n_b)
+    return counts
+
+
+def _train_epoch_loader(loader, graphs, trainer, ring):
+    """the default: the loader's reshuffled batches, through StepGraphs where there is one"""
+    counts = []
+    for i, item in enumerate(loader):
+        dev_batch = trainer.prepare_batch(item)
+        stats = graphs.step(dev_batch) if graphs is not None else trainer.train_step(dev_batch)
+        ring[i].copy_(stats[:4], non_blocking=True)
+        counts.append(int(item["label"].shape[0]))
+    return counts
+
+
+def _print_step_lines(params, epoch, ring, counts, multitask):
+    rows = ring[:len(counts)].cpu().tolist()
+    for i, (row, n_b) in enumerate(zip(rows, counts)):
+        if (i + 1) % params.log_every == 0:
+            line = {"epoch": epoch, "step": i, "Lall": row[0], "Acc": row[1] / max(1, n_b)}
+            if multitask:
+                line.update(Lce=row[2], Lmulti=row[3])
+            print(json.dumps(line), flush=True)
+
+
+# -- one test epoch (after every training epoch: mmbase.py:136,180-201), in two forms
+def _test_epoch_resident(res_eval):
+    """--resident_eval: graph replays over the resident test store, one device -> host copy (the training epoch ended with a
+    synchronisation).  Returns (confusion matrix on the host, seconds)."""
+    t1 = time.perf_counter()
+    cm_host = res_eval.epoch()
+    torch.cuda.synchronize()
+    return cm_host, time.perf_counter() - t1
+
+
+def _test_epoch_loader(trainer, test_loader, multiemo):
+    """returns (true, pred, true_multi, prob_multi); the last two are filled under ``multiemo``"""
+    true, pred, true_multi, prob_multi = [], [], [], []
+    for batch in test_loader:
+        if multiemo:           # mosei_test_step (mmbase.py:167-178)
+            logits, logits7 = trainer.to_mosei_multitask_logits(trainer.prepare_batch(batch))
+            true_multi.append(batch["emo_label"].cpu().numpy())
+            prob_multi.append(torch.sigmoid(logits7).cpu().numpy())
+            pred.extend(logits.argmax(-1).cpu().tolist())
+            true.extend(batch["senti2_label"].tolist())
+            continue
+        logits = trainer.to_logits(trainer.prepare_batch(batch))
+        if logits.dim() == 3:
+            logits = logits[batch["attention_mask"].bool().to(logits.device)]
+        pred.extend(logits.argmax(-1).cpu().tolist())
+        true.extend(batch["label"].tolist())
+    return true, pred, true_multi, prob_multi
+
+
+def _epoch_line(epoch, utt_per_s, rep, best, counters, n_steps, test_s, multiemo_rep):
+    """the epoch's JSON line; ``counters``: the ResidentEpochs or StepGraphs of the run, None for a plain eager loop"""
+    line = {"epoch": epoch, "train_utt_per_s": utt_per_s, "test": {k: rep[k] for k in rep if k != "cm"}, "best": best,
+            "graph_replays": counters.replays if counters else 0, "eager_steps": counters.eager if counters else n_steps,
+            "graphs_captured": counters.captures if counters else 0}
+    if test_s is not None:
+        line["test_s"] = test_s
+    if multiemo_rep is not None:
+        line["multiemo"] = multiemo_rep
+    return line
+
+
 def run(trainer_cls, params_cls, argv=None):
     params = params_cls()
     params.from_args(argv)
@@ -588,118 +726,43 @@ def run(trainer_cls, params_cls, argv=None):
         from . import checkpoint
         checkpoint.load(trainer, params.load)
     train_loader, test_loader = make_loaders(params, rank, world, device)
-    best = {}
-    # captured whole-step graphs (StepGraphs): capacity buckets where the trainer offers them, exact shapes otherwise.  Under
-    # data parallelism the captured step is the same one -- forward, backward, the RCCL all-reduce, the optimizer -- but
-    # every capture must happen at the same point on every rank: buckets are captured up front, in one order
-    # (StepGraphs.precapture); a trainer without buckets keeps the eager step there.
-    if hasattr(trainer, "capacity_bucket"):
-        trainer.t_cap = bucket_t_cap(train_loader, world, device)
-    graphs = StepGraphs(trainer, capture=params.get("graph_capture", True)) if params.get("graph_replay", True) else None
-    fixed = FixedBatches(train_loader, trainer, params.seed + rank) if params.get("fixed_batches", False) else None
-    if graphs is not None and world > 1 and fixed is None:
-        probe = trainer.prepare_batch(first_batch(train_loader))
-        if hasattr(trainer, "all_capacity_buckets") and trainer.all_capacity_buckets(probe):
-            graphs.precapture(probe)
-            graphs.lazy = False         # a batch outside every bucket runs eagerly (same collectives, no capture)
-        else:
-            graphs = None
+    graphs, fixed = _setup_graphs(params, trainer, train_loader, rank, world, device)
     n_steps = len(fixed) if fixed is not None else len(train_loader)
     ring = torch.zeros(max(1, n_steps), 4, dtype=torch.float32, device=device)    # per-step {loss, #correct, ...}: read once per epoch
-    resident, acc_prev = None, [0.0] * 4
-    if params.get("resident", False):
-        if world > 1 or not isinstance(train_loader, StoreLoader) or not hasattr(trainer, "resident_batch"):
-            raise SystemExit("--resident needs --device_collate, one rank and a trainer with resident batches (capacity mode)")
-        resident = ResidentEpochs(trainer, train_loader.store, params.train.batch_size, params.seed + rank,
-                                  capture=params.get("graph_capture", True))
-        if not resident.supported():
-            raise SystemExit("--resident: this configuration cannot run its step in capacity mode")
-        resident.plan(params.epoch)
-    res_eval = None
-    if params.get("resident_eval", False):      # the test epoch from HBM too, scored on the device (ResidentEval)
-        if resident is None:
-            raise SystemExit("--resident_eval needs --resident (the test epoch then runs from the HBM-resident test store)")
-        if not hasattr(trainer, "resident_eval_step"):
-            raise SystemExit("--resident_eval: this module's trainer has no resident_eval_step (--module=cogmen has one)")
-        if params.get("mosei_metric", "") == "multiemo":
-            raise SystemExit("--resident_eval: mosei_metric=multiemo reports multi-label metrics, which are no function of the "
-                             "confusion matrix the device returns")
-        res_eval = ResidentEval(trainer, test_loader.store, params.test.batch_size, capture=params.get("graph_capture", True))
-        if not res_eval.supported():
-            raise SystemExit("--resident_eval: this configuration cannot run its test step in capacity mode")
+    resident, res_eval = _setup_resident(params, trainer, train_loader, test_loader, rank, world)
+    best, acc_prev = {}, [0.0] * 4
+    log = rank == 0 and params.log_every
+    multiemo = params.get("mosei_metric", "") == "multiemo"
+    check_cluster = getattr(trainer.model, "check_cluster", lambda: None)
     for epoch in range(params.epoch):
         trainer.model.train()
-        t0, n_utt, counts = time.perf_counter(), 0, []
+        t0, counts = time.perf_counter(), []
         if resident is not None:
-            n_utt, n_st = resident.epoch()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            tot = resident.acc.cpu().tolist()                           # running totals: this epoch = the difference
-            acc, acc_prev = [a - b for a, b in zip(tot, acc_prev)], tot
-            if rank == 0 and params.log_every:
-                print(json.dumps({"epoch": epoch, "steps": n_st, "Lall": acc[0] / n_st, "Acc": acc[1] / max(1, n_utt)}), flush=True)
-        for i, item in enumerate(() if resident is not None else (fixed if fixed is not None else train_loader)):
-            if fixed is not None:
-                bid, (n_b, dev_batch) = item
-            else:
-                bid, n_b, dev_batch = None, int(item["label"].shape[0]), trainer.prepare_batch(item)
-            stats = graphs.step(dev_batch, key=bid, resident=fixed is not None) if graphs is not None else trainer.train_step(dev_batch)
-            ring[i].copy_(stats[:4], non_blocking=True)          # no device->host synchronisation inside the epoch
-            n_utt += n_b
-            counts.append(n_b)
+            n_utt, dt, acc_prev = _train_epoch_resident(resident, t0, acc_prev, epoch, log)
+        elif fixed is not None:
+            counts = _train_epoch_fixed(fixed, graphs, trainer, ring)
+        else:
+            counts = _train_epoch_loader(train_loader, graphs, trainer, ring)
         torch.cuda.synchronize()
-        if hasattr(trainer.model, "check_cluster"):
-            trainer.model.check_cluster()
+        check_cluster()
         if resident is None:
-            dt = time.perf_counter() - t0
-        if rank == 0 and params.log_every:
-            rows = ring[:len(counts)].cpu().tolist()
-            multitask = getattr(trainer, "multitask", False)
-            for i, (row, n_b) in enumerate(zip(rows, counts)):
-                if (i + 1) % params.log_every == 0:
-                    line = {"epoch": epoch, "step": i, "Lall": row[0], "Acc": row[1] / max(1, n_b)}
-                    if multitask:
-                        line.update(Lce=row[2], Lmulti=row[3])
-                    print(json.dumps(line), flush=True)
-        # test after every epoch (mmbase.py:136,180-201)
+            n_utt, dt = sum(counts), time.perf_counter() - t0
+        if log:
+            _print_step_lines(params, epoch, ring, counts, getattr(trainer, "multitask", False))
         trainer.model.eval()
-        true, pred = [], []
-        multiemo = params.get("mosei_metric", "") == "multiemo"
-        true_multi, prob_multi = [], []
-        cm_host, test_s = None, None
-        if res_eval is not None:       # graph replays over the resident test store, one device -> host copy (the training
-            t1 = time.perf_counter()   # epoch above ended with a synchronisation)
-            cm_host = res_eval.epoch()
-            torch.cuda.synchronize()
-            test_s = time.perf_counter() - t1
-        for batch in (test_loader if res_eval is None else ()):
-            if multiemo:           # mosei_test_step (mmbase.py:167-178)
-                logits, logits7 = trainer.to_mosei_multitask_logits(trainer.prepare_batch(batch))
-                true_multi.append(batch["emo_label"].cpu().numpy())
-                prob_multi.append(torch.sigmoid(logits7).cpu().numpy())
-                pred.extend(logits.argmax(-1).cpu().tolist())
-                true.extend(batch["senti2_label"].tolist())
-                continue
-            logits = trainer.to_logits(trainer.prepare_batch(batch))
-            if logits.dim() == 3:
-                logits = logits[batch["attention_mask"].bool().to(logits.device)]
-            pred.extend(logits.argmax(-1).cpu().tolist())
-            true.extend(batch["label"].tolist())
-        if hasattr(trainer.model, "check_cluster"):
-            trainer.model.check_cluster()      # a timeout inside to_logits would make the metrics below meaningless
+        cm_host = test_s = None
+        if res_eval is not None:
+            cm_host, test_s = _test_epoch_resident(res_eval)
+        else:
+            true, pred, true_multi, prob_multi = _test_epoch_loader(trainer, test_loader, multiemo)
+        check_cluster()      # a timeout inside to_logits would make the metrics below meaningless
         if rank == 0:
             rep = classification_report(true, pred, params.n_classes) if cm_host is None else report_from_cm(cm_host.numpy())
             for k in ("acc", "wa", "f1", "mif1", "maf1", "pre", "rec"):
                 best[k] = max(best.get(k, 0.0), rep[k])
-            line = {"epoch": epoch, "train_utt_per_s": n_utt / dt, "test": {k: rep[k] for k in rep if k != "cm"},
-                    "best": best, "graph_replays": (resident or graphs).replays if (resident or graphs) else 0,
-                    "eager_steps": (resident or graphs).eager if (resident or graphs) else len(counts),
-                    "graphs_captured": (resident or graphs).captures if (resident or graphs) else 0}
-            if test_s is not None:
-                line["test_s"] = test_s
-            if multiemo:
-                line["multiemo"] = multiemo_report(np.concatenate(true_multi), np.concatenate(prob_multi))
-            print(json.dumps(line), flush=True)
+            multiemo_rep = multiemo_report(np.concatenate(true_multi), np.concatenate(prob_multi)) if multiemo else None
+            print(json.dumps(_epoch_line(epoch, n_utt / dt, rep, best, resident or graphs, len(counts), test_s, multiemo_rep)),
+                  flush=True)
     if params.get("save") and rank == 0:
         from . import checkpoint
         checkpoint.save(trainer, params.save)

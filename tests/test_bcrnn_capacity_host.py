@@ -188,7 +188,7 @@ def test_a_reshuffled_ragged_loop_replays_a_handful_of_buckets():
             keys.add(bucket[0])
             g.step(b)
             steps += 1
-            assert g.cache[bucket[0]][0]["text_length"].tolist() == lens + [0] * (8 - len(lens))
+            assert g.cache[bucket[0]].static["text_length"].tolist() == lens + [0] * (8 - len(lens))
     n_buckets = len(tr.all_capacity_buckets(_batch([3])))
     assert 1 < len(keys) <= n_buckets == 3                    # 8 x 40 = 320 rows: 128 | 256 | 320
     assert g.captures == len(keys) and g.eager == g.captures and g.replays == steps - g.captures
