@@ -969,6 +969,16 @@ def dgcn_tail(slabs, n_slabs, slab_stride, rgcn_bias, g, window, W_rel, b_rel, W
         _call("erc_dgcn_tail_cap", *args, n_dev, label_rows)
 
 
+def dgcn_tail_eval(slabs, n_slabs, slab_stride, rgcn_bias, g, window, W_rel, b_rel, W_root, W1, b1, W2, b2, labels, n_classes,
+                   n_rows, Xc, ldx, cm, logits=None, n_dev=None, label_rows=None):
+    """DialogueGCN's tail in eval mode, scored on the device: cm int64 [C, C] (true x predicted) is added to
+    (erc_dgcn_tail_eval, ercgraft.h)"""
+    if cm.dtype != torch.int64 or cm.numel() != n_classes * n_classes or not cm.is_contiguous():
+        raise ErcGraftError("dgcn_tail_eval: cm must be a contiguous int64 [%d, %d] tensor" % (n_classes, n_classes))
+    _call("erc_dgcn_tail_eval", slabs, n_slabs, int(slab_stride), rgcn_bias, g["in_ptr"], g["in_src"], window, W_rel, b_rel, W_root,
+          W1, b1, W2, b2, labels, label_rows, n_classes, n_rows, n_dev, Xc, ldx, cm, logits)
+
+
 def head_ce_stats_floats(n_rows):
     return int(lib().erc_head_ce_stats_floats(n_rows))
 

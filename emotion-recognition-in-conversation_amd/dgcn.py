@@ -108,6 +108,7 @@ class DGCNModule(nn.Module):
         self.gcn = _GCN(hidden_size, H1, H1, n_speakers)
         self.clf = _Classifier(hidden_size + H1, 100, n_classes, dropout)
         self.flat, self._ws, self._seed = None, WorkspaceCache(), seed
+        self._eval_ws = WorkspaceCache()      # eval_scores' own buffers: never those of a (captured) training step
 
     def live_groups(self):
         g, c = self.gcn, self.clf
@@ -188,14 +189,18 @@ class DGCNModule(nn.Module):
         max_rows, max_win = capi.dgcn_tail_limits()
         return self.fused_tail and self.n_classes <= 8 and N <= max_rows and 0 <= self.wp <= max_win and 0 <= self.wf <= max_win
 
-    def _forward_impl(self, x, spk, lens, B, T, N, training, with_logits=True, tail=False, desc=None):
+    def _forward_impl(self, x, spk, lens, B, T, N, training, with_logits=True, tail=False, desc=None, capacity=None, ws=None):
         """``desc`` (int32 [2 B]: lengths | first store rows): RESIDENT batch -- x [U, D] / spk [U] are a feature store's
-        arrays, B / T / N are capacities (capacity mode is implied), no padded block exists."""
+        arrays, B / T / N are capacities (capacity mode is implied), no padded block exists.
+        ``capacity`` (None = the module's ``dynamic_n``): B / T / N are capacities whatever the module's state says
+        (eval_scores); ``ws``: the caller's own workspace instead of the training step's of this shape."""
         fp = self.flat
-        if (self.dynamic_n or desc is not None) and not (self.dynamic_n and tail and self.supports_capacity()):
+        capacity = self.dynamic_n if capacity is None else capacity
+        if (capacity or desc is not None) and not (capacity and tail and self.supports_capacity()):
             raise capi.ErcGraftError("DialogueGCN capacity mode needs the default fused training path (supports_capacity) "
                                      "with N_cap <= %d" % capi.dgcn_tail_limits()[0])
-        ws = self._workspace(B, T, N, x.device)
+        if ws is None:
+            ws = self._workspace(B, T, N, x.device)
         g, pl = ws["g"], ws["planner"]
         pl.reset()
         D, C, BT, XW = self.input_size, self.n_classes, B * T, G_DIM + H1
@@ -268,6 +273,48 @@ class DGCNModule(nn.Module):
         B, T, N = self._shape(input_tensor, text_length, label, kwargs.get("n_nodes"))
         ws = self._forward_impl(input_tensor, speaker_tensor, text_length, B, T, N, self.training)
         return ws["logits"], ws["Xc"][:, G_DIM:]
+
+    def _make_eval_workspace(self, B, T, N, device):
+        """what the capacity-mode forward up to the RGCN slabs and erc_dgcn_tail_eval touch: no gradient buffer"""
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        w = (self.wp if self.wp >= 0 else T) + (self.wf if self.wf >= 0 else T) + 1
+        E = max(1, N * min(w, T))
+        g = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), in_ptr=i32(N + 1), in_src=i32(E),
+                 in_typ=i32(E), out_ptr=i32(N + 1), out_dst=i32(E), out_typ=i32(E), out_eid=i32(E), counts=i32(2))
+        ws = dict(g=g, E=E, Xc=f32(N, G_DIM + H1), ATT=f32(N, G_DIM), norm=f32(E), Z=f32(N, self._kb * G_DIM),
+                  rgcn_slabs=f32(capi.brgcn_fwd_tile_slab_floats(N)), logits=f32(N, self.n_classes))
+        ws["planner"] = GemmPlanner(device, 1 << 20)      # (no product of this forward is wide enough to split K into slabs)
+        return ws
+
+    def eval_scores(self, batch, cm):
+        """Forward-only step in capacity form, scored on the device: the window graph build, the compact BiLSTM, EdgeAtt and
+        the RGCN tile launch in eval mode (no dropout), then the evaluation tail (csrc/dgcn_tail_eval.hip,
+        erc_dgcn_tail_eval), which reads the batch's node count from the device and ADDS its confusion matrix to ``cm``
+        (int64 [C, C], true x predicted).  No host synchronisation, capturable.  ``batch``: a resident batch (``desc`` +
+        ``caps``, as loss_and_grads takes) or a capacity-sized static one (B dialogue slots of which some may have length 0,
+        label [N_cap]).  Returns the step's own workspace (``logits`` [N_cap, C]: rows below the device count are valid).
+        Depends on neither ``dynamic_n`` nor ``train()`` / ``eval()`` and touches no training state (dropout RNG included)."""
+        if self.flat is None:
+            raise capi.ErcGraftError("call DGCNModule.finalize(device) before eval_scores")
+        x, spk, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
+        desc = batch.get("desc")
+        B, T, N = batch["caps"] if desc is not None else (x.shape[0], x.shape[1], int(ys.shape[0]))
+        if not self.supports_capacity(batch if desc is None else None) or N > capi.dgcn_tail_limits()[0]:
+            why = ("RGCNConv runs in relation space (the default for two speakers): --relation_space=False" if self.relation_space
+                   else "an unfused path, features of another dtype than the compute mode's, more than 8 classes, a window or "
+                   "N_cap = %d above the fused tail's limits %s" % (N, capi.dgcn_tail_limits()))
+            raise capi.ErcGraftError("DialogueGCN eval_scores needs capacity mode (supports_capacity): " + why)
+        ws = self._eval_ws.get(("eval", B, T, N), lambda: self._make_eval_workspace(B, T, N, x.device))
+        self._forward_impl(x, spk, lens, B, T, N, False, tail=True, desc=desc, capacity=True, ws=ws)
+        fp, g = self.flat, ws["g"]
+        slabs, n_slabs, stride = ws["tail_src"]
+        capi.dgcn_tail_eval(slabs, n_slabs, stride, fp.w("gcn.conv1.bias"), g, max(self.wp, self.wf),
+                            fp.w("gcn.conv2.lin_rel.weight"), fp.w("gcn.conv2.lin_rel.bias"), fp.w("gcn.conv2.lin_root.weight"),
+                            fp.w("clf.lin1.weight"), fp.w("clf.lin1.bias"), fp.w("clf.lin2.weight"), fp.w("clf.lin2.bias"), ys,
+                            self.n_classes, N, ws["Xc"], G_DIM + H1, cm, logits=ws["logits"], n_dev=g["counts"],
+                            label_rows=g["node_row"] if desc is not None else None)
+        return ws
 
     def loss_and_grads(self, batch, class_weight=None):
         x, spk, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
@@ -427,3 +474,13 @@ class DGCNTrainer(CapacityBuckets, TrainerBase):
     def _resident_ok(self, store, B_cap, T_cap, N_cap):
         want = torch.bfloat16 if self.model.compute == "bf16" else torch.float32
         return store.fused.dtype == want and store.fused.shape[1] == self.model.input_size and self._capacity_ok(B_cap, T_cap, N_cap)
+
+    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
+        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
+        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
+        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
+
+    def resident_eval_step(self, batch, cm):
+        """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
+        sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
+        return self.model.eval_scores(batch, cm)

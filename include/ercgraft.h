@@ -1047,6 +1047,28 @@ int erc_dgcn_tail_cap(const float* slabs, int n_slabs, int64_t slab_stride, cons
                       float* Hc, float* AGG, float* Zc, float* logits, float* dlogits, float* dZc, float* dXc, int lddx,
                       float* dAGG, float* dHc, float* stats, const int32_t* n_dev, const int32_t* label_rows, void* stream);
 
+/* DialogueGCN's tail in EVAL mode, scored on the device, in ONE launch (csrc/dgcn_tail_eval.hip): the forward half of
+ * erc_dgcn_tail with erc_head_eval's counting behind it.  Per row i < n:
+ *   Hc_i = sum_s slabs[s * slab_stride + i * 100 ..] + rgcn_bias                               (models/rgcn.py:345-355)
+ *   AGG_i = sum_{j -> i (in-CSR)} Hc_j ;  graph_out = AGG_i W_rel^T + b_rel + Hc_i W_root^T    (dgcn_models.py:42,46)
+ *   Zc = relu([Xc_i[0:200] | graph_out] W1^T + b1) -- eval(): no dropout, no RNG read;  logits = Zc W2^T + b2
+ *                                                                                              (dgcn_models.py:163-170)
+ *   pred = the first index of the maximum (torch.argmax);  cm[label * C + pred] += 1           (mmbase.py:180-201)
+ * cm: int64 [C, C] (true class x predicted class), ADDED TO -- the caller zeroes it before the first launch of a test epoch;
+ * integer counts (a histogram per workgroup, one atomic add per non-empty cell): the result does not depend on the order.
+ * logits [n_rows, C] (or NULL): the scores, written for the counted rows only.
+ * n = *n_dev clamped to [0, n_rows] (0 allowed); n_dev == NULL: n = n_rows (n_rows = 0 is no launch).  Rows at or beyond n are
+ * never read -- their slab, Xc and label entries -- nor counted (their in-CSR ranges are empty: erc_window_graph_build); a row
+ * whose label (labels[label_rows[i]] with label_rows, labels[i] without) lies outside [0, C) is not counted.  Xc [n_rows, ldx]
+ * is read-only, columns [0,200).  Writes nothing but cm and logits: gradients, stats, RNG state and Xc stay as they are.
+ * Limits as erc_dgcn_tail: window <= erc_dgcn_tail_max_window(), n_rows <= erc_dgcn_tail_max_rows(), n_classes <= 8, ldx and
+ * slab_stride multiples of 4, slabs / rgcn_bias / weights / Xc 16-byte aligned, cm 8-byte aligned.  Exact fp32 products. */
+int erc_dgcn_tail_eval(const float* slabs, int n_slabs, int64_t slab_stride, const float* rgcn_bias, const int32_t* in_ptr,
+                       const int32_t* in_src, int window, const float* W_rel, const float* b_rel, const float* W_root,
+                       const float* W1, const float* b1, const float* W2, const float* b2, const int64_t* labels,
+                       const int32_t* label_rows, int n_classes, int n_rows, const int32_t* n_dev, const float* Xc, int ldx,
+                       int64_t* cm, float* logits, void* stream);
+
 /* ------------------------------------------------------------------------
  * MMGCN (track_mm/mmgcn.py:56-123, track_mm/mmgcn_models.py:8-39,344-394,493-646).  Node rows are
  * modality-major: node (m, i) = m*N + i, i = node_off[b] + t, in the modality order [a, v, l] of
