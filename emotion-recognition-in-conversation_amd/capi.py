@@ -256,6 +256,20 @@ def cross_entropy(logits, ld, Cn, n_rows, row_map, labels, weight, grad_scale, d
     _call("erc_cross_entropy", logits, ld, Cn, n_rows, row_map, labels, weight, grad_scale, dlogits, lddl, stats)
 
 
+def cross_entropy_cap(logits, ld, Cn, n_cap, n_dev, row_map, labels, weight, grad_scale, dlogits, lddl, stats):
+    """erc_cross_entropy over the first *n_dev (device int32) of n_cap samples (ercgraft.h)"""
+    _call("erc_cross_entropy_cap", logits, ld, Cn, n_cap, n_dev, row_map, labels, weight, grad_scale, dlogits, lddl, stats)
+
+
+def rows_score(logits, ld, n_logit_rows, Cn, n_cap, n_dev, row_map, labels, cm):
+    """argmax of the rows row_map[i], i < *n_dev, counted into cm int64 [C, C] (true x predicted), which is added to"""
+    _call("erc_rows_score", logits, ld, n_logit_rows, Cn, n_cap, n_dev, row_map, labels, cm)
+
+
+def rows_score_max_classes():
+    return int(lib().erc_rows_score_max_classes())
+
+
 def adam_step(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, grad_scale, clip_norm, gnorm, state, shadow=None,
               shadow_off=0, shadow_n=0, skip_flag=None):
     _call("erc_adam_step", p, g, m, v, n, lr, b1, b2, eps, wd, int(decoupled), grad_scale, clip_norm, gnorm, state, shadow,
@@ -523,6 +537,13 @@ def dag_attn_sums(alpha, H1, ldo, pred, spk, B, T, A):
 
 def dag_meta(speaker_onehot, speaker_ids, sb, st, S, lengths, B, T, spk, pred, node_off, node_row):
     _call("erc_dag_meta", speaker_onehot, speaker_ids, sb, st, S, lengths, B, T, spk, pred, node_off, node_row)
+
+
+def dag_meta_cap(speaker_onehot, speaker_ids, sb, st, S, lengths, desc, store_speaker, store_label, zero_store_row, B, T, n_cap,
+                 spk, pred, node_off, node_row, x_row, label_out, counts):
+    """erc_dag_meta in capacity mode: bucket form (lengths + padded speakers) or resident form (desc + the store's arrays)"""
+    _call("erc_dag_meta_cap", speaker_onehot, speaker_ids, sb, st, S, lengths, desc, store_speaker, store_label, zero_store_row,
+          B, T, n_cap, spk, pred, node_off, node_row, x_row, label_out, counts)
 
 
 def _tcap_only(name, lengths, node_off):

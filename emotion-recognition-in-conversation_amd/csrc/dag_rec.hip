@@ -187,6 +187,89 @@ __global__ __launch_bounds__(256) void dag_meta_kernel(const float* __restrict__
     }
 }
 
+// CAPACITY form of the above: B dialogue slots (a missing one has length 0), T = T_cap, n_cap labels.  One workgroup per
+// slot.  Lengths come from lengths[] (bucket form: speakers from the padded one-hot / id tensor) or from desc[0..B)
+// (resident form: speakers, labels and feature rows from the flat store, first store row of slot b = desc[B + b]).
+// A length is clamped to [0, T]; positions t >= length and empty slots get speaker 0 whatever the tensor holds there.
+// Every store of node_row / label_out is guarded by n_cap and every store row by [0, zero_row]: a malformed length or
+// descriptor cannot make this kernel, or a consumer of its tables, touch memory outside the caller's buffers.
+__global__ __launch_bounds__(256) void dag_meta_cap_kernel(const float* __restrict__ onehot, const int64_t* __restrict__ ids,
+                                                           int64_t sb, int64_t st, int S, const int64_t* __restrict__ lengths,
+                                                           const int32_t* __restrict__ desc,
+                                                           const int64_t* __restrict__ store_spk,
+                                                           const int64_t* __restrict__ store_label, int zero_row, int B, int T,
+                                                           int n_cap, int32_t* __restrict__ spk, int32_t* __restrict__ pred,
+                                                           int32_t* __restrict__ node_off, int32_t* __restrict__ node_row,
+                                                           int32_t* __restrict__ x_row, int64_t* __restrict__ label_out,
+                                                           int32_t* __restrict__ counts) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    __shared__ int s_spk[1024];
+    __shared__ int red[3][256];
+    int before = 0, total = 0, longest = 0;
+    for (int i = tid; i < B; i += 256) {
+        const int len = min(max(desc ? (int)desc[i] : (int)lengths[i], 0), T);
+        total += len;
+        if (i < b) before += len;
+        longest = max(longest, len);
+    }
+    red[0][tid] = before, red[1][tid] = total, red[2][tid] = longest;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+            red[0][tid] += red[0][tid + o], red[1][tid] += red[1][tid + o];
+            red[2][tid] = max(red[2][tid], red[2][tid + o]);
+        }
+        __syncthreads();
+    }
+    const int noff = red[0][0], N = red[1][0];
+    const int L = min(max(desc ? (int)desc[b] : (int)lengths[b], 0), T);
+    const int first = desc ? (int)desc[B + b] : 0;
+    for (int t = tid; t < T; t += 256) {
+        int s = 0, srow = zero_row;
+        if (t < L) {
+            if (desc) {
+                srow = first + t;
+                if (srow < 0 || srow >= zero_row) srow = zero_row;      // outside the store: the zero row, speaker 0
+                else s = (int)store_spk[srow];
+            } else if (onehot) {  // argmax of the one-hot row (first maximum, like torch.argmax)
+                const float* row = onehot + (int64_t)b * sb + (int64_t)t * st;
+                float best = row[0];
+                for (int c = 1; c < S; ++c)
+                    if (row[c] > best) best = row[c], s = c;
+            } else {
+                s = (int)ids[(int64_t)b * sb + (int64_t)t * st];
+            }
+        }
+        s_spk[t] = s;
+        spk[b * T + t] = s;
+        if (x_row) x_row[b * T + t] = srow;
+        if (t < L && noff + t < n_cap) {
+            node_row[noff + t] = b * T + t;
+            if (label_out) label_out[noff + t] = srow < zero_row ? store_label[srow] : 0;
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < T; t += 256) {
+        int p = -1;
+        for (int j = t - 1; j >= 0; --j)
+            if (s_spk[j] == s_spk[t]) {
+                p = j;
+                break;
+            }
+        pred[b * T + t] = p;
+    }
+    if (tid == 0) {
+        node_off[b] = noff;
+        if (b == B - 1) node_off[B] = noff + L;
+        if (b == 0) counts[0] = N, counts[1] = red[2][0];
+    }
+    // the capacity tail [N, n_cap): a legal row (0) that no consumer may read, label 0
+    for (int64_t i = (int64_t)N + (int64_t)b * 256 + tid; i < n_cap; i += (int64_t)gridDim.x * 256) {
+        node_row[i] = 0;
+        if (label_out) label_out[i] = 0;
+    }
+}
+
 
 // ----------------------------------------------------------------------------------------------- forward
 // The forward runs the LAYERS as a pipeline: layer l needs, at its step i, only h^{(l-1)}_{i+1} of the layer below, so
@@ -995,6 +1078,29 @@ extern "C" int erc_dag_meta(const float* speaker_onehot, const int64_t* speaker_
     hipLaunchKernelGGL(dag_meta_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, speaker_onehot, speaker_ids, spk_sb,
                        spk_st, n_speakers, lengths, B, T, spk, pred, node_off, node_row);
     ERC_LAUNCH_CHECK("dag_meta");
+    return ERC_OK;
+}
+
+extern "C" int erc_dag_meta_cap(const float* speaker_onehot, const int64_t* speaker_ids, int64_t spk_sb, int64_t spk_st,
+                                int n_speakers, const int64_t* lengths, const int32_t* desc, const int64_t* store_speaker,
+                                const int64_t* store_label, int zero_store_row, int B, int T, int n_cap, int32_t* spk,
+                                int32_t* pred, int32_t* node_off, int32_t* node_row, int32_t* x_row, int64_t* label_out,
+                                int32_t* counts, void* stream) {
+    ERC_REQUIRE(spk && pred && node_off && node_row && counts, "dag_meta_cap: null pointer");
+    ERC_REQUIRE(B > 0 && T > 0 && T <= MAX_T && n_cap > 0, "dag_meta_cap: B=%d T=%d n_cap=%d (T <= %d)", B, T, n_cap, MAX_T);
+    if (desc) {
+        ERC_REQUIRE(!lengths && !speaker_onehot && !speaker_ids, "dag_meta_cap: desc (resident form) takes no padded tensors");
+        ERC_REQUIRE(store_speaker && store_label && x_row && label_out && zero_store_row >= 0,
+                    "dag_meta_cap: the resident form needs the store's speakers and labels, x_row and label_out");
+    } else {
+        ERC_REQUIRE(lengths && (speaker_onehot != nullptr) != (speaker_ids != nullptr) && n_speakers > 0,
+                    "dag_meta_cap: the bucket form needs lengths and one-hot OR ids");
+        ERC_REQUIRE(!store_speaker && !store_label && !x_row && !label_out, "dag_meta_cap: store arguments without desc");
+    }
+    hipLaunchKernelGGL(dag_meta_cap_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, speaker_onehot, speaker_ids, spk_sb,
+                       spk_st, n_speakers, lengths, desc, store_speaker, store_label, zero_store_row, B, T, n_cap, spk, pred,
+                       node_off, node_row, x_row, label_out, counts);
+    ERC_LAUNCH_CHECK("dag_meta_cap");
     return ERC_OK;
 }
 

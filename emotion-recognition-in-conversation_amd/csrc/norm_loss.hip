@@ -133,12 +133,16 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const float* __restri
 // weights [8 + 2w], [9 + 2w] partials of workgroup w, [4] (as int) arrival counter (zero between calls).
 constexpr int CE_MAXWG = 64;
 
+// CAP (erc_cross_entropy_cap): n_rows is a capacity, the batch's sample count is *n_dev (clamped to [0, n_rows]); samples at
+// or beyond it are not read, and a count of 0 gives loss 0 / stats 0 with nothing written to dlogits.
+template <bool CAP>
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits, int ld, int C,
                                                             int n_rows, const int32_t* __restrict__ row_map,
                                                             const int64_t* __restrict__ labels,
                                                             const float* __restrict__ weight, float grad_scale,
                                                             float* __restrict__ dlogits, int lddl,
-                                                            float* __restrict__ stats) {
+                                                            float* __restrict__ stats, const int32_t* __restrict__ n_dev) {
+    if (CAP) n_rows = min(max(*n_dev, 0), n_rows);
     __shared__ double red[256];
     double* const s_red = red;
     __shared__ double s_wsum;
@@ -230,13 +234,47 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
             __syncthreads();
         }
         if (tid == 0) {
-            stats[0] = (float)(lsum / wsum);
+            stats[0] = (CAP && n_rows == 0) ? 0.f : (float)(lsum / wsum);
             stats[1] = (float)s_red[0];
             stats[2] = (float)wsum;
             *reinterpret_cast<int*>(stats + 4) = 0;
         }
     }
 }
+
+// ------------------------------------------------------------ scoring of padded logits (erc_rows_score)
+// Sample i < n = clamp(*n_dev, 0, n_cap) reads logits row row_map[i] (or i), predicts the first index of the maximum and
+// counts cm[label * C + pred].  Integer counts: a histogram per workgroup in LDS, then one 64-bit vector atomic add per
+// non-empty cell, so the result does not depend on the order.  A NaN logit never wins (fmaxf skips it, and NaN == max is
+// false); a row of nothing but NaN, a label outside [0, C) and a row index outside [0, n_logit_rows) are not counted.
+constexpr int RS_MAXC = 16;
+constexpr int RS_MAXWG = 64;
+
+__global__ __launch_bounds__(256) void rows_score_kernel(const float* __restrict__ logits, int ld, int n_logit_rows, int C,
+                                                         int n_cap, const int32_t* __restrict__ n_dev,
+                                                         const int32_t* __restrict__ row_map,
+                                                         const int64_t* __restrict__ labels, unsigned long long* cm) {
+    __shared__ int s_cm[RS_MAXC * RS_MAXC];
+    const int tid = threadIdx.x;
+    s_cm[tid] = 0;      // 256 threads = RS_MAXC * RS_MAXC cells
+    __syncthreads();
+    const int n = min(max(*n_dev, 0), n_cap);
+    for (int i = blockIdx.x * 256 + tid; i < n; i += gridDim.x * 256) {
+        const int64_t row = row_map ? (int64_t)row_map[i] : (int64_t)i;
+        if (row < 0 || row >= n_logit_rows) continue;
+        const float* z = logits + row * ld;
+        float mx = z[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
+        int am = -1;
+        for (int c = C - 1; c >= 0; --c)
+            if (z[c] == mx) am = c;
+        const int64_t y = labels[i];
+        if (am >= 0 && y >= 0 && y < C) atomicAdd(&s_cm[(int)y * C + am], 1);
+    }
+    __syncthreads();
+    if (tid < C * C && s_cm[tid] > 0) atomicAdd(cm + tid, (unsigned long long)s_cm[tid]);
+}
+static_assert(RS_MAXC * RS_MAXC == 256, "one histogram cell per thread");
 
 // ------------------------------------------------------------ fused classifier tail
 // logits = Z W^T + b (C <= 8 classes, F <= 128 features), cross entropy, and the gradient wrt Z through the
@@ -564,9 +602,39 @@ extern "C" int erc_cross_entropy(const float* logits, int ld, int C, int n_rows,
     ERC_REQUIRE(C > 0 && n_rows > 0 && ld >= C, "cross_entropy: C=%d n_rows=%d ld=%d", C, n_rows, ld);
     int grid = erc_cdiv(n_rows, 256);
     if (grid > CE_MAXWG) grid = CE_MAXWG;
-    hipLaunchKernelGGL(cross_entropy_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_rows,
-                       row_map, labels, weight, grad_scale, dlogits, lddl, stats);
+    hipLaunchKernelGGL(cross_entropy_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_rows,
+                       row_map, labels, weight, grad_scale, dlogits, lddl, stats, (const int32_t*)nullptr);
     ERC_LAUNCH_CHECK("cross_entropy");
+    return ERC_OK;
+}
+
+extern "C" int erc_cross_entropy_cap(const float* logits, int ld, int C, int n_cap, const int32_t* n_dev,
+                                     const int32_t* row_map, const int64_t* labels, const float* weight, float grad_scale,
+                                     float* dlogits, int lddl, float* stats, void* stream) {
+    ERC_REQUIRE(logits && labels && stats && n_dev, "cross_entropy_cap: null pointer");
+    ERC_REQUIRE(C > 0 && n_cap > 0 && ld >= C && (!dlogits || lddl >= C), "cross_entropy_cap: C=%d n_cap=%d ld=%d lddl=%d", C,
+                n_cap, ld, lddl);
+    int grid = erc_cdiv(n_cap, 256);
+    if (grid > CE_MAXWG) grid = CE_MAXWG;
+    hipLaunchKernelGGL(cross_entropy_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_cap, row_map,
+                       labels, weight, grad_scale, dlogits, lddl, stats, n_dev);
+    ERC_LAUNCH_CHECK("cross_entropy_cap");
+    return ERC_OK;
+}
+
+extern "C" int erc_rows_score_max_classes(void) { return RS_MAXC; }
+
+extern "C" int erc_rows_score(const float* logits, int ld, int n_logit_rows, int C, int n_cap, const int32_t* n_dev,
+                              const int32_t* row_map, const int64_t* labels, int64_t* cm, void* stream) {
+    ERC_REQUIRE(logits && labels && n_dev && cm, "rows_score: null pointer");
+    ERC_REQUIRE(C > 0 && C <= RS_MAXC && n_cap > 0 && n_logit_rows > 0 && ld >= C, "rows_score: C=%d n_cap=%d rows=%d ld=%d (C <= %d)",
+                C, n_cap, n_logit_rows, ld, RS_MAXC);
+    ERC_REQUIRE(((uintptr_t)cm & 7) == 0, "rows_score: cm must be 8-byte aligned");
+    int grid = erc_cdiv(n_cap, 256);
+    if (grid > RS_MAXWG) grid = RS_MAXWG;
+    hipLaunchKernelGGL(rows_score_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, n_logit_rows, C, n_cap, n_dev,
+                       row_map, labels, reinterpret_cast<unsigned long long*>(cm));
+    ERC_LAUNCH_CHECK("rows_score");
     return ERC_OK;
 }
 

@@ -22,10 +22,12 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import TrainerBase
+from .capacity import CapacityBuckets, TrainerBase
 from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
 
 HID = 300
+MAX_T = 1021           # the recurrence's limit on the padded length (csrc/dag_rec.hip MAX_T: erc_dag_meta, erc_dag_rec_config)
+MAX_B = 4096           # dialogues per batch: one launch epoch word per dialogue group in rec_state
 LDG = 6 * HID + 4      # row pitch of the hoisted gate block: 1800 gate columns + the query-score column (+ pad to 16 bytes)
 
 
@@ -64,6 +66,15 @@ class DAGERCModule(nn.Module):
         self.flat = None
         self._ws = WorkspaceCache()
         self._seed = seed
+        # CAPACITY MODE (trainer.StepGraphs buckets, trainer.ResidentEpochs): the batch tensors are capacity-sized static
+        # buffers -- B dialogue slots of which some may have length 0, T the longest dialogue of the split, label [N_cap].
+        # The step computes all B*T padded rows anyway (dagerc.py:164-189) and masks in the loss: rows at or behind a
+        # dialogue's length never feed an earlier row (the DAG looks backwards) and get a zero dlogits row, so they add exact
+        # zeros to every weight gradient.  The batch's node count enters only the valid-row map, the loss and the scoring:
+        # erc_dag_meta_cap writes it to ws["counts"], erc_cross_entropy_cap / erc_rows_score read it there, and ONE captured
+        # HIP graph serves every batch that fits.  The recurrence runs T_cap steps whatever the batch's longest dialogue is.
+        self.dynamic_n = False
+        self._eval_ws = WorkspaceCache()      # eval_scores' own buffers: never those of a (captured) training step
 
     # ------------------------------------------------------------------ setup
     def live_groups(self):
@@ -101,50 +112,70 @@ class DAGERCModule(nn.Module):
         """workspace of the most recent forward (tests / bench read results out of it)"""
         return self._ws.last
 
-    def _workspace(self, B, T, N, device):
+    def _workspace(self, B, T, N, device, cap=False):
+        if cap:      # no launch scales with N: every node capacity of one (B_cap, T_cap) shares ONE workspace
+            return self._ws.get((B, T, "capacity"), lambda: self._make_workspace(B, T, B * T, device, cap=True))
         return self._ws.get((B, T, N), lambda: self._make_workspace(B, T, N, device))
 
-    def _make_workspace(self, B, T, N, device):
+    def supports_capacity(self, batch=None):
+        """Can a step run in capacity mode?  The class count must fit the scoring kernel; a batch must carry features of the
+        compute mode's dtype, int64 lengths and padded speakers (one-hot [B, T, S] float or ids [B, T])."""
+        ok = self.n_classes <= capi.rows_score_max_classes()
+        if ok and batch is not None:
+            x, spk, lens = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"]
+            ok = (x.dim() == 3 and x.dtype == (torch.bfloat16 if self.compute == "bf16" else torch.float32) and
+                  int(x.shape[2]) == self.emb_dim and lens.dtype == torch.int64 and
+                  ((spk.dim() == 3 and spk.dtype == torch.float32) or (spk.dim() == 2 and spk.dtype == torch.int64)))
+        return bool(ok)
+
+    def _make_workspace(self, B, T, N, device, cap=False, grads=True):
+        """``cap``: plus the capacity step's device counts, row map and gathered labels.  ``grads`` False (eval_scores): the
+        forward's buffers, configuration and tables alone."""
         BT, L, C, D = B * T, self.gnn_layers, self.n_classes, self.emb_dim
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        per_layer = lambda *s: [f32(*s) for _ in range(L)]
         ws = dict(
-            spk=i32(B, T), pred=i32(B, T), node_off=i32(B + 1), node_row=i32(max(N, 1)),
-            Hall=f32(BT, HID * (L + 1)), dHall=f32(BT, HID * (L + 1)),
-            GI=[f32(BT, LDG) for _ in range(L)], GH=[f32(BT, 6 * HID) for _ in range(L)],
-            Mseq=[f32(BT, HID) for _ in range(L)], R=[f32(BT, 2 * HID) for _ in range(L)],
-            ks=[f32(BT) for _ in range(L)], alpha=[torch.zeros(B, T, T, dtype=torch.float32, device=device) for _ in range(L)],
-            Y1=f32(BT, HID), Y2=f32(BT, HID), logits=f32(BT, C), dlogits=f32(BT, C), dY2=f32(BT, HID),
-            dY1=f32(BT, HID), DGI=[f32(BT, LDG) for _ in range(L)], DGH=[f32(BT, 6 * HID) for _ in range(L)],
-            # dM | dks | attention-weighted sums per layer (kept until the batched weight-gradient launch at the end of the step)
-            dM=[f32(BT, HID) for _ in range(L)], dks=[f32(BT) for _ in range(L)], A=[f32(BT, 2 * HID) for _ in range(L)],
-            stats=torch.zeros(256, dtype=torch.float32, device=device),
-        )
+            spk=i32(B, T), pred=i32(B, T), node_off=i32(B + 1), node_row=i32(max(N, 1)), Hall=f32(BT, HID * (L + 1)),
+            GI=per_layer(BT, LDG), GH=per_layer(BT, 6 * HID), Mseq=per_layer(BT, HID), R=per_layer(BT, 2 * HID), ks=per_layer(BT),
+            alpha=[torch.zeros(B, T, T, dtype=torch.float32, device=device) for _ in range(L)],
+            Y1=f32(BT, HID), Y2=f32(BT, HID), logits=f32(BT, C))
+        if grads:
+            ws.update(
+                dHall=f32(BT, HID * (L + 1)), dlogits=f32(BT, C), dY2=f32(BT, HID), dY1=f32(BT, HID),
+                DGI=per_layer(BT, LDG), DGH=per_layer(BT, 6 * HID),
+                # dM | dks | attention-weighted sums per layer (kept until the batched weight-gradient launch at the end of the step)
+                dM=per_layer(BT, HID), dks=per_layer(BT), A=per_layer(BT, 2 * HID),
+                stats=torch.zeros(256, dtype=torch.float32, device=device))
         # cfg = (elements per workgroup, dialogues per group, groups per launch, layers per launch) of the recurrence
         # kernels per direction, from the device's CU count and the occupancy query (csrc/dag_rec.hip);
         # ERC_DAG_EPC / ERC_DAG_DG / ERC_DAG_LPL force a forward configuration, ERC_DAG_BEPC / ERC_DAG_BDG a backward one
-        import os
-        if B > 4096:
+        if B > MAX_B:
             raise capi.ErcGraftError("DAG-ERC: more than 4096 dialogues per batch")
         env = lambda k: int(os.environ.get(k, 0))
-        ws["cfg_f"] = capi.dag_rec_config(0, B, T, L, env("ERC_DAG_EPC"), env("ERC_DAG_DG"), env("ERC_DAG_LPL"))
-        ws["cfg_b"] = capi.dag_rec_config(1, B, T, L, env("ERC_DAG_BEPC"), env("ERC_DAG_BDG"), env("ERC_DAG_BLPL"))
-        ws["cfg"] = (tuple(ws["cfg_f"]), tuple(ws["cfg_b"]))
         i64 = lambda n: torch.zeros(n // 8 + 1, dtype=torch.int64, device=device)
+        ws["cfg_f"] = capi.dag_rec_config(0, B, T, L, env("ERC_DAG_EPC"), env("ERC_DAG_DG"), env("ERC_DAG_LPL"))
         ws["scratch_f"] = i64(capi.dag_rec_scratch_bytes(0, B, T, ws["cfg_f"]))
-        ws["scratch_b"] = i64(capi.dag_rec_scratch_bytes(1, B, T, ws["cfg_b"]))
-        W5 = HID * (L + 1)
         lw = [self._layer_w(l) for l in range(L)]
         ws["tables"] = {k: capi.ptr_table([w[k] for w in lw]) for k in ("Wh", "bh", "W_hh_c", "b_hh_c", "W_ih_p", "b_ih_p", "Wr", "w_k")}
         ws["tables"].update(H1=capi.ptr_table([ws["Hall"][:, HID * (l + 1):] for l in range(L)]),
-                            Hl=capi.ptr_table([ws["Hall"][:, HID * l:] for l in range(L)]),
-                            **{k: capi.ptr_table(ws[k]) for k in ("GI", "Mseq", "GH", "R", "ks", "alpha", "DGI", "DGH", "dM", "dks")})
-        slab = 8 * BT * HID + 10 * (HID * self.in_dim) + 6 * L * (6 * HID * HID + 2 * HID * HID) + (1 << 20)
-        ws["planner"] = GemmPlanner(device, slab, grad=self.flat.grad)
-        # the fp32 weight gradients as three-term bf16 splits (csrc/wgrad.hip MB == 2, fp32-class: 3.54 -> 3.50 ms per step);
-        # ERC_DAG_X3=0: exact fp32 products
-        ws["planner"].mma_bf16 = 2 if os.environ.get("ERC_DAG_X3", "1") == "1" else 0
-        ws["jobs"] = None
+                            **{k: capi.ptr_table(ws[k]) for k in ("GI", "Mseq", "GH", "R", "ks", "alpha")})
+        if grads:
+            ws["cfg_b"] = capi.dag_rec_config(1, B, T, L, env("ERC_DAG_BEPC"), env("ERC_DAG_BDG"), env("ERC_DAG_BLPL"))
+            ws["cfg"] = (tuple(ws["cfg_f"]), tuple(ws["cfg_b"]))
+            ws["scratch_b"] = i64(capi.dag_rec_scratch_bytes(1, B, T, ws["cfg_b"]))
+            ws["tables"].update(Hl=capi.ptr_table([ws["Hall"][:, HID * l:] for l in range(L)]),
+                                **{k: capi.ptr_table(ws[k]) for k in ("DGI", "DGH", "dM", "dks")})
+            slab = 8 * BT * HID + 10 * (HID * self.in_dim) + 6 * L * (6 * HID * HID + 2 * HID * HID) + (1 << 20)
+            ws["planner"] = GemmPlanner(device, slab, grad=self.flat.grad)
+            # the fp32 weight gradients as three-term bf16 splits (csrc/wgrad.hip MB == 2, fp32-class: 3.54 -> 3.50 ms per step);
+            # ERC_DAG_X3=0: exact fp32 products
+            ws["planner"].mma_bf16 = 2 if os.environ.get("ERC_DAG_X3", "1") == "1" else 0
+            ws["jobs"] = None
+        else:
+            ws["planner"] = GemmPlanner(device, 8 * BT * HID + (1 << 20))      # the head's split-K slabs, nothing else
+        if cap:      # the batch's {node count, longest dialogue}; resident: the store rows of the padded rows, the gathered labels
+            ws.update(counts=i32(2), x_row=i32(BT), label=torch.zeros(BT, dtype=torch.int64, device=device))
         return ws
 
     def check_cluster(self):
@@ -168,14 +199,52 @@ class DAGERCModule(nn.Module):
                     Wr=fp.w("gather.%d.Wr0.weight" % l), w_k=fp.w("gather.%d.linear.weight" % l).view(-1)[HID:])
 
     # ---------------------------------------------------------------- forward
-    def _forward_impl(self, x, speaker_tensor, text_length, B, T, N, training):
+    def _meta_cap(self, ws, x, speaker_tensor, text_length, B, T, N, desc, store_label):
+        """erc_dag_meta_cap into ``ws``; returns the row map the consumers of x read the store through (resident) or None"""
+        if N > B * T or N < 1:
+            raise capi.ErcGraftError("DAG-ERC capacity mode: N_cap = %d outside [1, B_cap * T_cap = %d]" % (N, B * T))
+        out = (ws["spk"], ws["pred"], ws["node_off"], ws["node_row"])
+        if desc is not None:
+            if speaker_tensor.dim() != 1 or speaker_tensor.dtype != torch.int64 or store_label.dtype != torch.int64 or \
+                    desc.dtype != torch.int32 or int(desc.numel()) != 2 * B or x.dim() != 2 or \
+                    int(speaker_tensor.shape[0]) != int(x.shape[0]) - 1:
+                raise capi.ErcGraftError("DAG-ERC resident batch: features [U + 1, D] (a zero row appended), flat int64 speaker "
+                                         "ids and labels [U], desc int32 [2 B]")
+            capi.dag_meta_cap(None, None, 0, 0, 1, None, desc, speaker_tensor, store_label, int(x.shape[0]) - 1, B, T, N, *out,
+                              ws["x_row"], ws["label"], ws["counts"])
+            return ws["x_row"]
+        if text_length.dtype != torch.int64:
+            raise capi.ErcGraftError("DAG-ERC capacity mode needs int64 text_length")
+        if speaker_tensor.dim() == 3:
+            if speaker_tensor.stride(2) != 1 or speaker_tensor.dtype != torch.float32:
+                raise capi.ErcGraftError("DAG-ERC capacity mode: one-hot speakers must be fp32 with unit stride")
+            capi.dag_meta_cap(speaker_tensor, None, speaker_tensor.stride(0), speaker_tensor.stride(1), speaker_tensor.shape[2],
+                              text_length, None, None, None, 0, B, T, N, *out, None, None, ws["counts"])
+        else:
+            capi.dag_meta_cap(None, speaker_tensor, speaker_tensor.stride(0), speaker_tensor.stride(1), 1 << 30, text_length,
+                              None, None, None, 0, B, T, N, *out, None, None, ws["counts"])
+        return None
+
+    def _forward_impl(self, x, speaker_tensor, text_length, B, T, N, training, desc=None, capacity=None, ws=None,
+                      store_label=None):
+        """``capacity`` (None = the module's ``dynamic_n``): B / T / N are capacities, the batch's node count is on the device.
+        ``desc`` (int32 [2 B]: lengths | first store rows): RESIDENT batch -- x [U + 1, D] is a feature store with a zero row
+        appended, speaker_tensor [U] / store_label [U] its flat arrays; no padded block exists, the three consumers of x read
+        the store through ws["x_row"].  ``ws``: the caller's own workspace (eval_scores)."""
         fp, dev = self.flat, x.device
-        ws = self._workspace(B, T, N, dev)
+        capacity = self.dynamic_n if capacity is None else capacity
+        if desc is not None and not capacity:
+            raise capi.ErcGraftError("DAG-ERC: a resident batch (desc) runs in capacity mode (dynamic_n)")
+        if ws is None:
+            ws = self._workspace(B, T, N, dev, cap=capacity)
         pl = ws["planner"]
         pl.reset()
         BT, L, C, D, W5 = B * T, self.gnn_layers, self.n_classes, self.emb_dim, HID * (self.gnn_layers + 1)
         x_bf16 = x.dtype == torch.bfloat16
-        if speaker_tensor.dim() == 3:     # one-hot [B,T,S] (speaker_onehot=True, dagerc.py:41)
+        gather = None
+        if capacity:
+            gather = self._meta_cap(ws, x, speaker_tensor, text_length, B, T, N, desc, store_label)
+        elif speaker_tensor.dim() == 3:     # one-hot [B,T,S] (speaker_onehot=True, dagerc.py:41)
             if speaker_tensor.stride(2) != 1:
                 speaker_tensor = speaker_tensor.contiguous()
             capi.dag_meta(speaker_tensor.float() if speaker_tensor.dtype != torch.float32 else speaker_tensor, None,
@@ -186,7 +255,7 @@ class DAGERCModule(nn.Module):
                           1 << 30, text_length, B, T, ws["spk"], ws["pred"], ws["node_off"], ws["node_row"])
         Hall = ws["Hall"]
         # H0 = relu(fc1(x)) over ALL B*T rows, padded ones included (dagerc.py:164)
-        linear_fwd(pl, x, D, None, fp.w("fc1.weight"), fp.w("fc1.bias"), Hall, W5, BT, HID, D, act=1, x_bf16=x_bf16)
+        linear_fwd(pl, x, D, gather, fp.w("fc1.weight"), fp.w("fc1.bias"), Hall, W5, BT, HID, D, act=1, x_bf16=x_bf16)
         # all layers in one pipelined launch (csrc/dag_rec.hip): the hoisted products (gates of both cells' hoisted sides,
         # query score) are computed -- and saved to GI -- by the recurrence's own workgroups
         capi.dag_rec_fwd(Hall, W5, L, ws["tables"], ws["pred"], ws["spk"], B, T, W5, LDG, ws["cfg_f"], self.rec_state,
@@ -200,10 +269,10 @@ class DAGERCModule(nn.Module):
                       c_slab=BT * HID)
         xs = pl.ws[src + Sa * BT * HID:]
         if x_bf16:
-            capi.gemm_bf16x(x, D, 0, None, W0[:, W5:], self.in_dim, 0, None, 1, xs, HID, BT, HID, D, split_k=Sx,
+            capi.gemm_bf16x(x, D, 0, gather, W0[:, W5:], self.in_dim, 0, None, 1, xs, HID, BT, HID, D, split_k=Sx,
                             c_slab=BT * HID)
         else:
-            capi.gemm_f32(x, D, 0, None, W0[:, W5:], self.in_dim, 0, None, xs, HID, BT, HID, D, split_k=Sx,
+            capi.gemm_f32(x, D, 0, gather, W0[:, W5:], self.in_dim, 0, None, xs, HID, BT, HID, D, split_k=Sx,
                           c_slab=BT * HID)
         capi.slab_reduce(pl.ws[src:], Sa + Sx, BT * HID, fp.w("out_mlp.0.bias"), HID, 1, ws["Y1"], BT * HID)
         p = self.drop_p if training else 0.0
@@ -217,23 +286,55 @@ class DAGERCModule(nn.Module):
         if self.flat is None:
             raise capi.ErcGraftError("call DAGERCModule.finalize(device) before forward")
         B, T, N = self._shape(input_tensor, text_length, label, kwargs.get("n_nodes"))
-        ws = self._forward_impl(input_tensor, speaker_tensor, text_length, B, T, N, self.training)
+        ws = self._forward_impl(input_tensor, speaker_tensor, text_length, B, T, N, self.training, capacity=False)
         return ws["logits"].view(B, T, self.n_classes), None
+
+    def eval_scores(self, batch, cm):
+        """Forward-only step in capacity form, scored on the device: erc_dag_meta_cap, the forward in eval mode (no dropout)
+        and erc_rows_score, which reads the batch's node count from the device and ADDS its confusion matrix to ``cm`` (int64
+        [C, C], true x predicted).  No host synchronisation, capturable.  ``batch``: a resident batch (``desc`` + ``caps``, as
+        loss_and_grads takes) or a capacity-sized static one (B dialogue slots of which some may have length 0, label
+        [N_cap]).  Returns the step's own workspace (``logits`` [B*T, C] padded; ``node_row`` maps the valid ones).  Reads
+        neither ``training`` nor ``dynamic_n`` and touches no training state (dropout RNG included)."""
+        if self.flat is None:
+            raise capi.ErcGraftError("call DAGERCModule.finalize(device) before eval_scores")
+        x, spk, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
+        desc = batch.get("desc")
+        B, T, N = batch["caps"] if desc is not None else (x.shape[0], x.shape[1], int(ys.shape[0]))
+        if not self.supports_capacity(batch if desc is None else None):
+            raise capi.ErcGraftError("DAG-ERC eval_scores needs capacity mode (supports_capacity): at most %d classes, features "
+                                     "of the compute mode's dtype" % capi.rows_score_max_classes())
+        ws = self._eval_ws.get(("eval", B, T), lambda: self._make_workspace(B, T, B * T, x.device, cap=True, grads=False))
+        self._forward_impl(x, spk, lens, B, T, N, False, desc=desc, capacity=True, ws=ws, store_label=ys if desc is not None else None)
+        C = self.n_classes
+        capi.rows_score(ws["logits"], C, B * T, C, N, ws["counts"], ws["node_row"], ws["label"] if desc is not None else ys, cm)
+        return ws
 
     # --------------------------------------------------------------- training
     def loss_and_grads(self, batch):
         x, spk, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
-        B, T, N = self._shape(x, lens, ys)
+        desc = batch.get("desc")          # resident batch (trainer.ResidentEpochs): the store + 2 B int32 of batch description
+        cap = self.dynamic_n
+        if desc is not None and not cap:
+            raise capi.ErcGraftError("DAG-ERC: a resident batch (desc) runs in capacity mode (dynamic_n)")
+        B, T, N = batch["caps"] if desc is not None else self._shape(x, lens, ys)
         training = self.training
         self.flat.roll_health()      # a timeout of the previous step: counted, cleared -- this step runs normally
-        ws = self._forward_impl(x, spk, lens, B, T, N, training)
+        ws = self._forward_impl(x, spk, lens, B, T, N, training, desc=desc, store_label=ys if desc is not None else None)
+        gather = ws["x_row"] if desc is not None else None      # resident: x is the store, read through the step's row map
+        if desc is not None:
+            ys = ws["label"]
         fp, pl = self.flat, ws["planner"]
         BT, L, C, D, W5 = B * T, self.gnn_layers, self.n_classes, self.emb_dim, HID * (self.gnn_layers + 1)
         x_bf16 = x.dtype == torch.bfloat16
         off = fp.offsets
         # masked CE (dagerc.py:225-226): the mask is the valid-row map; padded rows get zero gradient
         ws["dlogits"].zero_()
-        capi.cross_entropy(ws["logits"], C, C, N, ws["node_row"], ys, None, 1.0, ws["dlogits"], C, ws["stats"])
+        if cap:      # N is the label capacity; the batch's count is ws["counts"][0]
+            capi.cross_entropy_cap(ws["logits"], C, C, N, ws["counts"], ws["node_row"], ys, None, 1.0, ws["dlogits"], C,
+                                   ws["stats"])
+        else:
+            capi.cross_entropy(ws["logits"], C, C, N, ws["node_row"], ys, None, 1.0, ws["dlogits"], C, ws["stats"])
         p = self.drop_p if training else 0.0
         capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("out_mlp.5.weight"), HID, 1, None, ws["dY2"], HID, BT, HID, C,
                       act=2, aux=ws["Y2"], ldaux=HID, act_scale=1.0 / (1.0 - p))
@@ -248,7 +349,7 @@ class DAGERCModule(nn.Module):
         capi.gemm_f32(ws["dY1"], HID, 0, None, W0, self.in_dim, 1, None, ws["dHall"], W5, BT, W5, HID)
         slab = linear_wgrad(pl, ws["dY1"], HID, ws["Hall"], W5, None, HID, W5, BT, off["out_mlp.0.weight"], None,
                             ld_w=self.in_dim, force_slab=x_bf16)
-        linear_wgrad(pl, ws["dY1"], HID, x, D, None, HID, D, BT, None, off["out_mlp.0.bias"], x_bf16=x_bf16,
+        linear_wgrad(pl, ws["dY1"], HID, x, D, gather, HID, D, BT, None, off["out_mlp.0.bias"], x_bf16=x_bf16,
                      slab=slab, col_off=W5)
         # all layers in one pipelined launch, top layer first (csrc/dag_rec.hip): leaves the gate gradients, dM and dks of
         # every layer and the complete gradient wrt H_0 (through fc1's relu mask) in block 0 of dHall
@@ -272,14 +373,19 @@ class DAGERCModule(nn.Module):
                          defer=True)
             linear_wgrad(pl, ws["dM"][l], HID, ws["A"][l][:, HID:], 2 * HID, None, HID, HID, BT,
                          off["gather.%d.Wr1.weight" % l], None, defer=True)
-        linear_wgrad(pl, ws["dHall"], W5, x, D, None, HID, D, BT, off["fc1.weight"], off["fc1.bias"], x_bf16=x_bf16)
+        linear_wgrad(pl, ws["dHall"], W5, x, D, gather, HID, D, BT, off["fc1.weight"], off["fc1.bias"], x_bf16=x_bf16)
         pl.reduce_into(ws, fp.grad)
         return ws["stats"]
 
 
-class DAGERCTrainer(TrainerBase):
+class DAGERCTrainer(CapacityBuckets, TrainerBase):
     """train_step / to_logits of track_mm/dagerc.py:201-237 (masked CE, clip_grad_norm_ 5, AdamW)."""
     BF16_INPUT = True
+    # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  No launch of the step scales with N, so
+    #    there is ONE node capacity per (B_cap, T_cap): N_cap = B_cap * T_cap (node_capacity clips the rounded count there).
+    #    trainer.ResidentLoop takes the same bucket, so a run holds one training graph and one evaluation graph.
+    N_BUCKET = 1 << 30
+    RESIDENT_N_BUCKET = N_BUCKET
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -292,6 +398,10 @@ class DAGERCTrainer(TrainerBase):
                                decoupled=(o.name == "AdamW"), clip_norm=5.0, seed=params.seed)
         self.model.rng_state = self.optim.rng_state
         self.optim.skip_flag = self.model.flat.health    # a recurrence exchange timed out (on any rank) -> the update is skipped
+        # capacity buckets are opt-in (--capacity_buckets=True; --resident implies them): the default stays the exact-shape
+        # step, whose dropout masks (keyed by the element index, so by T) a capacity-sized step does not reproduce
+        self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
+        self._store_ext = None
 
     def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
         self.model.train()
@@ -299,3 +409,75 @@ class DAGERCTrainer(TrainerBase):
         scale = all_reduce_grads(self.model.flat)
         self.optim.step(grad_scale=scale)
         return stats
+
+    def _capacity_ok(self, B_cap, T_cap, N_cap, batch=None):
+        """no bucket with the flag off, with the peer-to-peer exchange, beyond the recurrence's T or its 4096 dialogue groups,
+        with more classes than the scoring kernel counts, or for a batch of another dtype than the compute mode's"""
+        return bool(self.capacity and not self._p2p() and 0 < T_cap <= MAX_T and 0 < B_cap <= MAX_B and
+                    0 < N_cap <= B_cap * T_cap and self.model.supports_capacity(batch))
+
+    def _bucket(self, like, B_cap, T_cap, N_cap):
+        """the plugin's layout: one-hot speakers [B, T, S] (ids [B, T] are taken too)"""
+        x, spk, dev = like["input_tensor"], like["speaker_tensor"], self.device
+        D = int(x.shape[2])
+
+        def make():
+            # "extent" (host side): the [B, T, N] block the last batch occupied -- all that fill has to clear
+            return dict(input_tensor=torch.zeros(B_cap, T_cap, D, dtype=x.dtype, device=dev),
+                        speaker_tensor=torch.zeros((B_cap, T_cap) + tuple(spk.shape[2:]), dtype=spk.dtype, device=dev),
+                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
+                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev), extent=[0, 0, 0])
+
+        def fill(static, b):
+            # the step computes every padded row (finite garbage there is harmless: it meets a zero gradient row), but a row
+            # the batch does not own should not depend on an earlier batch: what the previous one occupied and this one does
+            # not cover is cleared (never the whole capacity buffer)
+            Bb, Tb = (int(v) for v in b["input_tensor"].shape[:2])
+            Nb = int(b["label"].shape[0])
+            Bp, Tp, Np = static["extent"]
+            for k in ("input_tensor", "speaker_tensor"):
+                static[k][:Bb, :Tb].copy_(b[k], non_blocking=True)
+                if Tp > Tb:
+                    static[k][:Bp, Tb:Tp].zero_()
+                if Bp > Bb:
+                    static[k][Bb:Bp, :min(Tb, Tp)].zero_()
+            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
+            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
+            static["label"][:Nb].copy_(b["label"], non_blocking=True)
+            if Np > Nb:
+                static["label"][Nb:Np].zero_()
+            static["extent"][:] = [Bb, Tb, Nb]
+
+        return ("capacity", B_cap, T_cap, N_cap), make, fill
+
+    def _precapture_caps(self, batch):
+        # built from train.batch_size and T_cap (trainer.bucket_t_cap) ALONE, never from the probe batch's shape: every rank
+        # captures the same one-element list
+        B_cap, T_cap = int(self.params.train.batch_size), int(getattr(self, "t_cap", 0))
+        if not self._capacity_ok(B_cap, T_cap, B_cap * T_cap, batch):
+            return None
+        return B_cap, T_cap, [B_cap * T_cap]
+
+    def _resident_ok(self, store, B_cap, T_cap, N_cap):
+        want = torch.bfloat16 if self.model.compute == "bf16" else torch.float32
+        return (store.fused.dtype == want and int(store.fused.shape[1]) == self.model.emb_dim and
+                self._capacity_ok(B_cap, T_cap, N_cap))
+
+    def _resident_inputs(self, store):
+        """fc1, the raw-feature block of out_mlp.0 and their weight gradients read the store's rows through the step's row map;
+        padded positions read a zero row, which the store does not have, so the features are kept once per store with one
+        appended.  The speakers are the store's flat ids."""
+        if self._store_ext is None or self._store_ext[0] is not store:
+            self._store_ext = (store, torch.cat([store.fused, torch.zeros(1, self.model.emb_dim, dtype=store.fused.dtype,
+                                                                            device=store.fused.device)]))
+        return self._store_ext[1], store.speaker
+
+    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
+        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
+        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
+        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
+
+    def resident_eval_step(self, batch, cm):
+        """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
+        sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
+        return self.model.eval_scores(batch, cm)

@@ -211,11 +211,11 @@ class StepGraphs:
     """Captured HIP graphs of the whole training step, least-recently-used eviction.
 
     * CAPACITY BUCKETS (trainers with capacity.CapacityBuckets: COGMEN in the bf16 compute mode, DialogueGCN on its default
-      path, bc-LSTM / bc-GRU with ``--capacity_buckets=True`` or ``--resident``).  The reference reshuffles
+      path, bc-LSTM / bc-GRU and DAG-ERC with ``--capacity_buckets=True`` or ``--resident``).  The reference reshuffles
       the dialogues every epoch and its last batch is smaller (lumo/trainer/trainer.py:429-442, mmbase.py:468), so (B, T, N)
       almost never repeats.  A bucket is a set of static capacity-sized input buffers -- ``batch_size`` dialogues (missing
       ones get length 0), the longest training dialogue of every rank, N rounded up to the trainer's N_BUCKET (COGMEN 256,
-      DialogueGCN and bc-LSTM / bc-GRU 128) -- plus one graph captured
+      DialogueGCN and bc-LSTM / bc-GRU 128; DAG-ERC always B * T: none of its launches scales with N) -- plus one graph captured
       over them; the step's kernels read the true node count from the device (COGMENModule.dynamic_n; the bc-RNN scans also
       the batch's longest dialogue), so every batch
       that fits replays that graph: a reshuffled epoch hits a handful of graphs.
@@ -357,13 +357,17 @@ class ResidentLoop:
     never materialised.  A step is 2 B int32 (a row of ``batch_table``) copied into the fixed descriptor ``cur_desc`` plus its
     node capacity -- the batch's node count rounded up to N_BUCKET, at most B * T, T the store's own longest dialogue.  The
     first visit of a capacity runs the subclass's ``_step`` eagerly on the trainer's resident batch of that capacity and then
-    captures it; every later step of that capacity is one copy, one dict lookup, one replay."""
+    captures it; every later step of that capacity is one copy, one dict lookup, one replay.  A trainer whose step does not
+    scale with N names its own node bucket (``RESIDENT_N_BUCKET``, clipped to B * T: DAG-ERC, one capacity per store)."""
 
     N_BUCKET = 128
 
     def __init__(self, trainer, store, batch_size, capture=True):
         self.trainer, self.store, self.B = trainer, store, int(batch_size)
         self.T = int(store.lengths.max())
+        named = getattr(trainer, "RESIDENT_N_BUCKET", None)
+        if named:
+            self.N_BUCKET = max(1, min(int(named), self.B * self.T))
         self.cur_desc = torch.zeros(2 * self.B, dtype=torch.int32, device=store.device)
         self.graphs, self.capture = {}, capture      # node capacity -> (graph or None, batch, workspace kept alive)
         self.replays = self.eager = self.captures = 0
@@ -412,7 +416,7 @@ class ResidentEpochs(ResidentLoop):
     descriptor buffer and replays the bucket's captured graph -- the projection launch reads feature rows, speakers and labels
     straight from the store (csrc/cogmen_project.hip, resident mode).  Host work per step: one 256-byte device copy + one
     graph launch.  Trainers with ``resident_batch``: COGMEN, DialogueGCN, bc-LSTM / bc-GRU (their layer-0 input projection
-    reads the store through the row map of erc_bcrnn_meta_cap)."""
+    reads the store through the row map of erc_bcrnn_meta_cap), DAG-ERC (the row map of erc_dag_meta_cap)."""
 
     def __init__(self, trainer, store, batch_size, seed, capture=True):
         super().__init__(trainer, store, batch_size, capture)

@@ -301,6 +301,23 @@ int erc_bn_lrelu_bwd(const float* x, int ldx, int N, int F, const float* gamma, 
 int erc_cross_entropy(const float* logits, int ld, int C, int n_rows, const int32_t* row_map,
                       const int64_t* labels, const float* weight, float grad_scale,
                       float* dlogits, int lddl, float* stats, void* stream);
+/* erc_cross_entropy in CAPACITY mode (DAG-ERC's masked CE, track_mm/dagerc.py:225-226, of a step whose launches are sized
+ * for n_cap labels): the batch's sample count is read on the device, n = *n_dev clamped to [0, n_cap].  Samples at or beyond
+ * n are not read (neither row_map, labels nor logits); the mean and stats are over n.  n == 0: stats[0..2] = 0, nothing is
+ * written to dlogits, no NaN.  Everything else (row_map, weight, stats layout, dlogits rows no sample maps to) as above. */
+int erc_cross_entropy_cap(const float* logits, int ld, int C, int n_cap, const int32_t* n_dev, const int32_t* row_map,
+                          const int64_t* labels, const float* weight, float grad_scale, float* dlogits, int lddl,
+                          float* stats, void* stream);
+/* Eval scoring of padded logits (mmbase.py:180-201 test_step: logits[attention_mask].argmax(-1) against the labels, then
+ * sklearn's confusion matrix, mmbase.py:259): for sample i < n = *n_dev clamped to [0, n_cap], row = row_map[i] (NULL: i) of
+ * logits [n_logit_rows, ld], pred = the first index of the maximum (torch.argmax), cm[labels[i] * C + pred] += 1.
+ * cm: int64 [C, C] (true x predicted), ADDED TO; integer counts through a histogram per workgroup and one vector atomic add
+ * per non-empty cell, as erc_head_eval: the result does not depend on the order.  Not counted: a label outside [0, C), a
+ * row index outside [0, n_logit_rows), a row whose logits are all NaN (a NaN never wins against a number).  Samples at or
+ * beyond n are neither read nor counted.  Writes nothing but cm.  C <= erc_rows_score_max_classes() (16). */
+int erc_rows_score(const float* logits, int ld, int n_logit_rows, int C, int n_cap, const int32_t* n_dev,
+                   const int32_t* row_map, const int64_t* labels, int64_t* cm, void* stream);
+int erc_rows_score_max_classes(void);
 
 /* ------------------------------------------------------------------------
  * K9  COGMEN's Transformer encoder block rnn.0 (track_mm/cogmen.py:94-102; contrib/nn.py:283-305: post-norm, ReLU,
@@ -764,6 +781,24 @@ int erc_gcnii_chain_set_spin_limit(int limit);
 int erc_dag_meta(const float* speaker_onehot, const int64_t* speaker_ids, int64_t spk_sb, int64_t spk_st,
                  int n_speakers, const int64_t* lengths, int B, int T,
                  int32_t* spk, int32_t* pred, int32_t* node_off, int32_t* node_row, void* stream);
+/* erc_dag_meta in CAPACITY mode: the index tables of a step sized for B dialogue slots (a missing one has length 0),
+ * T = T_cap and n_cap labels (replaces the same lines, dagerc.py:109-154, plus the mask of :225 and, resident, the collate
+ * of mmbase.py:344-455 for this module).  Two input forms:
+ *   BUCKET:   lengths int64 [B] + the padded speaker tensor, one-hot or ids, as erc_dag_meta takes them; desc and the store
+ *             arguments NULL, x_row / label_out NULL.
+ *   RESIDENT: desc int32 [2 B] (lengths | first store rows) + the store's flat speaker ids and labels (int64 [U]);
+ *             lengths and both speaker tensors NULL.  Additionally written: x_row [B*T] = the store row of padded row
+ *             b*T + t, zero_store_row where t >= length (the caller hands the features over with one zero row appended,
+ *             zero_store_row = U); label_out [n_cap] = the store label of the node's row, 0 for i >= N.
+ * spk, pred, node_off, node_row: exactly erc_dag_meta's for the valid rows; positions t >= length and empty slots get
+ * speaker 0 (pred follows from that), whatever the padded tensor holds there.  counts[0] = N = sum(lengths), counts[1] = the
+ * longest dialogue.  node_row[i] for N <= i < n_cap is 0: a legal row, which no consumer may read.  A length is clamped to
+ * [0, T], a store row outside [0, zero_store_row) reads as the zero row, node i >= n_cap is not written.  T <= 1021. */
+int erc_dag_meta_cap(const float* speaker_onehot, const int64_t* speaker_ids, int64_t spk_sb, int64_t spk_st,
+                     int n_speakers, const int64_t* lengths, const int32_t* desc, const int64_t* store_speaker,
+                     const int64_t* store_label, int zero_store_row, int B, int T, int n_cap, int32_t* spk, int32_t* pred,
+                     int32_t* node_off, int32_t* node_row, int32_t* x_row, int64_t* label_out, int32_t* counts,
+                     void* stream);
 
 /* ------------------------------------------------------------------------
  * K6: the recurrence (dagerc.py:167-189, dagerc_models.py:326-365), hidden size 300, per layer and step t:

@@ -15,6 +15,9 @@ class DAGERCParams(ERCParams):
         self.epoch = 30
         self.optim = Group(name="AdamW", lr=1e-3, weight_decay=1e-2)   # torch AdamW default decay, dagerc.py:39
         self.speaker_onehot = True                                 # dagerc.py:41
+        # capacity buckets (one captured graph per (B_cap, T_cap) instead of per exact shape) are opt-in here:
+        # --capacity_buckets=True, or --resident (with --device_collate), which implies them
+        self.capacity_buckets = False
 
     def iparams(self):
         super().iparams()
