@@ -136,9 +136,19 @@ __global__ __launch_bounds__(256) void row_normalize_bwd_kernel(const float* __r
 }
 
 __device__ __forceinline__ float sim_of(float c) { return 1.0f - acosf(SHRINK * c) / PI_F; }
+// Cosine (p, q) of a COS block [P][P], renormalised by the block's own diagonal: the grouped GEMM's |xhat_p|^2 is 1 only to a few
+// roundings, and at cos -> 1 (the diagonal itself, duplicate rows) such a rounding is the whole of 1 - cos, which acos and
+// dsim_dc amplify by 1e2 .. 5e4.  The diagonal comes out as exactly 1, and so do rows that coincide (same products, same order).
+__device__ __forceinline__ float cos_n(const float* __restrict__ blk, int P, int p, int q) {
+    return blk[(int64_t)p * P + q] / sqrtf(blk[(int64_t)p * P + p] * blk[(int64_t)q * P + q]);
+}
+// d sim / d c = SHRINK / (pi sqrt(1 - t^2)), t = SHRINK c.  Where |c| -> 1 (every diagonal entry, duplicate or opposite rows) 1 - t^2
+// is ~2e-5 and `1.0f - t * t` loses three digits to the roundings of t and of t * t; instead 1 - t^2 = (1 - t)(1 + t) with
+// 1 -+ t = (1 - SHRINK) + SHRINK (1 -+ c), whose differences are exact near the ends.
 __device__ __forceinline__ float dsim_dc(float c) {
-    const float t = SHRINK * c;
-    return SHRINK / (PI_F * sqrtf(fmaxf(1.0f - t * t, 1e-12f)));
+    constexpr float OMS = 1e-5f;     // 1 - 0.99999, not 1.0f - SHRINK (SHRINK itself is rounded by 1.4e-8)
+    const float omt = OMS + SHRINK * (1.0f - c), opt = OMS + SHRINK * (1.0f + c);
+    return SHRINK / (PI_F * sqrtf(fmaxf(omt * opt, 1e-12f)));
 }
 
 // COS blocks (raw cosines from the grouped GEMM) -> normalised adjacency blocks ADJ, normalised cross entries
@@ -156,17 +166,21 @@ __global__ __launch_bounds__(256) void adj_rows_kernel(const float* __restrict__
     // cross-modal same-utterance similarities of this node
     float cross = 0.f;
     const L4 mine = ld4(xhat + ((int64_t)m * N + off + p) * FD, lane);
+    const float nm = wave_sum(dt4(mine, mine));
     for (int n = 0; n < M; ++n) {
         if (n == m) continue;
-        const float c = wave_sum(dt4(mine, ld4(xhat + ((int64_t)n * N + off + p) * FD, lane)));
+        // renormalised: |xhat|^2 is 1 only to a rounding, and where the two rows coincide that rounding would be the whole of
+        // 1 - c (dsim_dc); dot and norms are summed in the same order, so coinciding rows give exactly 1
+        const L4 other = ld4(xhat + ((int64_t)n * N + off + p) * FD, lane);
+        const float c = wave_sum(dt4(mine, other)) / sqrtf(nm * wave_sum(dt4(other, other)));
         if (lane == 0) CCOS[((int64_t)b * M * M + m * M + n) * P + p] = c;
         cross += sim_of(c);
     }
-    const float* cr = COS + (((int64_t)b * M + m) * P + p) * P;
+    const float* blk = COS + ((int64_t)b * M + m) * P * P;
     float* ar = ADJ + (((int64_t)b * M + m) * P + p) * P;
     float rs = 0.f;
     for (int q = lane; q < L; q += 64) {
-        const float s = sim_of(cr[q]);
+        const float s = sim_of(cos_n(blk, P, p, q));
         ar[q] = s;
         rs += s;
     }
@@ -206,7 +220,7 @@ __global__ __launch_bounds__(256) void adj_bwd_rows_kernel(const float* __restri
     const int64_t base = ((int64_t)b * M + m) * P;
     float acc = 0.f;
     for (int q = lane; q < L; q += 64) {
-        const float s = sim_of(COS[(base + p) * P + q]);
+        const float s = sim_of(cos_n(COS + base * P, P, p, q));
         acc += (dADJ[(base + p) * P + q] + dADJ[(base + q) * P + p]) * s * (1.0f / sqrtf(DEG[(int64_t)m * N + off + q]));
     }
     acc = wave_sum(acc);
@@ -236,7 +250,7 @@ __global__ __launch_bounds__(256) void adj_bwd_entries_kernel(const float* __res
     const float up = 1.0f / sqrtf(DEG[(int64_t)m * N + off + p]), ddp = DD[(int64_t)m * N + off + p];
     // dS_pq = dA_pq u_p u_q + dd_p ; dcos = dS * dsim/dc ; G_pq = dcos_pq + dcos_qp
     for (int q = lane; q < L; q += 64) {
-        const float c = COS[(base + p) * P + q];  // symmetric up to rounding; use the (p,q) entry for both halves
+        const float c = cos_n(COS + base * P, P, p, q);  // symmetric up to rounding; use the (p,q) entry for both halves
         const float uu = up * (1.0f / sqrtf(DEG[(int64_t)m * N + off + q]));
         const float dpq = dADJ[(base + p) * P + q] * uu + ddp;
         const float dqp = dADJ[(base + q) * P + p] * uu + DD[(int64_t)m * N + off + q];

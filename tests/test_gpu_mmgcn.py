@@ -1,5 +1,6 @@
 """MMGCN on the GPU vs (a) golden vectors produced by the REFERENCE's own MMGCNModule and (b) the reference-pinned
-CPU oracle at larger shapes (eval mode: every dropout off)."""
+CPU oracle at larger shapes (eval mode: every dropout off), and (c) the training-mode step, dropout on, against the float64
+restatement of tests/mmgcn_step_ref.py given the masks the step applied."""
 import numpy as np
 import pytest
 import torch
@@ -231,3 +232,166 @@ def test_chain_poll_timeout_fails_the_step_on_the_device():
     tr.train_step(batch)
     assert int(tr.optim.state[0]) == step + 1 and int(tr.model.flat.health[0]) == 0
     tr.model.check_cluster()
+
+
+# ----------------------------------------------------------------------------- the training-mode step (dropout on)
+STEP_LENS, STEP_DIMS = (33, 1, 17, 5), dict(a=12, t=20, v=16)
+
+
+def _step_pair(mods, lens=STEP_LENS, S=2, C=6, seed=31):
+    from oracle.mmgcn import MMGCNOracle
+    from erc_amd.mmgcn import MMGCNModule
+    from tests.util_cases import make_batch_lengths
+    dims = STEP_DIMS
+    batch = make_batch_lengths(lens, dims, n_speakers=S, n_classes=C, seed=seed, modality=mods, batch_first=False,
+                               speaker_onehot=True)
+    for k in ("text_feature", "audio_feature", "visual_feature"):
+        batch.setdefault(k, None)
+    torch.manual_seed(4)
+    ref = MMGCNOracle(hidden_text=dims["t"], hidden_visual=dims["v"], hidden_audio=dims["a"], n_speakers=S, n_classes=C,
+                      modals=mods)
+    mine = MMGCNModule(hidden_text=dims["t"], hidden_visual=dims["v"], hidden_audio=dims["a"], n_speakers=S, n_classes=C,
+                       modals=mods)
+    mine.load_state_dict(ref.state_dict())
+    mine.finalize(DEV)
+    return ref, mine, batch
+
+
+def _regroup(xd, h, Mo, N):
+    cat = torch.cat([xd, h], dim=-1)
+    return torch.cat([cat[N * i:N * (i + 1)] for i in range(Mo)], dim=-1)
+
+
+def _applied_masks(mine, ws, B, T, N):
+    """the 0/1 keep masks of the step just run, read back from its own buffers (tests/mmgcn_step_ref.py's layouts)"""
+    from erc_amd.mmgcn import NLAYERS
+    Mo = len(mine.order)
+    X, XD, HD, H0, FE = ws["X"].cpu(), ws["XD"].cpu(), ws["HD"].cpu(), ws["_H0"].cpu(), ws["FE"].cpu()
+    assert ws["_XD"] is ws["XD"] and ws["_H0"] is ws["H0"], "dropout on: the separate XD / H0 buffers"
+    masks = {"x": XD != 0, "h0": (HD[1] != 0) | (H0 == 0), "layers": HD[2:NLAYERS + 2] != 0}
+    masks["fe"] = (FE != 0) | (_regroup(XD, HD[NLAYERS + 1], Mo, N) <= 0)
+    if "t" in mine.order:
+        lw = ws["lstm:lstm_l."]
+        l0, l0d = lw["H0"].cpu().view(T, B, 200), lw["H0d"].cpu().view(T, B, 200)
+        masks["lstm"] = (l0d != 0) | (l0 == 0)
+        _kept_scaled(l0d, l0, l0d != 0, mine.drop_p, "lstm")
+    _kept_scaled(XD, X, masks["x"], mine.drop_p, "x")
+    _kept_scaled(HD[1], H0, HD[1] != 0, mine.drop_p, "h0")
+    return masks
+
+
+def _kept_scaled(y, x, keep, p, site):
+    """kept entries are x * ks: the fp32 keep scale 1 / (1 - p) and the product round once each (2^-22 covers both and the
+    rounding of p itself)"""
+    want = x.double()[keep] / (1.0 - p)
+    assert bool(((y.double()[keep] - want).abs() <= 2.0 ** -22 * want.abs()).all()), site
+
+
+def _dropped_shares(masks, pre, p):
+    """per site the share of dropped entries among those the float64 step has clearly non-zero (> 1e-3: above any fp32 / float64
+    disagreement about a ReLU).  sigma <= sqrt(p (1 - p) / 5000) = 0.007 at the smallest site"""
+    shares = {}
+    for site, keep in masks.items():
+        v = pre[site]
+        clear = (v.abs() if site in ("x", "lstm") else v) > 1e-3
+        if site == "layers":
+            each = [1.0 - float(keep[l][clear[l]].double().mean()) for l in range(keep.shape[0])]
+            assert min(int(c.sum()) for c in clear) > 2000
+            assert all(abs(s - p) < 0.06 for s in each), each
+            shares["layers_min"], shares["layers_max"] = min(each), max(each)
+        assert int(clear.sum()) > 4000, (site, int(clear.sum()))
+        shares[site] = 1.0 - float(keep[clear].double().mean())
+        assert abs(shares[site] - p) < 0.04, (site, shares[site])
+    return shares
+
+
+@pytest.mark.parametrize("mods", ["atv", "av"])
+@pytest.mark.parametrize("form", ["chain", "per_layer"])
+def test_dropout_step_matches_oracle_with_the_applied_masks(form, mods, monkeypatch):
+    """One training-mode step (p = 0.4 at every site) against tests/mmgcn_step_ref.py in float64, which is given the keep masks
+    the step applied, read back from the step's own buffers.  What keeps the read-back from hiding an error: kept entries equal
+    the input times 1 / (1 - p); per site the dropped share among clearly non-zero entries is p within 0.04 (each of the 64
+    layers within 0.06); the masks of the streams 1000 (x) and 1001 (h0) are independent (agreeing on p^2 + (1 - p)^2 of the
+    entries, within 0.04).  Bounds: the eval-mode parity bounds of this file (logits 1e-4, loss 1e-5, gradients 5e-3 of each
+    parameter's largest entry); the float32 CPU run of the same restatement with the same masks is printed next to the step's
+    errors as the yardstick of fp32 rounding.
+    Measured (MI355X; the step against float64 | the float32 CPU run against float64; no bound had to be derived from the latter):
+        chain atv      logits 4.2e-07 loss 2.6e-08 grad 5.4e-06 | logits 8.0e-07 loss 1.5e-07 grad 1.2e-05
+        chain av       logits 5.8e-07 loss 9.4e-08 grad 9.1e-06 | logits 9.0e-06 loss 9.4e-08 grad 1.6e-05
+        per_layer atv  logits 5.4e-07 loss 9.4e-08 grad 4.3e-06 | as chain atv
+        per_layer av   logits 7.6e-07 loss 9.4e-08 grad 2.1e-06 | as chain av
+    dropped shares (atv): x 0.400, h0 0.400, layers 0.400 pooled (0.392 .. 0.405), fe 0.398, lstm 0.404; streams 1000 / 1001
+    agree on 0.524 of the entries (p^2 + (1 - p)^2 = 0.52)."""
+    from tests.mmgcn_step_ref import mmgcn_step_ref
+    if form == "per_layer":
+        monkeypatch.setenv("ERC_MM_CHAIN", "0")
+    ref, mine, batch = _step_pair(mods)
+    mine.train()
+    p, ks = mine.drop_p, 1.0 / (1.0 - mine.drop_p)
+    assert p == 0.4
+    stats = mine.loss_and_grads(to_device(batch, DEV)).cpu()
+    ws = mine._last_ws
+    assert ws["chain"] == (form == "chain") and ws["_p"] == p
+    assert int(mine.flat.health[0]) == 0
+    T, B = batch["speaker_tensor"].shape[:2]
+    N = int(batch["label"].shape[0])
+    masks = _applied_masks(mine, ws, B, T, N)
+    torch.set_num_threads(8)
+    want = mmgcn_step_ref(ref, batch, masks=masks, ks=ks)
+    shares = _dropped_shares(masks, want["pre"], p)
+    seen = ws["_H0"].cpu() != 0                     # where stream 1001's mask shows
+    agree = float((masks["x"][seen] == masks["h0"][seen]).double().mean())
+    assert abs(agree - (p * p + (1 - p) * (1 - p))) < 0.04, agree
+    assert not torch.equal(masks["layers"][0], masks["layers"][1])
+    f32 = mmgcn_step_ref(ref, batch, masks=masks, ks=ks, dtype=torch.float32)
+    got = ws["logits"].cpu().double()
+    e_logits, e_loss = float((got - want["logits"]).abs().max()), abs(float(stats[0]) - float(want["loss"]))
+    assert sorted(mine.flat.params) == sorted(want["grads"])
+    errs = {n: rel_err(mine.flat.g(n).cpu(), want["grads"][n]) for n in mine.flat.params}
+    y_errs = {n: rel_err(f32["grads"][n], want["grads"][n]) for n in mine.flat.params}
+    worst = max(errs, key=errs.get)
+    print("mmgcn-err dropout %s %s logits=%.2e loss=%.2e grad=%.2e (%s) | float32 cpu: logits=%.2e loss=%.2e grad=%.2e "
+          "grad(%s)=%.2e | dropped %s agree(1000,1001)=%.3f"
+          % (form, mods, e_logits, e_loss, errs[worst], worst, float((f32["logits"].double() - want["logits"]).abs().max()),
+             abs(float(f32["loss"]) - float(want["loss"])), max(y_errs.values()), worst, y_errs[worst],
+             " ".join("%s=%.3f" % kv for kv in sorted(shares.items())), agree))
+    assert e_logits < 1e-4
+    assert e_loss < 1e-5
+    assert errs[worst] < 5e-3, sorted(errs.items(), key=lambda kv: -kv[1])[:6]
+
+
+def test_consecutive_train_steps_draw_different_masks():
+    """two MMGCNTrainer.train_step calls on one batch: the input dropout (stream 1000) keeps different entries, independently"""
+    tr, batch = _mmgcn_trainer()
+    keeps = []
+    for _ in range(2):
+        tr.train_step(batch)
+        keeps.append((tr.model._last_ws["XD"] != 0).cpu())
+    p = tr.model.drop_p
+    assert not torch.equal(keeps[0], keeps[1])
+    assert abs(float((keeps[0] == keeps[1]).double().mean()) - (p * p + (1 - p) * (1 - p))) < 0.04
+    assert all(abs(1.0 - float(k.double().mean()) - p) < 0.04 for k in keeps)
+    assert int(tr.model.flat.health[0]) == 0
+
+
+def test_reused_workspace_carries_nothing_over():
+    """The workspace is cached per (B, T, N): a step on lengths (40, 10, 30) and then one on (10, 40, 30) share it.  Logits and
+    gradients of the second equal, bit for bit, those of a freshly finalised module that sees only the second batch."""
+    from erc_amd.mmgcn import MMGCNModule
+    ref, mine, first = _step_pair("atv", lens=(40, 10, 30), seed=41)
+    _, _, second = _step_pair("atv", lens=(10, 40, 30), seed=42)
+    fresh = MMGCNModule(hidden_text=STEP_DIMS["t"], hidden_visual=STEP_DIMS["v"], hidden_audio=STEP_DIMS["a"], n_speakers=2,
+                        n_classes=6, modals="atv")
+    fresh.load_state_dict(ref.state_dict())
+    fresh.finalize(DEV)
+    mine.eval(), fresh.eval()
+    mine.loss_and_grads(to_device(first, DEV))
+    ws1 = mine._last_ws
+    s_mine = mine.loss_and_grads(to_device(second, DEV)).cpu()
+    assert mine._last_ws is ws1, "both batches have (B, T, N) = (3, 40, 80)"
+    s_fresh = fresh.loss_and_grads(to_device(second, DEV)).cpu()
+    assert torch.equal(mine._last_ws["logits"], fresh._last_ws["logits"])
+    assert float(s_mine[0]) == float(s_fresh[0])
+    for n in mine.flat.params:
+        assert torch.equal(mine.flat.g(n), fresh.flat.g(n)), n
+    assert int(mine.flat.health[0]) == 0 and int(fresh.flat.health[0]) == 0
