@@ -24,20 +24,15 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import IEMOCAP6_WEIGHTS, CapacityBuckets, TrainerBase, bucket_sizes
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, linear_fwd, linear_wgrad
+from .capacity import CapacityBuckets, ConvEmotionTrainer, bucket_sizes
+from .engine import WorkspaceCache, FlatParams, GemmPlanner
+from .matchhead import ConvEmotionModule, MatchAttHead, Transform
 from .rnn import BiGRU2, BiLSTM2, gru_groups, lstm_groups
 
 D_E, D_HID, EW, MAX_T = 100, 100, 200, 110
 
 
-class _Transform(nn.Module):          # MatchingAttention('general2'): its one parameterised layer
-    def __init__(self, d):
-        super().__init__()
-        self.transform = nn.Linear(d, d, bias=True)
-
-
-class _BcRnnModule(nn.Module):
+class _BcRnnModule(ConvEmotionModule):
     CELL = None                       # "lstm" | "gru": the attribute / state_dict prefix of the RNN
 
     def __init__(self, D_m, D_e, D_h, n_classes=7, dropout=0.5, compute="f32", seed=1):
@@ -56,7 +51,7 @@ class _BcRnnModule(nn.Module):
         rnn = (nn.LSTM if self.CELL == "lstm" else nn.GRU)(input_size=D_m, hidden_size=D_e, num_layers=2, bidirectional=True,
                                                            dropout=dropout)
         setattr(self, self.CELL, rnn)
-        self.matchatt = _Transform(2 * D_e)
+        self.matchatt = Transform(2 * D_e)
         self.linear = nn.Linear(2 * D_e, D_h)
         self.smax_fc = nn.Linear(D_h, n_classes)
         # CAPACITY MODE (trainer.StepGraphs buckets, trainer.ResidentEpochs): the batch tensors are capacity-sized static
@@ -69,22 +64,15 @@ class _BcRnnModule(nn.Module):
 
     def live_groups(self):
         groups = (lstm_groups if self.CELL == "lstm" else gru_groups)(self.CELL + ".", getattr(self, self.CELL))
-        return groups + [[("matchatt.transform.weight", self.matchatt.transform.weight)],
-                         [("matchatt.transform.bias", self.matchatt.transform.bias)],
-                         [("linear.weight", self.linear.weight)], [("linear.bias", self.linear.bias)],
-                         [("smax_fc.weight", self.smax_fc.weight)], [("smax_fc.bias", self.smax_fc.bias)]]
+        return groups + MatchAttHead.groups("", self)
 
     def finalize(self, device):
         self.to(device)
         self.flat = FlatParams(self.live_groups(), device)
         self.enc = (BiLSTM2 if self.CELL == "lstm" else BiGRU2)(self.flat, self.CELL + ".", self.D_m, drop_p=self.drop_p)
+        self.head = MatchAttHead(self.flat, "", EW, D_HID, self.n_classes, self.drop_p)
         self.rng_state = torch.tensor([0, self._seed], dtype=torch.int64, device=device)
         return self
-
-    @property
-    def _last_ws(self):
-        """workspace of the most recent forward (tests / bench read results out of it)"""
-        return self._ws.last
 
     def _workspace(self, B, T, N, device, cap=False):
         if cap:
@@ -95,24 +83,17 @@ class _BcRnnModule(nn.Module):
         # zeros, not empty: a stale NaN must never reach a weight-gradient GEMM through a row the step did not touch
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        C, BT, D = self.n_classes, B * T, self.D_m
-        ws = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), M=f32(BT, EW), E=f32(N, EW), Q=f32(N, EW), A=f32(N, EW),
-                  P=f32(B * T * T), TH=f32(B * T * T), Zc=f32(N, D_HID), logits=f32(N, C), logp=f32(N, C),
-                  stats=f32(max(256, capi.head_ce_stats_floats(N))), dlogits=f32(N, C), dZc=f32(N, D_HID), dA=f32(N, EW),
-                  DZ=f32(B * T * T), dQ=f32(N, EW), dE=f32(N, EW), dM=f32(BT, EW))
+        BT, D = B * T, self.D_m
+        # capacity mode: one more row behind the padded RNN output (M) and behind the node gradient (dE), never written by
+        # anything: the zero row that node_row (capacity nodes) and pad_node (padded positions) point at
+        zrow = 1 if cap else 0
+        ws = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), M=f32(BT + zrow, EW), E=f32(N, EW), dM=f32(BT, EW),
+                  **self.head.buffers(B, T, N, device, dE_rows=N + zrow))
         if cap:
-            # one more row behind the padded RNN output and behind the node gradient, never written by anything: the zero row
-            # that node_row (capacity nodes) and pad_node (padded positions) point at
-            ws.update(M=f32(BT + 1, EW), dE=f32(N + 1, EW), pad_node=i32(BT), x_row=i32(BT), counts=i32(2),
-                      label=torch.zeros(N, dtype=torch.int64, device=device))
+            ws.update(pad_node=i32(BT), x_row=i32(BT), counts=i32(2), label=torch.zeros(N, dtype=torch.int64, device=device))
         ws["planner"] = GemmPlanner(device, 4 * BT * 800 + 10 * (800 * D + 800 * 200) + (1 << 21), grad=self.flat.grad)
         ws["jobs"] = None
         return ws
-
-    def _shape(self, x, lens, label, n_nodes=None):
-        T, B = int(x.shape[0]), int(x.shape[1])
-        N = int(label.shape[0]) if label is not None else (int(n_nodes) if n_nodes is not None else int(lens.sum().item()))
-        return B, T, N
 
     def _check(self, x, onehot, T):
         if T > MAX_T:
@@ -141,7 +122,6 @@ class _BcRnnModule(nn.Module):
             raise capi.ErcGraftError("bc%s: capacity mode needs fp32 features of width D_m=%d" % (self.CELL, self.D_m))
         if desc is None and lens.dtype != torch.int64:
             raise capi.ErcGraftError("bc%s: capacity mode needs int64 text_length" % self.CELL)
-        fp = self.flat
         ws = self._workspace(B, T, N, x.device, cap=True)
         pl = ws["planner"]
         pl.reset()
@@ -155,13 +135,8 @@ class _BcRnnModule(nn.Module):
                                 ws["counts"])
         self.enc.forward(pl, x, D, BT, B, T, 1, B, None, training, self.rng_state, ws["M"], EW, store=ws,
                          node_row=ws["x_row"] if desc is not None else None, t_dev=ws["counts"][1:])
-        E = ws["E"]
-        capi.gather_rows(ws["M"], EW, ws["node_row"], N, EW, E, EW)
-        linear_fwd(pl, E, EW, None, fp.w("matchatt.transform.weight"), fp.w("matchatt.transform.bias"), ws["Q"], EW, N, EW, EW)
-        capi.match_att_fwd(E, EW, ws["Q"], EW, ws["node_off"], B, T, EW, ws["A"], EW, ws["P"], ws["TH"])
-        p = self.drop_p if training else 0.0
-        linear_fwd(pl, ws["A"], EW, None, fp.w("linear.weight"), fp.w("linear.bias"), ws["Zc"], D_HID, N, D_HID, EW,
-                   act=3 if p > 0 else 1, drop_p=p, rng=self.rng_state)
+        capi.gather_rows(ws["M"], EW, ws["node_row"], N, EW, ws["E"], EW)
+        self.head.forward(pl, ws, ws["E"], ws["node_off"], B, T, N, training, self.rng_state, with_logits=False)
         ws["x"] = x
         return ws
 
@@ -171,25 +146,17 @@ class _BcRnnModule(nn.Module):
         if self.dynamic_n:
             raise capi.ErcGraftError("bc%s: capacity mode (dynamic_n) is the training step's (loss_and_grads)" % self.CELL)
         self._check(x, onehot, T)
-        fp = self.flat
         ws = self._workspace(B, T, N, x.device)
         pl = ws["planner"]
         pl.reset()
-        D, C, BT = self.D_m, self.n_classes, B * T
+        D, BT = self.D_m, B * T
         x, onehot = x.contiguous(), onehot.contiguous()
         # node_off / node_row (= t*B + b) of the valid rows; the speakers do not enter these models
         capi.dialogrnn_meta(onehot, int(onehot.shape[-1]), lens, B, T, N, ws["node_off"], ws["node_row"], ws["node_spk"])
         # unpacked: lengths=None runs every dialogue over all T padded steps, row t*B + b (sb = 1, st = B)
         self.enc.forward(pl, x, D, BT, B, T, 1, B, None, training, self.rng_state, ws["M"], EW, store=ws)
-        E = ws["E"]
-        capi.gather_rows(ws["M"], EW, ws["node_row"], N, EW, E, EW)
-        linear_fwd(pl, E, EW, None, fp.w("matchatt.transform.weight"), fp.w("matchatt.transform.bias"), ws["Q"], EW, N, EW, EW)
-        capi.match_att_fwd(E, EW, ws["Q"], EW, ws["node_off"], B, T, EW, ws["A"], EW, ws["P"], ws["TH"])
-        p = self.drop_p if training else 0.0
-        linear_fwd(pl, ws["A"], EW, None, fp.w("linear.weight"), fp.w("linear.bias"), ws["Zc"], D_HID, N, D_HID, EW,
-                   act=3 if p > 0 else 1, drop_p=p, rng=self.rng_state)
-        if with_logits:
-            linear_fwd(pl, ws["Zc"], D_HID, None, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ws["logits"], C, N, C, D_HID)
+        capi.gather_rows(ws["M"], EW, ws["node_row"], N, EW, ws["E"], EW)
+        self.head.forward(pl, ws, ws["E"], ws["node_off"], B, T, N, training, self.rng_state, with_logits)
         ws["x"] = x
         return ws
 
@@ -218,28 +185,9 @@ class _BcRnnModule(nn.Module):
         else:
             B, T, N = self._shape(x, lens, ys)
             ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=not head)
-        fp, pl, off = self.flat, ws["planner"], self.flat.offsets
-        C = self.n_classes
-        E, dE = ws["E"], ws["dE"]
-        p = self.drop_p if self.training else 0.0
-        # smax_fc + NLL of the log-softmax + their backward through the dropout / ReLU mask
-        if head:
-            capi.head_ce(ws["Zc"], D_HID, D_HID, C, N, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ys, class_weight,
-                         1.0 / (1.0 - p), ws["logits"], C, ws["dlogits"], C, ws["dZc"], D_HID, ws["stats"],
-                         n_dev=ws["counts"] if cap else None)
-        else:
-            capi.cross_entropy(ws["logits"], C, C, N, None, ys, class_weight, 1.0, ws["dlogits"], C, ws["stats"])
-            capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("smax_fc.weight"), D_HID, 1, None, ws["dZc"], D_HID, N, D_HID, C,
-                          act=2, aux=ws["Zc"], ldaux=D_HID, act_scale=1.0 / (1.0 - p))
-        linear_wgrad(pl, ws["dlogits"], C, ws["Zc"], D_HID, None, C, D_HID, N, off["smax_fc.weight"], off["smax_fc.bias"], defer=True)
-        capi.gemm_f32(ws["dZc"], D_HID, 0, None, fp.w("linear.weight"), EW, 1, None, ws["dA"], EW, N, EW, D_HID)
-        linear_wgrad(pl, ws["dZc"], D_HID, ws["A"], EW, None, D_HID, EW, N, off["linear.weight"], off["linear.bias"], defer=True)
-        # matching attention: dQ and dE (key side + score side); E is also the query transform's input
-        capi.match_att_bwd(E, EW, ws["Q"], EW, ws["dA"], EW, ws["node_off"], B, T, EW, ws["P"], ws["TH"], ws["DZ"], ws["dQ"], EW, dE, EW,
-                           n_cap=N if cap else 0)
-        linear_wgrad(pl, ws["dQ"], EW, E, EW, None, EW, EW, N, off["matchatt.transform.weight"], off["matchatt.transform.bias"],
-                     defer=True)
-        capi.gemm_f32(ws["dQ"], EW, 0, None, fp.w("matchatt.transform.weight"), EW, 1, None, dE, EW, N, EW, EW, accumulate=1)
+        pl, dE = ws["planner"], ws["dE"]
+        self.head.backward(pl, ws, ws["E"], ws["node_off"], B, T, N, ys, class_weight, self.training,
+                           n_dev=ws["counts"] if cap else None, n_cap=N if cap else 0)
         # back to the padded rows (zero on the padding: nothing downstream reads the RNN's output there), then the RNN
         dM = ws["dM"]
         if cap:
@@ -249,7 +197,7 @@ class _BcRnnModule(nn.Module):
             dM.zero_()
             capi.gather_rows(dE, EW, ws["node_row"], N, EW, dM, EW, scatter=1)
         self.enc.backward(pl, dM, EW)
-        pl.reduce_into(ws, fp.grad)
+        pl.reduce_into(ws, self.flat.grad)
         return ws["stats"]
 
 
@@ -263,34 +211,21 @@ class GRUModule(_BcRnnModule):
     CELL = "gru"
 
 
-class BcRnnTrainer(CapacityBuckets, TrainerBase):
+class BcRnnTrainer(CapacityBuckets, ConvEmotionTrainer):
     """train_step / to_logits for ``--module=bclstm`` and ``--module=bcgru``: class-weighted MaskedNLLLoss, Adam lr 3e-4, no
     weight decay (the defaults of the sibling plugin, track_mm/dgcnv2.py:22-48,184-219).  ``MODULE`` picks the cell."""
-    MODULE, NAME = None, None
+    MODULE = None
 
     def __init__(self, params, device):
-        self.params, self.device = params, torch.device(device)
-        compute = params.get("compute", "f32")
-        if compute != "f32":
-            raise capi.ErcGraftError("--module=%s runs in fp32 (the reference is fp32); --compute=%s is not supported"
-                                     % (self.NAME, compute))
-        self.class_weight = None
-        if params.get("loss_weights", True):
-            if params.n_classes != 6:
-                raise capi.ErcGraftError("--loss_weights uses the six hard-coded IEMOCAP-6 inverse frequencies "
-                                         "(dgcnv2.py:213-214); run %d-class datasets with --loss_weights=False" % params.n_classes)
-            self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
-        torch.manual_seed(params.seed)
-        self.model = self.MODULE(params.hidden_all, D_E, D_HID, n_classes=params.n_classes, dropout=params.get("dropout", 0.5),
-                                 compute=compute, seed=params.seed).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
+        super().__init__(params, device)
         # capacity buckets are opt-in (--capacity_buckets=True; --resident implies them): the default stays the exact-shape
         # step, whose dropout masks (keyed by the element index, so by B) a captured exact-shape graph must reproduce
         self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
         self._store_ext = None
+
+    def _build_model(self, params, compute):
+        return self.MODULE(params.hidden_all, D_E, D_HID, n_classes=params.n_classes, dropout=params.get("dropout", 0.5),
+                           compute=compute, seed=params.seed)
 
     # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  N_BUCKET 128 and "a batch of exactly its
     #    bucket's shape stays exact" are the mixin's defaults; ``self.capacity`` (set above) makes the buckets opt-in

@@ -1,12 +1,13 @@
-"""What the trainers share: the batch preparation and the plain training step (``TrainerBase``), and capacity mode's host
-side (``CapacityBuckets``) -- the buckets ``trainer.StepGraphs`` replays and the resident batch ``trainer.ResidentEpochs``
+"""What the trainers share: the batch preparation and the plain training step (``TrainerBase``), the constructor of the
+conv-emotion family (``ConvEmotionTrainer``), and capacity mode's host side (``CapacityBuckets``) -- the buckets ``trainer.StepGraphs`` replays and the resident batch ``trainer.ResidentEpochs``
 steps over.  A trainer in capacity mode keeps only its policy: N_BUCKET, the layout, the gate, the precapture list and
 the exact-shape rule (the table in DESIGN.md, "capacity mode: one implementation, per-trainer policy")."""
 import os
 
 import torch
 
-from .engine import all_reduce_grads
+from . import capi
+from .engine import FusedAdam, all_reduce_grads
 
 IEMOCAP6_WEIGHTS = [1 / 0.086747, 1 / 0.144406, 1 / 0.227883, 1 / 0.160585, 1 / 0.127711, 1 / 0.252668]  # dgcn.py:109-110, dgcnv2.py:213-214
 
@@ -45,6 +46,35 @@ class TrainerBase:
         scale = all_reduce_grads(self.model.flat)
         self.optim.step(grad_scale=scale)
         return stats
+
+
+class ConvEmotionTrainer(TrainerBase):
+    """What the trainers of the conv-emotion family (bc-LSTM / bc-GRU, DialogueRNN, conv-emotion DialogueGCN) share: fp32
+    only, the class-weighted loss, Adam lr 3e-4 without weight decay (track_mm/dgcnv2.py:22-48,184-219), and the dropout
+    counter of the model living in the optimizer.  A subclass names its ``--module`` value and builds its model."""
+    NAME = None
+
+    def __init__(self, params, device):
+        self.params, self.device = params, torch.device(device)
+        compute = params.get("compute", "f32")
+        if compute != "f32":
+            raise capi.ErcGraftError("--module=%s runs in fp32 (the reference is fp32); --compute=%s is not supported"
+                                     % (self.NAME, compute))
+        self.class_weight = None
+        if params.get("loss_weights", True):
+            if params.n_classes != 6:
+                raise capi.ErcGraftError("--loss_weights uses the six hard-coded IEMOCAP-6 inverse frequencies "
+                                         "(dgcnv2.py:213-214); run %d-class datasets with --loss_weights=False" % params.n_classes)
+            self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
+        torch.manual_seed(params.seed)
+        self.model = self._build_model(params, compute).finalize(self.device)
+        o = params.optim
+        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
+                               decoupled=(o.name == "AdamW"), seed=params.seed)
+        self.model.rng_state = self.optim.rng_state
+
+    def _build_model(self, params, compute):
+        raise NotImplementedError
 
 
 class CapacityBuckets:

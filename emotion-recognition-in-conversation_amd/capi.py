@@ -1069,12 +1069,18 @@ def dgcnv2_edge_att_bwd(S, ldS, g, B, T, wp, wf, dnorm, dS, dn_parts=1, dn_strid
           dn_parts, dn_stride, dS)
 
 
-def dgcnv2_nodal_fwd(E, lde, Q, ldq, node_off, B, T, A, lda, P, TH):
-    _call("erc_dgcnv2_nodal_fwd", E, lde, Q, ldq, node_off, B, T, A, lda, P, TH)
+# --------------------------------------------------------------------------- matching attention 'general2' (csrc/match_att.hip)
+def match_att_fwd(E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH):
+    _call("erc_match_att_fwd", E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH)
 
 
-def dgcnv2_nodal_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde):
-    _call("erc_dgcnv2_nodal_bwd", E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE, ldde)
+def match_att_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde, n_cap=0):
+    """``n_cap`` > 0: capacity mode, rows [node_off[B], n_cap) of dQ and dE are written 0 (ercgraft.h)"""
+    args = (E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde)
+    if n_cap:
+        _call("erc_match_att_bwd_cap", *args, n_cap)
+    else:
+        _call("erc_match_att_bwd", *args)
 
 
 # --------------------------------------------------------------------------- DialogueRNN (csrc/dialogrnn.hip)
@@ -1134,19 +1140,6 @@ def dialogrnn_scan_bwd(GX, ldgx, WT, params, offs, D_m, node_off, node_spk, B, T
                        dEmo, ldde, dGX, lddgx, dREC):
     _call("erc_dialogrnn_scan_bwd", GX, ldgx, WT, params, C.addressof(offs), D_m, node_off, node_spk, B, T, S, N, float(drop_p),
           float(drop_rec), rng, rng_stream, save, dEmo, ldde, dGX, lddgx, dREC)
-
-
-def match_att_fwd(E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH):
-    _call("erc_match_att_fwd", E, lde, Q, ldq, node_off, B, T, F, A, lda, P, TH)
-
-
-def match_att_bwd(E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde, n_cap=0):
-    """``n_cap`` > 0: capacity mode, rows [node_off[B], n_cap) of dQ and dE are written 0 (ercgraft.h)"""
-    args = (E, lde, Q, ldq, dA, ldda, node_off, B, T, F, P, TH, DZ, dQ, lddq, dE, ldde)
-    if n_cap:
-        _call("erc_match_att_bwd_cap", *args, n_cap)
-    else:
-        _call("erc_match_att_bwd", *args)
 
 
 def bcrnn_meta_cap(lengths, desc, store_label, zero_store_row, B, T, n_cap, node_off, node_row, pad_node, x_row, label_out, counts):

@@ -1,4 +1,5 @@
-// The two attentions of the conv-emotion DialogueGCN (track_mm/dgcnv2.py, track_mm/dgcnv2_models.py) and its batch tables.
+// The positional edge attention of the conv-emotion DialogueGCN (track_mm/dgcnv2.py, track_mm/dgcnv2_models.py) and its batch
+// tables.  Its nodal attention is the matching attention of match_att.hip at row width 300.
 //
 // Positional edge attention ('attn1', dgcnv2_models.py:533-566).  S = M Wscalar^T is computed by the caller over the B*T
 // padded, time-major rows of the sequence encoder's output (row t*B + b, 110 columns).  Row j of Wscalar scores every
@@ -8,48 +9,12 @@
 // (the softmax's own denominator cancels).  One wave per (dialogue, source position), lane t holding positions t and
 // t + 64 (T <= 110).  The backward writes dS [B*T, 110]: column p of dialogue b's rows belongs to source p alone, so every
 // element has one writer and no atomics are needed; columns p >= L_b are written as zeros.
-//
-// Nodal attention (MatchingAttention 'general2', dgcnv2_models.py:109-148,693-751) per dialogue over E = [x | conv2_out]
-// [N, 300] in node order (row node_off[b] + t), with Q = E W^T + b computed by the caller:
-//     th_tj = tanh(q_t . e_j),   p_tj = exp(th_tj) / sum_{k < L} exp(th_tk),   a_t = sum_j p_tj e_j
-// (|th| <= 1: no max subtraction; the padded exp(0) terms of the reference's softmax cancel in its renormalisation).
-// Forward: one workgroup per (dialogue, 16-query tile), keys streamed through LDS in chunks of 16 rows; p and th are
-// saved as [B, T, T].  Backward in two launches:
-//   query side, per (dialogue, 16-query tile):  dp = dA E^T,  dz = p (dp - rowsum(p dp)) (1 - th^2)  (saved),  dQ = dz E
-//   key side, per (dialogue, 16-key tile):      dE_j = sum_t p_tj dA_t + dz_tj Q_t
-// Every output element is written by one thread that sums in a fixed order: a step is bit-reproducible.
 #include "erc_common.h"
 
 namespace {
 
-constexpr int F = 300;             // E / Q / A row width
-constexpr int F4 = F / 4;
 constexpr int NSCAL = 110;         // rows of Wscalar: the reference's max_seq_len
-constexpr int TILE = 16;           // query / key rows per workgroup, and rows per streamed chunk
-constexpr int TPAD = 112;          // score row pitch in LDS (T <= 110)
 constexpr int NT = 256;
-constexpr int PER = (TILE * F4 + NT - 1) / NT;     // f4 outputs per thread of a [16, 300] tile
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float dot300(const float* a, const float* b) {
-    const f4* a4 = reinterpret_cast<const f4*>(a);
-    const f4* b4 = reinterpret_cast<const f4*>(b);
-    f4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 5
-    for (int k = 0; k < F4; ++k) acc += a4[k] * b4[k];
-    return (acc.x + acc.y) + (acc.z + acc.w);
-}
-
-// [16, 300] rows r0 .. r0 + 15 of a compact matrix into LDS; rows >= L are zero
-__device__ __forceinline__ void load_tile(float* dst, const float* src, int ld, int base, int r0, int L) {
-    for (int e = threadIdx.x; e < TILE * F4; e += NT) {
-        const int r = e / F4, k4 = e % F4;
-        f4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + r < L) v = reinterpret_cast<const f4*>(src + (int64_t)(base + r0 + r) * ld)[k4];
-        reinterpret_cast<f4*>(dst + r * F)[k4] = v;
-    }
-}
 
 // ------------------------------------------------------------------ batch tables
 __global__ void meta_kernel(const float* onehot, int S, const int64_t* lengths, int B, int T, int n_cap, int64_t* spk,
@@ -155,164 +120,6 @@ __global__ __launch_bounds__(NT) void edge_att_bwd_kernel(const float* __restric
     if (t1 < T) dS[((int64_t)t1 * B + b) * ldS + p] = in1 ? n1 * (dn1 - dot) : -1e-10f * n1 * dot;
 }
 
-// ------------------------------------------------------------------ nodal attention
-// out[16, 300] tile (rows r0..) += W[16, L] (LDS, pitch TPAD) times the dialogue's rows of X, streamed in chunks of 16
-__device__ __forceinline__ void tile_times_rows(f4 (&acc)[PER], const float* sW, const float* X, int ldx, int base, int L,
-                                                float* sChunk) {
-    for (int c0 = 0; c0 < L; c0 += TILE) {
-        __syncthreads();
-        load_tile(sChunk, X, ldx, base, c0, L);
-        __syncthreads();
-        const int nc = min(TILE, L - c0);
-#pragma unroll
-        for (int r = 0; r < PER; ++r) {
-            const int e = threadIdx.x + r * NT;
-            if (e >= TILE * F4) break;
-            const int qi = e / F4, k4 = e % F4;
-            for (int kj = 0; kj < nc; ++kj)
-                acc[r] += sW[qi * TPAD + c0 + kj] * reinterpret_cast<const f4*>(sChunk + kj * F)[k4];
-        }
-    }
-}
-
-// sS[16, L] = rows of sA (16 x 300) dotted with the dialogue's rows of X
-__device__ __forceinline__ void tile_dots(float* sS, const float* sA, const float* X, int ldx, int base, int L, int q0,
-                                          float* sChunk, bool do_tanh) {
-    for (int c0 = 0; c0 < L; c0 += TILE) {
-        __syncthreads();
-        load_tile(sChunk, X, ldx, base, c0, L);
-        __syncthreads();
-        const int qi = threadIdx.x / TILE, kj = threadIdx.x % TILE;
-        if (q0 + qi < L && c0 + kj < L) {
-            const float s = dot300(sA + qi * F, sChunk + kj * F);
-            sS[qi * TPAD + c0 + kj] = do_tanh ? tanhf(s) : s;
-        }
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(NT) void nodal_fwd_kernel(const float* __restrict__ E, int lde, const float* __restrict__ Q, int ldq,
-                                                       const int32_t* __restrict__ node_off, int T, float* __restrict__ A, int lda,
-                                                       float* __restrict__ Pg, float* __restrict__ THg) {
-    __shared__ __attribute__((aligned(16))) float sQ[TILE * F];
-    __shared__ __attribute__((aligned(16))) float sC[TILE * F];
-    __shared__ float sS[TILE * TPAD];
-    const int b = blockIdx.y, q0 = blockIdx.x * TILE;
-    const int base = node_off[b], L = node_off[b + 1] - base;
-    if (q0 >= L) return;
-    load_tile(sQ, Q, ldq, base, q0, L);
-    tile_dots(sS, sQ, E, lde, base, L, q0, sC, true);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int qi = wave; qi < TILE && q0 + qi < L; qi += NT / 64) {
-        float* row = sS + qi * TPAD;
-        const int64_t g = ((int64_t)b * T + q0 + qi) * T;
-        const float th0 = lane < L ? row[lane] : 0.f, th1 = lane + 64 < L ? row[lane + 64] : 0.f;
-        const float x0 = lane < L ? expf(th0) : 0.f, x1 = lane + 64 < L ? expf(th1) : 0.f;
-        const float inv = 1.f / wave_sum(x0 + x1);
-        if (lane < L) row[lane] = x0 * inv, Pg[g + lane] = x0 * inv, THg[g + lane] = th0;
-        if (lane + 64 < L) row[lane + 64] = x1 * inv, Pg[g + lane + 64] = x1 * inv, THg[g + lane + 64] = th1;
-    }
-    f4 acc[PER];
-#pragma unroll
-    for (int r = 0; r < PER; ++r) acc[r] = f4{0.f, 0.f, 0.f, 0.f};
-    tile_times_rows(acc, sS, E, lde, base, L, sC);
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-        const int e = threadIdx.x + r * NT;
-        if (e >= TILE * F4) break;
-        const int qi = e / F4, k4 = e % F4;
-        if (q0 + qi < L) reinterpret_cast<f4*>(A + (int64_t)(base + q0 + qi) * lda)[k4] = acc[r];
-    }
-}
-
-__global__ __launch_bounds__(NT) void nodal_bwd_q_kernel(const float* __restrict__ E, int lde, const float* __restrict__ dA, int ldda,
-                                                         const int32_t* __restrict__ node_off, int T, const float* __restrict__ Pg,
-                                                         const float* __restrict__ THg, float* __restrict__ DZg,
-                                                         float* __restrict__ dQ, int lddq) {
-    __shared__ __attribute__((aligned(16))) float sG[TILE * F];
-    __shared__ __attribute__((aligned(16))) float sC[TILE * F];
-    __shared__ float sS[TILE * TPAD];
-    const int b = blockIdx.y, q0 = blockIdx.x * TILE;
-    const int base = node_off[b], L = node_off[b + 1] - base;
-    if (q0 >= L) return;
-    load_tile(sG, dA, ldda, base, q0, L);
-    tile_dots(sS, sG, E, lde, base, L, q0, sC, false);          // dp
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int qi = wave; qi < TILE && q0 + qi < L; qi += NT / 64) {
-        float* row = sS + qi * TPAD;
-        const int64_t g = ((int64_t)b * T + q0 + qi) * T;
-        const float p0 = lane < L ? Pg[g + lane] : 0.f, p1 = lane + 64 < L ? Pg[g + lane + 64] : 0.f;
-        const float d0 = lane < L ? row[lane] : 0.f, d1 = lane + 64 < L ? row[lane + 64] : 0.f;
-        const float rs = wave_sum(p0 * d0 + p1 * d1);
-        if (lane < L) {
-            const float th = THg[g + lane], z = p0 * (d0 - rs) * (1.f - th * th);
-            row[lane] = z, DZg[g + lane] = z;
-        }
-        if (lane + 64 < L) {
-            const float th = THg[g + lane + 64], z = p1 * (d1 - rs) * (1.f - th * th);
-            row[lane + 64] = z, DZg[g + lane + 64] = z;
-        }
-    }
-    f4 acc[PER];
-#pragma unroll
-    for (int r = 0; r < PER; ++r) acc[r] = f4{0.f, 0.f, 0.f, 0.f};
-    tile_times_rows(acc, sS, E, lde, base, L, sC);
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-        const int e = threadIdx.x + r * NT;
-        if (e >= TILE * F4) break;
-        const int qi = e / F4, k4 = e % F4;
-        if (q0 + qi < L) reinterpret_cast<f4*>(dQ + (int64_t)(base + q0 + qi) * lddq)[k4] = acc[r];
-    }
-}
-
-__global__ __launch_bounds__(NT) void nodal_bwd_k_kernel(const float* __restrict__ Q, int ldq, const float* __restrict__ dA, int ldda,
-                                                         const int32_t* __restrict__ node_off, int T, const float* __restrict__ Pg,
-                                                         const float* __restrict__ DZg, float* __restrict__ dE, int ldde) {
-    __shared__ __attribute__((aligned(16))) float sG[TILE * F];
-    __shared__ __attribute__((aligned(16))) float sQ[TILE * F];
-    __shared__ float sP[TILE * TILE];
-    __shared__ float sZ[TILE * TILE];
-    const int b = blockIdx.y, k0 = blockIdx.x * TILE;
-    const int base = node_off[b], L = node_off[b + 1] - base;
-    if (k0 >= L) return;
-    f4 acc[PER];
-#pragma unroll
-    for (int r = 0; r < PER; ++r) acc[r] = f4{0.f, 0.f, 0.f, 0.f};
-    for (int i0 = 0; i0 < L; i0 += TILE) {
-        __syncthreads();
-        load_tile(sG, dA, ldda, base, i0, L);
-        load_tile(sQ, Q, ldq, base, i0, L);
-        {
-            const int ii = threadIdx.x / TILE, kj = threadIdx.x % TILE;
-            const bool ok = i0 + ii < L && k0 + kj < L;
-            const int64_t g = ((int64_t)b * T + i0 + ii) * T + k0 + kj;
-            sP[ii * TILE + kj] = ok ? Pg[g] : 0.f;
-            sZ[ii * TILE + kj] = ok ? DZg[g] : 0.f;
-        }
-        __syncthreads();
-        const int ni = min(TILE, L - i0);
-#pragma unroll
-        for (int r = 0; r < PER; ++r) {
-            const int e = threadIdx.x + r * NT;
-            if (e >= TILE * F4) break;
-            const int kj = e / F4, k4 = e % F4;
-            for (int ii = 0; ii < ni; ++ii)
-                acc[r] += sP[ii * TILE + kj] * reinterpret_cast<const f4*>(sG + ii * F)[k4] +
-                          sZ[ii * TILE + kj] * reinterpret_cast<const f4*>(sQ + ii * F)[k4];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-        const int e = threadIdx.x + r * NT;
-        if (e >= TILE * F4) break;
-        const int kj = e / F4, k4 = e % F4;
-        if (k0 + kj < L) reinterpret_cast<f4*>(dE + (int64_t)(base + k0 + kj) * ldde)[k4] = acc[r];
-    }
-}
-
-bool aligned16(const void* p, int ld) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0; }
-
 }  // namespace
 
 extern "C" int erc_dgcnv2_max_t(void) { return NSCAL; }
@@ -351,34 +158,5 @@ extern "C" int erc_dgcnv2_edge_att_bwd(const float* S, int ldS, const int32_t* n
     hipLaunchKernelGGL(edge_att_bwd_kernel, dim3(erc_cdiv(NSCAL, NT / 64), B), dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B,
                        T, wp, wf, out_ptr, out_dst, out_eid, dnorm, dn_parts, dn_stride, dS);
     ERC_LAUNCH_CHECK("dgcnv2_edge_att_bwd");
-    return ERC_OK;
-}
-
-extern "C" int erc_dgcnv2_nodal_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T,
-                                    float* A, int lda, float* P, float* TH, void* stream) {
-    ERC_REQUIRE(E && Q && node_off && A && P && TH, "dgcnv2_nodal_fwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && T <= NSCAL, "dgcnv2_nodal_fwd: bad sizes B=%d T=%d (T <= %d)", B, T, NSCAL);
-    ERC_REQUIRE(aligned16(E, lde) && aligned16(Q, ldq) && aligned16(A, lda), "dgcnv2_nodal_fwd: rows must be 16-byte aligned");
-    ERC_REQUIRE(lde >= F && ldq >= F && lda >= F, "dgcnv2_nodal_fwd: row pitches below %d", F);
-    hipLaunchKernelGGL(nodal_fwd_kernel, dim3(erc_cdiv(T, TILE), B), dim3(NT), 0, (hipStream_t)stream, E, lde, Q, ldq, node_off, T, A,
-                       lda, P, TH);
-    ERC_LAUNCH_CHECK("dgcnv2_nodal_fwd");
-    return ERC_OK;
-}
-
-extern "C" int erc_dgcnv2_nodal_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda,
-                                    const int32_t* node_off, int B, int T, const float* P, const float* TH, float* DZ, float* dQ,
-                                    int lddq, float* dE, int ldde, void* stream) {
-    ERC_REQUIRE(E && Q && dA && node_off && P && TH && DZ && dQ && dE, "dgcnv2_nodal_bwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && T <= NSCAL, "dgcnv2_nodal_bwd: bad sizes B=%d T=%d (T <= %d)", B, T, NSCAL);
-    ERC_REQUIRE(aligned16(E, lde) && aligned16(Q, ldq) && aligned16(dA, ldda) && aligned16(dQ, lddq) && aligned16(dE, ldde),
-                "dgcnv2_nodal_bwd: rows must be 16-byte aligned");
-    ERC_REQUIRE(lde >= F && ldq >= F && ldda >= F && lddq >= F && ldde >= F, "dgcnv2_nodal_bwd: row pitches below %d", F);
-    ERC_REQUIRE(dE != E && dE != Q && dE != dA && dQ != E && dQ != dA, "dgcnv2_nodal_bwd: outputs must not alias inputs");
-    const dim3 grid(erc_cdiv(T, TILE), B);
-    hipLaunchKernelGGL(nodal_bwd_q_kernel, grid, dim3(NT), 0, (hipStream_t)stream, E, lde, dA, ldda, node_off, T, P, TH, DZ, dQ, lddq);
-    ERC_LAUNCH_CHECK("dgcnv2_nodal_bwd_q");
-    hipLaunchKernelGGL(nodal_bwd_k_kernel, grid, dim3(NT), 0, (hipStream_t)stream, Q, ldq, dA, ldda, node_off, T, P, DZ, dE, ldde);
-    ERC_LAUNCH_CHECK("dgcnv2_nodal_bwd_k");
     return ERC_OK;
 }

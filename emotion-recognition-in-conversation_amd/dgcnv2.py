@@ -17,19 +17,14 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import IEMOCAP6_WEIGHTS, TrainerBase
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, linear_fwd, linear_wgrad, matmul_wgrad_io
+from .capacity import ConvEmotionTrainer
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, linear_fwd, linear_wgrad, matmul_wgrad_io
+from .matchhead import ConvEmotionModule, MatchAttHead, Transform
 from .rnn import BiLSTM2, lstm_groups
 
 G_DIM, H1, NB, NSCAL = 200, 100, 30, 110
 EW = G_DIM + H1            # row width of E = [features | conv2 output]
 DEAD = ("att_model.matchatt.", "att_model.simpleatt.", "att_model.att.")
-
-
-class _Transform(nn.Module):          # MatchingAttention('general2'): its one parameterised layer
-    def __init__(self, d):
-        super().__init__()
-        self.transform = nn.Linear(d, d, bias=True)
 
 
 class _SimpleAttention(nn.Module):
@@ -51,7 +46,7 @@ class _EdgeAttention(nn.Module):
     def __init__(self, d, max_seq_len):
         super().__init__()
         self.scalar = nn.Linear(d, max_seq_len, bias=False)
-        self.matchatt = _Transform(d)
+        self.matchatt = Transform(d)
         self.simpleatt = _SimpleAttention(d)
         self.att = _MlpAttention(d)
 
@@ -80,13 +75,13 @@ class _GraphNetwork(nn.Module):
         super().__init__()
         self.conv1 = _RGCNBasis(d, hidden, R, NB)
         self.conv2 = _GraphConv(hidden, hidden)
-        self.matchatt = _Transform(d + hidden)
+        self.matchatt = Transform(d + hidden)
         self.linear = nn.Linear(d + hidden, hidden)
         self.dropout = nn.Dropout(dropout)
         self.smax_fc = nn.Linear(hidden, n_classes)
 
 
-class DGCNModule(nn.Module):
+class DGCNModule(ConvEmotionModule):
     def __init__(self, base_model, input_size=100, hidden_size=100, n_speakers=2, window_past=10, window_future=10, n_classes=7,
                  listener_state=False, context_attention="general", dropout_rec=0.5, dropout=0.4, nodal_attention=True, avec=False,
                  compute="f32", seed=1):
@@ -124,24 +119,16 @@ class DGCNModule(nn.Module):
             [("graph_net.conv1.root", gn.conv1.root)], [("graph_net.conv1.bias", gn.conv1.bias)],
             [("graph_net.conv2.lin_rel.weight", gn.conv2.lin_rel.weight)], [("graph_net.conv2.lin_rel.bias", gn.conv2.lin_rel.bias)],
             [("graph_net.conv2.lin_root.weight", gn.conv2.lin_root.weight)],
-            [("graph_net.matchatt.transform.weight", gn.matchatt.transform.weight)],
-            [("graph_net.matchatt.transform.bias", gn.matchatt.transform.bias)],
-            [("graph_net.linear.weight", gn.linear.weight)], [("graph_net.linear.bias", gn.linear.bias)],
-            [("graph_net.smax_fc.weight", gn.smax_fc.weight)], [("graph_net.smax_fc.bias", gn.smax_fc.bias)],
-        ]
+        ] + MatchAttHead.groups("graph_net.", gn)
 
     def finalize(self, device):
         self.to(device)
         self.flat = FlatParams(self.live_groups(), device)
         if self.base_model == "LSTM":
             self.enc = BiLSTM2(self.flat, "lstm.", self.input_size, drop_p=self.drop_p)
+        self.head = MatchAttHead(self.flat, "graph_net.", EW, H1, self.n_classes, self.drop_p)
         self.rng_state = torch.tensor([0, self._seed], dtype=torch.int64, device=device)
         return self
-
-    @property
-    def _last_ws(self):
-        """workspace of the most recent forward (tests / bench read results out of it)"""
-        return self._ws.last
 
     def _workspace(self, B, T, N, device):
         return self._ws.get((B, T, N), lambda: self._make_workspace(B, T, N, device))
@@ -152,28 +139,20 @@ class DGCNModule(nn.Module):
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
         w = (self.wp if self.wp >= 0 else T) + (self.wf if self.wf >= 0 else T) + 1
         E = max(1, N * min(w, T))
-        C, BT, n_sl = self.n_classes, B * T, capi.brgcn_fwd_tile_slabs()
+        BT, n_sl = B * T, capi.brgcn_fwd_tile_slabs()
         g = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), in_ptr=i32(N + 1), in_src=i32(E),
                  in_typ=i32(E), out_ptr=i32(N + 1), out_dst=i32(E), out_typ=i32(E), out_eid=i32(E), counts=i32(2))
         ws = dict(g=g, E_cap=E, spk=torch.zeros(BT, dtype=torch.int64, device=device), node_row=i32(N),
                   M=f32(BT, G_DIM), S=f32(BT, NSCAL), norm=f32(E), Z=f32(N, NB * G_DIM), rgcn_slabs=f32(capi.brgcn_fwd_tile_slab_floats(N)),
-                  Hc=f32(N, H1), AGG=f32(N, H1), E=f32(N, EW), Q=f32(N, EW), A=f32(N, EW), P=f32(B * T * T), TH=f32(B * T * T),
-                  Zc=f32(N, H1), logits=f32(N, C),
-                  stats=f32(max(256, capi.head_ce_stats_floats(N))),
-                  dlogits=f32(N, C), dZc=f32(N, H1), dA=f32(N, EW), DZ=f32(B * T * T), dQ=f32(N, EW), dE=f32(N, EW),
+                  Hc=f32(N, H1), AGG=f32(N, H1), E=f32(N, EW),
                   dAGG=f32(N, H1), dHc=f32(N, H1), TT=f32(E, NB), dn_slabs=f32(n_sl * E), rgcn_dslabs=f32(n_sl * N * G_DIM),
-                  dS=f32(BT, NSCAL), dM=f32(BT, G_DIM))
+                  dS=f32(BT, NSCAL), dM=f32(BT, G_DIM), **self.head.buffers(B, T, N, device))
         D = self.input_size
         slab = 12 * N * H1 + 4 * BT * 800 + 10 * (800 * D + 800 * 200 + 2 * 400 * 100 * 2) + 4 * NB * G_DIM * H1 + \
             8 * (EW * EW + EW * H1 + NSCAL * G_DIM) + 4 * N * EW + (1 << 21)
         ws["planner"] = GemmPlanner(device, slab, grad=self.flat.grad)
         ws["jobs"] = None
         return ws
-
-    def _shape(self, x, lens, label, n_nodes=None):
-        T, B = int(x.shape[0]), int(x.shape[1])
-        N = int(label.shape[0]) if label is not None else (int(n_nodes) if n_nodes is not None else int(lens.sum().item()))
-        return B, T, N
 
     def _check(self, T):
         if T > NSCAL:
@@ -186,7 +165,7 @@ class DGCNModule(nn.Module):
         ws = self._workspace(B, T, N, x.device)
         g, pl = ws["g"], ws["planner"]
         pl.reset()
-        D, C, BT = self.input_size, self.n_classes, B * T
+        D, BT = self.input_size, B * T
         x, onehot = x.contiguous(), onehot.contiguous()
         capi.dgcnv2_meta(onehot, int(onehot.shape[-1]), lens, B, T, N, ws["spk"], ws["node_row"])
         capi.window_graph_build(lens, ws["spk"], 1, B, B, T, self.wp, self.wf, self.n_speakers, N, ws["E_cap"], g)
@@ -214,15 +193,7 @@ class DGCNModule(nn.Module):
         capi.gemm_f32(ws["Hc"], H1, 0, None, fp.w("graph_net.conv2.lin_root.weight"), H1, 0, None, gout, EW, N, H1, H1,
                       accumulate=1)
         # nodal attention over E, then the classifier
-        linear_fwd(pl, E, EW, None, fp.w("graph_net.matchatt.transform.weight"), fp.w("graph_net.matchatt.transform.bias"),
-                   ws["Q"], EW, N, EW, EW)
-        capi.dgcnv2_nodal_fwd(E, EW, ws["Q"], EW, g["node_off"], B, T, ws["A"], EW, ws["P"], ws["TH"])
-        p = self.drop_p if training else 0.0
-        linear_fwd(pl, ws["A"], EW, None, fp.w("graph_net.linear.weight"), fp.w("graph_net.linear.bias"), ws["Zc"], H1, N, H1, EW,
-                   act=3 if p > 0 else 1, drop_p=p, rng=self.rng_state)
-        if with_logits:
-            linear_fwd(pl, ws["Zc"], H1, None, fp.w("graph_net.smax_fc.weight"), fp.w("graph_net.smax_fc.bias"), ws["logits"], C,
-                       N, C, H1)
+        self.head.forward(pl, ws, E, g["node_off"], B, T, N, training, self.rng_state, with_logits)
         ws["x"] = x
         return ws
 
@@ -237,31 +208,11 @@ class DGCNModule(nn.Module):
         """F.cross_entropy(logits, label, weight) (dgcnv2.py:206) and every live gradient into flat.grad"""
         x, onehot, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
         B, T, N = self._shape(x, lens, ys)
-        head = self.n_classes <= 8
-        ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=not head)
+        ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=self.n_classes > 8)
         fp, g, pl, off = self.flat, ws["g"], ws["planner"], self.flat.offsets
-        C, BT = self.n_classes, B * T
+        BT = B * T
         E, dE = ws["E"], ws["dE"]
-        p = self.drop_p if self.training else 0.0
-        # smax_fc + cross entropy + their backward through the dropout / ReLU mask
-        if head:
-            capi.head_ce(ws["Zc"], H1, H1, C, N, fp.w("graph_net.smax_fc.weight"), fp.w("graph_net.smax_fc.bias"), ys, class_weight,
-                         1.0 / (1.0 - p), ws["logits"], C, ws["dlogits"], C, ws["dZc"], H1, ws["stats"])
-        else:
-            capi.cross_entropy(ws["logits"], C, C, N, None, ys, class_weight, 1.0, ws["dlogits"], C, ws["stats"])
-            capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("graph_net.smax_fc.weight"), H1, 1, None, ws["dZc"], H1, N, H1, C,
-                          act=2, aux=ws["Zc"], ldaux=H1, act_scale=1.0 / (1.0 - p))
-        linear_wgrad(pl, ws["dlogits"], C, ws["Zc"], H1, None, C, H1, N, off["graph_net.smax_fc.weight"],
-                     off["graph_net.smax_fc.bias"], defer=True)
-        capi.gemm_f32(ws["dZc"], H1, 0, None, fp.w("graph_net.linear.weight"), EW, 1, None, ws["dA"], EW, N, EW, H1)
-        linear_wgrad(pl, ws["dZc"], H1, ws["A"], EW, None, H1, EW, N, off["graph_net.linear.weight"], off["graph_net.linear.bias"],
-                     defer=True)
-        # nodal attention: dQ and dE (key side + score side); E is also the query transform's input
-        capi.dgcnv2_nodal_bwd(E, EW, ws["Q"], EW, ws["dA"], EW, g["node_off"], B, T, ws["P"], ws["TH"], ws["DZ"], ws["dQ"], EW, dE, EW)
-        linear_wgrad(pl, ws["dQ"], EW, E, EW, None, EW, EW, N, off["graph_net.matchatt.transform.weight"],
-                     off["graph_net.matchatt.transform.bias"], defer=True)
-        capi.gemm_f32(ws["dQ"], EW, 0, None, fp.w("graph_net.matchatt.transform.weight"), EW, 1, None, dE, EW, N, EW, EW,
-                      accumulate=1)
+        self.head.backward(pl, ws, E, g["node_off"], B, T, N, ys, class_weight, self.training)
         # GraphConv
         dG = dE[:, G_DIM:]
         capi.gemm_f32(dG, EW, 0, None, fp.w("graph_net.conv2.lin_rel.weight"), H1, 1, None, ws["dAGG"], H1, N, H1, H1)
@@ -299,27 +250,12 @@ class DGCNModule(nn.Module):
         return ws["stats"]
 
 
-class DGCNv2Trainer(TrainerBase):
+class DGCNv2Trainer(ConvEmotionTrainer):
     """train_step / to_logits of track_mm/dgcnv2.py:184-219 (class-weighted CE, Adam lr 3e-4, no weight decay)."""
+    NAME = "dgcnv2"
 
-    def __init__(self, params, device):
-        self.params, self.device = params, torch.device(device)
-        compute = params.get("compute", "f32")
-        if compute != "f32":
-            raise capi.ErcGraftError("--module=dgcnv2 runs in fp32 (the reference is fp32); --compute=%s is not supported" % compute)
-        self.class_weight = None
-        if params.get("loss_weights", True):
-            if params.n_classes != 6:
-                raise capi.ErcGraftError("--loss_weights uses the six hard-coded IEMOCAP-6 inverse frequencies "
-                                         "(dgcnv2.py:213-214); run %d-class datasets with --loss_weights=False" % params.n_classes)
-            self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
+    def _build_model(self, params, compute):
         base = params.get("base_model", "LSTM")
         base = "None" if base is None else base          # --base_model=None parses as the Python literal
-        torch.manual_seed(params.seed)
-        self.model = DGCNModule(base_model=base, input_size=params.hidden_all, hidden_size=100,
-                                n_speakers=params.n_speakers, n_classes=params.n_classes, context_attention="general",
-                                compute=compute, seed=params.seed).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
+        return DGCNModule(base_model=base, input_size=params.hidden_all, hidden_size=100, n_speakers=params.n_speakers,
+                          n_classes=params.n_classes, context_attention="general", compute=compute, seed=params.seed)

@@ -20,8 +20,9 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import IEMOCAP6_WEIGHTS, TrainerBase
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, linear_fwd, linear_wgrad
+from .capacity import ConvEmotionTrainer
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, linear_fwd, linear_wgrad
+from .matchhead import ConvEmotionModule, MatchAttHead, Transform
 
 D_G, D_E, D_HID, EW, MAX_T, MAX_S = 150, 100, 100, 200, 110, 9
 GXW = capi.DIALOGRNN_GXW
@@ -33,12 +34,6 @@ class _Attention(nn.Module):          # MatchingAttention(D_g, D_m, att_type='ge
     def __init__(self, d_m, d_g):
         super().__init__()
         self.transform = nn.Linear(d_m, d_g, bias=False)
-
-
-class _Transform(nn.Module):          # MatchingAttention('general2'): its one parameterised layer
-    def __init__(self, d):
-        super().__init__()
-        self.transform = nn.Linear(d, d, bias=True)
 
 
 class _Cell(nn.Module):
@@ -56,7 +51,7 @@ class _DialogueRNN(nn.Module):
         self.dialogue_cell = _Cell(D_m, D_g, D_p, D_e)
 
 
-class DialogRNNModule(nn.Module):
+class DialogRNNModule(ConvEmotionModule):
     def __init__(self, D_m, D_g, D_p, D_e, D_h, D_a=100, n_classes=7, listener_state=False, context_attention="simple",
                  dropout_rec=0.5, dropout=0.5, compute="f32", seed=1):
         super().__init__()
@@ -78,7 +73,7 @@ class DialogRNNModule(nn.Module):
         self.drop_cell, self.drop_emo, self.drop_p = float(dropout_rec), float(dropout) + 0.15, float(dropout)   # :436-438
         self.dialog_rnn_f = _DialogueRNN(D_m, D_g, D_p, D_e)
         self.dialog_rnn_r = _DialogueRNN(D_m, D_g, D_p, D_e)
-        self.matchatt = _Transform(2 * D_e)
+        self.matchatt = Transform(2 * D_e)
         self.linear = nn.Linear(2 * D_e, D_h)
         self.smax_fc = nn.Linear(D_h, n_classes)
         self.flat, self._ws, self._seed = None, WorkspaceCache(), seed
@@ -95,14 +90,12 @@ class DialogRNNModule(nn.Module):
                        for cell, k in (("g_cell", "weight_hh"), ("g_cell", "bias_hh"), ("p_cell", "weight_hh"), ("p_cell", "bias_hh"),
                                        ("e_cell", "weight_ih"), ("e_cell", "weight_hh"), ("e_cell", "bias_ih"), ("e_cell", "bias_hh"))]
             groups.append([(n + "attention.transform.weight", c.attention.transform.weight)])
-        return groups + [[("matchatt.transform.weight", self.matchatt.transform.weight)],
-                         [("matchatt.transform.bias", self.matchatt.transform.bias)],
-                         [("linear.weight", self.linear.weight)], [("linear.bias", self.linear.bias)],
-                         [("smax_fc.weight", self.smax_fc.weight)], [("smax_fc.bias", self.smax_fc.bias)]]
+        return groups + MatchAttHead.groups("", self)
 
     def finalize(self, device):
         self.to(device)
         self.flat = FlatParams(self.live_groups(), device)
+        self.head = MatchAttHead(self.flat, "", EW, D_HID, self.n_classes, self.drop_p)
         off = self.flat.offsets
         self.offs = capi.dialogrnn_offsets([off[d + ".dialogue_cell." + k] for d in DIRS for k in (
             "g_cell.weight_ih", "g_cell.weight_hh", "g_cell.bias_hh", "p_cell.weight_ih", "p_cell.weight_hh", "p_cell.bias_hh",
@@ -112,11 +105,6 @@ class DialogRNNModule(nn.Module):
         self.rng_state = torch.tensor([0, self._seed], dtype=torch.int64, device=device)
         return self
 
-    @property
-    def _last_ws(self):
-        """workspace of the most recent forward (tests / bench read results out of it)"""
-        return self._ws.last
-
     def _workspace(self, B, T, N, device):
         return self._ws.get((B, T, N), lambda: self._make_workspace(B, T, N, device))
 
@@ -124,23 +112,15 @@ class DialogRNNModule(nn.Module):
         # zeros, not empty: a stale NaN must never reach a weight-gradient GEMM through a row the step did not touch
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        C = self.n_classes
         ws = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), GX=f32(N, 2 * GXW), E=f32(N, EW),
-                  save=f32(capi.dialogrnn_save_floats(N, B, T)), Q=f32(N, EW), A=f32(N, EW), P=f32(B * T * T), TH=f32(B * T * T),
-                  Zc=f32(N, D_HID), logits=f32(N, C), logp=f32(N, C), stats=f32(max(256, capi.head_ce_stats_floats(N))),
-                  dlogits=f32(N, C), dZc=f32(N, D_HID), dA=f32(N, EW), DZ=f32(B * T * T), dQ=f32(N, EW), dE=f32(N, EW),
-                  dGX=f32(N, 2 * GXW), dREC=f32(2 * N * capi.DIALOGRNN_DREC_ROW))
+                  save=f32(capi.dialogrnn_save_floats(N, B, T)), dGX=f32(N, 2 * GXW), dREC=f32(2 * N * capi.DIALOGRNN_DREC_ROW),
+                  **self.head.buffers(B, T, N, device))
         ws["sv"] = capi.dialogrnn_planes(ws["save"], N, capi.DIALOGRNN_SAVE)
         ws["dr"] = capi.dialogrnn_planes(ws["dREC"], N, capi.DIALOGRNN_DREC)
         ws["alpha"] = capi.dialogrnn_alpha(ws["save"], N, B, T)
         ws["planner"] = GemmPlanner(device, 1 << 21, grad=self.flat.grad)
         ws["jobs"] = None
         return ws
-
-    def _shape(self, x, lens, label, n_nodes=None):
-        T, B = int(x.shape[0]), int(x.shape[1])
-        N = int(label.shape[0]) if label is not None else (int(n_nodes) if n_nodes is not None else int(lens.sum().item()))
-        return B, T, N
 
     def _check(self, x, onehot, T):
         if T > MAX_T:
@@ -154,7 +134,7 @@ class DialogRNNModule(nn.Module):
             raise capi.ErcGraftError("dialogrnn: input_tensor and speaker_tensor must be fp32 (one-hot speakers)")
 
     def _drops(self, training):
-        return (self.drop_cell, self.drop_emo, self.drop_p) if training else (0.0, 0.0, 0.0)
+        return (self.drop_cell, self.drop_emo) if training else (0.0, 0.0)
 
     def _forward_impl(self, x, onehot, lens, B, T, N, training, with_logits=True):
         self._check(x, onehot, T)
@@ -162,7 +142,7 @@ class DialogRNNModule(nn.Module):
         ws = self._workspace(B, T, N, x.device)
         pl = ws["planner"]
         pl.reset()
-        D, C, S = self.D_m, self.n_classes, int(onehot.shape[-1])
+        D, S = self.D_m, int(onehot.shape[-1])
         x, onehot = x.contiguous(), onehot.contiguous()
         capi.dialogrnn_meta(onehot, S, lens, B, T, N, ws["node_off"], ws["node_row"], ws["node_spk"])
         capi.dialogrnn_pack(fp.data, self.offs, D, self.WT)
@@ -174,16 +154,10 @@ class DialogRNNModule(nn.Module):
                        N, 900, D, ldw=D + D_G)
             linear_fwd(pl, x, D, ws["node_row"], fp.w(c + "attention.transform.weight"), None, GX[:, d * GXW + 900:], 2 * GXW,
                        N, D_G, D)
-        p_cell, p_emo, p_clf = self._drops(training)
+        p_cell, p_emo = self._drops(training)
         capi.dialogrnn_scan_fwd(GX, 2 * GXW, self.WT, fp.data, self.offs, D, ws["node_off"], ws["node_spk"], B, T, S, N, p_cell, p_emo,
                                 self.rng_state, RNG_STREAM, ws["E"], EW, ws["save"])
-        E = ws["E"]
-        linear_fwd(pl, E, EW, None, fp.w("matchatt.transform.weight"), fp.w("matchatt.transform.bias"), ws["Q"], EW, N, EW, EW)
-        capi.match_att_fwd(E, EW, ws["Q"], EW, ws["node_off"], B, T, EW, ws["A"], EW, ws["P"], ws["TH"])
-        linear_fwd(pl, ws["A"], EW, None, fp.w("linear.weight"), fp.w("linear.bias"), ws["Zc"], D_HID, N, D_HID, EW,
-                   act=3 if p_clf > 0 else 1, drop_p=p_clf, rng=self.rng_state)
-        if with_logits:
-            linear_fwd(pl, ws["Zc"], D_HID, None, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ws["logits"], C, N, C, D_HID)
+        self.head.forward(pl, ws, ws["E"], ws["node_off"], B, T, N, training, self.rng_state, with_logits)
         ws["x"], ws["S"] = x, S
         return ws
 
@@ -200,28 +174,12 @@ class DialogRNNModule(nn.Module):
         gradient into flat.grad"""
         x, onehot, lens, ys = batch["input_tensor"], batch["speaker_tensor"], batch["text_length"], batch["label"]
         B, T, N = self._shape(x, lens, ys)
-        head = self.n_classes <= 8
-        ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=not head)
+        ws = self._forward_impl(x, onehot, lens, B, T, N, self.training, with_logits=self.n_classes > 8)
         fp, pl, off = self.flat, ws["planner"], self.flat.offsets
-        C, D, S = self.n_classes, self.D_m, ws["S"]
-        E, dE, sv, dr = ws["E"], ws["dE"], ws["sv"], ws["dr"]
-        p_cell, p_emo, p_clf = self._drops(self.training)
-        # smax_fc + NLL of the log-softmax + their backward through the dropout / ReLU mask
-        if head:
-            capi.head_ce(ws["Zc"], D_HID, D_HID, C, N, fp.w("smax_fc.weight"), fp.w("smax_fc.bias"), ys, class_weight,
-                         1.0 / (1.0 - p_clf), ws["logits"], C, ws["dlogits"], C, ws["dZc"], D_HID, ws["stats"])
-        else:
-            capi.cross_entropy(ws["logits"], C, C, N, None, ys, class_weight, 1.0, ws["dlogits"], C, ws["stats"])
-            capi.gemm_f32(ws["dlogits"], C, 0, None, fp.w("smax_fc.weight"), D_HID, 1, None, ws["dZc"], D_HID, N, D_HID, C,
-                          act=2, aux=ws["Zc"], ldaux=D_HID, act_scale=1.0 / (1.0 - p_clf))
-        linear_wgrad(pl, ws["dlogits"], C, ws["Zc"], D_HID, None, C, D_HID, N, off["smax_fc.weight"], off["smax_fc.bias"], defer=True)
-        capi.gemm_f32(ws["dZc"], D_HID, 0, None, fp.w("linear.weight"), EW, 1, None, ws["dA"], EW, N, EW, D_HID)
-        linear_wgrad(pl, ws["dZc"], D_HID, ws["A"], EW, None, D_HID, EW, N, off["linear.weight"], off["linear.bias"], defer=True)
-        # matching attention: dQ and dE (key side + score side); E is also the query transform's input
-        capi.match_att_bwd(E, EW, ws["Q"], EW, ws["dA"], EW, ws["node_off"], B, T, EW, ws["P"], ws["TH"], ws["DZ"], ws["dQ"], EW, dE, EW)
-        linear_wgrad(pl, ws["dQ"], EW, E, EW, None, EW, EW, N, off["matchatt.transform.weight"], off["matchatt.transform.bias"],
-                     defer=True)
-        capi.gemm_f32(ws["dQ"], EW, 0, None, fp.w("matchatt.transform.weight"), EW, 1, None, dE, EW, N, EW, EW, accumulate=1)
+        D, S = self.D_m, ws["S"]
+        dE, sv, dr = ws["dE"], ws["sv"], ws["dr"]
+        p_cell, p_emo = self._drops(self.training)
+        self.head.backward(pl, ws, ws["E"], ws["node_off"], B, T, N, ys, class_weight, self.training)
         # both scans backwards in one launch
         GX, dGX = ws["GX"], ws["dGX"]
         capi.dialogrnn_scan_bwd(GX, 2 * GXW, self.WT, fp.data, self.offs, D, ws["node_off"], ws["node_spk"], B, T, S, N, p_cell, p_emo,
@@ -252,26 +210,12 @@ class DialogRNNModule(nn.Module):
         return ws["stats"]
 
 
-class DialogRNNTrainer(TrainerBase):
+class DialogRNNTrainer(ConvEmotionTrainer):
     """train_step / to_logits for ``--module=dialogrnn``: class-weighted MaskedNLLLoss, Adam lr 3e-4, no weight decay (the
     defaults of the sibling plugin, track_mm/dgcnv2.py:22-48,184-219)."""
+    NAME = "dialogrnn"
 
-    def __init__(self, params, device):
-        self.params, self.device = params, torch.device(device)
-        compute = params.get("compute", "f32")
-        if compute != "f32":
-            raise capi.ErcGraftError("--module=dialogrnn runs in fp32 (the reference is fp32); --compute=%s is not supported" % compute)
-        self.class_weight = None
-        if params.get("loss_weights", True):
-            if params.n_classes != 6:
-                raise capi.ErcGraftError("--loss_weights uses the six hard-coded IEMOCAP-6 inverse frequencies "
-                                         "(dgcnv2.py:213-214); run %d-class datasets with --loss_weights=False" % params.n_classes)
-            self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
-        torch.manual_seed(params.seed)
-        self.model = DialogRNNModule(params.hidden_all, D_G, D_G, D_E, D_HID, n_classes=params.n_classes, context_attention="general",
-                                     dropout_rec=params.get("dropout_rec", 0.5), dropout=params.get("dropout", 0.5),
-                                     compute=compute, seed=params.seed).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
+    def _build_model(self, params, compute):
+        return DialogRNNModule(params.hidden_all, D_G, D_G, D_E, D_HID, n_classes=params.n_classes, context_attention="general",
+                               dropout_rec=params.get("dropout_rec", 0.5), dropout=params.get("dropout", 0.5),
+                               compute=compute, seed=params.seed)

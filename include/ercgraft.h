@@ -1257,17 +1257,29 @@ int erc_dgcnv2_edge_att_fwd(const float* S, int ldS, const int32_t* node_off, in
 int erc_dgcnv2_edge_att_bwd(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
                             const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* dnorm,
                             int dn_parts, int64_t dn_stride, float* dS, void* stream);
-/* Nodal attention, MatchingAttention 'general2' (dgcnv2_models.py:109-148) as attentive_node_features applies it
- * (:693-720), on compact rows (node_off[b] + t) of E [N, 300] = [features | conv2 output] and Q = E W^T + b (a GEMM by
- * the caller): A_t = sum_j p_tj E_j, p_tj = softmax_j(tanh(Q_t . E_j)) over the dialogue's valid rows.  P and TH
- * [B, T, T] save p and tanh for the backward.  The backward writes dQ [N, 300] and dE [N, 300] = P^T dA + dZ^T Q
- * (the caller adds dQ W), and DZ [B, T, T] (the gradient wrt the pre-tanh scores).  Row pitches >= 300, multiples of 4,
+
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Matching attention 'general2' (MatchingAttention, dgcnv2_models.py:109-148; csrc/match_att.hip) per dialogue over its
+ * valid rows, for row width F.  Built: F = 200 (= 2 D_e: LSTMModel / GRUModel / DialogRNNModel.forward apply it to every
+ * time step, :473-480) and F = 300 (attentive_node_features of the conv-emotion DialogueGCN over E = [features | conv2
+ * output], :693-720); any other F, or T > 110, gives ERC_E_ARG before anything is launched.  Rows are compact
+ * (node_off[b] + t); Q = E W^T + b is a GEMM by the caller: A_t = sum_j p_tj E_j, p_tj = softmax_j(tanh(Q_t . E_j)).
+ * P and TH [B, T, T] save p and tanh for the backward.  The backward writes dQ [N, F] and dE [N, F] = P^T dA + dZ^T Q
+ * (the caller adds dQ W), and DZ [B, T, T] (the gradient wrt the pre-tanh scores).  Row pitches >= F, multiples of 4,
  * 16-byte aligned.  Every element is summed by one thread in a fixed order. */
-int erc_dgcnv2_nodal_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T, float* A,
-                         int lda, float* P, float* TH, void* stream);
-int erc_dgcnv2_nodal_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
-                         int B, int T, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE, int ldde,
-                         void* stream);
+int erc_match_att_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T, int F, float* A,
+                      int lda, float* P, float* TH, void* stream);
+int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
+                      int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE, int ldde,
+                      void* stream);
+/* erc_match_att_bwd_cap (n_cap = 0: erc_match_att_bwd): CAPACITY mode -- dQ and dE hold n_cap rows of which the batch uses
+ * the first node_off[B]; the rows [node_off[B], n_cap) of both are written 0 by the same two launches, so the caller's
+ * weight-gradient products may run over all n_cap rows whatever a larger batch left there.  Built for F = 200 alone
+ * (a tail row is written one column per thread of the 256): n_cap > 0 with F = 300 gives ERC_E_ARG. */
+int erc_match_att_bwd_cap(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
+                          int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE,
+                          int ldde, int n_cap, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------------------------------
@@ -1322,20 +1334,6 @@ int erc_dialogrnn_scan_bwd(const float* GX, int ldgx, const float* WT, const flo
                            const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N, float drop_p,
                            float drop_rec, const uint64_t* rng_state, uint64_t rng_stream, const float* save,
                            const float* dEmo, int ldde, float* dGX, int lddgx, float* dREC, void* stream);
-/* MatchingAttention 'general2' (dgcnv2_models.py:127-138,147) as DialogRNNModel.forward applies it to every time step
- * (:473-480), per dialogue over its valid rows, for row width F (built: F = 200 = 2 D_e).  Operands, saved buffers and
- * gradients as erc_dgcnv2_nodal_fwd / _bwd, which stay the 300-wide form. */
-int erc_match_att_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T, int F, float* A,
-                      int lda, float* P, float* TH, void* stream);
-int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
-                      int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE, int ldde,
-                      void* stream);
-/* erc_match_att_bwd_cap (n_cap = 0: erc_match_att_bwd): CAPACITY mode -- dQ and dE hold n_cap rows of which the batch uses
- * the first node_off[B]; the rows [node_off[B], n_cap) of both are written 0 by the same two launches, so the caller's
- * weight-gradient products may run over all n_cap rows whatever a larger batch left there. */
-int erc_match_att_bwd_cap(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,
-                          int B, int T, int F, const float* P, const float* TH, float* DZ, float* dQ, int lddq, float* dE,
-                          int ldde, int n_cap, void* stream);
 /* bc-LSTM / bc-GRU (LSTMModel / GRUModel, dgcnv2_models.py:389-425 / :350-386) in CAPACITY mode: the index tables of a step
  * whose launches are sized for B dialogue slots (missing ones: length 0), T = T_cap and n_cap nodes, from lengths [B] (int64)
  * or, RESIDENT, from desc [2 B] (int32: lengths | first store rows).  Rows are time-major (t*B + b, batch_first=False).

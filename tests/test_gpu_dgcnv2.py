@@ -1,6 +1,6 @@
-"""GPU: the conv-emotion DialogueGCN (--module=dgcnv2) on libercgraft -- the positional edge attention and the nodal
-attention against CPU autograd, the whole module against the reference's own DGCNModule (golden vectors) and the CPU
-restatement, dropout, HIP-graph replay, checkpoints and the command line."""
+"""GPU: the conv-emotion DialogueGCN (--module=dgcnv2) on libercgraft -- the positional edge attention against CPU autograd
+(the nodal attention: tests/test_gpu_match_att.py), the whole module against the reference's own DGCNModule (golden
+vectors) and the CPU restatement, dropout, HIP-graph replay, checkpoints and the command line."""
 import json
 import os
 import subprocess
@@ -120,40 +120,6 @@ def test_edge_attention_matches_autograd(S):
     assert float(ref.view(T, B, 110)[lens[0]:, 0, :lens[0]].abs().max()) > 0       # padded rows do receive gradient
     with pytest.raises(capi.ErcGraftError):
         capi.dgcnv2_edge_att_fwd(Sd, 110, gr, B, 111, 10, 10, norm)
-
-
-# ----------------------------------------------------------------------------------------------------- nodal attention
-def test_nodal_attention_matches_autograd():
-    """erc_dgcnv2_nodal_fwd / _bwd against CPU autograd of softmax(tanh(Q E^T)) E per dialogue (lengths 1..110, ragged);
-    E enters as keys and values, Q as the queries"""
-    lens = [110, 1, 37, 64, 17, 2]
-    B, T, N = len(lens), max(lens), sum(lens)
-    g = torch.Generator().manual_seed(4)
-    E = (torch.randn(N, 300, generator=g) * 0.1).requires_grad_()
-    Q = (torch.randn(N, 300, generator=g) * 0.1).requires_grad_()
-    outs, off = [], 0
-    for L in lens:
-        e, q = E[off:off + L], Q[off:off + L]
-        outs.append(torch.softmax(torch.tanh(q @ e.t()), -1) @ e)
-        off += L
-    A_ref = torch.cat(outs)
-    G = torch.randn(N, 300, generator=g)
-    (A_ref * G).sum().backward()
-    node_off = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device=DEV)
-    f32 = lambda *s: torch.zeros(*s, device=DEV)
-    Ed, Qd, A = E.detach().to(DEV), Q.detach().to(DEV), f32(N, 300)
-    P, TH, DZ, dQ, dE = f32(B * T * T), f32(B * T * T), f32(B * T * T), f32(N, 300), f32(N, 300)
-    capi.dgcnv2_nodal_fwd(Ed, 300, Qd, 300, node_off, B, T, A, 300, P, TH)
-    capi.dgcnv2_nodal_bwd(Ed, 300, Qd, 300, G.to(DEV), 300, node_off, B, T, P, TH, DZ, dQ, 300, dE, 300)
-    torch.cuda.synchronize()
-    assert _err(A, A_ref.detach()) < 1e-5
-    assert _err(dQ, Q.grad) <= 1e-5 * (float(Q.grad.abs().max()) + 1e-6)
-    assert _err(dE, E.grad) <= 1e-5 * (float(E.grad.abs().max()) + 1e-6)
-    # a second run is bit-identical (fixed summation order, no atomics)
-    dE2 = f32(N, 300)
-    capi.dgcnv2_nodal_bwd(Ed, 300, Qd, 300, G.to(DEV), 300, node_off, B, T, P, TH, DZ, dQ, 300, dE2, 300)
-    torch.cuda.synchronize()
-    assert torch.equal(dE, dE2)
 
 
 # ----------------------------------------------------------------------------------------------------- whole module

@@ -1,5 +1,5 @@
 """GPU: the DialogueRNN model (--module=dialogrnn) on libercgraft -- the two scans against the float64 chain of the CPU
-restatement, the 200-wide matching attention against CPU autograd, the whole module against the reference's own
+restatement (the matching attention: tests/test_gpu_match_att.py), the whole module against the reference's own
 DialogRNNModel (golden vectors) and the restatement, dropout, HIP-graph replay, checkpoints and the command line."""
 import json
 import os
@@ -167,41 +167,6 @@ def test_scans_refuse_long_dialogues_before_launch():
     with pytest.raises(capi.ErcGraftError, match="n_speakers"):
         capi.dialogrnn_scan_fwd(GX, 2 * GXW, m.WT, m.flat.data, m.offs, 8, node_off, spk, 1, 110, 10, N, 0.0, 0.0, None, 0, E, 200, save)
     assert capi.dialogrnn_max_t() == 110
-
-
-# ----------------------------------------------------------------------------------------------------- matching attention
-def test_matching_attention_200_matches_autograd():
-    """erc_match_att_fwd / _bwd (width 200) against CPU autograd of softmax(tanh(Q E^T)) E per dialogue (lengths 1..110,
-    ragged); E enters as keys and values, Q as the queries"""
-    lens = [110, 1, 37, 64, 17, 2]
-    B, T, N = len(lens), max(lens), sum(lens)
-    g = torch.Generator().manual_seed(4)
-    E = (torch.randn(N, 200, generator=g) * 0.1).requires_grad_()
-    Q = (torch.randn(N, 200, generator=g) * 0.1).requires_grad_()
-    outs, off = [], 0
-    for L in lens:
-        e, q = E[off:off + L], Q[off:off + L]
-        outs.append(torch.softmax(torch.tanh(q @ e.t()), -1) @ e)
-        off += L
-    A_ref = torch.cat(outs)
-    G = torch.randn(N, 200, generator=g)
-    (A_ref * G).sum().backward()
-    node_off = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device=DEV)
-    f32 = lambda *s: torch.zeros(*s, device=DEV)
-    Ed, Qd, A = E.detach().to(DEV), Q.detach().to(DEV), f32(N, 200)
-    P, TH, DZ, dQ, dE = f32(B * T * T), f32(B * T * T), f32(B * T * T), f32(N, 200), f32(N, 200)
-    capi.match_att_fwd(Ed, 200, Qd, 200, node_off, B, T, 200, A, 200, P, TH)
-    capi.match_att_bwd(Ed, 200, Qd, 200, G.to(DEV), 200, node_off, B, T, 200, P, TH, DZ, dQ, 200, dE, 200)
-    torch.cuda.synchronize()
-    assert _err(A, A_ref.detach()) < 1e-5
-    assert _err(dQ, Q.grad) <= 1e-5 * (float(Q.grad.abs().max()) + 1e-6)
-    assert _err(dE, E.grad) <= 1e-5 * (float(E.grad.abs().max()) + 1e-6)
-    dE2 = f32(N, 200)
-    capi.match_att_bwd(Ed, 200, Qd, 200, G.to(DEV), 200, node_off, B, T, 200, P, TH, DZ, dQ, 200, dE2, 200)
-    torch.cuda.synchronize()
-    assert torch.equal(dE, dE2)
-    with pytest.raises(capi.ErcGraftError, match="200"):
-        capi.match_att_fwd(Ed, 200, Qd, 200, node_off, B, T, 300, A, 200, P, TH)
 
 
 # ----------------------------------------------------------------------------------------------------- whole module

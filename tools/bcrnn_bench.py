@@ -83,12 +83,13 @@ def gpu_time(cell, dataset, B, replays, warmup):
 
 def cpu_time(cell, params, batch, steps):
     from erc_amd import bcrnn
+    from erc_amd.capacity import IEMOCAP6_WEIGHTS
     from tests.bcrnn_oracle import forward
     torch.set_num_threads(16)
     m = (bcrnn.LSTMModule if cell == "lstm" else bcrnn.GRUModule)(params.hidden_all, 100, 100, n_classes=params.n_classes)
     P = {k: torch.nn.Parameter(v.detach().clone()) for k, v in m.state_dict().items()}
     opt = torch.optim.Adam(list(P.values()), lr=3e-4)
-    w = torch.tensor(bcrnn.IEMOCAP6_WEIGHTS)
+    w = torch.tensor(IEMOCAP6_WEIGHTS)
     times = []
     for _ in range(steps):
         t0 = time.perf_counter()

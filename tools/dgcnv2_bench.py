@@ -63,7 +63,8 @@ def gpu_time(B, replays, warmup):
 
 
 def cpu_time(params, batch, steps):
-    from erc_amd.dgcnv2 import DGCNModule, IEMOCAP6_WEIGHTS
+    from erc_amd.capacity import IEMOCAP6_WEIGHTS
+    from erc_amd.dgcnv2 import DGCNModule
     from tests.dgcnv2_oracle import DEAD, forward
     torch.set_num_threads(16)
     m = DGCNModule("LSTM", input_size=params.hidden_all, n_speakers=params.n_speakers, n_classes=params.n_classes)

@@ -76,7 +76,8 @@ def gpu_time(dataset, B, replays, warmup):
 
 
 def cpu_time(params, batch, steps):
-    from erc_amd.dialogrnn import DialogRNNModule, IEMOCAP6_WEIGHTS
+    from erc_amd.capacity import IEMOCAP6_WEIGHTS
+    from erc_amd.dialogrnn import DialogRNNModule
     from tests.dialogrnn_oracle import forward
     torch.set_num_threads(16)
     m = DialogRNNModule(params.hidden_all, 150, 150, 100, 100, n_classes=params.n_classes, context_attention="general")
