@@ -222,7 +222,8 @@ def test_fused_rgcn_forward_tile_vs_unfused_and_reference_golden(golden, name):
 def test_rgcn_kernels_with_windows_wider_than_a_wavefront(S):
     """Context +-40 over dialogues of up to 110 utterances: in / out degrees up to 81, i.e. more edges per node than the 64
     lanes that hold a window's metadata -- the second pass of the window loops of the tile kernels (and, for two speakers,
-    of the relation-space kernels) against the separate basis-space kernels."""
+    of the relation-space kernels) against the separate basis-space kernels.  Kernel against kernel: what every form shares
+    passes here; tests/test_gpu_dgcn_ops.py holds each of them, and EdgeAtt, to a float64 restatement at degrees 64, 65, 110, 130."""
     from erc_amd import capi
     from erc_amd.cogmen import build_graph_tensors
     torch.manual_seed(11 + S)
