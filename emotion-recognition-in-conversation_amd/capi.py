@@ -783,6 +783,62 @@ def axpy_mask(x, mask, n, scale, accumulate, y):
     _call("erc_axpy_mask", x, mask, n, scale, accumulate, y)
 
 
+# -- MMGCN in capacity mode (ercgraft.h): n_dev is the device int32 node count, n_cap the capacity the launch is sized for
+def mm_meta_cap(lengths, qmask, q_st, q_sb, S, desc, store_spk, store_label, zero_store_row, B, T, n_cap, node_off, node_row,
+                node_pad, node_dlg, node_spk, pad_node, x_row, label_out, counts):
+    """bucket form (lengths + padded qmask) or resident form (desc + the store's speaker ids [+ labels])"""
+    _call("erc_mm_meta_cap", lengths, qmask, q_st, q_sb, S, desc, store_spk, store_label, zero_store_row, B, T, n_cap, node_off,
+          node_row, node_pad, node_dlg, node_spk, pad_node, x_row, label_out, counts)
+
+
+def mm_flatten_cap(src, lds, row_map, emb, spk, n_cap, n_dev, dst, ldd):
+    _call("erc_mm_flatten_cap", src, lds, row_map, emb, spk, n_cap, n_dev, dst, ldd)
+
+
+def mm_emb_grad_cap(dl, ld, spk, n_cap, n_dev, S, demb, ws):
+    _call("erc_mm_emb_grad_cap", dl, ld, spk, n_cap, n_dev, S, demb, ws)
+
+
+def mm_row_normalize_cap(x, n_mod, n_cap, n_dev, xhat, inv):
+    _call("erc_mm_row_normalize_cap", x, n_mod, n_cap, n_dev, xhat, inv)
+
+
+def mm_row_normalize_bwd_cap(xhat, inv, dxhat, n_mod, n_cap, n_dev, dx):
+    _call("erc_mm_row_normalize_bwd_cap", xhat, inv, dxhat, n_mod, n_cap, n_dev, dx)
+
+
+def mm_cross_apply_cap(CR, h, ldh, node_dlg, node_off, M, n_cap, n_dev, P, out, ldo):
+    _call("erc_mm_cross_apply_cap", CR, h, ldh, node_dlg, node_off, M, n_cap, n_dev, P, out, ldo)
+
+
+def mm_cross_grad_cap(dhi, ldd, h, ldh, node_dlg, node_off, M, n_cap, n_dev, P, dCR, planes=1, d_plane=0, h_plane=0):
+    _call("erc_mm_cross_grad_cap", dhi, ldd, h, ldh, node_dlg, node_off, M, n_cap, n_dev, P, dCR, planes, d_plane, h_plane)
+
+
+def gcnii_combine_bwd_cap(d_hd, hd, n_mod, n_cap, n_dev, theta, alpha, keep_scale, plain, dG, dhi, dh0, F, ld_d=0):
+    _call("erc_gcnii_combine_bwd_cap", d_hd, hd, n_mod, n_cap, n_dev, theta, alpha, keep_scale, plain, dG, dhi, dh0, F, ld_d)
+
+
+def dropout_fwd_cap(x, n_mod, n_cap, n_dev, row_w, drop_p, rng, rng_stream, y):
+    _call("erc_dropout_fwd_cap", x, n_mod, n_cap, n_dev, row_w, drop_p, rng, rng_stream, y)
+
+
+def mm_regroup_fwd_cap(xd, hl, M, n_cap, n_dev, drop_p, rng, rng_stream, FE):
+    _call("erc_mm_regroup_fwd_cap", xd, hl, M, n_cap, n_dev, drop_p, rng, rng_stream, FE)
+
+
+def mm_regroup_bwd_cap(dFE, FE, M, n_cap, n_dev, keep_scale, d_xd, d_h):
+    _call("erc_mm_regroup_bwd_cap", dFE, FE, M, n_cap, n_dev, keep_scale, d_xd, d_h)
+
+
+def axpy_mask_cap(x, mask, n_mod, n_cap, n_dev, row_w, scale, accumulate, y):
+    _call("erc_axpy_mask_cap", x, mask, n_mod, n_cap, n_dev, row_w, scale, accumulate, y)
+
+
+def mm_zero_tail(buf, ld, width, n_mod, n_cap, n_dev):
+    _call("erc_mm_zero_tail", buf, ld, width, n_mod, n_cap, n_dev)
+
+
 def clock_probe(out, iters):
     _call("erc_clock_probe", out, iters)
 

@@ -1183,6 +1183,67 @@ int erc_mm_regroup_bwd(const float* dFE, const float* FE, int M, int N, float ke
                        void* stream);
 /* y (+)= scale * x, optionally masked by mask != 0 */
 int erc_axpy_mask(const float* x, const float* mask, int64_t n, float scale, int accumulate, float* y, void* stream);
+/* MMGCN in CAPACITY mode (MMGCNModule.dynamic_n; one captured step serves every batch that fits its bucket): the launches are
+ * sized for B dialogue slots (missing ones: length 0), T = T_cap and n_cap nodes per modality; the batch's own node count n and
+ * longest dialogue are read on the device.  Modality m's rows start at m * n_cap; rows [m * n_cap + n, (m + 1) * n_cap) are TAIL
+ * rows.  Invariant of the step: a tail row's content is finite, and no tail row contributes to the loss, to a weight, bias,
+ * embedding or adjacency gradient, or to the confusion matrix; the gradient-side tail rows are exactly zero.
+ *
+ * erc_mm_meta_cap: the node tables, from lengths [B] (int64) + the padded time-major one-hot qmask (BUCKET form: desc,
+ * store_spk, store_label, x_row, label_out NULL) or from desc [2 B] (int32: lengths | first store rows) + the store's flat
+ * speaker ids (RESIDENT form: lengths, qmask NULL; store_label / label_out optional, together).  Lengths are clamped to
+ * [0, T] and to what n_cap still holds.
+ *   node_off [B+1]; per node i = node_off[b] + t < n: node_pad[i] = t*B + b (its row of the padded [T,B,.] blocks), node_row[i]
+ *   = the row its features are gathered from (bucket: t*B + b; resident: store row first[b] + t), node_dlg[i] = b, node_spk[i]
+ *   = argmax of its qmask row (resident: the store's id, clamped to [0, n_speakers)), label_out[i] = its store label.
+ *   Tail entries n <= i < n_cap: node_row = a row that is valid to read (bucket: 0; resident: zero_store_row), node_pad = 0,
+ *   node_dlg = 0, node_spk = 0, label_out = 0.
+ *   pad_node [B*T]: the node of padded row t*B + b, n_cap where t >= length (a zero row the caller keeps behind the text
+ *   modality's node gradient); x_row [B*T] (resident): the store row first[b] + t of padded row t*B + b, zero_store_row where
+ *   t >= length -- the text branch's layer-0 Linear gathers straight from the store through it.
+ *   counts[0] = n (n_dev), counts[1] = the longest dialogue of the batch (t_dev).  B <= 1024. */
+int erc_mm_meta_cap(const int64_t* lengths, const float* qmask, int64_t q_st, int64_t q_sb, int n_speakers, const int32_t* desc,
+                    const int64_t* store_spk, const int64_t* store_label, int zero_store_row, int B, int T, int n_cap,
+                    int32_t* node_off, int32_t* node_row, int32_t* node_pad, int32_t* node_dlg, int32_t* node_spk,
+                    int32_t* pad_node, int32_t* x_row, int64_t* label_out, int32_t* counts, void* stream);
+/* The row operators' capacity instances: n = *n_dev clamped to [0, n_cap]; what they compute on the rows < n of every modality
+ * is what the plain entry point computes (same arithmetic, same order; the dropout counter is the element index in the
+ * capacity-sized buffer).  Tail rows are never read as data:
+ *   erc_mm_flatten_cap            dst tail rows = 0
+ *   erc_mm_emb_grad_cap           the sums run over the rows < n
+ *   erc_mm_row_normalize_cap      xhat = 0 and inv = 0 on tail rows (x [n_mod * n_cap, 200])
+ *   erc_mm_row_normalize_bwd_cap  dx tail rows are WRITTEN 0 (rows < n: accumulated into, as the plain form)
+ *   erc_mm_cross_apply_cap / erc_mm_cross_grad_cap   tail rows are skipped (their sentinel dialogue owns no adjacency entry)
+ *   erc_gcnii_combine_bwd_cap     dG (and dhi) tail rows = 0, nothing added to dh0 (rows of F columns, n_mod * n_cap of them)
+ *   erc_dropout_fwd_cap           y tail rows = 0 (rows of row_w columns)
+ *   erc_mm_regroup_fwd_cap / erc_mm_regroup_bwd_cap   FE / d_xd / d_h tail rows = 0
+ *   erc_axpy_mask_cap             y tail rows are WRITTEN 0, accumulating or not */
+int erc_mm_flatten_cap(const float* src, int lds, const int32_t* row_map, const float* emb, const int32_t* spk, int n_cap,
+                       const int32_t* n_dev, float* dst, int ldd, void* stream);
+int erc_mm_emb_grad_cap(const float* dl, int ld, const int32_t* spk, int n_cap, const int32_t* n_dev, int n_speakers, float* demb,
+                        float* ws, void* stream);
+int erc_mm_row_normalize_cap(const float* x, int n_mod, int n_cap, const int32_t* n_dev, float* xhat, float* inv, void* stream);
+int erc_mm_row_normalize_bwd_cap(const float* xhat, const float* inv, const float* dxhat, int n_mod, int n_cap,
+                                 const int32_t* n_dev, float* dx, void* stream);
+int erc_mm_cross_apply_cap(const float* CR, const float* h, int ldh, const int32_t* node_dlg, const int32_t* node_off, int M,
+                           int n_cap, const int32_t* n_dev, int P, float* out, int ldo, void* stream);
+int erc_mm_cross_grad_cap(const float* dhi, int ldd, const float* h, int ldh, const int32_t* node_dlg, const int32_t* node_off,
+                          int M, int n_cap, const int32_t* n_dev, int P, float* dCR, int planes, int64_t d_plane,
+                          int64_t h_plane, void* stream);
+int erc_gcnii_combine_bwd_cap(const float* d_hd, const float* hd, int n_mod, int n_cap, const int32_t* n_dev, float theta,
+                              float alpha, float keep_scale, int plain, float* dG, float* dhi, float* dh0, int F, int ld_d,
+                              void* stream);
+int erc_dropout_fwd_cap(const float* x, int n_mod, int n_cap, const int32_t* n_dev, int row_w, float drop_p,
+                        const uint64_t* rng_state, uint64_t rng_stream, float* y, void* stream);
+int erc_mm_regroup_fwd_cap(const float* xd, const float* hl, int M, int n_cap, const int32_t* n_dev, float drop_p,
+                           const uint64_t* rng_state, uint64_t rng_stream, float* FE, void* stream);
+int erc_mm_regroup_bwd_cap(const float* dFE, const float* FE, int M, int n_cap, const int32_t* n_dev, float keep_scale,
+                           float* d_xd, float* d_h, void* stream);
+int erc_axpy_mask_cap(const float* x, const float* mask, int n_mod, int n_cap, const int32_t* n_dev, int row_w, float scale,
+                      int accumulate, float* y, void* stream);
+/* buf[m * n_cap + i, 0 .. width) = 0 for n <= i < n_cap, m < n_mod (row pitch ld): the tail rows of a buffer whose valid rows
+ * are written by a kernel that walks the dialogues through node_off (the GCNII chain's DG / DZ, the grouped products) */
+int erc_mm_zero_tail(float* buf, int64_t ld, int width, int n_mod, int n_cap, const int32_t* n_dev, void* stream);
 
 
 /* ------------------------------------------------------------------------

@@ -14,6 +14,9 @@ class MMGCNParams(ERCParams):
         self.dataset = "iemocap-cogmen-6"
         self.optim = Group(name="Adam", lr=0.0003, weight_decay=3e-5)          # mmgcn.py:34
         self.speaker_onehot, self.batch_first = True, False                    # mmgcn.py:39-40
+        # capacity buckets (one captured graph per (B_cap, T_cap, N_cap) instead of per exact shape) are opt-in here:
+        # --capacity_buckets=True, or --resident (with --device_collate), which implies them; --resident_eval with --resident
+        self.capacity_buckets = False
 
     def iparams(self):
         super().iparams()
