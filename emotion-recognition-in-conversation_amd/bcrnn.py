@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import CapacityBuckets, ConvEmotionTrainer, bucket_sizes
+from .capacity import CapacityBuckets, ConvEmotionTrainer, ZeroRowStores
 from .engine import WorkspaceCache, FlatParams, GemmPlanner
 from .matchhead import ConvEmotionModule, MatchAttHead, Transform
 from .rnn import BiGRU2, BiLSTM2, gru_groups, lstm_groups
@@ -217,19 +217,21 @@ class BcRnnTrainer(CapacityBuckets, ConvEmotionTrainer):
     MODULE = None
 
     def __init__(self, params, device):
-        super().__init__(params, device)
-        # capacity buckets are opt-in (--capacity_buckets=True; --resident implies them): the default stays the exact-shape
-        # step, whose dropout masks (keyed by the element index, so by B) a captured exact-shape graph must reproduce
-        self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
-        self._store_ext = None
+        # capacity buckets are opt-in: the default stays the exact-shape step, whose dropout masks (keyed by the element
+        # index, so by B) a captured exact-shape graph must reproduce
+        super().__init__(params, device, opt_in=True)
+        self._store_ext = ZeroRowStores()
 
     def _build_model(self, params, compute):
         return self.MODULE(params.hidden_all, D_E, D_HID, n_classes=params.n_classes, dropout=params.get("dropout", 0.5),
                            compute=compute, seed=params.seed)
 
     # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  N_BUCKET 128 and "a batch of exactly its
-    #    bucket's shape stays exact" are the mixin's defaults; ``self.capacity`` (set above) makes the buckets opt-in
+    #    bucket's shape stays exact" are the mixin's defaults, and so is the precapture list, built from train.batch_size
+    #    and T_cap alone; ``opt_in=True`` (above) makes the buckets opt-in
     TIME_MAJOR = True          # [T, B, D] features, [T, B, S] one-hot speakers
+    CLEAR_STALE = True         # the RNN is unpacked: it READS the padded rows t < T_eff of every dialogue slot, so they must
+    #                            be zero, not stale
 
     def _capacity_ok(self, B_cap, T_cap, N_cap, batch=None):
         """no bucket with the flag off, with the peer-to-peer exchange, above the matching attention's T or the head's classes,
@@ -241,56 +243,13 @@ class BcRnnTrainer(CapacityBuckets, ConvEmotionTrainer):
                   batch["text_length"].dtype == torch.int64)
         return bool(ok)
 
-    def _bucket(self, like, B_cap, T_cap, N_cap):
-        x, spk, dev = like["input_tensor"], like["speaker_tensor"], self.device
-        D, S = int(x.shape[2]), int(spk.shape[2])
-
-        def make():
-            # "extent" (host side): the [T, B, N] block the last batch occupied -- all that fill has to clear
-            return dict(input_tensor=torch.zeros(T_cap, B_cap, D, dtype=x.dtype, device=dev),
-                        speaker_tensor=torch.zeros(T_cap, B_cap, S, dtype=spk.dtype, device=dev),
-                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
-                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev), extent=[0, 0, 0])
-
-        def fill(static, b):
-            # the RNN is unpacked: it READS the padded rows t < T_eff of every dialogue slot, so they must be zero, not stale.
-            # Only what the previous batch occupied and this one does not cover is cleared (never the whole capacity buffer).
-            Tb, Bb = (int(v) for v in b["input_tensor"].shape[:2])
-            Nb = int(b["label"].shape[0])
-            Tp, Bp, Np = static["extent"]
-            for k in ("input_tensor", "speaker_tensor"):
-                static[k][:Tb, :Bb].copy_(b[k], non_blocking=True)
-                if Tp > Tb:
-                    static[k][Tb:Tp, :Bp].zero_()
-                if Bp > Bb:
-                    static[k][:min(Tb, Tp), Bb:Bp].zero_()
-            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
-            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
-            static["label"][:Nb].copy_(b["label"], non_blocking=True)
-            if Np > Nb:
-                static["label"][Nb:Np].zero_()
-            static["extent"][:] = [Tb, Bb, Nb]
-
-        return ("capacity", B_cap, T_cap, N_cap), make, fill
-
-    def _precapture_caps(self, batch):
-        # built from train.batch_size and T_cap (trainer.bucket_t_cap) ALONE, never from the probe batch's shape (the other two
-        # trainers go through the probe); the list includes the clipped top bucket B_cap * T_cap
-        B_cap, T_cap = int(self.params.train.batch_size), int(getattr(self, "t_cap", 0))
-        if not self._capacity_ok(B_cap, T_cap, self.N_BUCKET, batch):
-            return None
-        return B_cap, T_cap, bucket_sizes(self.N_BUCKET, B_cap * T_cap)
-
     def _resident_ok(self, store, B_cap, T_cap, N_cap):
         return store.fused.dtype == torch.float32 and int(store.fused.shape[1]) == self.model.D_m and self._capacity_ok(B_cap, T_cap, N_cap)
 
     def _resident_inputs(self, store):
         """The layer-0 projection reads the store's rows through the step's row map; padded positions read a zero row, which
         the store does not have, so the features are kept once per store with one appended.  No speakers: the model reads none."""
-        if self._store_ext is None or self._store_ext[0] is not store:
-            self._store_ext = (store, torch.cat([store.fused, torch.zeros(1, self.model.D_m, dtype=torch.float32,
-                                                                            device=store.fused.device)]))
-        return self._store_ext[1], None
+        return self._store_ext(store, store.fused), None
 
 
 class BcLstmTrainer(BcRnnTrainer):

@@ -21,7 +21,7 @@ from torch import nn
 
 from . import capi
 from .capacity import TrainerBase
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, linear_fwd, linear_wgrad
 
 H = 200
 MODS = ("a", "v", "t")          # order of the dense block of merged (cim.py:165-172): dense_a, dense_v, dense_t
@@ -251,6 +251,7 @@ class CIMTrainer(TrainerBase):
     (apply_bin), plus the 7-way BCE on logits7 when apply_multi (CMU-MOSEI only, cim.py:52-53); torch.optim.Adam(lr)
     without clipping or weight decay.  apply_bin=False is refused: the reference's cls2 would then get neither a gradient
     nor Adam state, a layout this port does not build."""
+    CLASS_WEIGHTED = False
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -268,18 +269,8 @@ class CIMTrainer(TrainerBase):
         self.model = CIMModule(text_dim=params.hidden_text, audio_dim=params.hidden_audio, visual_dim=params.hidden_visual,
                                hidden_size=H, n_classes=params.n_classes, seed=params.seed,
                                multitask=self.multitask).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
+        self._make_optim()
 
     def to_mosei_multitask_logits(self, batch):
         """(logits2 [N, C], logits7 [N, 7]) (mmbase.py:144, cim.py:190-191)"""
         return self.model(**batch)
-
-    def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
-        self.model.train()
-        stats = self.model.loss_and_grads(batch)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats

@@ -26,8 +26,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import CapacityBuckets, TrainerBase
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, all_reduce_grads, linear_fwd, linear_wgrad, \
+from .capacity import CapacityBuckets, ResidentEvalSteps, TrainerBase
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, SideStream, all_reduce_grads, linear_fwd, linear_wgrad, \
     matmul_wgrad_io
 
 F_HID = 100
@@ -741,7 +741,7 @@ def build_graph_tensors(text_length, speaker_tensor, wp, wf, n_speakers, n_nodes
     return g, ei, et
 
 
-class COGMENTrainer(CapacityBuckets, TrainerBase):
+class COGMENTrainer(CapacityBuckets, ResidentEvalSteps, TrainerBase):
     """train_step / to_logits of track_mm/cogmen.py:163-195 without lumo."""
     BF16_INPUT = True
 
@@ -753,11 +753,9 @@ class COGMENTrainer(CapacityBuckets, TrainerBase):
                                   n_classes=params.n_classes, compute=params.get("compute", "f32"),
                                   seed=params.seed,
                                   chained_encoder=params.get("chained_encoder", False)).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.weight_decay,
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state   # dropout offset advances with the optimizer step
-        self.optim.skip_flag = self.model.flat.health  # (nothing in this step raises it; StepGraphs.precapture's warm-ups do)
+        # --optim.weight_decay is required; the health word gates the update (nothing in this step raises it;
+        # StepGraphs.precapture's warm-ups do)
+        self._make_optim(weight_decay=None, health_gates=True)
         self.optim.enable_p2p()                        # ERC_DP_P2P=1 under torch.distributed: exchange fused into the optimizer
         import os
         if os.environ.get("ERC_FUSE_ADAM", "1") != "0" and self.model.enc_train is None:
@@ -804,16 +802,6 @@ class COGMENTrainer(CapacityBuckets, TrainerBase):
         probe = dict(input_tensor=store.fused.view(1, -1, D), speaker_tensor=store.speaker[None, :1])
         return (store.fused.dtype == (torch.float32 if self.model.terms > 1 else torch.bfloat16) and
                 self._capacity_ok(B_cap, T_cap, N_cap, probe))
-
-    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
-        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
-        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
-
-    def resident_eval_step(self, batch, cm):
-        """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
-        sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
-        return self.model.eval_scores(batch, cm)
 
     def train_step(self, batch):
         """forward + CE + backward + (DP all-reduce) + Adam.  Returns the device stats tensor."""

@@ -22,8 +22,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import CapacityBuckets, TrainerBase
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, all_reduce_grads, linear_fwd, linear_wgrad
+from .capacity import CapacityBuckets, ResidentEvalSteps, TrainerBase, ZeroRowStores
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, linear_fwd, linear_wgrad
 
 HID = 300
 MAX_T = 1021           # the recurrence's limit on the padded length (csrc/dag_rec.hip MAX_T: erc_dag_meta, erc_dag_rec_config)
@@ -378,14 +378,19 @@ class DAGERCModule(nn.Module):
         return ws["stats"]
 
 
-class DAGERCTrainer(CapacityBuckets, TrainerBase):
+class DAGERCTrainer(CapacityBuckets, ResidentEvalSteps, TrainerBase):
     """train_step / to_logits of track_mm/dagerc.py:201-237 (masked CE, clip_grad_norm_ 5, AdamW)."""
     BF16_INPUT = True
+    CLASS_WEIGHTED = False
     # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  No launch of the step scales with N, so
     #    there is ONE node capacity per (B_cap, T_cap): N_cap = B_cap * T_cap (node_capacity clips the rounded count there).
     #    trainer.ResidentLoop takes the same bucket, so a run holds one training graph and one evaluation graph.
     N_BUCKET = 1 << 30
     RESIDENT_N_BUCKET = N_BUCKET
+    # the plugin's layout, batch-first: one-hot speakers [B, T, S] (ids [B, T] are taken too).  The step computes every padded
+    # row (finite garbage there is harmless: it meets a zero gradient row), but a row the batch does not own should not depend
+    # on an earlier batch
+    CLEAR_STALE = True
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -393,70 +398,15 @@ class DAGERCTrainer(CapacityBuckets, TrainerBase):
         self.model = DAGERCModule(emb_dim=params.hidden_all, dropout=params.get("dropout", 0),
                                   n_classes=params.n_classes, gnn_layers=params.get("gnn_layers", 4),
                                   compute=params.get("compute", "f32"), seed=params.seed).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 1e-2),
-                               decoupled=(o.name == "AdamW"), clip_norm=5.0, seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
-        self.optim.skip_flag = self.model.flat.health    # a recurrence exchange timed out (on any rank) -> the update is skipped
-        # capacity buckets are opt-in (--capacity_buckets=True; --resident implies them): the default stays the exact-shape
-        # step, whose dropout masks (keyed by the element index, so by T) a capacity-sized step does not reproduce
-        self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
-        self._store_ext = None
-
-    def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
-        self.model.train()
-        stats = self.model.loss_and_grads(batch)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats
+        # health_gates: a recurrence exchange timed out (on any rank) -> the update is skipped
+        self._make_optim(weight_decay=1e-2, clip_norm=5.0, health_gates=True, opt_in=True)
+        self._store_ext = ZeroRowStores()
 
     def _capacity_ok(self, B_cap, T_cap, N_cap, batch=None):
         """no bucket with the flag off, with the peer-to-peer exchange, beyond the recurrence's T or its 4096 dialogue groups,
         with more classes than the scoring kernel counts, or for a batch of another dtype than the compute mode's"""
         return bool(self.capacity and not self._p2p() and 0 < T_cap <= MAX_T and 0 < B_cap <= MAX_B and
                     0 < N_cap <= B_cap * T_cap and self.model.supports_capacity(batch))
-
-    def _bucket(self, like, B_cap, T_cap, N_cap):
-        """the plugin's layout: one-hot speakers [B, T, S] (ids [B, T] are taken too)"""
-        x, spk, dev = like["input_tensor"], like["speaker_tensor"], self.device
-        D = int(x.shape[2])
-
-        def make():
-            # "extent" (host side): the [B, T, N] block the last batch occupied -- all that fill has to clear
-            return dict(input_tensor=torch.zeros(B_cap, T_cap, D, dtype=x.dtype, device=dev),
-                        speaker_tensor=torch.zeros((B_cap, T_cap) + tuple(spk.shape[2:]), dtype=spk.dtype, device=dev),
-                        text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
-                        label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev), extent=[0, 0, 0])
-
-        def fill(static, b):
-            # the step computes every padded row (finite garbage there is harmless: it meets a zero gradient row), but a row
-            # the batch does not own should not depend on an earlier batch: what the previous one occupied and this one does
-            # not cover is cleared (never the whole capacity buffer)
-            Bb, Tb = (int(v) for v in b["input_tensor"].shape[:2])
-            Nb = int(b["label"].shape[0])
-            Bp, Tp, Np = static["extent"]
-            for k in ("input_tensor", "speaker_tensor"):
-                static[k][:Bb, :Tb].copy_(b[k], non_blocking=True)
-                if Tp > Tb:
-                    static[k][:Bp, Tb:Tp].zero_()
-                if Bp > Bb:
-                    static[k][Bb:Bp, :min(Tb, Tp)].zero_()
-            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
-            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
-            static["label"][:Nb].copy_(b["label"], non_blocking=True)
-            if Np > Nb:
-                static["label"][Nb:Np].zero_()
-            static["extent"][:] = [Bb, Tb, Nb]
-
-        return ("capacity", B_cap, T_cap, N_cap), make, fill
-
-    def _precapture_caps(self, batch):
-        # built from train.batch_size and T_cap (trainer.bucket_t_cap) ALONE, never from the probe batch's shape: every rank
-        # captures the same one-element list
-        B_cap, T_cap = int(self.params.train.batch_size), int(getattr(self, "t_cap", 0))
-        if not self._capacity_ok(B_cap, T_cap, B_cap * T_cap, batch):
-            return None
-        return B_cap, T_cap, [B_cap * T_cap]
 
     def _resident_ok(self, store, B_cap, T_cap, N_cap):
         want = torch.bfloat16 if self.model.compute == "bf16" else torch.float32
@@ -467,17 +417,4 @@ class DAGERCTrainer(CapacityBuckets, TrainerBase):
         """fc1, the raw-feature block of out_mlp.0 and their weight gradients read the store's rows through the step's row map;
         padded positions read a zero row, which the store does not have, so the features are kept once per store with one
         appended.  The speakers are the store's flat ids."""
-        if self._store_ext is None or self._store_ext[0] is not store:
-            self._store_ext = (store, torch.cat([store.fused, torch.zeros(1, self.model.emb_dim, dtype=store.fused.dtype,
-                                                                            device=store.fused.device)]))
-        return self._store_ext[1], store.speaker
-
-    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
-        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
-        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
-
-    def resident_eval_step(self, batch, cm):
-        """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
-        sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
-        return self.model.eval_scores(batch, cm)
+        return self._store_ext(store, store.fused), store.speaker

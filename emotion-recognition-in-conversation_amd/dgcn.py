@@ -12,8 +12,9 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import IEMOCAP6_WEIGHTS, CapacityBuckets, TrainerBase, bucket_sizes
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, linear_fwd, linear_wgrad, \
+from .capacity import IEMOCAP6_WEIGHTS  # noqa: F401  (the tests read the weights from here)
+from .capacity import CapacityBuckets, ResidentEvalSteps, TrainerBase, bucket_sizes, iemocap6_class_weight
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, SideStream, linear_fwd, linear_wgrad, \
     matmul_wgrad_io
 from .rnn import BiLSTM2, lstm_groups
 
@@ -429,7 +430,7 @@ class DGCNModule(nn.Module):
         return ws["stats"]
 
 
-class DGCNTrainer(CapacityBuckets, TrainerBase):
+class DGCNTrainer(CapacityBuckets, ResidentEvalSteps, TrainerBase):
     """train_step / to_logits of track_mm/dgcn.py:96-134 (class-weighted CE, Adam lr 3e-4)."""
     BF16_INPUT = True
 
@@ -445,16 +446,8 @@ class DGCNTrainer(CapacityBuckets, TrainerBase):
                 raise ValueError("--relation_space=True: %d relations, the relation-space kernels hold at most %d"
                                  % (self.model.R, capi.rrgcn_max_relations()))
             self.model.relation_space = bool(rs)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
-        self.class_weight = None
-        if params.get("loss_weights", True):
-            if params.n_classes != 6:
-                raise ValueError("--loss_weights uses the six hard-coded IEMOCAP-6 inverse frequencies "
-                                 "(dgcn.py:109-110); run %d-class datasets with --loss_weights=False" % params.n_classes)
-            self.class_weight = torch.tensor(IEMOCAP6_WEIGHTS, dtype=torch.float32, device=self.device)
+        self._make_optim()
+        self.class_weight = iemocap6_class_weight(params, self.device, ValueError, "dgcn.py:109-110")
 
     # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets).  N_BUCKET 128, batch-first, a batch of
     #    exactly its bucket's shape stays on the exact-shape path: the mixin's defaults
@@ -474,13 +467,3 @@ class DGCNTrainer(CapacityBuckets, TrainerBase):
     def _resident_ok(self, store, B_cap, T_cap, N_cap):
         want = torch.bfloat16 if self.model.compute == "bf16" else torch.float32
         return store.fused.dtype == want and store.fused.shape[1] == self.model.input_size and self._capacity_ok(B_cap, T_cap, N_cap)
-
-    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
-        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
-        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
-
-    def resident_eval_step(self, batch, cm):
-        """one forward-only step scored on the device: adds the batch's confusion matrix to ``cm`` (int64 [C, C]); no host
-        sync.  Returns the step's buffers (the caller of a captured step keeps them alive)."""
-        return self.model.eval_scores(batch, cm)

@@ -18,8 +18,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .capacity import CapacityBuckets, TrainerBase, bucket_sizes
-from .engine import WorkspaceCache, FlatParams, FusedAdam, GemmPlanner, SideStream, all_reduce_grads, linear_fwd, linear_wgrad, \
+from .capacity import CapacityBuckets, ResidentEvalSteps, TrainerBase, ZeroRowStores
+from .engine import WorkspaceCache, FlatParams, GemmPlanner, SideStream, linear_fwd, linear_wgrad, \
     matmul_wgrad_io
 from .rnn import BiLSTM2, lstm_groups
 
@@ -609,12 +609,15 @@ class MMGCNModule(nn.Module):
         return ws["stats"]
 
 
-class MMGCNTrainer(CapacityBuckets, TrainerBase):
+class MMGCNTrainer(CapacityBuckets, ResidentEvalSteps, TrainerBase):
     """train_step / to_logits of track_mm/mmgcn.py:126-157 (CE, Adam lr 3e-4 wd 3e-5)."""
     # -- capacity mode: the policy (the implementation is capacity.CapacityBuckets; the table in DESIGN.md).  Opt-in
     #    (--capacity_buckets=True; --resident implies it): the default stays the exact-shape step.  The node launches (the
     #    Linear / GCNII products over Mo * N rows, Call = h0 U at 12 800 columns) scale with N_cap: N_BUCKET 128, as elsewhere.
+    CLASS_WEIGHTED = False
     TIME_MAJOR = True          # [T, B, d_m] feature blocks per modality, [T, B, S] one-hot speakers
+    CLEAR_STALE = True         # the text branch's BiLSTM is unpacked: it READS the padded rows t < T_eff of every dialogue
+    #                            slot, which the reference pads with zeros
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -622,24 +625,14 @@ class MMGCNTrainer(CapacityBuckets, TrainerBase):
         self.model = MMGCNModule(hidden_text=params.hidden_text, hidden_visual=params.hidden_visual,
                                  hidden_audio=params.hidden_audio, n_speakers=params.n_speakers,
                                  n_classes=params.n_classes, modals=params.modality, seed=params.seed).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0),
-                               decoupled=(o.name == "AdamW"), seed=params.seed)
-        self.model.rng_state = self.optim.rng_state
-        self.optim.skip_flag = self.model.flat.health    # a chain exchange timed out (on any rank) -> the update is skipped
-        self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
-        self._store_ext = {}
+        self._make_optim(health_gates=True, opt_in=True)      # a chain exchange timed out (on any rank) -> the update is skipped
+        self._store_ext = ZeroRowStores()
 
-    def train_step(self, batch):      # (TrainerBase's step passes a class weight; this loss takes none)
-        self.model.train()
-        stats = self.model.loss_and_grads(batch)
-        scale = all_reduce_grads(self.model.flat)
-        self.optim.step(grad_scale=scale)
-        return stats
+    def _feature_keys(self):
+        return tuple(_KEY[m] for m in self.model.order)
 
-    def _bt(self, batch):
-        T, B = batch["speaker_tensor"].shape[:2]
-        return int(B), int(T)
+    def _absent_keys(self):
+        return tuple(k for k in _KEY.values() if k not in self._feature_keys())
 
     def _capacity_ok(self, B_cap, T_cap, N_cap, batch=None):
         """no bucket with the flag off; where the one-launch chain is off (ERC_MM_CHAIN=0, T_cap > 128) or B_cap * modalities
@@ -653,49 +646,6 @@ class MMGCNTrainer(CapacityBuckets, TrainerBase):
                     int(batch[_KEY[m]].shape[2]) == self.model.dims[m] for m in self.model.order)
         return bool(ok)
 
-    def _bucket(self, like, B_cap, T_cap, N_cap):
-        """the plugin's layout, time-major: one feature block per modality, one-hot speakers, lengths, labels"""
-        spk, dev, keys = like["speaker_tensor"], self.device, [_KEY[m] for m in self.model.order]
-        S = int(spk.shape[2])
-
-        def make():
-            # "extent" (host side): the [T, B, N] block the last batch occupied -- all that fill has to clear
-            static = {k: torch.zeros(T_cap, B_cap, int(like[k].shape[2]), dtype=like[k].dtype, device=dev) for k in keys}
-            static.update({k: None for k in _KEY.values() if k not in keys})
-            static.update(speaker_tensor=torch.zeros(T_cap, B_cap, S, dtype=spk.dtype, device=dev),
-                          text_length=torch.zeros(B_cap, dtype=like["text_length"].dtype, device=dev),
-                          label=torch.zeros(N_cap, dtype=like["label"].dtype, device=dev), extent=[0, 0, 0])
-            return static
-
-        def fill(static, b):
-            # the text branch's BiLSTM is unpacked: it READS the padded rows t < T_eff of every dialogue slot, which the
-            # reference pads with zeros.  Only what the previous batch occupied and this one does not cover is cleared.
-            Tb, Bb = (int(v) for v in b["speaker_tensor"].shape[:2])
-            Nb = int(b["label"].shape[0])
-            Tp, Bp, Np = static["extent"]
-            for k in keys + ["speaker_tensor"]:
-                static[k][:Tb, :Bb].copy_(b[k], non_blocking=True)
-                if Tp > Tb:
-                    static[k][Tb:Tp, :Bp].zero_()
-                if Bp > Bb:
-                    static[k][:min(Tb, Tp), Bb:Bp].zero_()
-            static["text_length"].zero_()                     # dialogues the batch does not have: length 0
-            static["text_length"][:Bb].copy_(b["text_length"], non_blocking=True)
-            static["label"][:Nb].copy_(b["label"], non_blocking=True)
-            if Np > Nb:
-                static["label"][Nb:Np].zero_()
-            static["extent"][:] = [Tb, Bb, Nb]
-
-        return ("capacity", B_cap, T_cap, N_cap), make, fill
-
-    def _precapture_caps(self, batch):
-        # built from train.batch_size and T_cap (trainer.bucket_t_cap) ALONE, never from the probe batch's shape: every rank
-        # captures the same list, smallest first, the clipped top bucket B_cap * T_cap included
-        B_cap, T_cap = int(self.params.train.batch_size), int(getattr(self, "t_cap", 0))
-        if not self._capacity_ok(B_cap, T_cap, min(self.N_BUCKET, B_cap * T_cap), batch):
-            return None
-        return B_cap, T_cap, bucket_sizes(self.N_BUCKET, B_cap * T_cap)
-
     def _resident_ok(self, store, B_cap, T_cap, N_cap):
         return all(m in store.feats and store.feats[m].dtype == torch.float32 and
                    int(store.feats[m].shape[1]) == self.model.dims[m] for m in self.model.order) and \
@@ -704,12 +654,7 @@ class MMGCNTrainer(CapacityBuckets, TrainerBase):
     def _resident_inputs(self, store):
         """The Linear layers read the store's rows through the step's row maps; tail nodes and padded positions read a zero
         row, which the stores do not have, so each modality's features are kept once per store with one appended."""
-        ent = self._store_ext.get(id(store))
-        if ent is None or ent[0] is not store:
-            zero = lambda x: torch.zeros(1, x.shape[1], dtype=x.dtype, device=x.device)
-            ent = self._store_ext[id(store)] = (store, {m: torch.cat([store.feats[m], zero(store.feats[m])])
-                                                        for m in self.model.order})
-        return ent[1], store.speaker
+        return self._store_ext(store, {m: store.feats[m] for m in self.model.order}), store.speaker
 
     def resident_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
         """trainer.ResidentEpochs: the "batch" of a step whose dialogues stay in the HBM-resident store -- the per-modality
@@ -722,14 +667,3 @@ class MMGCNTrainer(CapacityBuckets, TrainerBase):
         batch.update({_KEY[m]: feats[m] for m in self.model.order})
         batch.update(speaker_tensor=spk, text_length=None, label=store.label, desc=cur_desc, caps=(B_cap, T_cap, N_cap))
         return batch
-
-    def resident_eval_batch(self, store, cur_desc, B_cap, T_cap, N_cap):
-        """trainer.ResidentEval: the "batch" of a test step read from the HBM-resident test store (same dict as
-        ``resident_batch``), or None under the conditions ``resident_batch`` refuses."""
-        return self.resident_batch(store, cur_desc, B_cap, T_cap, N_cap)
-
-    def resident_eval_step(self, batch, cm):
-        """one forward-only step (eval mode, p = 0, a workspace of its own) scored on the device: adds the batch's confusion
-        matrix to ``cm`` (int64 [C, C]); no host sync; neither the training flag nor the dropout counter is touched.  Returns
-        the step's buffers (the caller of a captured step keeps them alive)."""
-        return self.model.eval_scores(batch, cm)

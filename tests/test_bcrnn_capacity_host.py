@@ -265,3 +265,15 @@ def test_resident_without_device_collate_still_exits_with_the_existing_message(m
     with pytest.raises(SystemExit) as exc:
         _patched_run(monkeypatch, argv, BcGruTrainer)
     assert str(exc.value) == "--resident needs --device_collate, one rank and a trainer with resident batches (capacity mode)"
+
+
+def test_resident_eval_with_bclstm_still_exits_with_the_existing_message(monkeypatch):
+    """trainer.run asks hasattr(trainer, "resident_eval_step"): these trainers have no scored test step and must not get one
+    from a shared base"""
+    from erc_amd.bcrnn import BcGruTrainer, BcLstmTrainer
+    assert not hasattr(BcLstmTrainer, "resident_eval_step") and not hasattr(BcGruTrainer, "resident_eval_step")
+    argv = ["--dataset=meld-mmgcn-7", "--loss_weights=False", "--device=cpu", "--epoch=0", "--n_train=12", "--n_test=4",
+            "--train.batch_size=4", "--device_collate", "--resident", "--resident_eval"]
+    with pytest.raises(SystemExit) as exc:
+        _patched_run(monkeypatch, argv, BcLstmTrainer)
+    assert str(exc.value) == "--resident_eval: this module's trainer has no resident_eval_step (--module=cogmen has one)"

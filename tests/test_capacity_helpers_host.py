@@ -34,3 +34,28 @@ def test_batch_table_equals_the_two_constructions_it_replaced():
     want = np.concatenate([flat_l.reshape(steps, B), flat_o.reshape(steps, B)], axis=1)
     assert np.array_equal(batch_table(lens, offs, np.arange(n), B), want)
     assert want[-1].tolist() == [22, 2, 0, 0, int(offs[8]), int(offs[9]), 0, 0]      # zeros in the last batch's empty slots
+
+
+def test_zero_row_stores_keep_one_extension_per_store():
+    """one tensor or a dict of them, a zero row appended; the same object for the same store, another for another store, and
+    both still there when the two alternate (a run's train and test store)"""
+    import types
+    from erc_amd.capacity import ZeroRowStores
+    ext = ZeroRowStores()
+    train = types.SimpleNamespace(fused=torch.ones(10, 6, dtype=torch.bfloat16))
+    test = types.SimpleNamespace(fused=torch.ones(4, 6, dtype=torch.bfloat16))
+    a, b = ext(train, train.fused), ext(test, test.fused)
+    assert a.shape == (11, 6) and a.dtype == torch.bfloat16 and torch.equal(a[:10], train.fused) and float(a[10].abs().sum()) == 0
+    assert b.shape == (5, 6) and torch.equal(b[:4], test.fused) and float(b[4].abs().sum()) == 0
+    assert a is not b
+    for _ in range(2):                                                    # alternating stores: nothing is rebuilt
+        assert ext(train, train.fused) is a and ext(test, test.fused) is b
+    # identity, not equality: a store that merely looks the same gets an extension of its own
+    twin = types.SimpleNamespace(fused=train.fused)
+    assert ext(twin, twin.fused) is not a and ext(train, train.fused) is a
+    # a dict of tensors (one per modality): every entry extended, the dict itself cached
+    mm = types.SimpleNamespace(feats=dict(a=torch.ones(3, 2), v=torch.ones(3, 5, dtype=torch.float64)))
+    d = ext(mm, mm.feats)
+    assert set(d) == {"a", "v"} and d["a"].shape == (4, 2) and d["v"].shape == (4, 5) and d["v"].dtype == torch.float64
+    assert all(torch.equal(d[m][:3], mm.feats[m]) and float(d[m][3].abs().sum()) == 0 for m in d)
+    assert ext(mm, mm.feats) is d and ext(train, train.fused) is a

@@ -118,3 +118,13 @@ def test_resident_batch_refusals():
     split = _trainer(terms=3)
     assert split.resident_batch(mk(torch.float32), desc, 4, 70, 256)["caps"] == (4, 70, 256)
     assert split.resident_batch(store, desc, 4, 70, 256) is None
+
+
+def test_a_bucket_carries_the_models_arguments_alone():
+    """forward(**batch) runs on the static dict: no host-side bookkeeping key ("extent") may be in it"""
+    tr = _trainer()
+    key, make, fill = tr.capacity_bucket(_batch([5, 9]))
+    static = make()
+    fill(static, _batch([5, 9]))
+    fill(static, _batch([3]))
+    assert set(static) == {"input_tensor", "speaker_tensor", "text_length", "label"}

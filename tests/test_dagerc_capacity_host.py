@@ -123,6 +123,16 @@ def test_fill_clears_what_the_previous_batch_left():
     assert torch.equal(static["input_tensor"], big["input_tensor"]) and static["text_length"].tolist() == [9, 8, 10, 7, 6]
 
 
+@pytest.mark.parametrize("onehot", [True, False])
+def test_fill_after_any_sequence_of_batches_equals_a_fresh_buffer(onehot):
+    from tests.util_capacity import FILL_SEQ, assert_fill_equals_a_fresh_buffer
+    tr = _trainer(batch_size=4)
+    tr.t_cap = 12
+    batches = [_batch(lens, tr, onehot=onehot) for lens in FILL_SEQ]
+    assert_fill_equals_a_fresh_buffer(tr, batches, "input_tensor")
+    assert tr.capacity_bucket(batches[0])[1]()["speaker_tensor"].shape == ((4, 12, 2) if onehot else (4, 12))
+
+
 def test_precapture_list_is_the_single_bucket_with_full_synthetic_lengths():
     tr = _trainer(batch_size=8)
     tr.t_cap = 33

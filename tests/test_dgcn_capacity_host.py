@@ -166,3 +166,14 @@ def test_resident_flag_reaches_a_dgcn_trainer(monkeypatch):
             "--train.batch_size=4", "--device_collate", "--resident"]
     assert trainer_mod.run(DGCNTrainer, ERCParams, argv) == {}
     assert len(built) == 1 and built[0].supported()
+
+
+def test_a_bucket_carries_the_models_arguments_alone():
+    """forward(**batch) runs on the static dict: no host-side bookkeeping key ("extent") may be in it"""
+    tr = _trainer(batch_size=4)
+    tr.t_cap = 12
+    key, make, fill = tr.capacity_bucket(_batch([5, 9]))
+    static = make()
+    fill(static, _batch([5, 9]))
+    fill(static, _batch([3]))
+    assert set(static) == {"input_tensor", "speaker_tensor", "text_length", "label"}

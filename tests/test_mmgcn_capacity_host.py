@@ -110,6 +110,16 @@ def test_make_and_fill_are_time_major_and_empty_slots_get_length_zero():
     assert torch.equal(static["audio_feature"], big["audio_feature"]) and static["text_length"].tolist() == [9, 8, 10, 7, 6]
 
 
+@pytest.mark.parametrize("modality", ["atv", "av"])
+def test_fill_after_any_sequence_of_batches_equals_a_fresh_buffer(modality):
+    from tests.util_capacity import FILL_SEQ, assert_fill_equals_a_fresh_buffer
+    tr = _trainer(batch_size=4, modality=modality)
+    tr.t_cap = 12
+    batches = [_batch(lens, tr) for lens in FILL_SEQ]
+    assert_fill_equals_a_fresh_buffer(tr, batches, "audio_feature")
+    assert (tr.capacity_bucket(batches[0])[1]()["text_feature"] is None) == (modality == "av")
+
+
 def test_a_two_modality_bucket_holds_only_its_modalities():
     tr = _trainer(batch_size=4, modality="av")
     tr.t_cap = 12
