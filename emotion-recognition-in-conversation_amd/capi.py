@@ -1206,3 +1206,36 @@ def bcrnn_meta_cap(lengths, desc, store_label, zero_store_row, B, T, n_cap, node
 
 def log_softmax_rows(x, ldx, Cn, n_rows, y, ldy):
     _call("erc_log_softmax_rows", x, ldx, Cn, n_rows, y, ldy)
+
+
+# --------------------------------------------------------------------------- launch chain (csrc/launch_chain.hip)
+def chain_order(n_nodes, edges):
+    """path order of nodes 0 .. n_nodes-1 under ``edges`` [(from, to), ...]; raises unless they form one simple path"""
+    ne = len(edges)
+    fr, to = (C.c_int32 * max(1, ne))(*[e[0] for e in edges]), (C.c_int32 * max(1, ne))(*[e[1] for e in edges])
+    order = (C.c_int32 * max(1, n_nodes))()
+    _call("erc_chain_order", n_nodes, ne, C.addressof(fr), C.addressof(to), C.addressof(order))
+    return list(order)[:n_nodes]
+
+
+def chain_build(raw_graph):
+    """(chain handle, None), or (0, reason) when the hipGraph_t ``raw_graph`` is not one path of kernel nodes.  The handle
+    points INTO the graph: keep the graph alive and free the chain first (ercgraft.h)."""
+    handle = int(lib().erc_chain_build(raw_graph))
+    return (handle, None) if handle else (0, lib().erc_last_error().decode())
+
+
+def chain_len(chain):
+    n = int(lib().erc_chain_len(chain))
+    if n < 0:
+        _check(n, "erc_chain_len")
+    return n
+
+
+def chain_run(chain):
+    """the chain's launches, in order, on the current stream"""
+    _check(lib().erc_chain_run(chain, stream()), "erc_chain_run")
+
+
+def chain_free(chain):
+    _check(lib().erc_chain_free(chain), "erc_chain_free")

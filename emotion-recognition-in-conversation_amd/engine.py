@@ -689,14 +689,78 @@ class _Fork:
         return False
 
 
+def step_replay_mode():
+    """ERC_STEP_REPLAY: ``launches`` | ``graph`` | unset (launches where the captured graph allows it, graph replay otherwise)"""
+    mode = os.environ.get("ERC_STEP_REPLAY", "") or "auto"
+    if mode not in ("auto", "graph", "launches"):
+        raise capi.ErcGraftError("ERC_STEP_REPLAY=%s: expected 'graph' or 'launches'" % mode)
+    return mode
+
+
+class CapturedStep:
+    """``fn()`` (``steps`` consecutive calls of it) captured into one HIP graph on the current device, and the way to replay it.
+
+    Between two replays of an executable graph the queue idles for several microseconds, while kernels launched one by one
+    cross the step boundary like any kernel boundary (DESIGN.md finding 64).  So a capture that is ONE PATH OF THIS LIBRARY'S
+    KERNELS -- the single-rank fused steps -- is replayed as plain launches from C (capi.chain_run, csrc/launch_chain.hip:
+    one foreign call per replay); anything else -- memcpy / memset nodes, forked branches, the RCCL nodes of the N > 1 step,
+    kernels of torch's -- is replayed as the graph, as before.  ``ERC_STEP_REPLAY=graph`` forces graph replay (A/B runs, the
+    escape hatch), ``ERC_STEP_REPLAY=launches`` raises when the capture is not eligible.
+
+    The chain points into the hipGraph_t (the kernels' argument storage is the graph's): this object owns both, keeps the
+    graph for as long as the chain exists and frees the chain first."""
+
+    def __init__(self, fn, steps=1, mode=None):
+        self.mode = mode or step_replay_mode()
+        self.chain, self.refused = 0, None
+        keep = self.mode != "graph"
+        self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            for _ in range(steps):
+                self.out = fn()
+        if keep:
+            self.chain, self.refused = capi.chain_build(self.graph.raw_cuda_graph())
+            if not self.chain:
+                if self.mode == "launches":
+                    raise capi.ErcGraftError("ERC_STEP_REPLAY=launches: the captured step cannot be replayed as plain launches: %s"
+                                             % self.refused)
+                self.graph.instantiate()
+        self.launches = capi.chain_len(self.chain) if self.chain else None
+        self._run = capi.lib().erc_chain_run if self.chain else None
+
+    @property
+    def replays_by(self):
+        return "launches" if self.chain else "graph"
+
+    def replay(self):
+        if self.chain:
+            capi._check(self._run(self.chain, torch.cuda.current_stream().cuda_stream), "erc_chain_run")
+        else:
+            self.graph.replay()
+
+    def close(self):
+        """the chain first, then the graph it points into"""
+        chain, self.chain = self.chain, 0
+        if chain:
+            capi.chain_free(chain)
+        self.graph = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # interpreter shutdown: the library may be gone already
+            pass
+
+
 class GraphedStep:
     """Capture ``fn()`` (a whole training step whose every launch goes to the current stream and which
-    performs no host synchronisation) into one HIP graph and replay it.  The inputs of ``fn`` must live in
+    performs no host synchronisation) into one HIP graph and replay it (``CapturedStep``: as plain launches where the
+    capture allows it).  The inputs of ``fn`` must live in
     fixed device buffers; shapes are static per captured graph (one graph per (B, T, N) bucket)."""
 
     def __init__(self, fn, warmup=2, steps=1):
         """``steps`` > 1 captures that many consecutive calls of ``fn`` into the one graph (a loop whose next batches are already
-        resident: the ~5.5 us bubble between two graph launches is paid once per ``steps`` steps)."""
+        resident: the bubble between two graph launches is paid once per ``steps`` steps)."""
         self.fn = fn
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -705,12 +769,10 @@ class GraphedStep:
                 self.out = fn()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            for _ in range(steps):
-                self.out = fn()
+        self.captured = CapturedStep(fn, steps=steps)
+        self.out = self.captured.out
         self.warmup_steps, self.steps = warmup, steps
 
     def __call__(self):
-        self.graph.replay()
+        self.captured.replay()
         return self.out

@@ -31,6 +31,7 @@ from torch.utils.data import DataLoader
 from . import capi
 from .capacity import node_capacity
 from .collate import ERCCollate
+from .engine import CapturedStep
 from .synthetic import make_dialogues, make_mosei_dialogues
 
 
@@ -240,10 +241,8 @@ class StepGraphs:
     #    execute what it records)
     def _capture(self, fn):
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = fn()
-        return g, out
+        g = CapturedStep(fn)      # .replay(): plain launches from C where the capture is one path of kernels, else the graph
+        return g, g.out
 
     def _sync(self):
         torch.cuda.synchronize()
@@ -375,10 +374,7 @@ class ResidentLoop:
     # -- the one place that touches the HIP runtime (a test replaces it with a recorder that does not execute what it records)
     def _capture(self, fn):
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            fn()
-        return g
+        return CapturedStep(fn)
 
     def _caps_of(self, counts):
         return [node_capacity(c, self.N_BUCKET, self.B * self.T) for c in counts]

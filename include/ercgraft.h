@@ -1410,6 +1410,39 @@ int erc_bcrnn_meta_cap(const int64_t* lengths, const int32_t* desc, const int64_
 int erc_log_softmax_rows(const float* x, int ldx, int C, int n_rows, float* y, int ldy, void* stream);
 
 
+/* ------------------------------------------------------------------------
+ * Launch chain: a captured step replayed as PLAIN kernel launches from native code.
+ * A training step captured into a HIP graph (one stream, kernels only) is a simple path of kernel nodes.  Replaying the
+ * graph leaves the queue idle between two replays (DESIGN.md findings 48, 64); the same kernels launched one by one on a
+ * stream follow each other across the step boundary like inside the step.  Launching them from C costs the host one
+ * foreign call per step instead of one per kernel.
+ *
+ *   erc_chain_order   pure host function.  Nodes 0 .. n_nodes-1, edge e runs from_host[e] -> to_host[e].  If the edges form
+ *                     ONE SIMPLE PATH over all nodes (exactly one root, every node at most one predecessor and one
+ *                     successor, no node left over) order_host [n_nodes] receives the nodes in path order and the result
+ *                     is ERC_OK; anything else (two roots, a fork, a join, a duplicate edge, a cycle, an index out of range,
+ *                     n_nodes <= 0) is ERC_E_ARG.  A single node without edges is a path.
+ *   erc_chain_build   graph_host: a hipGraph_t (NOT an executable graph).  Returns a chain handle, or 0 when the graph is
+ *                     not eligible (erc_last_error says why): every node must be a kernel node whose arguments are given
+ *                     as kernelParams (no `extra` buffer) and whose function is one of THIS LIBRARY's kernels (a framework's own
+ *                     kernel may depend on state the framework refreshes when it replays the graph itself), and the
+ *                     nodes must form one simple path; the order comes from the graph's EDGES (hipGraphGetNodes
+ *                     promises none).  The handle stores function, grid, block, dynamic LDS bytes and the kernelParams
+ *                     pointer of every node.  LIFETIME: those kernelParams pointers, and the argument storage behind them,
+ *                     BELONG TO THE GRAPH -- the caller keeps the hipGraph_t alive and unmodified for as long as the chain
+ *                     exists and frees the chain first.  The handle itself is a small host allocation (the one exception
+ *                     to "no entry point allocates"); no device memory is allocated, nothing is synchronised.
+ *   erc_chain_len     number of launches of the chain (negative: not a chain handle).
+ *   erc_chain_run     one hipLaunchKernel per node, in path order, on `stream`; allocates nothing, waits for nothing.  The
+ *                     first failing launch ends the run: ERC_E_LAUNCH, erc_last_error names the node.
+ *   erc_chain_free    frees the handle (0 is accepted).
+ */
+int erc_chain_order(int n_nodes, int n_edges, const int32_t* from_host, const int32_t* to_host, int32_t* order_host);
+int64_t erc_chain_build(void* graph_host);
+int erc_chain_len(int64_t chain);
+int erc_chain_run(int64_t chain, void* stream);
+int erc_chain_free(int64_t chain);
+
 /* Test support (not part of the data path): fills the LDS of every CU with NaN bit patterns, so that a persistent
  * kernel that reads LDS it did not initialise fails its parity test deterministically.  sink: one int32, may be NULL. */
 int erc_test_poison_lds(int32_t* sink, void* stream);

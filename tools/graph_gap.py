@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """How much of a COGMEN step is the bubble BETWEEN two graph launches?  Times K steps replayed as K one-step graphs against
-K / S replays of an S-step graph, and the host cost of a replay call."""
+K / S replays of an S-step graph, and the host cost of a replay call.
+
+``graph_gap.py replay`` runs only the first part: the captured step replayed as the HIP graph against the same capture
+replayed as plain launches from C (engine.CapturedStep, csrc/launch_chain.hip), alternating, three rounds (DESIGN.md
+finding 64)."""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -15,6 +19,39 @@ for _ in range(3):
     tr.train_step(batch)
 torch.cuda.synchronize()
 K = 2400
+
+from erc_amd.engine import CapturedStep
+for rnd in range(3):
+    for mode in ("graph", "launches"):
+        st = CapturedStep(lambda: tr.train_step(batch), mode=mode)
+        for _ in range(50):
+            st.replay()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(K):
+            st.replay()
+        t_host = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        # the host's own cost of a replay: short bursts into an EMPTY queue (over K back-to-back replays the queue fills and
+        # the enqueue call waits for the GPU, so t_host / K tends to the GPU's time per step whatever the host costs)
+        bursts = []
+        for _ in range(20):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(8):
+                st.replay()
+            bursts.append((time.perf_counter() - t1) / 8 * 1e6)
+        torch.cuda.synchronize()
+        bursts.sort()
+        print("round %d, replay by %-8s (%s kernels): %.2f us per step; host enqueue %.2f us per step over %d back-to-back "
+              "replays, %.2f us (median of 20 bursts of 8 into an empty queue, min %.2f)" % (
+                  rnd, st.replays_by, st.launches if st.launches else "graph of", t / K * 1e6, t_host / K * 1e6, K,
+                  bursts[len(bursts) // 2], bursts[0]), flush=True)
+        st.close()
+if sys.argv[1:] == ["replay"]:
+    sys.exit(0)
+
 for S in (1, 2, 4, 8):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
