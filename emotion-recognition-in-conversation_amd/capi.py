@@ -1232,6 +1232,11 @@ def chain_len(chain):
     return n
 
 
+def set_store_mode(through):
+    """erc_set_store_mode: the step's 16-byte output stores write-through (True, the library's default) or plain (ercgraft.h)"""
+    _call("erc_set_store_mode", 1 if through else 0)
+
+
 def chain_run(chain):
     """the chain's launches, in order, on the current stream"""
     _check(lib().erc_chain_run(chain, stream()), "erc_chain_run")

@@ -25,6 +25,7 @@
 // wrote; the kernels only rely on |source - target| <= 5 (checked by the host wrapper through wp / wf).
 #include "erc_common.h"
 #include "split_dev.h"
+#include "store_dev.h"
 
 namespace {
 
@@ -181,6 +182,9 @@ struct CgFwdP {
     float* Mf;                     // out fp32 [N, ldmf >= 900]
     float* H1f;                    // out fp32 [N, ldh1f >= 100]
     int ldmf, ldh1f;
+    // output stores (csrc/store_dev.h): wt != 0 issues the 16-byte output stores write-through; *_rows != 0: that output leaves as
+    // 16-byte row pieces of its LDS tile (its pitch and base allow it), 0: as the per-lane stores of the stage that makes it
+    int wt, mb_rows, h1_rows, h2_rows;
 };
 
 template <int NT>
@@ -395,10 +399,10 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
                     const int grp = (q >> 2) * 2 + (q & 1);            // which group block q would hold
                     const uint32_t v = ((q >> 1) & 1) == a ? pk4[grp] : 0u;
                     mrow[q * (CG_F / 2) + lane] = v;
-                    if (own) grow[q * (CG_F / 2) + lane] = v;
+                    if (own && !p.mb_rows) grow[q * (CG_F / 2) + lane] = v;
                 }
                 mrow[CG_R * (CG_F / 2) + lane] = pks;
-                if (own) grow[CG_R * (CG_F / 2) + lane] = pks;
+                if (own && !p.mb_rows) grow[CG_R * (CG_F / 2) + lane] = pks;
             }
             if (own && lane < CG_R) {
                 const int grp = (lane >> 2) * 2 + (lane & 1);
@@ -455,13 +459,13 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
                 const uint32_t pk = (uint32_t)f2bf(m0) | ((uint32_t)f2bf(m1) << 16);
                 if (act) {
                     mrow[q * (CG_F / 2) + lane] = pk;
-                    if (own) grow[q * (CG_F / 2) + lane] = pk;
+                    if (own && !p.mb_rows) grow[q * (CG_F / 2) + lane] = pk;
                 }
             }
             const uint32_t pks = (uint32_t)f2bf(self.x) | ((uint32_t)f2bf(self.y) << 16);
             if (act) {
                 mrow[CG_R * (CG_F / 2) + lane] = pks;
-                if (own) grow[CG_R * (CG_F / 2) + lane] = pks;
+                if (own && !p.mb_rows) grow[CG_R * (CG_F / 2) + lane] = pks;
             }
             if (own && lane < CG_R) p.inv_cnt[(int64_t)node * CG_R + lane] = cnt_l > 0 ? 1.0f / (float)cnt_l : 0.f;   // kept for the backward
         }
@@ -560,7 +564,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
                 if constexpr (!X) {
                     const unsigned short hb = col < CG_F ? f2bf(v) : (unsigned short)0;
                     sH1[e * CG_SH1 + col] = hb;
-                    if (col < CG_F && e >= CG_HL && e < CG_HL + CG_TR && node < N) p.H1b[(int64_t)node * p.ldh1b + col] = hb;
+                    if (!p.h1_rows && col < CG_F && e >= CG_HL && e < CG_HL + CG_TR && node < N) p.H1b[(int64_t)node * p.ldh1b + col] = hb;
                 } else {
                     float rem = col < CG_F ? v : 0.f;      // the NT terms of the value, one per plane
 #pragma unroll
@@ -575,9 +579,39 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
     } else if (w == 7) {
         // columns [112, 128) of the H1 tile are K padding of the next product
         for (int i = lane; i < 32 * 16 * NT; i += 64) sH1[(i >> 9) * (FW_SH1_BYTES / 2) + ((i >> 4) & 31) * CG_SH1 + 112 + (i & 15)] = 0;
+    } else if (!X && w >= 8) {
+        // own rows of the M tile -> global as 16-byte row pieces, by the eight wavefronts that have nothing to add to the H1 tile:
+        // the M tile is complete and stays untouched until the barrier below (stage C overwrites it behind that one).  16 rows x 113
+        // pieces, four per thread; the last piece of a row carries columns [900, 904) of the tile's zeroed K padding into the
+        // buffer's pad columns
+        if (p.mb_rows) {      // uniform
+            constexpr int PCS = (CG_KM * 2 + 15) / 16;
+            static_assert(PCS * 8 <= CG_SM && CG_TR * PCS <= 4 * 512 && (CG_SM * 2) % 16 == 0, "row pieces of the M tile");
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = tid - 512 + 512 * j;
+                const int li = i / PCS, q = i % PCS;
+                const int node = r0 + li;
+                if (i < CG_TR * PCS && node < N)
+                    st_out16(p.Mb + (int64_t)node * p.ldmb + 8 * q, *reinterpret_cast<const f32x4*>(sM + (CG_HL + li) * CG_SM + 8 * q), p.wt);
+            }
+        }
     }
     __syncthreads();
     CG_STAMP(3);
+
+    if constexpr (!X) {
+        // own rows of the H1 tile -> global as 16-byte row pieces (complete behind the barrier above; stage C only reads it): 16 rows
+        // x 13 pieces, the last one with the tile's zero columns [100, 104) for the buffer's pad columns
+        if (p.h1_rows) {      // uniform
+            constexpr int PCS = (CG_F * 2 + 15) / 16;
+            static_assert(PCS * 8 <= CG_SH1 && CG_TR * PCS <= CG_NTH && (CG_SH1 * 2) % 16 == 0, "row pieces of the H1 tile");
+            const int li = tid / PCS, q = tid % PCS;
+            const int node = r0 + li;
+            if (tid < CG_TR * PCS && node < N)
+                st_out16(p.H1b + (int64_t)node * p.ldh1b + 8 * q, *reinterpret_cast<const f32x4*>(sH1 + (CG_HL + li) * CG_SH1 + 8 * q), p.wt);
+        }
+    }
 
     // ---- stage C: QKVS = H1 Wq^T + bq, 25 column tiles over the 16 wavefronts, both row tiles; K = 128 (4 blocks)
     {
@@ -644,7 +678,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
         const int li = i / 100, q = i % 100;
         const int node = r0 + li;
         if (i < CG_TR * 100 && node < N)
-            *reinterpret_cast<f32x4*>(p.QKVS + (int64_t)node * 400 + 4 * q) = *reinterpret_cast<const f32x4*>(sQ + (CG_HL + li) * CG_SQ + 4 * q);
+            st_out16(p.QKVS + (int64_t)node * 400 + 4 * q, *reinterpret_cast<const f32x4*>(sQ + (CG_HL + li) * CG_SQ + 4 * q), p.wt);
     }
 
     // ---- stage D: attention of the 16 own rows (one per wavefront), softmax grouped by target; lane l < 50 owns
@@ -691,7 +725,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
         // invalid rows (past N) put zeros into the BatchNorm sums
         if (act) *reinterpret_cast<float2*>(sH2 + li * CG_F + c2) = y;
         if (valid) {
-            if (act) *reinterpret_cast<float2*>(p.H2 + (int64_t)node * p.ldh2 + c2) = y;
+            if (act && !p.h2_rows) *reinterpret_cast<float2*>(p.H2 + (int64_t)node * p.ldh2 + c2) = y;
             float mine = 0.f;
 #pragma unroll
             for (int u = 0; u < CG_CH; ++u)
@@ -705,6 +739,13 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
     // ---- BatchNorm statistics (torch.nn.BatchNorm1d in training mode, cogmen.py:67): column sums of this tile in
     //      fp64, published with write-through stores; the last workgroup to arrive adds the tiles in order
     __syncthreads();
+    // own rows of the H2 tile -> global as 16-byte row pieces (the barrier above is the BatchNorm sums'; h2_rows implies bn_fused):
+    // 16 rows x 25 pieces, by wavefronts that take no part in the column sums
+    if (p.h2_rows && tid >= 512 && tid < 512 + CG_TR * (CG_F / 4)) {
+        const int li = (tid - 512) / (CG_F / 4), q = (tid - 512) % (CG_F / 4);
+        const int node = r0 + li;
+        if (node < N) st_out16(p.H2 + (int64_t)node * p.ldh2 + 4 * q, *reinterpret_cast<const f32x4*>(sH2 + li * CG_F + 4 * q), p.wt);
+    }
     if (tid < 2 * CG_F) {
         const int c = tid % CG_F, sq = tid / CG_F;
         double s = 0.0;
@@ -868,6 +909,8 @@ struct CgBwdP {
     uint64_t* stamps;
     int stamp_block;
     int64_t qT_plane, wb_plane;    // split compute modes: WqT / Wb are NT term planes, this many elements apart
+    // output stores (csrc/store_dev.h; as CgFwdP): the bf16 dQKVS / dH1 rows leave as 16-byte row pieces of their LDS tiles
+    int wt, dq_rows, dh1_rows;
 };
 
 template <int NT>
@@ -1142,7 +1185,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
                     for (int t = 0; t < NT; ++t) sDQw[t * DQPW + em * (CG_SDQ / 2) + 150 + cp] = tt[t];
                 }
                 const int node = mb + em;
-                if (em >= CG_HL && em < CG_HL + CG_TR && node < N) {
+                if ((X || !p.dq_rows) && em >= CG_HL && em < CG_HL + CG_TR && node < N) {
                     if (p.grads_bf16) *reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned short*>(p.dQKVS) + (int64_t)node * 400 + 3 * CG_F + 2 * cp) = (uint32_t)f2bf(gv.x) | ((uint32_t)f2bf(gv.y) << 16);
                     else *reinterpret_cast<float2*>(p.dQKVS + (int64_t)node * 400 + 3 * CG_F + 2 * cp) = gv;
                 }
@@ -1196,7 +1239,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
                             sDQ[t * (BX_DQPLANE / 2) + em * CG_SDQ + coff + 16 * cti + r] = __builtin_bit_cast(unsigned short, hb);
                         }
                     }
-                    if (nv && em >= CG_HL && em < CG_HL + CG_TR) {
+                    if ((X || !p.dq_rows) && nv && em >= CG_HL && em < CG_HL + CG_TR) {
                         if (p.grads_bf16) reinterpret_cast<unsigned short*>(p.dQKVS)[(int64_t)node * 400 + coff + 16 * cti + r] = f2bf(acc[q]);
                         else p.dQKVS[(int64_t)node * 400 + coff + 16 * cti + r] = acc[q];
                     }
@@ -1206,6 +1249,20 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
     }
     __syncthreads();
     CG_STAMP(3);
+
+    if constexpr (!X) {
+        // own rows of the dQKVS tile (bf16) -> global as 16-byte row pieces: 16 rows x 50 pieces.  The tile is complete behind
+        // the barrier above and is only read from here on; a row of a node inside the graph holds exactly the values the
+        // per-lane stores would write
+        if (p.dq_rows && tid < CG_TR * 50) {
+            static_assert((CG_SDQ * 2) % 16 == 0 && CG_TR * 50 <= CG_NTH, "row pieces of the dQKVS tile");
+            const int li = tid / 50, q = tid % 50;
+            const int node = r0 + li;
+            if (node < N)
+                st_out16(reinterpret_cast<unsigned short*>(p.dQKVS) + (int64_t)node * 400 + 8 * q,
+                         *reinterpret_cast<const f32x4*>(sDQ + (CG_HL + li) * CG_SDQ + 8 * q), p.wt);
+        }
+    }
 
     // ---- stage 3: dH1 = dQKVS WqT^T (K = 416: 13 blocks split 7 + 6 over the two wavefronts of a column tile), both row tiles
     {
@@ -1267,7 +1324,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
                         const float v = h ? acc1[i] + p1[i] : acc0[i] + p0[i];
                         sDH1[e * CG_F + col] = v;
                         const int node = mb + e;
-                        if (e >= CG_HL && e < CG_HL + CG_TR && node < N) {
+                        if ((X || !p.dh1_rows) && e >= CG_HL && e < CG_HL + CG_TR && node < N) {
                             if (p.grads_bf16) reinterpret_cast<unsigned short*>(p.dH1)[(int64_t)node * p.lddh1 + col] = f2bf(v);
                             else p.dH1[(int64_t)node * p.lddh1 + col] = v;
                         }
@@ -1277,6 +1334,25 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
     }
     __syncthreads();
     CG_STAMP(4);
+
+    if constexpr (!X) {
+        // own rows of the dH1 tile (fp32 in LDS, complete behind the barrier above, only read from here on) -> global as bf16, in
+        // 16-byte row pieces: 16 rows x 13 pieces of 8 columns; the last piece holds columns [96, 100) and zeros for the
+        // buffer's pad columns [100, 104)
+        if (p.dh1_rows && tid < CG_TR * 13) {
+            const int li = tid / 13, q = tid % 13;
+            const int node = r0 + li;
+            const float* const src = sDH1 + (CG_HL + li) * CG_F + 8 * q;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(src);
+            f32x4 hi = {0.f, 0.f, 0.f, 0.f};
+            if (q < 12) hi = *reinterpret_cast<const f32x4*>(src + 4);
+            const uint32_t d0 = (uint32_t)f2bf(lo[0]) | ((uint32_t)f2bf(lo[1]) << 16), d1 = (uint32_t)f2bf(lo[2]) | ((uint32_t)f2bf(lo[3]) << 16);
+            const uint32_t d2 = (uint32_t)f2bf(hi[0]) | ((uint32_t)f2bf(hi[1]) << 16), d3 = (uint32_t)f2bf(hi[2]) | ((uint32_t)f2bf(hi[3]) << 16);
+            if (node < N)
+                st_out16(reinterpret_cast<unsigned short*>(p.dH1) + (int64_t)node * p.lddh1 + 8 * q,
+                         (f32x4){__builtin_bit_cast(float, d0), __builtin_bit_cast(float, d1), __builtin_bit_cast(float, d2), __builtin_bit_cast(float, d3)}, p.wt);
+        }
+    }
 
     // ---- stage 4: dP = transposed relation means of dH1 for the 16 own rows (one per wavefront): block r of row j
     //      = sum over out-edges (j -> i, relation r) of dH1[i] / count_r(i); block 8 = dH1[j].  Scalar-branch
@@ -1502,6 +1578,11 @@ static int fwd_tile_launch(int terms, const float* H0, int ldh0, int n_nodes, in
     p.N = n_nodes; p.ldh0 = ldh0; p.ldh2 = ldh2; p.bn_fused = bn_fused;
     p.node_spk = node_spk; p.two_spk = n_speakers == 2 ? 1 : 0; p.n_dev = n_dev;
     p.health = health, p.events = events;
+    // output stores (struct CgFwdP): row pieces need 16-byte rows that hold every piece; other pitches keep the per-lane stores
+    p.wt = erc_store_mode();
+    p.mb_rows = terms == 1 && ldmb % 8 == 0 && ldmb >= 8 * ((CG_KM + 7) / 8) && ((uintptr_t)Mb & 15) == 0;
+    p.h1_rows = terms == 1 && ldh1b % 8 == 0 && ldh1b >= 8 * ((CG_F + 7) / 8) && ((uintptr_t)H1b & 15) == 0;
+    p.h2_rows = bn_fused != 0 && ldh2 % 4 == 0 && ((uintptr_t)H2 & 15) == 0;
     p.stamps = g_cg_stamps; p.stamp_block = tiles / 2;
     if (terms == 1) hipLaunchKernelGGL(cogmen_fwd_tile_kernel<1>, dim3(tiles), dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
     else if (terms == 2) hipLaunchKernelGGL(cogmen_fwd_tile_kernel<2>, dim3(tiles), dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
@@ -1576,6 +1657,10 @@ static int bwd_tile_launch(int terms, const float* dY, const float* H2, int ldh2
     p.node_spk = node_spk; p.two_spk = n_speakers == 2 ? 1 : 0; p.n_dev = n_dev;
     p.head_part = head_part; p.head_parts = head_parts; p.hp_floats = head_part_floats; p.bn_bwd_out = const_cast<float*>(bn_bwd);
     p.dgamma = dgamma; p.dbeta = dbeta; p.stats = stats;
+    // output stores (struct CgBwdP): row pieces for the bf16 gradients whose rows are 16-byte multiples (dQKVS: 800 bytes)
+    p.wt = erc_store_mode();
+    p.dq_rows = terms == 1 && grads_bf16 && ((uintptr_t)dQKVS & 15) == 0;
+    p.dh1_rows = terms == 1 && grads_bf16 && lddh1 % 8 == 0 && lddh1 >= 8 * ((CG_F + 7) / 8) && ((uintptr_t)dH1 & 15) == 0;
     p.stamps = g_cg_stamps; p.stamp_block = erc_cdiv(n_nodes, CG_TR) / 2;
     const dim3 grid(erc_cdiv(n_nodes, CG_TR));
     if (terms == 1) hipLaunchKernelGGL(cogmen_bwd_tile_kernel<1>, grid, dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "erc_common.h"
+#include "store_dev.h"
 
 extern "C" int erc_chain_order(int n_nodes, int n_edges, const int32_t* from_host, const int32_t* to_host, int32_t* order_host) {
     ERC_REQUIRE(n_nodes > 0 && order_host != nullptr, "chain_order: n_nodes=%d (need >= 1 and an output array)", n_nodes);
@@ -155,5 +156,15 @@ extern "C" int erc_chain_free(int64_t chain) {
     ERC_REQUIRE(c != nullptr, "chain_free: not a chain handle");
     c->magic = 0;
     delete c;
+    return ERC_OK;
+}
+
+// ---- store mode of the step's output stores (csrc/store_dev.h): process-wide, read by the launching entry points when they
+//      fill a kernel's parameter struct -- so a captured launch keeps the mode it was captured with
+static int g_store_mode = 1;
+int erc_store_mode(void) { return g_store_mode; }
+extern "C" int erc_set_store_mode(int mode) {
+    ERC_REQUIRE(mode == 0 || mode == 1, "set_store_mode: mode = %d (0 plain, 1 write-through)", mode);
+    g_store_mode = mode;
     return ERC_OK;
 }

@@ -28,6 +28,7 @@
 #include "erc_common.h"
 #include "optim_dev.h"
 #include "split_dev.h"
+#include "store_dev.h"
 #include <string.h>
 
 namespace {
@@ -80,7 +81,8 @@ struct W2Adam {
     // item that has summed its quads over the tile's splits publishes them (write-through, system scope) at their flat gradient
     // offsets in this rank's publish buffer, posts (epoch, health bit) to every rank's flag array, waits (bounded) for the same
     // item of every rank and continues with the RANK-ORDERED sum: bit-identical replicas, no RCCL call, no optimizer launch.
-    int x_world, x_rank, x_spin, x_pad;
+    int x_world, x_rank, x_spin;
+    int wt;                // != 0: the finished gradient / parameter / moment quads leave as write-through stores (store_dev.h)
     float* x_pub[8];
     int32_t* x_flags[8];
     int64_t* x_epoch;      // [512] one exchange counter per work item (private to its workgroup)
@@ -90,14 +92,9 @@ static_assert(sizeof(W2Desc) == 112, "W2Desc layout");
 
 __device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// 16-byte write-through store / cache-bypassing load of a slab quad (sc0 sc1 = system scope: the partial tiles cross XCDs,
-// whose L2s are not coherent with each other).  The compiler does not count inline-asm loads: the caller waits (vmcnt).
-__device__ __forceinline__ void st_sc1_x4(float* p, f32x4 v) {
-    // (s_nop: a store of more than 64 bits needs wait states before its data registers may be overwritten, and the compiler's
-    //  hazard recognizer does not look inside an asm statement -- without them a v_cndmask scheduled right behind the store
-    //  replaced the last dword of lanes 12-15 of every 16: finding 44)
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
+// 16-byte write-through store (st_out16<true>, csrc/store_dev.h) / cache-bypassing load of a slab quad (sc0 sc1 = system scope: the
+// partial tiles cross XCDs, whose L2s are not coherent with each other).  The compiler does not count inline-asm loads: the
+// caller waits (vmcnt).
 __device__ __forceinline__ f32x4 ld_sc1_x4(const float* p) {
     f32x4 v;
     asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v) : "v"(p) : "memory");
@@ -164,8 +161,16 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
     auto adam_quad = [&](const int64_t off, const f32x4 gq, const f32x4 pq, const f32x4 mq, const f32x4 vq) __attribute__((always_inline)) -> float4 {
         float4 pv = make_float4(pq.x, pq.y, pq.z, pq.w), mv = make_float4(mq.x, mq.y, mq.z, mq.w), vv = make_float4(vq.x, vq.y, vq.z, vq.w);
         ac.upd(pv.x, gq.x, mv.x, vv.x), ac.upd(pv.y, gq.y, mv.y, vv.y), ac.upd(pv.z, gq.z, mv.z, vv.z), ac.upd(pv.w, gq.w, mv.w, vv.w);
-        *(ERC_GLOBAL f32x4*)(ad.data + off) = (f32x4){pv.x, pv.y, pv.z, pv.w};
-        *(ERC_GLOBAL f32x4*)(ad.m + off) = (f32x4){mv.x, mv.y, mv.z, mv.w}, *(ERC_GLOBAL f32x4*)(ad.v + off) = (f32x4){vv.x, vv.y, vv.z, vv.w};
+        // write-through (nothing in this launch reads these quads again: pq / mq / vq were loaded in front, the shadows are made from
+        // pv) in the bf16 form only: the split forms sit at 256 VGPRs, and with the second store path compiled in they ran 1.0 us
+        // longer in EITHER mode (31.3 -> 32.3 us at f32x32, DESIGN.md finding 65) -- they keep the plain stores and their code
+        if (NT == 1 && ad.wt) {
+            st_out16<true>(ad.data + off, (f32x4){pv.x, pv.y, pv.z, pv.w});
+            st_out16<true>(ad.m + off, (f32x4){mv.x, mv.y, mv.z, mv.w}), st_out16<true>(ad.v + off, (f32x4){vv.x, vv.y, vv.z, vv.w});
+        } else {
+            *(ERC_GLOBAL f32x4*)(ad.data + off) = (f32x4){pv.x, pv.y, pv.z, pv.w};
+            *(ERC_GLOBAL f32x4*)(ad.m + off) = (f32x4){mv.x, mv.y, mv.z, mv.w}, *(ERC_GLOBAL f32x4*)(ad.v + off) = (f32x4){vv.x, vv.y, vv.z, vv.w};
+        }
         return pv;
     };
     // the bf16 shadows of up to 8 updated quads: ONE pass over the table's descriptors (read from the LDS copy, not unrolled)
@@ -648,7 +653,7 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
                 if (direct) {
                     store_c(tid + 256 * (u & 1), 2 * P + (u >> 1), s);
                 } else {  // slab layout [h][u & 1][thread] quads: one 16-byte write-through store per thread, 1 KB runs per wave instruction
-                    st_sc1_x4(slab + ((4 * P + u) * 256 + tid) * 4, s);
+                    st_out16<true>(slab + ((4 * P + u) * 256 + tid) * 4, s);
                 }
             }
         }
@@ -778,7 +783,7 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
                     if (r == ad.x_rank) mypub = ad.x_pub[r];
 #pragma unroll
                 for (int o = 0; o < 8; ++o)
-                    if (o < owned && valid[o] == 4) st_sc1_x4(mypub + poff + off[o], res[o]);
+                    if (o < owned && valid[o] == 4) st_out16<true>(mypub + poff + off[o], res[o]);
                 if (bdst) __hip_atomic_store(mypub + poff + boff, bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 adam_on = x_rendezvous(!adam_on) && adam_on;
                 bump_step();
@@ -804,7 +809,8 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
     #pragma unroll 1
             for (int it = 0; it < owned; ++it) {
                 if (valid[0] == 4) {
-                    *(ERC_GLOBAL f32x4*)(ad.grad + off[0]) = res[0];
+                    if (NT == 1 && ad.wt) st_out16<true>(ad.grad + off[0], res[0]);
+                    else *(ERC_GLOBAL f32x4*)(ad.grad + off[0]) = res[0];
                     if (upd) {
                         const float4 pv = adam_quad(off[0], res[0], pq[0], mq[0], vq[0]);
                         if (it == 0) W2_STAMP(13);
@@ -1035,6 +1041,7 @@ static int w2_adam_entry(int terms, const void* table, int n_desc, const int32_t
     ad.grad_scale = grad_scale, ad.data = p, ad.grad = g, ad.m = m, ad.v = v, ad.state = state, ad.skip = health, ad.health = health;
     ad.seq = counters + n_tiles;
     ad.spin_limit = g_w2_spin_limit;
+    ad.wt = (x || terms > 1) ? 0 : erc_store_mode();      // (the N > 1 step and the split forms keep plain stores)
     if (x) {
         ERC_REQUIRE(x->world >= 2 && x->world <= 8 && x->rank >= 0 && x->rank < x->world && x->epoch && x->n_pad >= n && x->n_pad % 4 == 0 &&
                         (int32_t*)x->health == health, "wgrad_adam_p2p: bad exchange descriptor (2 <= world <= 8; health = the exchange's health word)");

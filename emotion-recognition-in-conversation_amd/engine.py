@@ -697,6 +697,15 @@ def step_replay_mode():
     return mode
 
 
+def step_store_mode():
+    """ERC_STEP_STORES: ``through`` (default: the step's 16-byte output stores are write-through, no dirty lines wait in the L2s
+    at a kernel's end) | ``plain`` (the same stores as plain ones: A/B runs).  DESIGN.md finding 65."""
+    mode = os.environ.get("ERC_STEP_STORES", "") or "through"
+    if mode not in ("plain", "through"):
+        raise capi.ErcGraftError("ERC_STEP_STORES=%s: expected 'plain' or 'through'" % mode)
+    return mode
+
+
 class CapturedStep:
     """``fn()`` (``steps`` consecutive calls of it) captured into one HIP graph on the current device, and the way to replay it.
 
@@ -712,6 +721,8 @@ class CapturedStep:
 
     def __init__(self, fn, steps=1, mode=None):
         self.mode = mode or step_replay_mode()
+        self.stores = step_store_mode()
+        capi.set_store_mode(self.stores == "through")      # read by the launches as they are captured; a replay keeps it
         self.chain, self.refused = 0, None
         keep = self.mode != "graph"
         self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()

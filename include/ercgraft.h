@@ -1443,6 +1443,17 @@ int erc_chain_len(int64_t chain);
 int erc_chain_run(int64_t chain, void* stream);
 int erc_chain_free(int64_t chain);
 
+/* Output stores of the single-rank COGMEN step's kernels (csrc/store_dev.h, DESIGN.md finding 65): mode 1 (the default) issues
+ * the 16-byte output stores of erc_cogmen_fwd_tile(_x) (QKVS, H2, and in the bf16 form the Mb and H1b rows), of erc_cogmen_bwd_tile
+ * (the bf16 dQKVS and dH1 rows) and of erc_wgrad_bf16_adam (gradient, parameter and moment quads) write-through, so that no
+ * dirty lines wait in the L2s at the kernel's end; mode 0 issues the same stores plain.  Narrower stores are always plain; the
+ * split weight-gradient forms, the wide form and erc_wgrad_adam_p2p always store plain.  Results are bit-identical.  Rows that
+ * leave as 16-byte pieces (pitch a multiple of 16 bytes, 16-byte aligned base) get zeros in the pad columns of their last piece
+ * (Mb [900, 904), H1b / dH1 [100, 104)); other pitches keep the narrow stores.  Process-wide; read when a launch is ENQUEUED: a
+ * captured step keeps the mode it was captured with.  Python sets it from ERC_STEP_STORES=plain|through before it captures a step.
+ * Anything but 0 or 1 is ERC_E_ARG. */
+int erc_set_store_mode(int mode);
+
 /* Test support (not part of the data path): fills the LDS of every CU with NaN bit patterns, so that a persistent
  * kernel that reads LDS it did not initialise fails its parity test deterministically.  sink: one int32, may be NULL. */
 int erc_test_poison_lds(int32_t* sink, void* stream);
