@@ -402,7 +402,8 @@ def cogmen_project_graph_ok(K, n_out, B, ldx, ldw):
 
 def cogmen_project_graph(x, ldx, W, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, B, T, wp, wf, n_speakers, n_cap, e_cap, g,
                          desc=None, terms=1, w_plane=0):
-    """input projection + window graph in one launch (csrc/cogmen_project.hip); g: the graph dict of window_graph_build.
+    """input projection + window graph in one launch (csrc/cogmen_project.hip); g: the graph dict of window_graph_build, plus an
+    optional ``node_rec`` (int32 [n_cap + 1, 4]: the node records the tile kernels derive their graph slices from, ercgraft.h).
     desc (int32 [2 B]: lengths | first store rows): resident mode -- x / speakers are a store's [U, ldx] / [U] arrays.
     terms = 2 | 3: split compute mode -- x fp32, W = that many bf16 term planes ``w_plane`` elements apart"""
     sb, st = (0, speakers.stride(0)) if desc is not None else (speakers.stride(0), speakers.stride(1))
@@ -411,11 +412,11 @@ def cogmen_project_graph(x, ldx, W, ldw, bias, H0, ldh0, n_out, K, lengths, spea
             raise ErcGraftError("cogmen_project_graph: split modes take the fp32 feature block")
         _call("erc_cogmen_project_graph_x", terms, x, ldx, W, w_plane, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, sb, st,
               B, T, wp, wf, n_speakers, n_cap, e_cap, g["node_off"], g["node_row"], g["node_spk"], g["in_ptr"], g["in_src"],
-              g["in_typ"], g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], g["counts"], desc)
+              g["in_typ"], g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], g["counts"], desc, g.get("node_rec"))
         return
     _call("erc_cogmen_project_graph", x, ldx, W, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, sb, st, B, T, wp, wf,
           n_speakers, n_cap, e_cap, g["node_off"], g["node_row"], g["node_spk"], g["in_ptr"], g["in_src"], g["in_typ"],
-          g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], g["counts"], desc)
+          g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], g["counts"], desc, g.get("node_rec"))
 
 
 def cogmen_set_stamps(t):
@@ -441,11 +442,11 @@ def cogmen_fwd_tile(H0, ldh0, N, wp, wf, g, WcatT, b1, Wq, bq, scale, Mb, ldmb, 
     if terms > 1:
         _call("erc_cogmen_fwd_tile_x", terms, H0, ldh0, N, wp, wf, g["in_ptr"], g["in_src"], g["in_typ"], WcatT, catT_plane, b1,
               Wq, q_plane, bq, scale, Mb, ldmb, inv_cnt, H1b, ldh1b, QKVS, H2, ldh2, alpha, int(bn_fused), running_mean,
-              running_var, momentum, eps, saved, bn_ws, g["node_spk"], n_speakers, n_dev, health, events)
+              running_var, momentum, eps, saved, bn_ws, g["node_spk"], n_speakers, n_dev, health, events, g.get("node_rec"))
         return
     _call("erc_cogmen_fwd_tile", H0, ldh0, N, wp, wf, g["in_ptr"], g["in_src"], g["in_typ"], WcatT, b1, Wq, bq, scale, Mb, ldmb,
           inv_cnt, H1b, ldh1b, QKVS, H2, ldh2, alpha, int(bn_fused), running_mean, running_var, momentum, eps, saved, bn_ws,
-          g["node_spk"], n_speakers, n_dev, health, events)
+          g["node_spk"], n_speakers, n_dev, health, events, g.get("node_rec"))
 
 
 def cogmen_bwd_tile(dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, g, inv_cnt, WqT, Wb, scale, dQKVS, dH1,
@@ -456,12 +457,12 @@ def cogmen_bwd_tile(dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, 
         _call("erc_cogmen_bwd_tile_x", terms, dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, g["in_ptr"],
               g["in_src"], g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], inv_cnt, WqT, qT_plane, Wb, wb_plane, scale,
               dQKVS, dH1, dH0, lddh0, g["node_spk"], n_speakers, head_part, head_parts,
-              head_fused_part_floats() if head_part is not None else 0, dgamma, dbeta, stats, lddh1, n_dev)
+              head_fused_part_floats() if head_part is not None else 0, dgamma, dbeta, stats, lddh1, n_dev, g.get("node_rec"))
         return
     _call("erc_cogmen_bwd_tile", dY, H2, ldh2, N, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, g["in_ptr"], g["in_src"],
           g["out_ptr"], g["out_dst"], g["out_typ"], g["out_eid"], inv_cnt, WqT, Wb, scale, dQKVS, dH1, dH0, lddh0, g["node_spk"],
           n_speakers, head_part, head_parts, head_fused_part_floats() if head_part is not None else 0, dgamma, dbeta, stats,
-          int(grads_bf16), lddh1, n_dev)
+          int(grads_bf16), lddh1, n_dev, g.get("node_rec"))
 
 
 def grad_norm(g, n, grad_scale, gnorm, ws):
@@ -1230,6 +1231,12 @@ def chain_len(chain):
     if n < 0:
         _check(n, "erc_chain_len")
     return n
+
+
+def set_tile_slices(closed):
+    """erc_set_tile_slices: the tile kernels derive their graph slices from the node records (True, the library's default) or read
+    the CSR (ercgraft.h)"""
+    _call("erc_set_tile_slices", 1 if closed else 0)
 
 
 def set_store_mode(through):

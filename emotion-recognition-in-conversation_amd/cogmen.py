@@ -250,12 +250,13 @@ class COGMENModule(nn.Module):
         C, F, D = self.n_classes, F_HID, self.input_size
         g = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), in_ptr=i32(N + 1), in_src=i32(E),
                  in_typ=i32(E), out_ptr=i32(N + 1), out_dst=i32(E), out_typ=i32(E), out_eid=i32(E), counts=i32(2))
+        node_rec = i32(N + 1, 4)     # node records of the projection launch (ercgraft.h); in g only while that launch builds the graph
         if self.terms > 1:
             # split modes: every buffer between the launches is fp32 (the weight-gradient launch expands its operands itself);
             # zero-filled once: capacity mode reads rows beyond the true count (masked) and dlogits' pad columns
             z32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
             ws = dict(
-                g=g, E=E, fused=True,
+                g=g, E=E, fused=True, node_rec=node_rec,
                 H0=f32(N, F), M=z32(N, 9 * F), inv_cnt=f32(N, N_REL), H1=z32(N, F), QKVS=f32(N, 4 * F),
                 alpha=f32(E), H2=f32(N, F), H3=z32(N, F), Z=z32(N, F), logits=f32(N, C),
                 bn_saved=f32(2 * F), bn_ws=f32(capi.bn_ws_floats(F)), stats=torch.zeros(1024, dtype=torch.float32, device=device),
@@ -269,7 +270,7 @@ class COGMENModule(nn.Module):
             ws["jobs"] = None
             return ws
         ws = dict(
-            g=g, E=E, fused=True,
+            g=g, E=E, fused=True, node_rec=node_rec,
             H0=f32(N, F), Mb=bf(N, PM), inv_cnt=f32(N, N_REL), H1b=bf(N, PA), QKVS=f32(N, 4 * F),
             alpha=f32(E), H2=f32(N, F), H3=f32(N, F), Z=f32(N, F), logits=f32(N, C),
             bn_saved=f32(2 * F), bn_ws=f32(capi.bn_ws_floats(F)), stats=torch.zeros(1024, dtype=torch.float32, device=device),
@@ -325,6 +326,8 @@ class COGMENModule(nn.Module):
         if self.dynamic_n and not (project_graph and ws.get("fused") and upto_h2 and N <= self.BN_FUSED_MAX_N):
             raise capi.ErcGraftError("COGMEN capacity mode needs the fused bf16 training path (supports_capacity)")
         nd = g["counts"] if self.dynamic_n else None
+        # the node records are written by the projection launch only: a graph from erc_window_graph_build has none, its tiles read the CSR
+        g["node_rec"] = ws.get("node_rec") if project_graph else None
         if project_graph:
             capi.cogmen_project_graph(x, D, self.w1_shadow, D, fp.w("rnn.1.bias"), ws["H0"], F, F, D, text_length,
                                       speaker_tensor, B, T, WP, WF, self.n_speakers, N, ws["E"], g, desc=desc,
@@ -403,7 +406,8 @@ class COGMENModule(nn.Module):
         bf = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=device)
         E, F = N * (WP + WF + 1), F_HID
         g = dict(node_off=i32(B + 1), node_row=i32(N), node_spk=i32(N), in_ptr=i32(N + 1), in_src=i32(E),
-                 in_typ=i32(E), out_ptr=i32(N + 1), out_dst=i32(E), out_typ=i32(E), out_eid=i32(E), counts=i32(2))
+                 in_typ=i32(E), out_ptr=i32(N + 1), out_dst=i32(E), out_typ=i32(E), out_eid=i32(E), counts=i32(2),
+                 node_rec=i32(N + 1, 4))
         ws = dict(g=g, E=E, H0=f32(N, F), inv_cnt=f32(N, N_REL), QKVS=f32(N, 4 * F), alpha=f32(E), H2=f32(N, F),
                   logits=z32(N, self.n_classes))
         if self.terms > 1:

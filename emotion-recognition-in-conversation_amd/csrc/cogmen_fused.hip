@@ -185,9 +185,16 @@ struct CgFwdP {
     // output stores (csrc/store_dev.h): wt != 0 issues the 16-byte output stores write-through; *_rows != 0: that output leaves as
     // 16-byte row pieces of its LDS tile (its pitch and base allow it), 0: as the per-lane stores of the stage that makes it
     int wt, mb_rows, h1_rows, h2_rows;
+    // CLOSED-FORM graph slices (two-speaker graphs; null: read the CSR): node_rec [N + 1][4] = {position in the dialogue, dialogue
+    // length, first in-edge, first out-edge} as erc_cogmen_project_graph writes them.  The sources of a target are the rows within
+    // [position - wf, position + wp] of its dialogue, so stage 0 needs the records of its mid rows and no load of in_ptr / in_src / in_typ
+    const int32_t* node_rec;
+    int wp, wf;
 };
 
-template <int NT>
+// CL: closed-form graph slices (p.node_rec, two-speaker graphs) -- an instance of its own, so that neither form carries the other's
+// loads, branches and live scalars
+template <int NT, bool CL>
 __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p) {
     constexpr bool X = NT > 1;
     using XM = FxMap<X ? NT : 2>;
@@ -223,7 +230,11 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
 
     // ---- stage 0: H0 rows [r0-10, r0+26) and the CSR slice of the mid rows -> LDS; zero the K padding of the M tile
     const int m_lo = min(max(mb, 0), N), m_hi = min(max(mb + CG_MID, 0), N);
-    const int E_lo = p.in_ptr[m_lo], E_hi = min(p.in_ptr[m_hi], E_lo + FW_ECAP);
+    constexpr bool closed = CL;                    // sIp from the node records, sSrc[e] = first source node of mid row e
+    int E_lo = 0, E_hi = 0;                        // (closed form: in-edges are addressed by sIp alone)
+    if constexpr (!closed) E_lo = p.in_ptr[m_lo], E_hi = min(p.in_ptr[m_hi], E_lo + FW_ECAP);
+    int4 rec = make_int4(0, 0, 0, 0);
+    if (closed && tid < CG_MID + 1) rec = *reinterpret_cast<const int4*>(p.node_rec + 4 * (int64_t)min(max(mb + tid, 0), N));
     // B fragments of the H1 product: wavefront (ct = w & 7, kh = w >> 3) owns column tile ct and the K blocks
     // [15 kh, 15 kh + 15) (kh = 1: 14); requested now, they arrive during the aggregation
     const int ct = w & 7, kh = w >> 3;
@@ -240,11 +251,15 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
             const float m = ok ? 1.f : 0.f;
             *reinterpret_cast<f32x4*>(sH0 + e * CG_F + 4 * q) = (f32x4){v.x * m, v.y * m, v.z * m, v.w * m};
         }
-        if (tid < CG_MID + 1) sIp[tid] = p.in_ptr[min(max(mb + tid, 0), N)];
-        if (tid >= 64 && tid < 64 + FW_ECAP) {
-            const int i = tid - 64;
-            const int ei = min(E_lo + i, max(E_hi - 1, E_lo));
-            sSrc[i] = p.in_src[ei], sTyp[i] = p.in_typ[ei];
+        if (closed) {
+            if (tid < CG_MID + 1) sIp[tid] = rec.z, sSrc[tid] = min(max(mb + tid, 0), N) - min(rec.x, p.wf);
+        } else {
+            if (tid < CG_MID + 1) sIp[tid] = p.in_ptr[min(max(mb + tid, 0), N)];
+            if (tid >= 64 && tid < 64 + FW_ECAP) {
+                const int i = tid - 64;
+                const int ei = min(E_lo + i, max(E_hi - 1, E_lo));
+                sSrc[i] = p.in_src[ei], sTyp[i] = p.in_typ[ei];
+            }
         }
         if (tid >= 960 && tid < 960 + CG_OUT) {      // speakers of the outer rows (-1: no such node)
             const int node = ob + tid - 960;
@@ -290,7 +305,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
     //      (two adds executed per edge instead of an 8-way select chain), the edge loop stays rolled (two edges per
     //      trip; the code of this kernel runs once per launch from a cold instruction cache), and the mean is
     //      sum * rcp(count) with one Newton step (3 instructions; IEEE division is ~25).
-    if (X || p.two_spk) {     // (the split modes exist for two-speaker graphs only: the host checks)
+    if (X || closed || p.two_spk) {     // (the split modes and the closed form exist for two-speaker graphs only: the host checks)
         // Two speakers (the reference's GNN(n_speakers = 2), cogmen.py:62-64): the relation of an edge is
         // 4 spk(source) + 2 spk(target) + (source < target ? 0 : 1) and the sources of a target are a contiguous run of rows,
         // so the four non-empty relation sums of a target are DIFFERENCES of per-speaker prefix sums over the tile's rows: a
@@ -334,7 +349,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
             const int e0 = __builtin_amdgcn_readfirstlane(min(max(sIp[e] - E_lo, 0), FW_ECAP - 1));
             const int nwin = __builtin_amdgcn_readfirstlane(valid ? min(max(sIp[e + 1] - sIp[e], 0), CG_CH) : 0);
             const int te = e + CG_HL;                                                        // outer row of the target
-            const int lo = __builtin_amdgcn_readfirstlane(min(max(sSrc[e0] - ob, 0), te));   // first / one-past-last source row
+            const int lo = __builtin_amdgcn_readfirstlane(min(max(sSrc[closed ? e : e0] - ob, 0), te));   // first / one-past-last source row
             const int hi1 = nwin > 0 ? min(lo + nwin, CG_OUT) : lo;
             const int a = __builtin_amdgcn_readfirstlane(max(sSpk[te], 0));                  // target speaker
             const int past_hi = min(te, hi1);        // sources [lo, te) are "past" (direction bit 0), [te, hi1) the rest
@@ -696,7 +711,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
         const float2 sk = *reinterpret_cast<const float2*>(sQ + e * CG_SQ + 3 * CG_F + c2);
         int ljs[CG_CH];
 #pragma unroll
-        for (int u = 0; u < CG_CH; ++u) ljs[u] = sSrc[min(e0 + min(u, max(nwin - 1, 0)), FW_ECAP - 1)];
+        for (int u = 0; u < CG_CH; ++u) ljs[u] = closed ? sSrc[e] + min(u, max(nwin - 1, 0)) : sSrc[min(e0 + min(u, max(nwin - 1, 0)), FW_ECAP - 1)];
         float2 kv[CG_CH], vv[CG_CH];
 #pragma unroll
         for (int u = 0; u < CG_CH; ++u) {
@@ -911,9 +926,14 @@ struct CgBwdP {
     int64_t qT_plane, wb_plane;    // split compute modes: WqT / Wb are NT term planes, this many elements apart
     // output stores (csrc/store_dev.h; as CgFwdP): the bf16 dQKVS / dH1 rows leave as 16-byte row pieces of their LDS tiles
     int wt, dq_rows, dh1_rows;
+    // CLOSED-FORM graph slices (two-speaker graphs; null: read the CSR), as CgFwdP: the records of the outer rows and the speakers of
+    // the outer rows give sIp, the first source of every target, and the out-edges of the own rows (target, relation, 1 / count) -- no
+    // load of in_ptr / in_src / out_ptr / out_dst / out_typ / inv_cnt; alpha is addressed through the first record's in-edge index
+    const int32_t* node_rec;
+    int wp, wf;
 };
 
-template <int NT>
+template <int NT, bool CL>      // (CL: as cogmen_fwd_tile_kernel)
 __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p) {
     constexpr bool X = NT > 1;
     using XM = BxMap<X ? NT : 2>;
@@ -950,10 +970,27 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
     // ---- stage 0: graph slices and row tiles -> LDS
     const int o_lo_node = min(max(ob, 0), N), o_hi_node = min(max(ob + CG_OUT, 0), N);
     const int m_lo_node = min(max(mb, 0), N), m_hi_node = min(max(mb + CG_MID, 0), N);
-    const int E_lo = p.in_ptr[o_lo_node], E_hi = min(p.in_ptr[o_hi_node], E_lo + BW_ECAP);
-    const int O_lo = p.out_ptr[m_lo_node], O_hi = min(p.out_ptr[m_hi_node], O_lo + BW_OCAP);
-    if (tid < CG_OUT + 1) sIp[tid] = p.in_ptr[min(max(ob + tid, 0), N)];
-    if (tid >= 64 && tid < 64 + CG_MID + 1) sOp[tid - 64] = p.out_ptr[min(max(mb + tid - 64, 0), N)];
+    constexpr bool closed = CL;
+    int E_lo, E_hi, O_lo = 0, O_hi = 0;
+    if constexpr (closed) {
+        E_lo = p.node_rec[4 * (int64_t)o_lo_node + 2], E_hi = min(p.node_rec[4 * (int64_t)o_hi_node + 2], E_lo + BW_ECAP);
+        // outer row t: sIp as below, sSrc[t] = first source node, sOd[t] / sOd[64 + t] = position / dialogue length; sOt[t] = speaker (-1: no such node)
+        if (tid < CG_OUT + 1) {
+            const int nc = min(max(ob + tid, 0), N);
+            const int4 rec = *reinterpret_cast<const int4*>(p.node_rec + 4 * (int64_t)nc);
+            sIp[tid] = rec.z, sSrc[tid] = nc - min(rec.x, p.wf), sOd[tid] = rec.x, sOd[64 + tid] = rec.y;
+        }
+        if (tid >= 64 && tid < 64 + CG_OUT) {
+            const int node = ob + tid - 64;
+            const int sp = p.node_spk[min(max(node, 0), N - 1)];
+            sOt[tid - 64] = (node >= 0 && node < N) ? sp : -1;
+        }
+    } else {
+        E_lo = p.in_ptr[o_lo_node], E_hi = min(p.in_ptr[o_hi_node], E_lo + BW_ECAP);
+        O_lo = p.out_ptr[m_lo_node], O_hi = min(p.out_ptr[m_hi_node], O_lo + BW_OCAP);
+        if (tid < CG_OUT + 1) sIp[tid] = p.in_ptr[min(max(ob + tid, 0), N)];
+        if (tid >= 64 && tid < 64 + CG_MID + 1) sOp[tid - 64] = p.out_ptr[min(max(mb + tid - 64, 0), N)];
+    }
     if (tid >= 128 && tid < 128 + CG_TR) sSpkOwn[tid - 128] = p.node_spk[min(r0 + tid - 128, N - 1)];
     double* const sHp = reinterpret_cast<double*>(lds + (X ? XM::E_OFF : BW_SDQ_OFF));                  // [4][256] partial sums of the head records
     float* const sBnB = reinterpret_cast<float*>(lds + (X ? XM::E_OFF : BW_SDQ_OFF) + 4 * 256 * 8);     // [224] mean dY | mean dY * xhat
@@ -1002,11 +1039,13 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
             const int ei = min(E_lo + tid, max(E_hi - 1, E_lo));
             const bool ok = E_lo + tid < E_hi;
             const float a = p.alpha[ei];
-            const int sj = p.in_src[ei];
             sAl[tid] = ok ? a : 0.f;
-            sSrc[tid] = ok ? sj : 0;
+            if (!closed) {
+                const int sj = p.in_src[ei];
+                sSrc[tid] = ok ? sj : 0;
+            }
         }
-        if (tid >= 512 && tid < 512 + BW_OCAP) {
+        if (!closed && tid >= 512 && tid < 512 + BW_OCAP) {
             const int i = tid - 512;
             const int oi = min(O_lo + i, max(O_hi - 1, O_lo));
             const bool ok = O_lo + i < O_hi;
@@ -1120,7 +1159,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
             const int tc = min(t, CG_OUT - 1);
             const int e0 = min(max(sIp[tc] - E_lo, 0), BW_ECAP - 1);
             const int cnt = tv ? min(max(sIp[tc + 1] - sIp[tc], 0), CG_CH) : 0;
-            const int lo = sSrc[e0];                           // first source node of the target's in-edges
+            const int lo = sSrc[closed ? tc : e0];             // first source node of the target's in-edges
             const int o0 = (fb + 16 * bi + r) - lo, o1 = o0 + 16;   // edge position of source column r of the two tiles
             const bool k0 = o0 >= 0 && o0 < cnt, k1 = o1 >= 0 && o1 < cnt;
             const float al0 = k0 ? sAl[min(e0 + max(o0, 0), BW_ECAP - 1)] : 0.f;
@@ -1363,19 +1402,44 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
         uint32_t* const sDPw = reinterpret_cast<uint32_t*>(sDP);
         const int li = w, em = CG_HL + li, node = r0 + li;
         const bool valid = node < N;
-        const int o0 = __builtin_amdgcn_readfirstlane(sOp[em] - O_lo), o1 = __builtin_amdgcn_readfirstlane(sOp[em + 1] - O_lo);
-        const int nwin = valid ? min(max(o1 - o0, 0), CG_CH) : 0;
-        const int xb = max(o0, 0);
-        // lane u holds out-edge u of the row
-        const int xm = min(xb + min(lane, max(nwin - 1, 0)), BW_OCAP - 1);
-        const int my_off = min(max(sOd[xm] - mb, 0), CG_MID - 1) * CG_F, my_typ = lane < nwin ? sOt[xm] : CG_R;
-        const float my_w = sOw[xm];
+        int nwin, my_off, my_typ;
+        float my_w;
+        if (closed) {
+            // the out-edges of source j (position pp of a dialogue of L rows, speaker b) go to the targets at positions
+            // [pp - wp, pp + wf]; lane u holds the u-th: relation 4 b + 2 spk(target) + (pp < k ? 0 : 1), and the count of
+            // (target, relation) is the number of rows with speaker b in the past / future half of the target's own window -- the
+            // same speaker masks and the same 1.0f / (float)c the forward tile stores as inv_cnt
+            const int to = 2 * CG_HL + li;                                   // outer row of the source
+            const int pp = __builtin_amdgcn_readfirstlane(sOd[to]), L = __builtin_amdgcn_readfirstlane(sOd[64 + to]);
+            const int klo = max(0, pp - p.wp);
+            nwin = valid ? min(max(min(L - 1, pp + p.wf) - klo + 1, 0), CG_CH) : 0;
+            const int my_spk = lane < CG_OUT ? sOt[lane] : -1;
+            const unsigned long long mask0 = __ballot(my_spk == 0), mask1 = __ballot(my_spk == 1);
+            const int b = __builtin_amdgcn_readfirstlane(min(max(sSpkOwn[li], 0), 1));
+            const int kp = klo + min(lane, max(nwin - 1, 0));                // position of this lane's target
+            const int tk = min(max(to + kp - pp, CG_HL), CG_OUT - CG_HL - 1);   // its outer row
+            const int dir = pp < kp ? 0 : 1;
+            const int x0 = dir ? tk : tk - min(kp, p.wf), x1 = dir ? tk + min(p.wp, max(L - 1 - kp, 0)) + 1 : tk;   // rows of the counted half window
+            const unsigned long long rm = x1 > x0 ? ((~0ull >> (64 - (x1 - x0))) << x0) : 0ull;
+            const int c = __popcll((b ? mask1 : mask0) & rm);
+            my_off = (tk - CG_HL) * CG_F;
+            my_typ = lane < nwin ? 4 * b + 2 * min(max(sOt[tk], 0), 1) + dir : CG_R;
+            my_w = c > 0 ? 1.0f / (float)c : 0.f;
+        } else {
+            const int o0 = __builtin_amdgcn_readfirstlane(sOp[em] - O_lo), o1 = __builtin_amdgcn_readfirstlane(sOp[em + 1] - O_lo);
+            nwin = valid ? min(max(o1 - o0, 0), CG_CH) : 0;
+            const int xb = max(o0, 0);
+            // lane u holds out-edge u of the row
+            const int xm = min(xb + min(lane, max(nwin - 1, 0)), BW_OCAP - 1);
+            my_off = min(max(sOd[xm] - mb, 0), CG_MID - 1) * CG_F, my_typ = lane < nwin ? sOt[xm] : CG_R;
+            my_w = sOw[xm];
+        }
         float s0[CG_R], s1[CG_R];
 #pragma unroll
         for (int q = 0; q < CG_R; ++q) s0[q] = s1[q] = 0.f;
         float t0[4] = {0.f, 0.f, 0.f, 0.f}, t1[4] = {0.f, 0.f, 0.f, 0.f};      // (two-speaker path) the four non-empty relation blocks
         int b4 = 0;
-        if (X || p.two_spk) {
+        if (X || closed || p.two_spk) {
             // two speakers: an out-edge of a source with speaker b has relation 4 b + (2 spk(target) + dir), so only the
             // four blocks 4 b .. 4 b + 3 of the row are non-empty: all 12 target rows are requested at once and a 4-way
             // scalar branch picks the accumulator (the rolled two-edges-per-trip loop below pays an LDS round trip per trip)
@@ -1512,12 +1576,12 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
 }
 
 bool ensure_lds(const void* kernel, int bytes) {
-    static const void* known[4];
+    static const void* known[12];
     static int n_known = 0;
     for (int i = 0; i < n_known; ++i)
         if (known[i] == kernel) return true;
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-    if (n_known < 4) known[n_known++] = kernel;
+    if (n_known < 12) known[n_known++] = kernel;
     return true;
 }
 
@@ -1532,6 +1596,15 @@ extern "C" int erc_cogmen_set_stamps(uint64_t* stamps) {
     return ERC_OK;
 }
 
+// ---- graph slices of the tile kernels: 1 (default) = closed form from the node records where a launch is given them (two-speaker
+//      graphs), 0 = always the CSR.  Process-wide, read when a launch is enqueued (as erc_set_store_mode): a captured step keeps its form
+static int g_tile_slices = 1;
+extern "C" int erc_set_tile_slices(int mode) {
+    ERC_REQUIRE(mode == 0 || mode == 1, "set_tile_slices: mode = %d (0 csr, 1 closed)", mode);
+    g_tile_slices = mode;
+    return ERC_OK;
+}
+
 extern "C" int64_t erc_cogmen_fwd_tile_ws_doubles(int n_nodes) { return (int64_t)erc_cdiv(n_nodes, CG_TR) * 2 * CG_F + 2; }
 
 static int fwd_tile_launch(int terms, const float* H0, int ldh0, int n_nodes, int wp, int wf, const int32_t* in_ptr,
@@ -1540,7 +1613,7 @@ static int fwd_tile_launch(int terms, const float* H0, int ldh0, int n_nodes, in
                            void* H1b, int ldh1b, float* QKVS, float* H2, int ldh2, float* alpha, int bn_fused,
                            float* running_mean, float* running_var, float momentum, float eps, float* saved,
                            double* bn_ws, const int32_t* node_spk, int n_speakers, const int32_t* n_dev, int32_t* health,
-                           int32_t* events, void* stream) {
+                           int32_t* events, const int32_t* node_rec, void* stream) {
     ERC_REQUIRE(H0 && in_ptr && in_src && in_typ && WcatT && b1 && Wq && bq && Mb && inv_cnt && H1b && QKVS && H2 && alpha && node_spk,
                 "cogmen_fwd_tile: null pointer");
     ERC_REQUIRE(!health == !events, "cogmen_fwd_tile: health and events come together");
@@ -1556,11 +1629,11 @@ static int fwd_tile_launch(int terms, const float* H0, int ldh0, int n_nodes, in
                 "cogmen_fwd_tile_x: terms = %d (2 | 3), two-speaker graphs only (n_speakers = %d), plane strides multiples of 8", terms, n_speakers);
     ERC_REQUIRE(bn_fused >= 0 && bn_fused <= 2 && (bn_fused != 1 || (running_mean && running_var && saved)) && (!bn_fused || bn_ws),
                 "cogmen_fwd_tile: BatchNorm operands");
-    const void* kern = terms == 1 ? reinterpret_cast<const void*>(cogmen_fwd_tile_kernel<1>)
-                     : terms == 2 ? reinterpret_cast<const void*>(cogmen_fwd_tile_kernel<2>)
-                                  : reinterpret_cast<const void*>(cogmen_fwd_tile_kernel<3>);
+    const bool closed = g_tile_slices && n_speakers == 2 && node_rec;      // (struct CgFwdP: closed-form graph slices)
+    void (*const kern)(const CgFwdP) = closed ? (terms == 1 ? cogmen_fwd_tile_kernel<1, true> : terms == 2 ? cogmen_fwd_tile_kernel<2, true> : cogmen_fwd_tile_kernel<3, true>)
+                                              : (terms == 1 ? cogmen_fwd_tile_kernel<1, false> : terms == 2 ? cogmen_fwd_tile_kernel<2, false> : cogmen_fwd_tile_kernel<3, false>);
     const int lds_bytes = terms == 1 ? FW_LDS : terms == 2 ? FxMap<2>::LDS : FxMap<3>::LDS;
-    ERC_REQUIRE(ensure_lds(kern, lds_bytes), "cogmen_fwd_tile: %d bytes of LDS refused", lds_bytes);
+    ERC_REQUIRE(ensure_lds(reinterpret_cast<const void*>(kern), lds_bytes), "cogmen_fwd_tile: %d bytes of LDS refused", lds_bytes);
     CgFwdP p{};
     p.H0 = H0; p.in_ptr = in_ptr; p.in_src = in_src; p.in_typ = in_typ; p.WcatT = (const unsigned short*)WcatT; p.b1 = b1;
     p.Wq = (const unsigned short*)Wq; p.bq = bq; p.inv_cnt = inv_cnt;
@@ -1578,15 +1651,15 @@ static int fwd_tile_launch(int terms, const float* H0, int ldh0, int n_nodes, in
     p.N = n_nodes; p.ldh0 = ldh0; p.ldh2 = ldh2; p.bn_fused = bn_fused;
     p.node_spk = node_spk; p.two_spk = n_speakers == 2 ? 1 : 0; p.n_dev = n_dev;
     p.health = health, p.events = events;
+    ERC_REQUIRE(((uintptr_t)node_rec & 15) == 0, "cogmen_fwd_tile: node_rec must be 16-byte aligned");
+    p.node_rec = closed ? node_rec : nullptr; p.wp = wp; p.wf = wf;
     // output stores (struct CgFwdP): row pieces need 16-byte rows that hold every piece; other pitches keep the per-lane stores
     p.wt = erc_store_mode();
     p.mb_rows = terms == 1 && ldmb % 8 == 0 && ldmb >= 8 * ((CG_KM + 7) / 8) && ((uintptr_t)Mb & 15) == 0;
     p.h1_rows = terms == 1 && ldh1b % 8 == 0 && ldh1b >= 8 * ((CG_F + 7) / 8) && ((uintptr_t)H1b & 15) == 0;
     p.h2_rows = bn_fused != 0 && ldh2 % 4 == 0 && ((uintptr_t)H2 & 15) == 0;
     p.stamps = g_cg_stamps; p.stamp_block = tiles / 2;
-    if (terms == 1) hipLaunchKernelGGL(cogmen_fwd_tile_kernel<1>, dim3(tiles), dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
-    else if (terms == 2) hipLaunchKernelGGL(cogmen_fwd_tile_kernel<2>, dim3(tiles), dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(cogmen_fwd_tile_kernel<3>, dim3(tiles), dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("cogmen_fwd_tile");
     return ERC_OK;
 }
@@ -1597,10 +1670,10 @@ extern "C" int erc_cogmen_fwd_tile(const float* H0, int ldh0, int n_nodes, int w
                                    int ldh1b, float* QKVS, float* H2, int ldh2, float* alpha, int bn_fused,
                                    float* running_mean, float* running_var, float momentum, float eps, float* saved,
                                    double* bn_ws, const int32_t* node_spk, int n_speakers, const int32_t* n_dev, int32_t* health,
-                                   int32_t* events, void* stream) {
+                                   int32_t* events, const int32_t* node_rec, void* stream) {
     return fwd_tile_launch(1, H0, ldh0, n_nodes, wp, wf, in_ptr, in_src, in_typ, WcatT, 0, b1, Wq, 0, bq, scale, Mb, ldmb, inv_cnt, H1b,
                            ldh1b, QKVS, H2, ldh2, alpha, bn_fused, running_mean, running_var, momentum, eps, saved, bn_ws, node_spk,
-                           n_speakers, n_dev, health, events, stream);
+                           n_speakers, n_dev, health, events, node_rec, stream);
 }
 
 // Split compute modes (terms = 2 | 3): WcatT / Wq = that many bf16 term planes (ErcShadowTab mode 1, planes catT_plane / q_plane
@@ -1612,11 +1685,11 @@ extern "C" int erc_cogmen_fwd_tile_x(int terms, const float* H0, int ldh0, int n
                                      int ldmf, float* inv_cnt, float* H1f, int ldh1f, float* QKVS, float* H2, int ldh2,
                                      float* alpha, int bn_fused, float* running_mean, float* running_var, float momentum,
                                      float eps, float* saved, double* bn_ws, const int32_t* node_spk, int n_speakers,
-                                     const int32_t* n_dev, int32_t* health, int32_t* events, void* stream) {
+                                     const int32_t* n_dev, int32_t* health, int32_t* events, const int32_t* node_rec, void* stream) {
     ERC_REQUIRE(terms == 2 || terms == 3, "cogmen_fwd_tile_x: terms = %d (2 or 3)", terms);
     return fwd_tile_launch(terms, H0, ldh0, n_nodes, wp, wf, in_ptr, in_src, in_typ, WcatT, catT_plane, b1, Wq, q_plane, bq, scale, Mf,
                            ldmf, inv_cnt, H1f, ldh1f, QKVS, H2, ldh2, alpha, bn_fused, running_mean, running_var, momentum, eps, saved,
-                           bn_ws, node_spk, n_speakers, n_dev, health, events, stream);
+                           bn_ws, node_spk, n_speakers, n_dev, health, events, node_rec, stream);
 }
 
 static int bwd_tile_launch(int terms, const float* dY, const float* H2, int ldh2, int n_nodes, int wp, int wf, const float* gamma,
@@ -1626,7 +1699,7 @@ static int bwd_tile_launch(int terms, const float* dY, const float* H2, int ldh2
                            const void* Wb, int64_t wb_plane, float scale, void* dQKVS, void* dH1, void* dH0, int lddh0,
                            const int32_t* node_spk, int n_speakers, const float* head_part, int head_parts,
                            int head_part_floats, float* dgamma, float* dbeta, float* stats, int grads_bf16, int lddh1,
-                           const int32_t* n_dev, void* stream) {
+                           const int32_t* n_dev, const int32_t* node_rec, void* stream) {
     ERC_REQUIRE(!head_part || (head_parts > 0 && head_part_floats >= 227 && head_part_floats <= 256 && dgamma && dbeta && stats),
                 "cogmen_bwd_tile: head record operands");
     ERC_REQUIRE(dY && H2 && gamma && saved && bn_bwd && QKVS && alpha && in_ptr && in_src && out_ptr && out_dst && out_typ &&
@@ -1642,11 +1715,11 @@ static int bwd_tile_launch(int terms, const float* dY, const float* H2, int ldh2
                                wb_plane > 0 && wb_plane % 8 == 0 && ((uintptr_t)dQKVS & 7) == 0),
                 "cogmen_bwd_tile_x: terms = %d (2 | 3), two-speaker graphs only (n_speakers = %d), fp32 gradients, plane strides multiples of 8",
                 terms, n_speakers);
-    const void* kern = terms == 1 ? reinterpret_cast<const void*>(cogmen_bwd_tile_kernel<1>)
-                     : terms == 2 ? reinterpret_cast<const void*>(cogmen_bwd_tile_kernel<2>)
-                                  : reinterpret_cast<const void*>(cogmen_bwd_tile_kernel<3>);
+    const bool closed = g_tile_slices && n_speakers == 2 && node_rec;      // (struct CgBwdP: closed-form graph slices)
+    void (*const kern)(const CgBwdP) = closed ? (terms == 1 ? cogmen_bwd_tile_kernel<1, true> : terms == 2 ? cogmen_bwd_tile_kernel<2, true> : cogmen_bwd_tile_kernel<3, true>)
+                                              : (terms == 1 ? cogmen_bwd_tile_kernel<1, false> : terms == 2 ? cogmen_bwd_tile_kernel<2, false> : cogmen_bwd_tile_kernel<3, false>);
     const int lds_bytes = terms == 1 ? BW_LDS : terms == 2 ? BxMap<2>::LDS : BxMap<3>::LDS;
-    ERC_REQUIRE(ensure_lds(kern, lds_bytes), "cogmen_bwd_tile: %d bytes of LDS refused", lds_bytes);
+    ERC_REQUIRE(ensure_lds(reinterpret_cast<const void*>(kern), lds_bytes), "cogmen_bwd_tile: %d bytes of LDS refused", lds_bytes);
     CgBwdP p{};
     p.dY = dY; p.H2 = H2; p.gamma = gamma; p.saved = saved; p.bn_bwd = bn_bwd; p.QKVS = QKVS; p.alpha = alpha;
     p.in_ptr = in_ptr; p.in_src = in_src; p.out_ptr = out_ptr; p.out_dst = out_dst; p.out_typ = out_typ; p.out_eid = out_eid;
@@ -1657,15 +1730,15 @@ static int bwd_tile_launch(int terms, const float* dY, const float* H2, int ldh2
     p.node_spk = node_spk; p.two_spk = n_speakers == 2 ? 1 : 0; p.n_dev = n_dev;
     p.head_part = head_part; p.head_parts = head_parts; p.hp_floats = head_part_floats; p.bn_bwd_out = const_cast<float*>(bn_bwd);
     p.dgamma = dgamma; p.dbeta = dbeta; p.stats = stats;
+    ERC_REQUIRE(((uintptr_t)node_rec & 15) == 0, "cogmen_bwd_tile: node_rec must be 16-byte aligned");
+    p.node_rec = closed ? node_rec : nullptr; p.wp = wp; p.wf = wf;
     // output stores (struct CgBwdP): row pieces for the bf16 gradients whose rows are 16-byte multiples (dQKVS: 800 bytes)
     p.wt = erc_store_mode();
     p.dq_rows = terms == 1 && grads_bf16 && ((uintptr_t)dQKVS & 15) == 0;
     p.dh1_rows = terms == 1 && grads_bf16 && lddh1 % 8 == 0 && lddh1 >= 8 * ((CG_F + 7) / 8) && ((uintptr_t)dH1 & 15) == 0;
     p.stamps = g_cg_stamps; p.stamp_block = erc_cdiv(n_nodes, CG_TR) / 2;
     const dim3 grid(erc_cdiv(n_nodes, CG_TR));
-    if (terms == 1) hipLaunchKernelGGL(cogmen_bwd_tile_kernel<1>, grid, dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
-    else if (terms == 2) hipLaunchKernelGGL(cogmen_bwd_tile_kernel<2>, grid, dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(cogmen_bwd_tile_kernel<3>, grid, dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kern, grid, dim3(CG_NTH), lds_bytes, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("cogmen_bwd_tile");
     return ERC_OK;
 }
@@ -1677,10 +1750,10 @@ extern "C" int erc_cogmen_bwd_tile(const float* dY, const float* H2, int ldh2, i
                                    const void* Wb, float scale, void* dQKVS, void* dH1, void* dH0, int lddh0,
                                    const int32_t* node_spk, int n_speakers, const float* head_part, int head_parts,
                                    int head_part_floats, float* dgamma, float* dbeta, float* stats, int grads_bf16, int lddh1,
-                                   const int32_t* n_dev, void* stream) {
+                                   const int32_t* n_dev, const int32_t* node_rec, void* stream) {
     return bwd_tile_launch(1, dY, H2, ldh2, n_nodes, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, in_ptr, in_src, out_ptr, out_dst, out_typ,
                            out_eid, inv_cnt, WqT, 0, Wb, 0, scale, dQKVS, dH1, dH0, lddh0, node_spk, n_speakers, head_part, head_parts,
-                           head_part_floats, dgamma, dbeta, stats, grads_bf16, lddh1, n_dev, stream);
+                           head_part_floats, dgamma, dbeta, stats, grads_bf16, lddh1, n_dev, node_rec, stream);
 }
 
 // Split compute modes (terms = 2 | 3): WqT / Wb = that many bf16 term planes, qT_plane / wb_plane elements apart; the three gradient
@@ -1692,9 +1765,9 @@ extern "C" int erc_cogmen_bwd_tile_x(int terms, const float* dY, const float* H2
                                      const void* WqT, int64_t qT_plane, const void* Wb, int64_t wb_plane, float scale, float* dQKVS,
                                      float* dH1, float* dH0, int lddh0, const int32_t* node_spk, int n_speakers,
                                      const float* head_part, int head_parts, int head_part_floats, float* dgamma, float* dbeta,
-                                     float* stats, int lddh1, const int32_t* n_dev, void* stream) {
+                                     float* stats, int lddh1, const int32_t* n_dev, const int32_t* node_rec, void* stream) {
     ERC_REQUIRE(terms == 2 || terms == 3, "cogmen_bwd_tile_x: terms = %d (2 or 3)", terms);
     return bwd_tile_launch(terms, dY, H2, ldh2, n_nodes, wp, wf, gamma, saved, bn_bwd, QKVS, alpha, in_ptr, in_src, out_ptr, out_dst,
                            out_typ, out_eid, inv_cnt, WqT, qT_plane, Wb, wb_plane, scale, dQKVS, dH1, dH0, lddh0, node_spk, n_speakers,
-                           head_part, head_parts, head_part_floats, dgamma, dbeta, stats, 0, lddh1, n_dev, stream);
+                           head_part, head_parts, head_part_floats, dgamma, dbeta, stats, 0, lddh1, n_dev, node_rec, stream);
 }

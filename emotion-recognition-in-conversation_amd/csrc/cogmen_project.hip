@@ -47,7 +47,23 @@ struct PgP {
     // dialogue slot b (0: empty slot), desc[B + b] = its first row in the store.  X / speakers are then the store's [U, ldx]
     // feature rows / [U] speaker ids, lengths is unused, and node_row holds store rows: no padded [B, T, D] block exists.
     const int32_t* desc;
+    // NODE RECORDS (or null): node_rec [n_cap + 1][4] = {position in the dialogue, dialogue length, index of the node's first in-edge,
+    // index of its first out-edge} -- with the speakers, everything the CSR arrays of a node hold in closed form (the tile kernels of
+    // csrc/cogmen_fused.hip derive their graph slices from them).  Record N = {0, 0, E, E}: an empty window.
+    int32_t* node_rec;
 };
+
+// p.node_rec, loaded WHERE IT IS USED.  Kernel arguments are loaded in the entry block, and this kernel is at its scalar-register
+// limit: one more pointer live from the entry on put two arguments into spill lanes, each behind a wait of its own in front of the
+// weight-fragment loads (+0.45 us per launch).  A volatile load from the argument segment stays at its place.  (The split modes'
+// instances keep the plain field: they spill either way, and with the late load they were given a private segment.)  PgP is the
+// kernel's only parameter: the argument segment begins with it.
+template <int NT>
+__device__ __forceinline__ int32_t* pg_node_rec(const PgP& p) {
+    if constexpr (NT > 1) return p.node_rec;
+    const char __attribute__((address_space(4)))* const args = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(int32_t* const volatile __attribute__((address_space(4)))*)(args + offsetof(PgP, node_rec));
+}
 
 // NT: bf16 terms per operand value (1: the bf16 compute mode); PG_NT: column tiles of 16 per workgroup; NWG: workgroups that
 // share a row group (ids id, id + 8, ..: one XCD), NWG * PG_NT >= 7
@@ -130,6 +146,8 @@ __global__ __launch_bounds__(512) void cogmen_project_graph_kernel(const PgP p) 
         if (tid == 0) {
             p.counts[0] = N, p.counts[1] = Etot;
             if (cap_ok) p.in_ptr[N] = Etot, p.out_ptr[N] = Etot;
+            int32_t* const node_rec = pg_node_rec<NT>(p);
+            if (cap_ok && node_rec) *reinterpret_cast<int4*>(node_rec + 4 * (int64_t)N) = make_int4(0, 0, Etot, Etot);
         }
     }
     if (!cap_ok || N <= 0) return;
@@ -251,6 +269,7 @@ __global__ __launch_bounds__(512) void cogmen_project_graph_kernel(const PgP p) 
                 // in-edges of target pp: sources j in [pp - wf, pp + wp]  (canonical order: target-major, then source)
                 const int lo = max(0, pp - p.wf), hi = min(Lb - 1, pp + p.wp);
                 const int base = eoff + erc_window_prefix(pp, Lb, p.wf, p.wp);
+                int32_t* const node_rec = pg_node_rec<NT>(p);      // (requested in front of the edge loop, used behind it)
                 if (slot == 0 && nv) p.node_row[n] = s_base[b] + pp, p.node_spk[n] = sp, p.in_ptr[n] = base;
                 for (int j = lo + slot; j <= hi; j += 16) {
                     const int sj = j == lo + slot ? s_nb : (int)spk[(int64_t)j * p.spk_st];
@@ -260,6 +279,8 @@ __global__ __launch_bounds__(512) void cogmen_project_graph_kernel(const PgP p) 
                         p.in_typ[e] = 2 * (sj * p.S + sp) + (j < pp ? 0 : 1);
                     }
                 }
+                if (slot == 0 && nv && node_rec)
+                    *reinterpret_cast<int4*>(node_rec + 4 * (int64_t)n) = make_int4(pp, Lb, base, eoff + erc_window_prefix(pp, Lb, p.wp, p.wf));
             } else {
                 // out-edges of source pp: targets k in [pp - wp, pp + wf]; out_eid = the edge's slot in the by-target CSR
                 const int lo = max(0, pp - p.wp), hi = min(Lb - 1, pp + p.wf);
@@ -291,19 +312,20 @@ static int project_graph_launch(int terms, const void* X, int ldx, const void* W
                                 int64_t spk_st, int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
                                 int32_t* node_off, int32_t* node_row, int32_t* node_spk, int32_t* in_ptr, int32_t* in_src,
                                 int32_t* in_typ, int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
-                                int32_t* counts, const int32_t* desc, void* stream) {
+                                int32_t* counts, const int32_t* desc, int32_t* node_rec, void* stream) {
     ERC_REQUIRE(X && W && bias && H0 && (lengths || desc) && speakers && node_off && node_row && node_spk && in_ptr && in_src && in_typ &&
                     out_ptr && out_dst && out_typ && out_eid && counts,
                 "cogmen_project_graph: null pointer");
     ERC_REQUIRE(erc_cogmen_project_graph_ok(K, n_out, B, ldx, ldw) && ((uintptr_t)X & (terms > 1 ? 15 : 7)) == 0 && ((uintptr_t)W & 7) == 0 &&
                     ldh0 >= n_out && T > 0 && n_speakers > 0 && n_cap > 0 && e_cap > 0,
                 "cogmen_project_graph: unsupported sizes K=%d n_out=%d B=%d T=%d (erc_cogmen_project_graph_ok)", K, n_out, B, T);
+    ERC_REQUIRE(((uintptr_t)node_rec & 15) == 0, "cogmen_project_graph: node_rec must be 16-byte aligned");
     ERC_REQUIRE(wp >= -1 && wf >= -1, "cogmen_project_graph: window must be >= -1");
     ERC_REQUIRE(terms >= 1 && terms <= 3 && (terms == 1 || (w_plane > 0 && w_plane % 4 == 0)), "cogmen_project_graph: terms=%d w_plane=%lld",
                 terms, (long long)w_plane);
     PgP p{X, (const unsigned short*)W, w_plane, bias, H0, ldx, ldw, ldh0, K, n_out, lengths, speakers, spk_sb, spk_st,
           B, T, wp < 0 ? T : wp, wf < 0 ? T : wf, n_speakers, n_cap, e_cap, node_off, node_row, node_spk, in_ptr, in_src, in_typ,
-          out_ptr, out_dst, out_typ, out_eid, counts, desc};
+          out_ptr, out_dst, out_typ, out_eid, counts, desc, node_rec};
     // 128 pairs of workgroups (bf16 mode: column tiles 0-3 | 4-6); 64 quads in the split modes (two tiles each: 96 / 144 registers of
     // resident weight fragments per lane; measured at config 2: two terms 13.8 us as quads, 16.0 as 80 triples of three tiles; three terms
     // 17.2 us as quads, 20.9 as 32 octets of one tile)
@@ -319,10 +341,10 @@ extern "C" int erc_cogmen_project_graph(const void* X, int ldx, const void* W, i
                                         int64_t spk_st, int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
                                         int32_t* node_off, int32_t* node_row, int32_t* node_spk, int32_t* in_ptr,
                                         int32_t* in_src, int32_t* in_typ, int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ,
-                                        int32_t* out_eid, int32_t* counts, const int32_t* desc, void* stream) {
+                                        int32_t* out_eid, int32_t* counts, const int32_t* desc, int32_t* node_rec, void* stream) {
     return project_graph_launch(1, X, ldx, W, 0, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, spk_sb, spk_st, B, T, wp, wf,
                                 n_speakers, n_cap, e_cap, node_off, node_row, node_spk, in_ptr, in_src, in_typ, out_ptr, out_dst,
-                                out_typ, out_eid, counts, desc, stream);
+                                out_typ, out_eid, counts, desc, node_rec, stream);
 }
 
 // Split compute modes: X fp32 [rows, ldx] (16-byte aligned rows), W = `terms` (2 | 3) bf16 planes [n_out, ldw], w_plane elements apart
@@ -332,9 +354,9 @@ extern "C" int erc_cogmen_project_graph_x(int terms, const float* X, int ldx, co
                                           int64_t spk_sb, int64_t spk_st, int B, int T, int wp, int wf, int n_speakers, int n_cap,
                                           int e_cap, int32_t* node_off, int32_t* node_row, int32_t* node_spk, int32_t* in_ptr,
                                           int32_t* in_src, int32_t* in_typ, int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ,
-                                          int32_t* out_eid, int32_t* counts, const int32_t* desc, void* stream) {
+                                          int32_t* out_eid, int32_t* counts, const int32_t* desc, int32_t* node_rec, void* stream) {
     ERC_REQUIRE(terms == 2 || terms == 3, "cogmen_project_graph_x: terms = %d (2 or 3)", terms);
     return project_graph_launch(terms, X, ldx, W, w_plane, ldw, bias, H0, ldh0, n_out, K, lengths, speakers, spk_sb, spk_st, B, T, wp,
                                 wf, n_speakers, n_cap, e_cap, node_off, node_row, node_spk, in_ptr, in_src, in_typ, out_ptr, out_dst,
-                                out_typ, out_eid, counts, desc, stream);
+                                out_typ, out_eid, counts, desc, node_rec, stream);
 }

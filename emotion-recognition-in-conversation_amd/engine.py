@@ -706,6 +706,15 @@ def step_store_mode():
     return mode
 
 
+def tile_slice_mode():
+    """ERC_TILE_SLICES: ``closed`` (default: the COGMEN tile kernels derive their graph slices from the node records of the
+    projection launch) | ``csr`` (they read the CSR arrays: A/B runs).  DESIGN.md finding 66."""
+    mode = os.environ.get("ERC_TILE_SLICES", "") or "closed"
+    if mode not in ("csr", "closed"):
+        raise capi.ErcGraftError("ERC_TILE_SLICES=%s: expected 'csr' or 'closed'" % mode)
+    return mode
+
+
 class CapturedStep:
     """``fn()`` (``steps`` consecutive calls of it) captured into one HIP graph on the current device, and the way to replay it.
 
@@ -723,6 +732,8 @@ class CapturedStep:
         self.mode = mode or step_replay_mode()
         self.stores = step_store_mode()
         capi.set_store_mode(self.stores == "through")      # read by the launches as they are captured; a replay keeps it
+        self.slices = tile_slice_mode()
+        capi.set_tile_slices(self.slices == "closed")
         self.chain, self.refused = 0, None
         keep = self.mode != "graph"
         self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()

@@ -525,7 +525,7 @@ int erc_cogmen_fwd_tile(const float* H0, int ldh0, int n_nodes, int wp, int wf, 
                         int ldh1b, float* QKVS, float* H2, int ldh2, float* alpha, int bn_fused,
                         float* running_mean, float* running_var, float momentum, float eps, float* saved,
                         double* bn_ws, const int32_t* node_spk, int n_speakers, const int32_t* n_dev, int32_t* health,
-                        int32_t* events, void* stream);
+                        int32_t* events, const int32_t* node_rec, void* stream);
 /* Backward of the same: dY [N,100] = dL/d(BatchNorm output) (erc_head_fused), BatchNorm's elementwise backward
  * (gamma, saved, bn_bwd as erc_bn_bwd_apply), TransformerConv backward (target and source side), dH1 = dQKVS Wq,
  * the transposed relation means and dH0 = dP [W_r^T].  Outputs fp32: dQKVS [N,400], dH1 [N,100], dH0 [N, lddh0] --
@@ -540,7 +540,7 @@ int erc_cogmen_bwd_tile(const float* dY, const float* H2, int ldh2, int n_nodes,
                         const void* Wb, float scale, void* dQKVS, void* dH1, void* dH0, int lddh0,
                         const int32_t* node_spk, int n_speakers, const float* head_part, int head_parts,
                         int head_part_floats, float* dgamma, float* dbeta, float* stats, int grads_bf16, int lddh1,
-                        const int32_t* n_dev, void* stream);
+                        const int32_t* n_dev, const int32_t* node_rec, void* stream);
 /* SPLIT COMPUTE MODES (terms = 2 | 3; "f32x2" / "f32x3"): the same two launches at fp32-class accuracy -- what the reference's
  * fp32 GNN.forward / backward computes (track_mm/cogmen.py:61-74,187-188) -- on the bf16 matrix cores.  The weights are read
  * from `terms` bf16 PLANES per operand (ErcShadowTab with terms planes, *_plane elements apart: the bf16 expansion w = t0 + t1
@@ -555,7 +555,7 @@ int erc_cogmen_fwd_tile_x(int terms, const float* H0, int ldh0, int n_nodes, int
                           int ldmf, float* inv_cnt, float* H1f, int ldh1f, float* QKVS, float* H2, int ldh2,
                           float* alpha, int bn_fused, float* running_mean, float* running_var, float momentum,
                           float eps, float* saved, double* bn_ws, const int32_t* node_spk, int n_speakers,
-                          const int32_t* n_dev, int32_t* health, int32_t* events, void* stream);
+                          const int32_t* n_dev, int32_t* health, int32_t* events, const int32_t* node_rec, void* stream);
 int erc_cogmen_bwd_tile_x(int terms, const float* dY, const float* H2, int ldh2, int n_nodes, int wp, int wf,
                           const float* gamma, const float* saved, const float* bn_bwd, const float* QKVS,
                           const float* alpha, const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr,
@@ -563,7 +563,7 @@ int erc_cogmen_bwd_tile_x(int terms, const float* dY, const float* H2, int ldh2,
                           const void* WqT, int64_t qT_plane, const void* Wb, int64_t wb_plane, float scale, float* dQKVS,
                           float* dH1, float* dH0, int lddh0, const int32_t* node_spk, int n_speakers,
                           const float* head_part, int head_parts, int head_part_floats, float* dgamma, float* dbeta,
-                          float* stats, int lddh1, const int32_t* n_dev, void* stream);
+                          float* stats, int lddh1, const int32_t* n_dev, const int32_t* node_rec, void* stream);
 /* n_dev (here, in erc_cogmen_fwd_tile and in erc_head_fused{,_bn}; NULL = off): CAPACITY MODE.  n_nodes / n_rows is then the
  * capacity the grid and the buffers are sized for and the true count (<= capacity) is read from device memory -- counts[0]
  * of erc_cogmen_project_graph -- so that ONE captured HIP graph serves every batch whose node count fits the capacity
@@ -586,7 +586,7 @@ int erc_cogmen_project_graph(const void* X, int ldx, const void* W, int ldw, con
                              int64_t spk_st, int B, int T, int wp, int wf, int n_speakers, int n_cap, int e_cap,
                              int32_t* node_off, int32_t* node_row, int32_t* node_spk, int32_t* in_ptr, int32_t* in_src,
                              int32_t* in_typ, int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ, int32_t* out_eid,
-                             int32_t* counts, const int32_t* desc, void* stream);
+                             int32_t* counts, const int32_t* desc, int32_t* node_rec, void* stream);
 /* SPLIT COMPUTE MODES (terms = 2 | 3; "f32x2" / "f32x3"): the same launch with the fp32 feature block the reference feeds
  * rnn.1 (track_mm/cogmen.py:103-105,147) -- X fp32 [rows, ldx], 16-byte aligned rows -- and W = `terms` bf16 planes [n_out, ldw],
  * w_plane elements apart (ErcShadowTab mode 0, terms planes: the bf16 expansion of rnn.1.weight).  Every A fragment is
@@ -597,12 +597,25 @@ int erc_cogmen_project_graph_x(int terms, const float* X, int ldx, const void* W
                                int64_t spk_sb, int64_t spk_st, int B, int T, int wp, int wf, int n_speakers, int n_cap,
                                int e_cap, int32_t* node_off, int32_t* node_row, int32_t* node_spk, int32_t* in_ptr,
                                int32_t* in_src, int32_t* in_typ, int32_t* out_ptr, int32_t* out_dst, int32_t* out_typ,
-                               int32_t* out_eid, int32_t* counts, const int32_t* desc, void* stream);
+                               int32_t* out_eid, int32_t* counts, const int32_t* desc, int32_t* node_rec, void* stream);
 /* desc (or NULL): RESIDENT mode.  The batch is a list of B dialogue slots of a feature store that lives in HBM: desc[b] =
  * length of slot b (0 = empty), desc[B + b] = its first row in the store; X = the store's [U, ldx] bf16 feature rows,
  * speakers = its [U] speaker ids (element stride spk_st), lengths is unused (may be NULL), node_row receives STORE rows (the
  * weight-gradient gather and erc_head_fused's label_rows read the store through it).  No padded [B, T, D] block exists:
  * a training step needs 2 B int32 of new input. */
+
+/* node_rec (or NULL): NODE RECORDS, int32 [n_cap + 1][4], 16-byte aligned.  erc_cogmen_project_graph(_x) writes record n =
+ * {position of node n in its dialogue, length of that dialogue, index of its first in-edge (= in_ptr[n]), index of its first
+ * out-edge (= out_ptr[n])} next to the CSR arrays, and record N = {0, 0, E, E}.  The graph is a window graph: with the speakers,
+ * a node's record holds everything its CSR entries do.  erc_cogmen_fwd_tile(_x) / erc_cogmen_bwd_tile(_x), given the records of
+ * a TWO-SPEAKER graph built with the same (wp, wf), derive the graph slices of a tile from them in closed form instead of loading
+ * in_ptr / in_src / in_typ (forward) and in_ptr / in_src / out_ptr / out_dst / out_typ / inv_cnt (backward): the same integers,
+ * bit-identical results, fewer dependent loads in front of the first stage (DESIGN.md finding 66).  NULL, n_speakers != 2 or
+ * erc_set_tile_slices(0): the CSR is read as before.
+ * erc_set_tile_slices: 1 (the default) = closed form where records are given, 0 = always the CSR.  Process-wide; read when a launch
+ * is ENQUEUED, so a captured step keeps the form it was captured with.  Python sets it from ERC_TILE_SLICES=csr|closed before it
+ * captures a step.  Anything but 0 or 1 is ERC_E_ARG. */
+int erc_set_tile_slices(int mode);
 
 /* diagnostic: phase stamps (10 ns ticks) of the middle workgroup of the following erc_cogmen_{fwd,bwd}_tile launches,
  * 8 x uint64 device memory; NULL switches them off (tools/cogmen_stamps.py) */

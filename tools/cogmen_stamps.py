@@ -3,6 +3,8 @@
 launches with phase stamps switched on and prints the middle workgroup's per-phase time.
 
     python tools/cogmen_stamps.py [--batch 32]
+
+ERC_TILE_SLICES=csr|closed picks the form of the tile kernels' graph slices (default closed, as in a captured step).
 """
 import argparse
 import os
@@ -18,8 +20,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     a = ap.parse_args()
     from bench import synthetic_batch
-    from erc_amd import capi
+    from erc_amd import capi, engine
     import track_mm.cogmen as plugin
+    slices = engine.tile_slice_mode()
+    capi.set_tile_slices(slices == "closed")      # read by every launch below as it is enqueued, the replayed ones included
+    print("tile slices: %s" % slices)
     params = plugin.ParamsType().from_args(["--dataset=iemocap-cogmen-sbert-6", "--modality=atv", "--compute=bf16"])
     tr = plugin.COGMENTrainer(params, "cuda:0")
     batch = tr.prepare_batch(synthetic_batch(params, a.batch, 110, seed=1))
