@@ -547,60 +547,49 @@ def dag_meta_cap(speaker_onehot, speaker_ids, sb, st, S, lengths, desc, store_sp
           B, T, n_cap, spk, pred, node_off, node_row, x_row, label_out, counts)
 
 
-def _tcap_only(name, lengths, node_off):
-    if lengths is not None or node_off is not None:
-        raise ErcGraftError("%s: t_dev is the unpacked padded-row form (lengths=None, node_off=None)" % name)
+def _scan(base, args, lengths_at, t_at, t_dev, zero_to=0):
+    """One hidden-100 scan launch.  ``args`` is the argument tuple of ``erc_<base>``, with lengths and node_off at position
+    ``lengths_at``.  ``t_dev`` chooses ``erc_<base>_tcap``, the unpacked padded-row form: it takes neither of the two and has
+    t_dev at position ``t_at`` (behind T); else ``zero_to`` > 0 chooses ``erc_<base>_cap``, which takes it last."""
+    if t_dev is not None:
+        if args[lengths_at] is not None or args[lengths_at + 1] is not None:
+            raise ErcGraftError("%s: t_dev is the unpacked padded-row form (lengths=None, node_off=None)" % base)
+        args = args[:lengths_at] + args[lengths_at + 2:]
+        _call("erc_%s_tcap" % base, *args[:t_at], t_dev, *args[t_at:])
+    elif zero_to:
+        _call("erc_%s_cap" % base, *args, zero_to)
+    else:
+        _call("erc_" + base, *args)
 
 
 def lstm_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
                   rng_stream, gates, Cst, Hprev, t_dev=None):
     """``t_dev`` (device int32; unpacked padded rows): T is a capacity, *t_dev steps run (erc_lstm_scan_fwd_tcap, ercgraft.h)"""
-    if t_dev is not None:
-        _tcap_only("lstm_scan_fwd", lengths, node_off)
-        _call("erc_lstm_scan_fwd_tcap", GX, ldgx, W_hh, b_hh, sb, st, B, T, t_dev, Hout, ldh, Hdrop, ldhd, drop_p, rng, rng_stream,
-              gates, Cst, Hprev)
-        return
-    _call("erc_lstm_scan_fwd", GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
-          rng_stream, gates, Cst, Hprev)
+    _scan("lstm_scan_fwd", (GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng, rng_stream,
+                            gates, Cst, Hprev), 4, 8, t_dev)
 
 
 def lstm_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX, zero_to=0,
                   t_dev=None):
     """``zero_to`` > 0 (compact rows): dGX rows [node_off[B], zero_to) are written 0 too (capacity mode); ``t_dev`` (unpacked
     padded rows): *t_dev steps run, dGX rows t >= *t_dev are written 0 (erc_lstm_scan_bwd_tcap)"""
-    args = (W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
-    if t_dev is not None:
-        _tcap_only("lstm_scan_bwd", lengths, node_off)
-        _call("erc_lstm_scan_bwd_tcap", W_hh, sb, st, B, T, t_dev, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX)
-    elif zero_to:
-        _call("erc_lstm_scan_bwd_cap", *args, zero_to)
-    else:
-        _call("erc_lstm_scan_bwd", *args)
+    _scan("lstm_scan_bwd", (W_hh, lengths, node_off, sb, st, B, T, gates, Cst, dHout, lddh, drop_p, rng, rng_stream, dGX), 1, 5,
+          t_dev, zero_to)
 
 
 def gru100_scan_fwd(GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
                     rng_stream, gates, ghn, Hprev, t_dev=None):
     """hidden-100 weight-stationary GRU scan, one layer x both directions (csrc/gru100.hip; ercgraft.h); ``t_dev`` as
     lstm_scan_fwd (erc_gru100_scan_fwd_tcap)"""
-    if t_dev is not None:
-        _tcap_only("gru100_scan_fwd", lengths, node_off)
-        _call("erc_gru100_scan_fwd_tcap", GX, ldgx, W_hh, b_hh, sb, st, B, T, t_dev, Hout, ldh, Hdrop, ldhd, drop_p, rng, rng_stream,
-              gates, ghn, Hprev)
-        return
-    _call("erc_gru100_scan_fwd", GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
-          rng_stream, gates, ghn, Hprev)
+    _scan("gru100_scan_fwd", (GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, Hout, ldh, Hdrop, ldhd, drop_p, rng,
+                              rng_stream, gates, ghn, Hprev), 4, 8, t_dev)
 
 
 def gru100_scan_bwd(W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX, dGH,
                     t_dev=None):
     """``t_dev`` as lstm_scan_bwd: dGX / dGH rows t >= *t_dev are written 0 (erc_gru100_scan_bwd_tcap)"""
-    if t_dev is not None:
-        _tcap_only("gru100_scan_bwd", lengths, node_off)
-        _call("erc_gru100_scan_bwd_tcap", W_hh, sb, st, B, T, t_dev, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX,
-              dGH)
-        return
-    _call("erc_gru100_scan_bwd", W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream,
-          dGX, dGH)
+    _scan("gru100_scan_bwd", (W_hh, lengths, node_off, sb, st, B, T, gates, ghn, Hprev, dHout, lddh, drop_p, rng, rng_stream, dGX,
+                              dGH), 1, 5, t_dev)
 
 
 def gather_rows(src, lds, map_, N, F, dst, ldd, scatter=0):

@@ -96,10 +96,9 @@ __device__ __forceinline__ f32x4 tile_product(const float* sA, int pa, int l15, 
 constexpr int TNW = 8;              // wavefronts of a workgroup
 constexpr int TNTH = 64 * TNW;
 
-// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load in flight, and the weight
-// fragments of the NEXT phase are requested before each barrier (a phase would otherwise start with an L2 round trip per tile:
+// The phases meet at lds_barrier() (erc_common.h), not __syncthreads(): the weight fragments of the NEXT phase are requested
+// before each barrier and must stay in flight across it (a phase would otherwise start with an L2 round trip per tile:
 // measured 50 us for the launch with four wavefronts and loads issued per tile, against ~6 us of matrix-core time)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // CAP: the capacity-mode instance of the kernel (n_dev / label_rows may be set); the exact-shape instance compiles without them
 template <bool CAP>

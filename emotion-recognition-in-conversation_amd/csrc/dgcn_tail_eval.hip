@@ -72,8 +72,7 @@ __device__ __forceinline__ f32x4 tile_product(const float* sA, int pa, int l15, 
     return acc;
 }
 
-// workgroup barrier that orders LDS traffic only (the weight fragments of the NEXT phase stay in flight across it)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// the phases meet at lds_barrier() (erc_common.h): the weight fragments of the NEXT phase stay in flight across it
 
 __global__ __launch_bounds__(TNTH) void dgcn_tail_eval_kernel(const TailEvalP p) {
     __shared__ __attribute__((aligned(16))) float sX[TR * PX];      // [features | graph_out | 0]

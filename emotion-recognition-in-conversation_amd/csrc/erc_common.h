@@ -30,6 +30,10 @@ extern "C" void erc_set_error(const char* fmt, ...);
 static inline int erc_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 #ifdef __HIPCC__
+// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load, store and LDS-DMA request
+// in flight (vmcnt), which serialises whatever a kernel prefetches across the barrier behind it
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // full-wave (64 lane) sum, result in every lane
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -73,10 +73,8 @@ __device__ __forceinline__ int ld_i32(const int* p) { return __hip_atomic_load(p
 __device__ __forceinline__ void st_i32(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // one workgroup's 64 layers; MTC = 16-row MFMA tiles compiled in (1: 16-row parts, 2: 32-row parts)
-// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global load, which
-// would serialise the register prefetches (next layer's weights, c_l) behind each barrier
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
+// its barriers are lds_barrier() (erc_common.h): __syncthreads() would serialise the register prefetches (next layer's
+// weights, c_l) behind each barrier
 template <bool BWD, int MTC>
 __device__ __forceinline__ void chain_body(const Chain& p, float* smem, int b, int L, int nparts, int m, int part, int RW) {
     const int tid = threadIdx.x, lane = tid & 63, q4 = lane >> 4, l15 = lane & 15;

@@ -10,20 +10,24 @@
 // are requested one chunk ahead, the chunk's results leave at its end.  The backward scan keeps the transposed slices in
 // registers the same way and leaves all weight gradients to GEMMs over the gate gradients it writes (dGX, dGH) and the saved
 // h_{t-1}.  Every output element is produced by one thread in a fixed order (no atomics); no workgroup waits for another.
-// Plain HIP C++: the LDS-only barrier is the workgroup fence on the local address space around s_barrier.
-#include "erc_common.h"
+// What it shares with lstm.hip -- row maps, step counts, the chunked LDS layout, DPP moves, activations, the dropout
+// uniform -- is csrc/rnn100_dev.h.
+#include "rnn100_dev.h"
 
 namespace {
+using namespace rnn100;
 
-constexpr int H = 100;
 constexpr int G3 = 300;
-constexpr int NTH = 512;
-constexpr int SC = 8;              // steps per chunk: one round of global loads / stores per SC steps
-// vectors that every thread reads (h_{t-1}: 100 values, the recurrent gate gradients: 300) sit in LDS as chunks of 25 values
-// padded to 28 (16-byte rows, chunks 28 banks apart: the distinct addresses of one wavefront read never share a bank)
-constexpr int CHK = 25, CHP = 28;
-constexpr int HP = 4 * CHP;        // hidden state
-constexpr int DGP = 12 * CHP;      // recurrent gate gradients
+constexpr int DGP = 12 * CHP;      // recurrent gate gradients in LDS (rnn100_dev.h: chunks of 25 padded to 28)
+
+// barrier that orders LDS traffic only: __syncthreads() fences global memory too, and so would wait for the chunk's loads
+// and stores in flight at every step.  In builtins (the workgroup fence on the local address space around s_barrier), not
+// erc_common.h's lds_barrier(): that asm statement's memory clobber makes the compiler schedule the forward kernel differently
+__device__ __forceinline__ void lds_fence_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 struct GruP {
     const float* GX; int ldgx;           // hoisted pre-activations, direction d at columns [300d, 300d+300)
@@ -46,52 +50,6 @@ struct GruP {
     float* dGH;                          // [rows,600] the recurrent side: the n block scaled by r  (0 on padded rows)
     const int32_t* t_dev;                // *_tcap entry points (padded rows, unpacked): every dialogue runs *t_dev <= T steps
 };
-
-// rows of a dialogue: row(t) = base + t * step
-struct RowMap {
-    int64_t base, step;
-    __device__ __forceinline__ int64_t operator()(int t) const { return base + (int64_t)t * step; }
-};
-__device__ __forceinline__ RowMap rows_of(const GruP& p, int b) {
-    return p.node_off ? RowMap{(int64_t)p.node_off[b], 1} : RowMap{(int64_t)b * p.sb, p.st};
-}
-__device__ __forceinline__ int length_of(const GruP& p, int b) {
-    if (p.node_off) return p.lengths ? (int)p.lengths[b] : p.node_off[b + 1] - p.node_off[b];
-    return p.lengths ? min((int)p.lengths[b], p.T) : p.T;      // padded rows: never past the T rows of the dialogue
-}
-// T capacity (TDEV): the launch is sized for T = T_cap, the batch's own longest dialogue is read from the device.  Everything
-// below depends on the step count through L alone, so a (dialogue, direction) computes exactly what a launch with T = *t_dev
-// computes, in the same order, and the rows t >= *t_dev fall to the padded-position tails (zero outputs / gate gradients).
-template <bool TDEV>
-__device__ __forceinline__ int steps_of(const GruP& p, int b) {
-    return TDEV ? min(max(*p.t_dev, 0), p.T) : length_of(p, b);
-}
-typedef float f2 __attribute__((ext_vector_type(2)));
-// barrier that orders LDS traffic only: __syncthreads() fences global memory too, and so would wait for the chunk's loads
-// and stores in flight at every step
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-// sigmoid / tanh on the hardware exponential and reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each; absolute error < 3e-7)
-__device__ __forceinline__ float fast_sigm(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x));
-}
-__device__ __forceinline__ float fast_tanh(float x) { return 2.0f * fast_sigm(2.0f * x) - 1.0f; }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// value of lane Q of the caller's quad (lanes 4u .. 4u+3), in every lane of the quad: one DPP move, no LDS
-template <int Q>
-__device__ __forceinline__ float quad_bcast(float v) { return dpp_mov<Q * 0x55>(v); }
-// sum over the quad, the same bits in its four lanes (xor 1, then xor 2: both orders add the same two pairs)
-__device__ __forceinline__ float quad_sum(float v) {
-    v += dpp_mov<0xB1>(v);
-    return v + dpp_mov<0x4E>(v);
-}
-__device__ __forceinline__ int chunk_pos(int k) { return (k / CHK) * CHP + k % CHK; }
 
 // Thread layout of both scans: quad u = tid / 4 (< 100 live) owns hidden unit u.  Forward: lane q of the quad multiplies the
 // unit's THREE gate rows by h[25q .. 25q+25) (75 weights in registers, 25 LDS values a step), the quad sums by DPP and every
@@ -147,7 +105,7 @@ __global__ __launch_bounds__(NTH) void gru100_fwd_kernel(GruP p) {
                 if (gstore) p.gates[row * (2 * G3) + gcol] = o_gate[r];
                 float val = o_unit[r];
                 if (dropping && q == 3) {
-                    const float uu = erc_uniform(rseed, roff, (uint64_t)row * 2 * H + d * H + uc);
+                    const float uu = drop_uniform(rseed, roff, row, d, uc);
                     val = uu >= p.drop_p ? val * keep_scale : 0.f;
                 }
                 if (ostore) obase[row * opitch + d * H + uc] = val;
@@ -194,7 +152,7 @@ __global__ __launch_bounds__(NTH) void gru100_fwd_kernel(GruP p) {
                 o_unit[r] = q == 0 ? hprev : q == 1 ? hn : h;      // lane 3: h, dropped when it is stored
                 if (live && q == 0) s_h[cur ^ 1][chunk_pos(u)] = h;
                 hprev = h;
-                lds_barrier();
+                lds_fence_barrier();
             }
         }
     }
@@ -278,7 +236,7 @@ __global__ __launch_bounds__(NTH) void gru100_bwd_kernel(GruP p) {
             const int s = max(s0 - r, 0);
             float g = X.g[r];
             if (dropped) {     // uniform
-                const float uu = erc_uniform(rseed, roff, (uint64_t)(row_first + (int64_t)s * dstep) * 2 * H + d * H + uc);
+                const float uu = drop_uniform(rseed, roff, row_first + (int64_t)s * dstep, d, uc);
                 g = uu >= p.drop_p ? g * keep_scale : 0.f;
             }
             const float gq = X.gq[r];
@@ -301,7 +259,7 @@ __global__ __launch_bounds__(NTH) void gru100_bwd_kernel(GruP p) {
                 o_x[r] = dh * fX[r];
                 o_h[r] = dp;
                 if (gstore) s_dp[buf][chunk_pos(q * H + u)] = dp;
-                lds_barrier();
+                lds_fence_barrier();
                 const float* dv = s_dp[buf] + pc * CHP;
                 f2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
 #pragma unroll
@@ -312,12 +270,7 @@ __global__ __launch_bounds__(NTH) void gru100_bwd_kernel(GruP p) {
                 }
                 float acc[4] = {a01.x, a01.y, a23.x, a23.y};
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {   // sum over the 16 lanes of the row: quad xor 1 / xor 2, half mirror, mirror
-                    acc[r4] += dpp_mov<0xB1>(acc[r4]);
-                    acc[r4] += dpp_mov<0x4E>(acc[r4]);
-                    acc[r4] += dpp_mov<0x141>(acc[r4]);
-                    acc[r4] += dpp_mov<0x140>(acc[r4]);
-                }
+                for (int r4 = 0; r4 < 4; ++r4) acc[r4] = row16_sum(acc[r4]);
                 dh_rec = (myr == 0 ? acc[0] : myr == 1 ? acc[1] : myr == 2 ? acc[2] : acc[3]) + dh * fZ[r];
             }
         }
@@ -348,22 +301,47 @@ __global__ __launch_bounds__(NTH) void gru100_bwd_kernel(GruP p) {
         }
 }
 
+// the checks and the parameter fill of the forward / backward entry points; `name` is the entry point's, `tcap` its T-capacity
+// form (t_dev instead of lengths / node_off)
+int check_and_fill(const char* name, GruP& p, const float* GX, int ldgx, const float* W_hh, const float* b_hh,
+                   const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st, int B, int T, bool tcap,
+                   const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p, const uint64_t* rng_state,
+                   uint64_t rng_stream, float* gates, float* ghn, float* Hprev) {
+    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && ghn && Hprev && (t_dev || !tcap), "%s: null pointer", name);
+    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G3 && ldh >= 2 * H, "%s: bad sizes B=%d T=%d ldgx=%d ldh=%d", name, B, T, ldgx, ldh);
+    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "%s: ldhd=%d < 200", name, ldhd);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%g outside [0, 1)", name, (double)drop_p);
+    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "%s: dropout needs rng_state", name);
+    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.lengths = lengths; p.node_off = node_off;
+    p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev; p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.ghn = ghn; p.Hprev = Hprev;
+    return ERC_OK;
+}
+
+int check_and_fill(const char* name, GruP& p, const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb,
+                   int64_t st, int B, int T, bool tcap, const int32_t* t_dev, const float* gates, const float* ghn,
+                   const float* Hprev, const float* dHout, int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream,
+                   float* dGX, float* dGH) {
+    ERC_REQUIRE(W_hh && gates && ghn && Hprev && dHout && dGX && dGH && (t_dev || !tcap), "%s: null pointer", name);
+    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "%s: bad sizes B=%d T=%d lddh=%d", name, B, T, lddh);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%g outside [0, 1)", name, (double)drop_p);
+    ERC_REQUIRE(drop_p <= 0.f || rng_state, "%s: dropout needs rng_state", name);
+    p.W_hh = W_hh; p.lengths = lengths; p.node_off = node_off; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
+    p.gates = const_cast<float*>(gates); p.ghn = const_cast<float*>(ghn); p.Hprev = const_cast<float*>(Hprev);
+    p.dHout = dHout; p.lddh = lddh; p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.dGH = dGH;
+    return ERC_OK;
+}
+
 }  // namespace
 
 extern "C" int erc_gru100_scan_fwd(const float* GX, int ldgx, const float* W_hh, const float* b_hh, const int64_t* lengths,
                                    const int32_t* node_off, int64_t sb, int64_t st, int B, int T, float* Hout, int ldh,
                                    float* Hdrop, int ldhd, float drop_p, const uint64_t* rng_state, uint64_t rng_stream,
                                    float* gates, float* ghn, float* Hprev, void* stream) {
-    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && ghn && Hprev, "gru100_scan_fwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G3 && ldh >= 2 * H, "gru100_scan_fwd: bad sizes B=%d T=%d ldgx=%d ldh=%d", B, T, ldgx,
-                ldh);
-    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "gru100_scan_fwd: ldhd=%d < 200", ldhd);
-    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru100_scan_fwd: drop_p=%g outside [0, 1)", (double)drop_p);
-    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "gru100_scan_fwd: dropout needs rng_state");
     GruP p{};
-    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.lengths = lengths; p.node_off = node_off;
-    p.sb = sb; p.st = st; p.B = B; p.T = T; p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.ghn = ghn; p.Hprev = Hprev;
+    if (int e = check_and_fill("gru100_scan_fwd", p, GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, false, nullptr, Hout,
+                               ldh, Hdrop, ldhd, drop_p, rng_state, rng_stream, gates, ghn, Hprev))
+        return e;
     hipLaunchKernelGGL(gru100_fwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru100_scan_fwd");
     return ERC_OK;
@@ -373,14 +351,10 @@ extern "C" int erc_gru100_scan_bwd(const float* W_hh, const int64_t* lengths, co
                                    int B, int T, const float* gates, const float* ghn, const float* Hprev, const float* dHout,
                                    int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX,
                                    float* dGH, void* stream) {
-    ERC_REQUIRE(W_hh && gates && ghn && Hprev && dHout && dGX && dGH, "gru100_scan_bwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "gru100_scan_bwd: bad sizes B=%d T=%d lddh=%d", B, T, lddh);
-    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru100_scan_bwd: drop_p=%g outside [0, 1)", (double)drop_p);
-    ERC_REQUIRE(drop_p <= 0.f || rng_state, "gru100_scan_bwd: dropout needs rng_state");
     GruP p{};
-    p.W_hh = W_hh; p.lengths = lengths; p.node_off = node_off; p.sb = sb; p.st = st; p.B = B; p.T = T;
-    p.gates = const_cast<float*>(gates); p.ghn = const_cast<float*>(ghn); p.Hprev = const_cast<float*>(Hprev);
-    p.dHout = dHout; p.lddh = lddh; p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.dGH = dGH;
+    if (int e = check_and_fill("gru100_scan_bwd", p, W_hh, lengths, node_off, sb, st, B, T, false, nullptr, gates, ghn, Hprev,
+                               dHout, lddh, drop_p, rng_state, rng_stream, dGX, dGH))
+        return e;
     hipLaunchKernelGGL(gru100_bwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru100_scan_bwd");
     return ERC_OK;
@@ -391,16 +365,10 @@ extern "C" int erc_gru100_scan_fwd_tcap(const float* GX, int ldgx, const float* 
                                         int B, int T, const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd,
                                         float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* gates, float* ghn,
                                         float* Hprev, void* stream) {
-    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && ghn && Hprev && t_dev, "gru100_scan_fwd_tcap: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G3 && ldh >= 2 * H, "gru100_scan_fwd_tcap: bad sizes B=%d T=%d ldgx=%d ldh=%d", B, T,
-                ldgx, ldh);
-    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "gru100_scan_fwd_tcap: ldhd=%d < 200", ldhd);
-    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru100_scan_fwd_tcap: drop_p=%g outside [0, 1)", (double)drop_p);
-    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "gru100_scan_fwd_tcap: dropout needs rng_state");
     GruP p{};
-    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
-    p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.ghn = ghn; p.Hprev = Hprev;
+    if (int e = check_and_fill("gru100_scan_fwd_tcap", p, GX, ldgx, W_hh, b_hh, nullptr, nullptr, sb, st, B, T, true, t_dev, Hout,
+                               ldh, Hdrop, ldhd, drop_p, rng_state, rng_stream, gates, ghn, Hprev))
+        return e;
     hipLaunchKernelGGL(gru100_fwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru100_scan_fwd_tcap");
     return ERC_OK;
@@ -410,14 +378,10 @@ extern "C" int erc_gru100_scan_bwd_tcap(const float* W_hh, int64_t sb, int64_t s
                                         const float* gates, const float* ghn, const float* Hprev, const float* dHout, int lddh,
                                         float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH,
                                         void* stream) {
-    ERC_REQUIRE(W_hh && gates && ghn && Hprev && dHout && dGX && dGH && t_dev, "gru100_scan_bwd_tcap: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "gru100_scan_bwd_tcap: bad sizes B=%d T=%d lddh=%d", B, T, lddh);
-    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru100_scan_bwd_tcap: drop_p=%g outside [0, 1)", (double)drop_p);
-    ERC_REQUIRE(drop_p <= 0.f || rng_state, "gru100_scan_bwd_tcap: dropout needs rng_state");
     GruP p{};
-    p.W_hh = W_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
-    p.gates = const_cast<float*>(gates); p.ghn = const_cast<float*>(ghn); p.Hprev = const_cast<float*>(Hprev);
-    p.dHout = dHout; p.lddh = lddh; p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.dGH = dGH;
+    if (int e = check_and_fill("gru100_scan_bwd_tcap", p, W_hh, nullptr, nullptr, sb, st, B, T, true, t_dev, gates, ghn, Hprev,
+                               dHout, lddh, drop_p, rng_state, rng_stream, dGX, dGH))
+        return e;
     hipLaunchKernelGGL(gru100_bwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru100_scan_bwd_tcap");
     return ERC_OK;

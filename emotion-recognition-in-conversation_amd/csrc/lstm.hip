@@ -8,13 +8,12 @@
 // broadcast from LDS, so a step costs ~100 LDS broadcasts + 100 FMAs per thread and touches HBM only for the
 // GX row (requested 4 steps ahead) and the saved state.  The backward scan keeps the transposed slices in registers the same way and
 // leaves all weight gradients to GEMMs over the saved gate gradients.
-#include "erc_common.h"
+#include "rnn100_dev.h"
 
 namespace {
+using namespace rnn100;      // constants, row maps, step counts, DPP moves, activations, dropout uniform
 
-constexpr int H = 100;
 constexpr int G4 = 400;
-constexpr int NTH = 512;
 
 struct LstmP {
     const float* GX; int ldgx;           // hoisted pre-activations, direction d at columns [400d, 400d+400)
@@ -48,56 +47,8 @@ unsigned long long* g_lstm_stamps = nullptr;
         }                                                                                          \
     } while (0)
 
-// rows of a dialogue: row(t) = base + t * step
-struct RowMap {
-    int64_t base, step;
-    __device__ __forceinline__ int64_t operator()(int t) const { return base + (int64_t)t * step; }
-};
-__device__ __forceinline__ RowMap rows_of(const LstmP& p, int b) {
-    return p.node_off ? RowMap{(int64_t)p.node_off[b], 1} : RowMap{(int64_t)b * p.sb, p.st};
-}
-__device__ __forceinline__ int length_of(const LstmP& p, int b) {
-    return p.lengths ? (int)p.lengths[b] : p.node_off ? p.node_off[b + 1] - p.node_off[b] : p.T;
-}
-// T capacity (TDEV): the launch is sized for T = T_cap, the batch's own longest dialogue is read from the device.  Everything
-// below depends on the step count through L alone, so a (dialogue, direction) computes exactly what a launch with T = *t_dev
-// computes, in the same order, and the rows t >= *t_dev fall to the padded-position tails (zero outputs / gate gradients).
-template <bool TDEV>
-__device__ __forceinline__ int steps_of(const LstmP& p, int b) {
-    return TDEV ? min(max(*p.t_dev, 0), p.T) : length_of(p, b);
-}
-typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
-// barrier that orders LDS traffic only: __syncthreads() would also wait for the LDS-DMA requests in flight (vmcnt)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// sigmoid / tanh on the hardware exponential and reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each; absolute error < 3e-7):
-// 4 and 6 instructions -- the library expf + IEEE division + tanhf were 90 of the 230 instructions of a step, and the
-// step is bound by instruction issue (two wavefronts per SIMD, finding 26)
-__device__ __forceinline__ float fast_sigm(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x));
-}
-__device__ __forceinline__ float fast_tanh(float x) { return 2.0f * fast_sigm(2.0f * x) - 1.0f; }
-
-// value of lane Q of the caller's quad (lanes 4u .. 4u+3), in every lane of the quad: one DPP move, no LDS
-template <int Q>
-__device__ __forceinline__ float quad_bcast(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), Q * 0x55, 0xF, 0xF, true));
-}
-// Global memory is touched once per SC steps, not per step: the wavefront's memory counter (vmcnt) retires loads and
-// stores in issue order, so a step that stores its results and then needs a prefetched operand waits for its own stores --
-// one L2 round trip (~0.9 us) per step whatever the prefetch distance.  A chunk's operands are requested one chunk ahead
-// and its results are kept in registers until the chunk ends; inside a chunk a step is LDS + ALU only.
-constexpr int SC = 8;
-// Vectors that every thread reads (h_{t-1}: 100 values, the gate gradients: 400) sit in LDS as chunks of 25 values padded
-// to 28 (16-byte rows, chunks 28 banks apart: the distinct addresses of one wavefront read never share a bank).
-constexpr int CHK = 25, CHP = 28;
-constexpr int HP = 4 * CHP;        // hidden state
-constexpr int DPP_ = 16 * CHP;     // gate gradients
-__device__ __forceinline__ int chunk_pos(int k) { return (k / CHK) * CHP + k % CHK; }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
+constexpr int DPP_ = 16 * CHP;     // gate gradients in LDS (rnn100_dev.h: chunks of 25 padded to 28)
 
 // Thread layout of both scans: quad u = tid / 4 (< 100 live) owns hidden unit u, lane q = tid % 4 of the quad its gate q
 // (i|f|g|o).  The four gates of a unit meet through DPP moves inside the quad, the cell state / the recurrent gradients
@@ -107,6 +58,7 @@ template <bool TDEV>
 __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
     const int L = steps_of<TDEV>(p, b);
+    const int tail0 = TDEV ? L : max(L, 0);      // first padded position: a length from the device may be negative (*t_dev is clamped)
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_h[2][HP];
     const int u = tid >> 2, q = tid & 3;
@@ -179,7 +131,7 @@ __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
                 if (live) *gp = o_gate[r];
                 float val = o_unit[r];
                 if (dropping) {    // uniform
-                    const float uu = erc_uniform(rseed, roff, (uint64_t)row * 2 * H + d * H + uc);
+                    const float uu = drop_uniform(rseed, roff, row, d, uc);
                     val = q < 3 ? val : uu >= p.drop_p ? val * keep_scale : 0.f;
                 }
                 if (ostore) *up = val;
@@ -251,7 +203,7 @@ __global__ __launch_bounds__(NTH) void lstm_fwd_kernel(LstmP p) {
     if (L > 0) store_chunk((L - 1) / SC * SC);
     // padded positions: zero output (pad_packed_sequence) -- only meaningful for padded row addressing
     if (!p.node_off)
-        for (int t = L; t < p.T; ++t) {
+        for (int t = tail0; t < p.T; ++t) {
             const int64_t row = rmap(t);
             if (tid < H) {
                 p.Hout[row * p.ldh + d * H + tid] = 0.f;
@@ -264,6 +216,7 @@ template <bool ZERO_ROWS, bool TDEV>     // capacity modes (zero_to > 0 | t_dev)
 __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
     const int b = blockIdx.x, d = blockIdx.y, tid = threadIdx.x;
     const int L = steps_of<TDEV>(p, b);
+    const int tail0 = TDEV ? L : max(L, 0);      // first padded position: a length from the device may be negative (*t_dev is clamped)
     const RowMap rmap = rows_of(p, b);
     __shared__ __attribute__((aligned(16))) float s_dp[2][DPP_];     // gate gradients of the step, entry q*H + j chunked
     const int u = tid >> 2, q = tid & 3;
@@ -331,7 +284,7 @@ __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
             const float cprev = s > 0 ? X.c[r + 1] : 0.f;
             float g = X.g[r];
             if (dropped) {     // uniform
-                const float uu = erc_uniform(rseed, roff, (uint64_t)rmap(t_of(s)) * 2 * H + d * H + uc);
+                const float uu = drop_uniform(rseed, roff, rmap(t_of(s)), d, uc);
                 g = uu >= p.drop_p ? g * keep_scale : 0.f;
             }
             const float gq = X.gq[r];
@@ -366,12 +319,7 @@ __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
                 }
                 float acc[4] = {a01.x, a01.y, a23.x, a23.y};
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {   // sum over the 16 lanes of the row: quad xor 1 / xor 2, half mirror, mirror
-                    acc[r4] += dpp_mov<0xB1>(acc[r4]);
-                    acc[r4] += dpp_mov<0x4E>(acc[r4]);
-                    acc[r4] += dpp_mov<0x141>(acc[r4]);
-                    acc[r4] += dpp_mov<0x140>(acc[r4]);
-                }
+                for (int r4 = 0; r4 < 4; ++r4) acc[r4] = row16_sum(acc[r4]);
                 dh_rec = myr == 0 ? acc[0] : myr == 1 ? acc[1] : myr == 2 ? acc[2] : acc[3];
             }
         }
@@ -403,10 +351,42 @@ __global__ __launch_bounds__(NTH) void lstm_bwd_kernel(LstmP p) {
         for (int64_t row = (int64_t)p.node_off[p.B] + b; row < p.zero_to; row += p.B)
             if (tid < G4) p.dGX[row * 2 * G4 + d * G4 + tid] = 0.f;
     if (!p.node_off)
-        for (int t = L; t < p.T; ++t) {
+        for (int t = tail0; t < p.T; ++t) {
             const int64_t row = rmap(t);
             if (tid < G4) p.dGX[row * 2 * G4 + d * G4 + tid] = 0.f;
         }
+}
+
+// the checks and the parameter fill of the forward / backward entry points; `name` is the entry point's, `tcap` its T-capacity
+// form (t_dev instead of lengths / node_off)
+int check_and_fill(const char* name, LstmP& p, const float* GX, int ldgx, const float* W_hh, const float* b_hh,
+                   const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st, int B, int T, bool tcap,
+                   const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p, const uint64_t* rng_state,
+                   uint64_t rng_stream, float* gates, float* Cst, float* Hprev) {
+    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && Cst && Hprev && (t_dev || !tcap), "%s: null pointer", name);
+    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G4 && ldh >= 2 * H, "%s: bad sizes B=%d T=%d ldgx=%d ldh=%d", name, B, T, ldgx, ldh);
+    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "%s: ldhd=%d < 200", name, ldhd);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%g outside [0, 1)", name, (double)drop_p);
+    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "%s: dropout needs rng_state", name);
+    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.lengths = lengths; p.node_off = node_off;
+    p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev; p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.Cst = Cst; p.Hprev = Hprev;
+    return ERC_OK;
+}
+
+int check_and_fill(const char* name, LstmP& p, const float* W_hh, const int64_t* lengths, const int32_t* node_off, int64_t sb,
+                   int64_t st, int B, int T, bool tcap, const int32_t* t_dev, const float* gates, const float* Cst,
+                   const float* dHout, int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX,
+                   int zero_to) {
+    ERC_REQUIRE(W_hh && gates && Cst && dHout && dGX && (t_dev || !tcap), "%s: null pointer", name);
+    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "%s: bad sizes B=%d T=%d lddh=%d", name, B, T, lddh);
+    ERC_REQUIRE(zero_to <= 0 || node_off, "%s: zero_to needs compact rows (node_off)", name);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%g outside [0, 1)", name, (double)drop_p);
+    ERC_REQUIRE(drop_p <= 0.f || rng_state, "%s: dropout needs rng_state", name);
+    p.W_hh = W_hh; p.lengths = lengths; p.node_off = node_off; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
+    p.gates = const_cast<float*>(gates); p.Cst = const_cast<float*>(Cst); p.dHout = dHout; p.lddh = lddh;
+    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.zero_to = zero_to;
+    return ERC_OK;
 }
 
 }  // namespace
@@ -421,13 +401,10 @@ extern "C" int erc_lstm_scan_fwd(const float* GX, int ldgx, const float* W_hh, c
                                  const int64_t* lengths, const int32_t* node_off, int64_t sb, int64_t st, int B, int T,
                                  float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p, const uint64_t* rng_state,
                                  uint64_t rng_stream, float* gates, float* Cst, float* Hprev, void* stream) {
-    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && Cst && Hprev, "lstm_scan_fwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G4 && ldh >= 2 * H, "lstm_scan_fwd: bad sizes B=%d T=%d", B, T);
-    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "lstm_scan_fwd: dropout needs rng_state");
     LstmP p{};
-    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.lengths = lengths; p.node_off = node_off;
-    p.sb = sb; p.st = st; p.B = B; p.T = T; p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.Cst = Cst; p.Hprev = Hprev;
+    if (int e = check_and_fill("lstm_scan_fwd", p, GX, ldgx, W_hh, b_hh, lengths, node_off, sb, st, B, T, false, nullptr, Hout,
+                               ldh, Hdrop, ldhd, drop_p, rng_state, rng_stream, gates, Cst, Hprev))
+        return e;
     p.stamps = g_lstm_stamps;
     hipLaunchKernelGGL(lstm_fwd_kernel<false>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("lstm_scan_fwd");
@@ -438,14 +415,10 @@ extern "C" int erc_lstm_scan_bwd_cap(const float* W_hh, const int64_t* lengths, 
                                      int64_t st, int B, int T, const float* gates, const float* Cst, const float* dHout,
                                      int lddh, float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX,
                                      int zero_to, void* stream) {
-    ERC_REQUIRE(W_hh && gates && Cst && dHout && dGX, "lstm_scan_bwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0, "lstm_scan_bwd: bad sizes B=%d T=%d", B, T);
-    ERC_REQUIRE(zero_to <= 0 || node_off, "lstm_scan_bwd: zero_to needs compact rows (node_off)");
-    ERC_REQUIRE(drop_p <= 0.f || rng_state, "lstm_scan_bwd: dropout needs rng_state");
     LstmP p{};
-    p.W_hh = W_hh; p.lengths = lengths; p.node_off = node_off; p.sb = sb; p.st = st; p.B = B; p.T = T;
-    p.gates = const_cast<float*>(gates); p.Cst = const_cast<float*>(Cst); p.dHout = dHout; p.lddh = lddh;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.zero_to = zero_to;
+    if (int e = check_and_fill("lstm_scan_bwd", p, W_hh, lengths, node_off, sb, st, B, T, false, nullptr, gates, Cst, dHout, lddh,
+                               drop_p, rng_state, rng_stream, dGX, zero_to))
+        return e;
     if (zero_to > 0)
         hipLaunchKernelGGL((lstm_bwd_kernel<true, false>), dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     else
@@ -467,14 +440,10 @@ extern "C" int erc_lstm_scan_fwd_tcap(const float* GX, int ldgx, const float* W_
                                       int T, const int32_t* t_dev, float* Hout, int ldh, float* Hdrop, int ldhd, float drop_p,
                                       const uint64_t* rng_state, uint64_t rng_stream, float* gates, float* Cst, float* Hprev,
                                       void* stream) {
-    ERC_REQUIRE(GX && W_hh && b_hh && Hout && gates && Cst && Hprev && t_dev, "lstm_scan_fwd_tcap: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && ldgx >= 2 * G4 && ldh >= 2 * H, "lstm_scan_fwd_tcap: bad sizes B=%d T=%d", B, T);
-    ERC_REQUIRE(!Hdrop || ldhd >= 2 * H, "lstm_scan_fwd_tcap: ldhd=%d < 200", ldhd);
-    ERC_REQUIRE(!(Hdrop && drop_p > 0.f) || rng_state, "lstm_scan_fwd_tcap: dropout needs rng_state");
     LstmP p{};
-    p.GX = GX; p.ldgx = ldgx; p.W_hh = W_hh; p.b_hh = b_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
-    p.Hout = Hout; p.ldh = ldh; p.Hdrop = Hdrop; p.ldhd = ldhd;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.gates = gates; p.Cst = Cst; p.Hprev = Hprev;
+    if (int e = check_and_fill("lstm_scan_fwd_tcap", p, GX, ldgx, W_hh, b_hh, nullptr, nullptr, sb, st, B, T, true, t_dev, Hout,
+                               ldh, Hdrop, ldhd, drop_p, rng_state, rng_stream, gates, Cst, Hprev))
+        return e;
     hipLaunchKernelGGL(lstm_fwd_kernel<true>, dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("lstm_scan_fwd_tcap");
     return ERC_OK;
@@ -483,13 +452,10 @@ extern "C" int erc_lstm_scan_fwd_tcap(const float* GX, int ldgx, const float* W_
 extern "C" int erc_lstm_scan_bwd_tcap(const float* W_hh, int64_t sb, int64_t st, int B, int T, const int32_t* t_dev,
                                       const float* gates, const float* Cst, const float* dHout, int lddh, float drop_p,
                                       const uint64_t* rng_state, uint64_t rng_stream, float* dGX, void* stream) {
-    ERC_REQUIRE(W_hh && gates && Cst && dHout && dGX && t_dev, "lstm_scan_bwd_tcap: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && lddh >= 2 * H, "lstm_scan_bwd_tcap: bad sizes B=%d T=%d lddh=%d", B, T, lddh);
-    ERC_REQUIRE(drop_p <= 0.f || rng_state, "lstm_scan_bwd_tcap: dropout needs rng_state");
     LstmP p{};
-    p.W_hh = W_hh; p.sb = sb; p.st = st; p.B = B; p.T = T; p.t_dev = t_dev;
-    p.gates = const_cast<float*>(gates); p.Cst = const_cast<float*>(Cst); p.dHout = dHout; p.lddh = lddh;
-    p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX;
+    if (int e = check_and_fill("lstm_scan_bwd_tcap", p, W_hh, nullptr, nullptr, sb, st, B, T, true, t_dev, gates, Cst, dHout, lddh,
+                               drop_p, rng_state, rng_stream, dGX, 0))
+        return e;
     hipLaunchKernelGGL((lstm_bwd_kernel<false, true>), dim3(B, 2), dim3(NTH), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("lstm_scan_bwd_tcap");
     return ERC_OK;

@@ -7,6 +7,8 @@ formed from them <= 1e-4 of the reference's largest entry, for a random upstream
 write are filled with NaN beforehand and stay NaN; dGX / dGH are exactly zero on the padded rows of the packed form; a
 second backward run is bit-identical.  Each case prints the kernel's output error as a multiple of the error of the same
 chain evaluated in float32 on the CPU."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -194,3 +196,43 @@ def test_gru100_scan_refuses_bad_arguments():
                     (dict(p=0.5), "rng_state"), (dict(p=-0.1, rng=rng), "drop_p")):
         with pytest.raises(capi.ErcGraftError, match=msg):
             bwd(**kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _padded_rows_run(lens):
+    """forward (with the dropped copy) + backward on batch-major padded rows, B = 2, T = 9, with the given lengths: every output,
+    saved buffer and gate gradient, on the CPU.  Everything is NaN beforehand."""
+    B, T = 2, 9
+    n = B * T
+    g = torch.Generator().manual_seed(99)
+    W = ((torch.rand(2, G3, H, generator=g) * 2 - 1) * 0.1).to(DEV)
+    bh = ((torch.rand(2, G3, generator=g) * 2 - 1) * 0.1).to(DEV)
+    GX, up = (torch.randn(n, 2 * G3, generator=g) * 0.5).to(DEV), torch.randn(n, 2 * H, generator=g).to(DEV)
+    nan = lambda w: torch.full((n, w), float("nan"), device=DEV)
+    o = dict(Hout=nan(2 * H), Hdrop=nan(2 * H), gates=nan(2 * G3), ghn=nan(2 * H), Hprev=nan(2 * H), dGX=nan(2 * G3), dGH=nan(2 * G3))
+    rng = torch.tensor([3, 1234], dtype=torch.int64, device=DEV)
+    lengths = torch.tensor(lens, dtype=torch.int64, device=DEV)
+    capi.gru100_scan_fwd(GX, 2 * G3, W, bh, lengths, None, T, 1, B, T, o["Hout"], 2 * H, o["Hdrop"], 2 * H, 0.5, rng, 0x77,
+                         o["gates"], o["ghn"], o["Hprev"])
+    capi.gru100_scan_bwd(W, lengths, None, T, 1, B, T, o["gates"], o["ghn"], o["Hprev"], up, 2 * H, 0.5, rng, 0x77, o["dGX"],
+                         o["dGH"])
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in o.items()}
+
+
+@pytest.mark.parametrize("lens", [(12, 9), (0, 9)])
+def test_padded_row_lengths_stay_inside_the_dialogues_rows(lens):
+    """``lengths`` is a device input.  On padded rows a dialogue owns T rows: a longer length runs T steps and never reaches the
+    next dialogue's rows, a zero length leaves zero outputs and zero gate gradients.  T = 9 crosses one chunk boundary of the
+    scans (8 steps): chunk store, chunk request and tail meet.  Bit for bit against the run with lengths [9, 9]."""
+    T = 9
+    ref, got = _padded_rows_run((9, 9)), _padded_rows_run(lens)
+    assert all(torch.isfinite(v).all() for v in ref.values())
+    if lens[0] > T:
+        for k in ref:
+            assert torch.equal(got[k], ref[k]), k
+    else:
+        for k in ("Hout", "Hdrop", "dGX", "dGH"):
+            assert bool((got[k][:T] == 0).all()), k
+        for k in ref:
+            assert torch.equal(got[k][T:], ref[k][T:]), k

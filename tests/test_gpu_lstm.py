@@ -1,5 +1,7 @@
 """BiLSTM (2 layers, hidden 100/direction) on libercgraft vs torch.nn.LSTM on the CPU: packed (DialogueGCN
 SeqContext) and unpacked-over-padding (MMGCN text branch) runs, outputs and every gradient."""
+import functools
+
 import pytest
 import torch
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
@@ -173,3 +175,47 @@ def test_packed_bilstm_vs_reference_seqcontext(golden, name):
     capi.slab_reduce_batched(pl.ws, flat.grad, pl.job_table(), len(pl.jobs), pl.max_numel)
     # the generator's names: "rnn." + SeqContext.named_parameters() = "rnn.rnn.<param>"
     check_grad_digest(fx, [("rnn.rnn." + n, flat.g("rnn." + n)) for n, _ in holder.rnn.named_parameters()], tol=1e-3)
+
+
+@functools.lru_cache(maxsize=None)
+def _padded_rows_run(lens):
+    """forward + backward (train mode) on batch-major padded rows, B = 2, T = 9, D = 20, with the given lengths: every output,
+    saved buffer and gate gradient, on the CPU.  What the scans must write is NaN beforehand."""
+    B, T, D = 2, 9, 20
+    g = torch.Generator().manual_seed(5)
+    x, gout = torch.randn(B * T, D, generator=g) * 0.5, torch.randn(B * T, 200, generator=g)
+    torch.manual_seed(5)
+    lstm = torch.nn.LSTM(D, 100, dropout=0.4, bidirectional=True, num_layers=2, batch_first=True)
+    run, flat, pl = _runner(lstm, D)
+    ws = run._buf(B * T, DEV)
+    for t in [ws["H0"], ws["H0d"]] + ws["dGX"]:
+        t.fill_(float("nan"))
+    out = torch.full((B * T, 200), float("nan"), device=DEV)
+    rng = torch.tensor([3, 99], dtype=torch.int64, device=DEV)
+    run.forward(pl, x.to(DEV), D, B * T, B, T, T, 1, torch.tensor(lens).to(DEV), True, rng, out, 200)
+    run.backward(pl, gout.to(DEV), 200)
+    torch.cuda.synchronize()
+    assert run._own["lstm:rnn."] is ws
+    res = {"out": out.cpu(), "H0": ws["H0"].cpu(), "H0d": ws["H0d"].cpu()}
+    for k in ("gates", "Cst", "Hprev", "dGX"):
+        res[k + "0"], res[k + "1"] = ws[k][0].cpu(), ws[k][1].cpu()
+    return res
+
+
+@pytest.mark.parametrize("lens", [(12, 9), (0, 9)])
+def test_padded_row_lengths_stay_inside_the_dialogues_rows(lens):
+    """``lengths`` is a device input.  On padded rows a dialogue owns T rows: a longer length runs T steps (it once ran on into
+    the next dialogue's rows: [12, 9] read and overwrote rows of dialogue 1), a zero length leaves zero outputs and zero gate
+    gradients.  T = 9 crosses one chunk boundary of the scans (8 steps): chunk store, chunk request and tail meet.  Bit for bit
+    against the run with lengths [9, 9]."""
+    T = 9
+    ref, got = _padded_rows_run((9, 9)), _padded_rows_run(lens)
+    assert all(torch.isfinite(v).all() for v in ref.values())
+    if lens[0] > T:
+        for k in ref:
+            assert torch.equal(got[k], ref[k]), k
+    else:
+        for k in ("out", "H0", "H0d", "dGX0", "dGX1"):
+            assert bool((got[k][:T] == 0).all()), k
+        for k in ref:
+            assert torch.equal(got[k][T:], ref[k][T:]), k
