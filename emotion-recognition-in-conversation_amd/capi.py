@@ -1073,6 +1073,19 @@ def gru_scan_bwd(W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, dro
     _call("erc_gru_scan_bwd", W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH)
 
 
+def cim_meta_cap(lengths, desc, store_label, store_emo, tail_row, B, T, n_cap, node_off, node_row, lengths_out, label_out, emo_out,
+                 counts):
+    """the tables of a capacity-sized CIM step, from lengths (bucket form) or desc (resident form) (ercgraft.h)"""
+    _call("erc_cim_meta_cap", lengths, desc, store_label, store_emo, tail_row, B, T, n_cap, node_off, node_row, lengths_out,
+          label_out, emo_out, counts)
+
+
+def gru_scan_bwd_cap(W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH, zero_to):
+    """gru_scan_bwd, and rows [node_off[B], zero_to) of dGX / dGH written 0"""
+    _call("erc_gru_scan_bwd_cap", W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng, rng_stream, dGX, dGH,
+          zero_to)
+
+
 def cim_max_t():
     return int(lib().erc_cim_max_t())
 
@@ -1095,6 +1108,18 @@ def ce_bce_multitask(logits, ld, Cn, n_rows, labels, emo_label, lde, w_ce, w_bce
                             % (n_rows, tuple(labels.shape), tuple(emo_label.shape)))
     _call("erc_ce_bce_multitask", logits, ld, Cn, n_rows, labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl,
           stats)
+
+
+def ce_bce_multitask_cap(logits, ld, Cn, n_cap, n_dev, labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats):
+    """ce_bce_multitask over the first *n_dev (device int32) of n_cap rows; dlogits rows beyond are written 0 (ercgraft.h)"""
+    if labels.dtype != torch.int64 or emo_label.dtype != torch.int64 or n_dev.dtype != torch.int32:
+        raise ErcGraftError("ce_bce_multitask_cap: label and emo_label must be int64, n_dev int32")
+    if labels.numel() < n_cap or emo_label.dim() != 2 or emo_label.shape[0] < n_cap or emo_label.shape[1] < 7 \
+            or emo_label.stride(1) != 1 or logits.numel() < (n_cap - 1) * ld + Cn + 7:
+        raise ErcGraftError("ce_bce_multitask_cap: operands smaller than %d rows (label %s, emo_label %s)"
+                            % (n_cap, tuple(labels.shape), tuple(emo_label.shape)))
+    _call("erc_ce_bce_multitask_cap", logits, ld, Cn, n_cap, n_dev, labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits,
+          lddl, stats)
 
 
 # --------------------------------------------------------------------------- conv-emotion DialogueGCN (csrc/dgcnv2_att.hip)

@@ -16,7 +16,11 @@
 // pair), so its contributions -- the classifier's, then per pair the x-side and the y-side terms -- add up in a fixed order
 // without atomics: a step is bit-reproducible.  The last phase applies drop1 / ReLU's mask (dense > 0) and the inverted
 // dropout scale, leaving the gradient wrt the adapters' pre-activations in the dense block.
+//
+// Capacity mode launches both kernels with (B_cap, T_cap): a dialogue slot of length 0 (node_off[b + 1] == node_off[b]) leaves
+// its workgroups at their first statement -- no softmax over an empty row, nothing read, nothing written.
 #include "erc_common.h"
+#include "cim_meta.h"
 
 namespace {
 
@@ -59,6 +63,18 @@ __global__ void cim_meta_kernel(const int64_t* lengths, int B, int T, int n_cap,
         for (int t = threadIdx.x; t < L; t += blockDim.x)
             if (o + t < n_cap) node_row[o + t] = b * T + t;
     }
+}
+
+// erc_cim_meta_cap: one workgroup; the arithmetic is cim_meta.h's (a host program runs the same functions)
+constexpr int META_THREADS = 1024;
+
+__global__ __launch_bounds__(META_THREADS) void cim_meta_cap_kernel(CimMetaP p) {
+    __shared__ int s_off[1025];
+    if (threadIdx.x == 0) cim_meta_prefix(p, s_off);
+    __syncthreads();
+    for (int b = threadIdx.x; b <= p.B; b += META_THREADS) cim_meta_slot(p, s_off, b);
+    for (int i = threadIdx.x; i < p.B * p.T; i += META_THREADS) cim_meta_entry(p, s_off, i);
+    for (int i = s_off[p.B] + threadIdx.x; i < p.n_cap; i += META_THREADS) cim_meta_tail(p, i);
 }
 
 __global__ __launch_bounds__(FWD_THREADS) void cim_attn_fwd_kernel(float* merged, const int32_t* node_off, int T, int B,
@@ -208,6 +224,29 @@ extern "C" int erc_cim_meta(const int64_t* lengths, int B, int T, int n_cap, int
     ERC_REQUIRE(B > 0 && B <= 1024 && T > 0 && n_cap > 0, "cim_meta: bad sizes B=%d T=%d n_cap=%d", B, T, n_cap);
     hipLaunchKernelGGL(cim_meta_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lengths, B, T, n_cap, node_off, node_row);
     ERC_LAUNCH_CHECK("cim_meta");
+    return ERC_OK;
+}
+
+extern "C" int erc_cim_meta_cap(const int64_t* lengths, const int32_t* desc, const int64_t* store_label, const int64_t* store_emo,
+                                int tail_row, int B, int T, int n_cap, int32_t* node_off, int32_t* node_row,
+                                int64_t* lengths_out, int64_t* label_out, int64_t* emo_out, int32_t* counts, void* stream) {
+    ERC_REQUIRE(node_off && node_row && lengths_out && counts, "cim_meta_cap: null pointer");
+    ERC_REQUIRE((lengths != nullptr) != (desc != nullptr),
+                "cim_meta_cap: give lengths (bucket form) or desc (resident form), one of them");
+    ERC_REQUIRE(desc || !(store_label || store_emo || label_out || emo_out),
+                "cim_meta_cap: the bucket form (lengths) gathers no labels: store_label, store_emo, label_out, emo_out are the "
+                "resident form's");
+    ERC_REQUIRE((store_label != nullptr) == (label_out != nullptr) && (store_emo != nullptr) == (emo_out != nullptr),
+                "cim_meta_cap: resident form: store_label with label_out, store_emo with emo_out");
+    ERC_REQUIRE(B > 0 && B <= 1024 && T > 0 && n_cap > 0 && (int64_t)n_cap <= (int64_t)B * T,
+                "cim_meta_cap: bad sizes B=%d T=%d n_cap=%d (B <= 1024, n_cap <= B * T)", B, T, n_cap);
+    ERC_REQUIRE(T <= CIM_MAX_T, "cim_meta_cap: dialogues of up to %d utterances are supported (T_cap=%d)", CIM_MAX_T, T);
+    ERC_REQUIRE(tail_row >= 0 && (desc || tail_row <= B * T),
+                "cim_meta_cap: tail_row %d is neither a row of the padded block nor the one behind it (%d)", tail_row, B * T);
+    CimMetaP p{lengths, desc, store_label, store_emo, tail_row, B, T, n_cap, node_off, node_row, lengths_out, label_out, emo_out,
+               counts};
+    hipLaunchKernelGGL(cim_meta_cap_kernel, dim3(1), dim3(META_THREADS), 0, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK("cim_meta_cap");
     return ERC_OK;
 }
 

@@ -14,6 +14,10 @@
 // forward reads the TRANSPOSED copy W_hh^T [200, 600] (erc_transpose_batched, once per step of training), thread j < 600
 // owns gate row j and walks k, so every load of a wavefront is 256 contiguous bytes; the backward needs W_hh^T g, for which
 // the stored [600, 200] layout is already the coalesced one (thread = column k, 5 threads per column split the 600 rows).
+//
+// Capacity mode (B dialogue slots, `rows` a capacity): a slot of length 0 runs no step in either kernel, and both write only
+// the rows node_off[b] + t, t < length -- rows at or beyond node_off[B] keep what they held.  The forward needs no other form;
+// the backward's erc_gru_scan_bwd_cap also writes 0 into the tail rows of dGX / dGH, which enter weight-gradient products.
 #include "erc_common.h"
 
 namespace {
@@ -42,6 +46,7 @@ struct GruP {
     const float* dH;      // [3][rows][400]   gradient wrt Hout (wrt Hdrop when drop_p > 0)
     float* dGX;           // [3][rows][1200]  gradient wrt the input-side pre-activations
     float* dGH;           // [3][rows][1200]  ... wrt the recurrent-side pre-activations (n block scaled by r)
+    int64_t zero_to;      // erc_gru_scan_bwd_cap: rows [node_off[B], zero_to) of dGX / dGH are written 0 (0: none)
 };
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -100,6 +105,8 @@ __global__ __launch_bounds__(FWD_THREADS) void gru_fwd_kernel(GruP p) {
     }
 }
 
+// ZERO_TAIL (zero_to > 0): its own instance, so that the exact-shape launch keeps the code it always had
+template <bool ZERO_TAIL>
 __global__ __launch_bounds__(BWD_THREADS) void gru_bwd_kernel(GruP p) {
     const int b = blockIdx.x, d = blockIdx.y, m = blockIdx.z, tid = threadIdx.x;
     const int L = min((int)p.lengths[b], p.T);
@@ -113,6 +120,13 @@ __global__ __launch_bounds__(BWD_THREADS) void gru_bwd_kernel(GruP p) {
     if (dropped) roff = p.rng[0], rseed = p.rng[1];
     const float keep_scale = dropped ? 1.0f / (1.0f - p.drop_p) : 1.0f;
     const int kcol = tid % H, part = tid / H;
+    // capacity mode: the tail rows [n, zero_to) no dialogue owns, this (direction, modality)'s 600 columns of them dealt out
+    // over the B workgroups -- the weight-gradient products then run over zero_to rows whatever an earlier batch left there
+    if (ZERO_TAIL && tid < G3)
+        for (int64_t r = max(p.node_off[p.B], 0) + b; r < p.zero_to; r += p.B) {
+            p.dGX[mg + r * 2 * G3 + d * G3 + tid] = 0.f;
+            p.dGH[mg + r * 2 * G3 + d * G3 + tid] = 0.f;
+        }
     float dh_rec = 0.f, dh_direct = 0.f;
     for (int s = L - 1; s >= 0; --s) {
         const int t = d == 0 ? s : L - 1 - s;
@@ -180,18 +194,32 @@ extern "C" int erc_gru_scan_fwd(const float* GX, const float* W_hhT, const float
     return ERC_OK;
 }
 
-extern "C" int erc_gru_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int B, int T,
-                                int64_t rows, const float* gates, const float* ghn, const float* Hprev, const float* dH,
-                                float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH,
-                                void* stream) {
+extern "C" int erc_gru_scan_bwd_cap(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int B, int T,
+                                    int64_t rows, const float* gates, const float* ghn, const float* Hprev, const float* dH,
+                                    float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH,
+                                    int64_t zero_to, void* stream) {
     ERC_REQUIRE(W_hh && lengths && node_off && gates && ghn && Hprev && dH && dGX && dGH, "gru_scan_bwd: null pointer");
     ERC_REQUIRE(B > 0 && T > 0 && rows > 0, "gru_scan_bwd: bad sizes B=%d T=%d rows=%lld", B, T, (long long)rows);
+    ERC_REQUIRE(zero_to >= 0 && zero_to <= rows, "gru_scan_bwd: zero_to %lld outside [0, rows=%lld]", (long long)zero_to,
+                (long long)rows);
     ERC_REQUIRE(drop_p <= 0.f || rng_state, "gru_scan_bwd: dropout needs rng_state");
     ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gru_scan_bwd: drop_p %f", drop_p);
     GruP p = common(lengths, node_off, B, T, rows);
     p.W = W_hh; p.gates = const_cast<float*>(gates); p.ghn = const_cast<float*>(ghn); p.Hprev = const_cast<float*>(Hprev);
     p.dH = dH; p.drop_p = drop_p; p.rng = rng_state; p.rng_stream = rng_stream; p.dGX = dGX; p.dGH = dGH;
-    hipLaunchKernelGGL(gru_bwd_kernel, dim3(B, 2, 3), dim3(BWD_THREADS), 0, (hipStream_t)stream, p);
+    p.zero_to = zero_to;
+    if (zero_to > 0)
+        hipLaunchKernelGGL(gru_bwd_kernel<true>, dim3(B, 2, 3), dim3(BWD_THREADS), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(gru_bwd_kernel<false>, dim3(B, 2, 3), dim3(BWD_THREADS), 0, (hipStream_t)stream, p);
     ERC_LAUNCH_CHECK("gru_scan_bwd");
     return ERC_OK;
+}
+
+extern "C" int erc_gru_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int B, int T,
+                                int64_t rows, const float* gates, const float* ghn, const float* Hprev, const float* dH,
+                                float drop_p, const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH,
+                                void* stream) {
+    return erc_gru_scan_bwd_cap(W_hh, lengths, node_off, B, T, rows, gates, ghn, Hprev, dH, drop_p, rng_state, rng_stream, dGX,
+                                dGH, 0, stream);
 }

@@ -440,19 +440,29 @@ __device__ __forceinline__ double block_sum_fixed(double v, double* red) {
     return red[0];
 }
 
+// CAP (erc_ce_bce_multitask_cap): n_rows is a capacity and the batch's sample count n = *n_dev clamped to [0, n_rows].  Both
+// means run over n; rows at or beyond n are not read, and their dlogits rows are WRITTEN 0 (the head's weight-gradient
+// product and the GEMM behind dmerged run over all n_rows rows).  n == 0: every term is 0, not 0 / 0.
+template <bool CAP>
 __global__ __launch_bounds__(256) void ce_bce_multitask_kernel(const float* __restrict__ logits, int ld, int C,
                                                                int n_rows, const int64_t* __restrict__ labels,
                                                                const int64_t* __restrict__ emo, int lde, float w_ce,
                                                                float w_bce, float grad_scale,
                                                                float* __restrict__ dlogits, int lddl,
-                                                               float* __restrict__ stats) {
+                                                               float* __restrict__ stats, const int32_t* __restrict__ n_dev) {
     __shared__ double red[256];
     __shared__ int s_last;
     const int tid = threadIdx.x;
-    const float coef_ce = (float)((double)w_ce / (double)n_rows) * grad_scale;
-    const float coef_bce = (float)((double)w_bce / (7.0 * (double)n_rows)) * grad_scale;
+    const int n_cap = n_rows;
+    if (CAP) n_rows = min(max(*n_dev, 0), n_cap);
+    const bool empty = CAP && n_rows == 0;
+    const float coef_ce = empty ? 0.f : (float)((double)w_ce / (double)n_rows) * grad_scale;
+    const float coef_bce = empty ? 0.f : (float)((double)w_bce / (7.0 * (double)n_rows)) * grad_scale;
     double ce_acc = 0.0, bce_acc = 0.0;
     int hit = 0;
+    if (CAP && dlogits)
+        for (int i = n_rows + blockIdx.x * 256 + tid; i < n_cap; i += gridDim.x * 256)
+            for (int c = 0; c < C + MT_EMO; ++c) dlogits[(int64_t)i * lddl + c] = 0.f;
     for (int i = blockIdx.x * 256 + tid; i < n_rows; i += gridDim.x * 256) {
         const float* z = logits + (int64_t)i * ld;
         const int y = (int)labels[i];
@@ -512,7 +522,7 @@ __global__ __launch_bounds__(256) void ce_bce_multitask_kernel(const float* __re
         const double hsum = block_sum_fixed(h, red);
         const double bsum = block_sum_fixed(b, red);
         if (tid == 0) {
-            const double lce = lsum / (double)n_rows, lmulti = bsum / (7.0 * (double)n_rows);
+            const double lce = empty ? 0.0 : lsum / (double)n_rows, lmulti = empty ? 0.0 : bsum / (7.0 * (double)n_rows);
             stats[0] = (float)((double)w_ce * lce + (double)w_bce * lmulti);
             stats[1] = (float)hsum;
             stats[2] = (float)lce;
@@ -646,8 +656,22 @@ extern "C" int erc_ce_bce_multitask(const float* logits, int ld, int C, int n_ro
                 "ce_bce_multitask: C=%d n_rows=%d ld=%d lde=%d lddl=%d", C, n_rows, ld, lde, lddl);
     int grid = erc_cdiv(n_rows, 256);
     if (grid > MT_MAXWG) grid = MT_MAXWG;
-    hipLaunchKernelGGL(ce_bce_multitask_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_rows,
-                       labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats);
+    hipLaunchKernelGGL(ce_bce_multitask_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_rows,
+                       labels, emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats, (const int32_t*)nullptr);
     ERC_LAUNCH_CHECK("ce_bce_multitask");
+    return ERC_OK;
+}
+
+extern "C" int erc_ce_bce_multitask_cap(const float* logits, int ld, int C, int n_cap, const int32_t* n_dev, const int64_t* labels,
+                                        const int64_t* emo_label, int lde, float w_ce, float w_bce, float grad_scale,
+                                        float* dlogits, int lddl, float* stats, void* stream) {
+    ERC_REQUIRE(logits && labels && emo_label && stats && n_dev, "ce_bce_multitask_cap: null pointer");
+    ERC_REQUIRE(C > 0 && n_cap > 0 && ld >= C + MT_EMO && lde >= MT_EMO && (!dlogits || lddl >= C + MT_EMO),
+                "ce_bce_multitask_cap: C=%d n_cap=%d ld=%d lde=%d lddl=%d", C, n_cap, ld, lde, lddl);
+    int grid = erc_cdiv(n_cap, 256);
+    if (grid > MT_MAXWG) grid = MT_MAXWG;
+    hipLaunchKernelGGL(ce_bce_multitask_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, logits, ld, C, n_cap, labels,
+                       emo_label, lde, w_ce, w_bce, grad_scale, dlogits, lddl, stats, n_dev);
+    ERC_LAUNCH_CHECK("ce_bce_multitask_cap");
     return ERC_OK;
 }

@@ -1289,7 +1289,9 @@ int erc_gru_scan_bwd(const float* W_hh, const int64_t* lengths, const int32_t* n
  * columns 600 + 100 m hold dense_m (m = a, v, t); the forward writes pair p of (av, va, ta, tv, at, vt) to columns
  * [100p, 100p+100) and saves the softmax to Pbuf [6][B][T][T].  The backward reads dmerged[:, 0:600), ADDS the gradient
  * wrt every dense_m to dmerged[:, 600:900) in a fixed order (no atomics), then multiplies that block by
- * (dense > 0 ? mask_scale : 0): drop1 and ReLU's backward (cim.py:152-158).  T <= erc_cim_max_t(), else ERC_E_ARG. */
+ * (dense > 0 ? mask_scale : 0): drop1 and ReLU's backward (cim.py:152-158).  T <= erc_cim_max_t(), else ERC_E_ARG.
+ * Capacity mode launches both with (B_cap, T_cap) and Pbuf [6][B_cap][T_cap][T_cap]: a dialogue of length 0 is a no-op (no
+ * softmax over an empty row, nothing read or written), and only the rows of a dialogue are touched. */
 int erc_cim_max_t(void);
 int erc_cim_attn_fwd(float* merged, const int32_t* node_off, int B, int T, float* Pbuf, void* stream);
 int erc_cim_attn_bwd(const float* merged, float* dmerged, const int32_t* node_off, int B, int T, const float* Pbuf,
@@ -1308,6 +1310,45 @@ int erc_cim_attn_bwd(const float* merged, float* dmerged, const int32_t* node_of
 int erc_ce_bce_multitask(const float* logits, int ld, int C, int n_rows, const int64_t* label, const int64_t* emo_label,
                          int lde, float w_ce, float w_bce, float grad_scale, float* dlogits, int lddl, float* stats,
                          void* stream);
+/* CIM in CAPACITY mode (CIMModule.dynamic_n; one captured step serves every batch that fits its bucket): every launch is sized
+ * for B = B_cap dialogue slots (missing ones: length 0), T = T_cap and n_cap compact rows; the batch's own row count n is on
+ * the device.  Rows [n, n_cap) are TAIL rows.  The invariant of the step, link by link:
+ *   forward buffers (GX, Hout, Hdrop, merged, logits): a tail row holds whatever an earlier batch left, or Linear(tail_row's
+ *     features) in GX; it is finite, and nothing that walks node_off / lengths (the scans, the attention) reads or writes it;
+ *   dlogits tail rows = 0: WRITTEN by erc_ce_bce_multitask_cap; single task: by erc_mm_zero_tail after erc_cross_entropy_cap;
+ *   dmerged tail rows = 0: dmerged = dlogits W is a GEMM over all n_cap rows, and a zero row gives a zero row; the attention
+ *     backward touches only the rows of a dialogue;
+ *   dH tail rows = 0: dH_m = dmerged[:, 600 + 100 m ..] W_adapter, again a GEMM over n_cap rows;
+ *   dGX, dGH tail rows = 0: WRITTEN by erc_gru_scan_bwd_cap (zero_to = n_cap).
+ * So every weight-gradient product (dlogits^T merged, dpre^T H, dGX^T x, dGH^T Hprev) may run over n_cap rows: a tail row adds
+ * 0 * finite.
+ *
+ * erc_cim_meta_cap: the tables of such a step, in one of two forms (both or neither: ERC_E_ARG).
+ *   BUCKET form: lengths int64 [B], 0 for absent slots; desc, store_label, store_emo, label_out, emo_out NULL.  node_row of
+ *     node node_off[b] + t is b*T + t, its row of the padded [B, T, .] feature blocks; tail_row in [0, B*T] (B*T: a zero row the
+ *     caller keeps behind each block).
+ *   RESIDENT form: desc int32 [2 B] = lengths | first store rows; lengths NULL.  node_row = the store row first[b] + t;
+ *     tail_row = the zero row behind the store's features (the store has tail_row rows; a descriptor row outside it reads the zero
+ *     row and label 0).  Optional, each pair together: store_label int64 [tail_row] -> label_out [n_cap]; store_emo int64
+ *     [tail_row, 7] -> emo_out [n_cap, 7]; tail entries 0.
+ *   Both: every length is clamped to [0, T] and to what n_cap still holds; node_off [B+1]; node_row [n_cap], tail entries =
+ *     tail_row; lengths_out int64 [B] = the clamped lengths, which erc_gru_scan_fwd / _bwd read; counts int32 [2] = n, the
+ *     longest dialogue.  B <= 1024, n_cap <= B*T, T <= erc_cim_max_t() (else ERC_E_ARG, before any launch). */
+int erc_cim_meta_cap(const int64_t* lengths, const int32_t* desc, const int64_t* store_label, const int64_t* store_emo,
+                     int tail_row, int B, int T, int n_cap, int32_t* node_off, int32_t* node_row, int64_t* lengths_out,
+                     int64_t* label_out, int64_t* emo_out, int32_t* counts, void* stream);
+/* erc_gru_scan_bwd, and rows [node_off[B], zero_to) of dGX and dGH (all three modalities, both directions) are written 0;
+ * zero_to in [0, rows], 0 = erc_gru_scan_bwd itself.  The forward scan has no capacity form: a slot of length 0 runs no step
+ * and rows at or beyond node_off[B] are not written. */
+int erc_gru_scan_bwd_cap(const float* W_hh, const int64_t* lengths, const int32_t* node_off, int B, int T, int64_t rows,
+                         const float* gates, const float* ghn, const float* Hprev, const float* dH, float drop_p,
+                         const uint64_t* rng_state, uint64_t rng_stream, float* dGX, float* dGH, int64_t zero_to, void* stream);
+/* erc_ce_bce_multitask over the first n = clamp(*n_dev, 0, n_cap) of n_cap rows: both means run over n, rows at or beyond n are
+ * not read, dlogits rows [n, n_cap) are WRITTEN 0 (columns 0 .. C+7), and n == 0 gives zero stats (no 0 / 0).  Same stats
+ * layout, fixed-order partials and no float atomics as the exact form. */
+int erc_ce_bce_multitask_cap(const float* logits, int ld, int C, int n_cap, const int32_t* n_dev, const int64_t* label,
+                             const int64_t* emo_label, int lde, float w_ce, float w_bce, float grad_scale, float* dlogits,
+                             int lddl, float* stats, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * conv-emotion DialogueGCN (track_mm/dgcnv2.py, track_mm/dgcnv2_models.py; csrc/dgcnv2_att.hip).  Batches are time-major

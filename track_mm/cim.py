@@ -18,6 +18,10 @@ class CIMParams(ERCParams):
         self.optim = Group(name="Adam", lr=0.001, weight_decay=0)                 # cim.py:42
         self.apply_multi = True
         self.apply_bin = True
+        # capacity buckets (one captured graph per (B_cap, T_cap, N_cap) instead of per exact shape) are opt-in here:
+        # --capacity_buckets=True, or --resident (with --device_collate), which implies them; --resident_eval with --resident
+        # (not on CMU-MOSEI with its multi-label metrics)
+        self.capacity_buckets = False
 
     def iparams(self):
         super().iparams()
