@@ -31,6 +31,9 @@ constexpr int HF_NT = 7;       // column tiles of 16 (F <= 100 -> 7 tiles, the l
 constexpr int HF_MAXF = 100;
 constexpr int HF_MAXC = 8;
 constexpr int HF_PART = 2 * 112 + 4;  // floats per workgroup partial record: column sums of dY | of dY * xhat | loss part, hits, weight sum, pad
+// The arrival counter lives in the pad slot of record 0: the same word for every n_rows.  (Behind the last record, as it was,
+// a launch of fewer rows on a workspace last used by a larger one found that launch's record there -- never the last arriver.)
+constexpr int HF_COUNTER = HF_PART - 1;
 constexpr int BS_G = 256;      // workgroups of the statistics pass: capacity of the partial records (one per CU for N > 8 192 rows)
 constexpr int BS_G_SMALL = 64; // ... up to 8 192 rows (the last arriver's sum over the partials is the longer part there)
 
@@ -1228,7 +1231,7 @@ static int head_fused_launch(const float* H2, int ldh, int n_rows, int F, int C,
         const int tiles = erc_cdiv(n_rows, 16);
         const int grid_w = erc_cdiv(tiles, 4) < 512 ? erc_cdiv(tiles, 4) : 512;
         p.part = ws;
-        p.counter = reinterpret_cast<int*>(ws + (int64_t)grid_w * HF_PART);
+        p.counter = reinterpret_cast<int*>(ws + HF_COUNTER);
         hipLaunchKernelGGL(head_rows_kernel, dim3(grid_w), dim3(256), 0, (hipStream_t)stream, p);
         ERC_LAUNCH_CHECK("head_fused (rows)");
         return ERC_OK;
@@ -1236,7 +1239,7 @@ static int head_fused_launch(const float* H2, int ldh, int n_rows, int F, int C,
     const int rpw = erc_head_fused_rows_per_workgroup(n_rows) / 16;
     const int grid = erc_cdiv(n_rows, 16 * rpw);
     p.part = ws;
-    p.counter = reinterpret_cast<int*>(ws + (int64_t)grid * HF_PART);
+    p.counter = reinterpret_cast<int*>(ws + HF_COUNTER);
     if (rpw == 2) {
         if (bn_part) hipLaunchKernelGGL((head_fused_kernel<true, 2>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
         else hipLaunchKernelGGL((head_fused_kernel<false, 2>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);

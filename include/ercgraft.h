@@ -394,7 +394,8 @@ int erc_bn_batch_stats(const float* x, int ldx, int N, int F, float* running_mea
  * H2 [n_rows, ldh]; H3, Z, dZ, dY [n_rows, F]; logits, dlogits [n_rows, C]; W0 [F,F], W3 [C,F] row-major.
  * F <= 100, F % 4 == 0, C <= 8, 16-byte aligned H2 / gamma / beta / saved / W0 / H3.  Dropout uses the counter RNG
  * of erc_gemm_f32 act = 3 (element index row * F + col; rng_state = {offset, seed}), so the mask is the one
- * a separate Linear launch would draw.  ws: erc_head_fused_ws_floats(n_rows) floats, zero before the first call. */
+ * a separate Linear launch would draw.  ws: erc_head_fused_ws_floats(n_rows) floats, zero before the first call; it may then
+ * serve launches of any smaller n_rows too (the arrival counter is the pad word of record 0, reset by every launch). */
 int64_t erc_head_fused_ws_floats(int n_rows);
 int erc_head_fused(const float* H2, int ldh, int n_rows, int F, int C, const float* gamma, const float* beta,
                    const float* saved, float slope, const float* W0, const float* b0, const float* W3,
@@ -567,7 +568,9 @@ int erc_cogmen_bwd_tile_x(int terms, const float* dY, const float* H2, int ldh2,
 /* n_dev (here, in erc_cogmen_fwd_tile and in erc_head_fused{,_bn}; NULL = off): CAPACITY MODE.  n_nodes / n_rows is then the
  * capacity the grid and the buffers are sized for and the true count (<= capacity) is read from device memory -- counts[0]
  * of erc_cogmen_project_graph -- so that ONE captured HIP graph serves every batch whose node count fits the capacity
- * (rows >= the true count are masked exactly like the partial last tile; erc_wgrad_bf16 takes the same word as k_dev). */
+ * (rows >= the true count are masked exactly like the partial last tile; erc_wgrad_bf16 takes the same word as k_dev).
+ * erc_head_fused{,_bn} clamp the count to [1, n_rows]: at *n_dev = 0 row 0 is processed as if the count were 1 (the loss and the
+ * BatchNorm means divide by the count); only erc_head_eval takes a count of 0. */
 /* grads_bf16 != 0: dQKVS [N, 400], dH1 [N, lddh1], dH0 [N, lddh0] are written as bf16 (pitches in elements, pad columns
  * untouched): they are only ever operands of the bf16 weight-gradient products (erc_wgrad_bf16), so the rounding moves from
  * that kernel's loads to these stores.  Otherwise fp32 (lddh1 >= 100). */
