@@ -254,7 +254,9 @@ extern "C" int erc_match_att_bwd_cap(const float* E, int lde, const float* Q, in
     ERC_REQUIRE(aligned16(E, lde) && aligned16(Q, ldq) && aligned16(dA, ldda) && aligned16(dQ, lddq) && aligned16(dE, ldde),
                 "match_att_bwd: rows must be 16-byte aligned");
     ERC_REQUIRE(lde >= F && ldq >= F && ldda >= F && lddq >= F && ldde >= F, "match_att_bwd: row pitches below %d", F);
-    ERC_REQUIRE(dE != E && dE != Q && dE != dA && dQ != E && dQ != dA, "match_att_bwd: outputs must not alias inputs");
+    // dQ == Q included: the key-side launch reads Q after the query-side launch has written dQ
+    ERC_REQUIRE(dE != E && dE != Q && dE != dA && dQ != E && dQ != Q && dQ != dA && dQ != dE,
+                "match_att_bwd: outputs must not alias inputs or each other");
     const auto launch = n_cap > 0 ? launch_bwd<200, true> : F == 200 ? launch_bwd<200, false> : launch_bwd<300, false>;
     return launch(dim3(erc_cdiv(T, TILE), B), (hipStream_t)stream, E, lde, Q, ldq, dA, ldda, node_off, B, T, P, TH, DZ, dQ, lddq, dE,
                   ldde, n_cap);

@@ -1385,7 +1385,8 @@ int erc_dgcnv2_edge_att_bwd(const float* S, int ldS, const int32_t* node_off, in
  * (node_off[b] + t); Q = E W^T + b is a GEMM by the caller: A_t = sum_j p_tj E_j, p_tj = softmax_j(tanh(Q_t . E_j)).
  * P and TH [B, T, T] save p and tanh for the backward.  The backward writes dQ [N, F] and dE [N, F] = P^T dA + dZ^T Q
  * (the caller adds dQ W), and DZ [B, T, T] (the gradient wrt the pre-tanh scores).  Row pitches >= F, multiples of 4,
- * 16-byte aligned.  Every element is summed by one thread in a fixed order. */
+ * 16-byte aligned.  Every element is summed by one thread in a fixed order.  dQ and dE alias no input and not each other
+ * (the backward is two launches: the second reads Q after the first wrote dQ), else ERC_E_ARG. */
 int erc_match_att_fwd(const float* E, int lde, const float* Q, int ldq, const int32_t* node_off, int B, int T, int F, float* A,
                       int lda, float* P, float* TH, void* stream);
 int erc_match_att_bwd(const float* E, int lde, const float* Q, int ldq, const float* dA, int ldda, const int32_t* node_off,

@@ -134,12 +134,15 @@ def test_gru_scan_matches_torch_gru(lens, d_in):
 
 # ----------------------------------------------------------------------------------------------------- attention
 def test_attention_matches_autograd():
-    """erc_cim_attn_fwd / _bwd against CPU autograd of attention_op on ragged dialogues (lengths 1..110)"""
+    """erc_cim_attn_fwd / _bwd against CPU autograd of attention_op on ragged dialogues (lengths 1..110); the dense values
+    are what ReLU and drop1 leave (about half exact zeros), so the backward's mask tail takes both arms at a scale other than 1"""
     from tests.cim_oracle import PAIRS, cross_attention
     lens = [7, 1, 110, 23]
     N, B, T = sum(lens), len(lens), max(lens)
     g = torch.Generator().manual_seed(2)
-    dense = {m: (torch.rand(N, 100, generator=g) * 0.6 + 0.05).requires_grad_() for m in "avt"}
+    keep = {m: torch.rand(N, 100, generator=g) < 0.5 for m in "avt"}
+    dense = {m: ((torch.rand(N, 100, generator=g) * 0.6 + 0.05) * keep[m]).requires_grad_() for m in "avt"}
+    mask_scale = 1.0 / (1.0 - 0.3)
     outs = [cross_attention(dense[x], dense[y], lens) for x, y in PAIRS]
     G = torch.randn(N, 600, generator=g)
     Gd = torch.randn(N, 300, generator=g)
@@ -151,11 +154,12 @@ def test_attention_matches_autograd():
     P = torch.zeros(6 * B * T * T, device=DEV)
     capi.cim_attn_fwd(mg, node_off, B, T, P)
     dm = torch.cat([G, Gd], -1).to(DEV)
-    capi.cim_attn_bwd(mg, dm, node_off, B, T, P, 1.0)
+    capi.cim_attn_bwd(mg, dm, node_off, B, T, P, mask_scale)
     torch.cuda.synchronize()
     assert _err(mg, merged) < 1e-5
     for i, m in enumerate("avt"):
-        want = dense[m].grad + Gd[:, 100 * i:100 * i + 100]
+        want = (dense[m].grad + Gd[:, 100 * i:100 * i + 100]) * keep[m] * mask_scale
+        assert (~keep[m]).any() and bool((dm[:, 600 + 100 * i:700 + 100 * i].cpu()[~keep[m]] == 0).all()), m
         assert _err(dm[:, 600 + 100 * i:700 + 100 * i], want) <= 1e-5 * (float(want.abs().max()) + 1), m
     # T above the LDS limit is refused before launch
     with pytest.raises(capi.ErcGraftError):
