@@ -35,8 +35,6 @@ __constant__ int c_py[6] = {1, 0, 0, 1, 2, 2};
 
 inline int64_t lds_floats(int T) { return 2 * (int64_t)T * D + (int64_t)T * T + T; }
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float dot100(const float* a, const float* b) {
     const f4* a4 = reinterpret_cast<const f4*>(a);
     const f4* b4 = reinterpret_cast<const f4*>(b);

@@ -29,9 +29,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int CG_F = 100;                    // channels (the reference hard-codes 100: cogmen.py:116-122)
 constexpr int CG_R = 8;                      // relations (GNN(n_speakers = 2): cogmen.py:62-64)
 constexpr int CG_HL = 5;                     // halo = max(wp, wf)
@@ -98,34 +95,6 @@ struct FxMap {
     static_assert(RED_OFF + FW_RED_BYTES + 16 <= PFX_OFF + FW_PFX_BYTES && PFX_OFF % 16 == 0 && LDS <= 160 * 1024, "split forward LDS map");
     static_assert(2048 + 4 * 2 * CG_F * 8 <= FX_MPLANE && FX_ZERO + 8 <= 2048, "segment totals of the prefix scan live in the M area, clear of the zero slots");
 };
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ double ld_sc1d(const double* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1d(double* p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// CG_CH (<= 16) per-lane partial dot products -> every lane gets all wave totals: one 16-value butterfly
-__device__ __forceinline__ void wave_sums_ch(const float (&part)[16], float (&tot)[CG_CH], int lane) {
-    float b[8], c[4], d[2];
-    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8, h2 = lane & 4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (h5 ? part[8 + j] : part[j]) + __shfl_xor(h5 ? part[j] : part[8 + j], 32, 64);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = (h4 ? b[4 + j] : b[j]) + __shfl_xor(h4 ? b[j] : b[4 + j], 16, 64);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) d[j] = (h3 ? c[2 + j] : c[j]) + __shfl_xor(h3 ? c[j] : c[2 + j], 8, 64);
-    float e = (h2 ? d[1] : d[0]) + __shfl_xor(h2 ? d[0] : d[1], 4, 64);
-    e += __shfl_xor(e, 2, 64);
-    e += __shfl_xor(e, 1, 64);
-#pragma unroll
-    for (int u = 0; u < CG_CH; ++u) tot[u] = __shfl(e, ((u >> 3) & 1) * 32 + ((u >> 2) & 1) * 16 + ((u >> 1) & 1) * 8 + (u & 1) * 4, 64);
-}
 
 // diagnostic phase stamps (tools/cogmen_stamps.py): the 100 MHz real-time counter, written by thread 0 of one workgroup
 #define CG_STAMP(slot)                                                                                            \
@@ -286,7 +255,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
     }
     __builtin_amdgcn_sched_barrier(0);   // the tile / graph loads above are queued first
     bf16x8 bx[X ? 1 : KH0];
-    sp_u32x4 bxr[X ? FX_PF<NT> : 1][X ? NT : 1];      // split modes: a ring of FX_PF K blocks x NT term planes
+    u32x4 bxr[X ? FX_PF<NT> : 1][X ? NT : 1];      // split modes: a ring of FX_PF K blocks x NT term planes
     if constexpr (!X) {
 #pragma unroll
         for (int u = 0; u < KH0; ++u) bx[u] = *reinterpret_cast<const bf16x8*>(brow + 512 * min(u, nkb - 1));
@@ -294,7 +263,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
 #pragma unroll
         for (int u = 0; u < FX_PF<NT>; ++u)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) bxr[u][t] = *reinterpret_cast<const sp_u32x4*>(brow + t * p.catT_plane + 512 * min(u, nkb - 1));
+            for (int t = 0; t < NT; ++t) bxr[u][t] = *reinterpret_cast<const u32x4*>(brow + t * p.catT_plane + 512 * min(u, nkb - 1));
     }
     __syncthreads();
     CG_STAMP(1);
@@ -522,16 +491,16 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
                         ad0[hh] = (need == 0 || need == 1 + spk0) ? rb0 + cc : FX_ZERO;
                         ad1[hh] = (need == 0 || need == 1 + spk1) ? rb1 + cc : FX_ZERO;
                     }
-                    sp_u32x4 fa0[NT], fa1[NT], fb[NT];
+                    u32x4 fa0[NT], fa1[NT], fb[NT];
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         const unsigned char* const pl = mbase + t * FX_MPLANE;
                         const uint2 x0 = *reinterpret_cast<const uint2*>(pl + ad0[0]), x1 = *reinterpret_cast<const uint2*>(pl + ad0[1]);
                         const uint2 y0 = *reinterpret_cast<const uint2*>(pl + ad1[0]), y1 = *reinterpret_cast<const uint2*>(pl + ad1[1]);
-                        fa0[t] = (sp_u32x4){x0.x, x0.y, x1.x, x1.y}, fa1[t] = (sp_u32x4){y0.x, y0.y, y1.x, y1.y};
+                        fa0[t] = (u32x4){x0.x, x0.y, x1.x, x1.y}, fa1[t] = (u32x4){y0.x, y0.y, y1.x, y1.y};
                         fb[t] = bxr[u % FX_PF<NT>][t];
                         if (u + FX_PF<NT> < KH0)      // (compile time) refill the ring slot: K block u + FX_PF, clamped (a block past the end is never multiplied)
-                            bxr[u % FX_PF<NT>][t] = *reinterpret_cast<const sp_u32x4*>(brow + t * p.catT_plane + 512 * min(u + FX_PF<NT>, nkb - 1));
+                            bxr[u % FX_PF<NT>][t] = *reinterpret_cast<const u32x4*>(brow + t * p.catT_plane + 512 * min(u + FX_PF<NT>, nkb - 1));
                     }
                     acc0 = sp_mfma<NT>(fa0, fb, acc0);
                     acc1 = sp_mfma<NT>(fa1, fb, acc1);
@@ -546,7 +515,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
     // B fragments of the QKVS product (wavefront w: column tiles w and w + 16 of 25; K = 128): in flight across the barrier
     // (split modes: the first column tile's NT planes; the second tile's are requested while the first is multiplied)
     bf16x8 fq[X ? 1 : 2][4];
-    sp_u32x4 fqx[X ? 4 : 1][X ? NT : 1];
+    u32x4 fqx[X ? 4 : 1][X ? NT : 1];
     float qbias[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -559,7 +528,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-                for (int t = 0; t < NT; ++t) fqx[kb][t] = *reinterpret_cast<const sp_u32x4*>(bq + t * p.q_plane + 512 * kb);
+                for (int t = 0; t < NT; ++t) fqx[kb][t] = *reinterpret_cast<const u32x4*>(bq + t * p.q_plane + 512 * kb);
         }
         qbias[j] = p.bq[16 * qt + r];
     }
@@ -648,13 +617,13 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
                 const unsigned short* const bq1 = p.Wq + ((int64_t)min(w + 16, 24) * 4 * 64 + lane) * 8;
 #pragma unroll
                 for (int kb = 0; kb < 4; ++kb) {
-                    sp_u32x4 fa0[NT], fa1[NT], fb[NT];
+                    u32x4 fa0[NT], fa1[NT], fb[NT];
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         const unsigned short* const pl = sH1 + t * (FW_SH1_BYTES / 2) + 32 * kb + 8 * g;
-                        fa0[t] = *reinterpret_cast<const sp_u32x4*>(pl + r * CG_SH1), fa1[t] = *reinterpret_cast<const sp_u32x4*>(pl + (16 + r) * CG_SH1);
+                        fa0[t] = *reinterpret_cast<const u32x4*>(pl + r * CG_SH1), fa1[t] = *reinterpret_cast<const u32x4*>(pl + (16 + r) * CG_SH1);
                         fb[t] = fqx[kb][t];
-                        if (j == 0 && NT == 2) fqx[kb][t] = *reinterpret_cast<const sp_u32x4*>(bq1 + t * p.q_plane + 512 * kb);
+                        if (j == 0 && NT == 2) fqx[kb][t] = *reinterpret_cast<const u32x4*>(bq1 + t * p.q_plane + 512 * kb);
                     }
                     acc[0] = sp_mfma<NT>(fa0, fb, acc[0]);
                     acc[1] = sp_mfma<NT>(fa1, fb, acc[1]);
@@ -664,7 +633,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
 #pragma unroll
                     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-                        for (int t = 0; t < NT; ++t) fqx[kb][t] = *reinterpret_cast<const sp_u32x4*>(bq1 + t * p.q_plane + 512 * kb);
+                        for (int t = 0; t < NT; ++t) fqx[kb][t] = *reinterpret_cast<const u32x4*>(bq1 + t * p.q_plane + 512 * kb);
                 }
             } else {
 #pragma unroll
@@ -821,16 +790,6 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_fwd_tile_kernel(const CgFwdP p)
         }
         if (p.stamps && tid == 0) p.stamps[7] = __builtin_amdgcn_s_memrealtime();   // the last arriver, whichever tile it is
     }
-}
-
-// sum over the 16 lanes of a row (lanes 16 g .. 16 g + 15), in every lane: DPP exchanges, no LDS traffic
-template <int CTRL>
-__device__ __forceinline__ float cg_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float cg_row16_sum(float v) {
-    v += cg_dpp<0xB1>(v), v += cg_dpp<0x4E>(v), v += cg_dpp<0x141>(v), v += cg_dpp<0x140>(v);   // quad xor 1 / xor 2, row_half_mirror, row_mirror
-    return v;
 }
 
 // ------------------------------------------------------------------------------------------------------ backward
@@ -1165,7 +1124,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
             const float al0 = k0 ? sAl[min(e0 + max(o0, 0), BW_ECAP - 1)] : 0.f;
             const float al1 = k1 ? sAl[min(e0 + max(o1, 0), BW_ECAP - 1)] : 0.f;
             const float x0 = k0 ? al0 * a0 : 0.f, x1 = k1 ? al1 * a1 : 0.f;
-            const float tsum = cg_row16_sum(x0 + x1);
+            const float tsum = row16_sum(x0 + x1);
             const float d0 = k0 ? al0 * (a0 - tsum) * p.scale : 0.f, d1 = k1 ? al1 * (a1 - tsum) * p.scale : 0.f;
             float* drow = sDS + t * BW_BAND + 16 * bi + r;
             float* arow = sAL + t * BW_BAND + 16 * bi + r;
@@ -1179,7 +1138,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
     // B fragments of the dH1 product (K = 416: blocks [7 kh, 7 kh + 7), the second half has 6): requested now
     const unsigned short* const brow3 = p.WqT + ((int64_t)(min(ct, CG_NT - 1) * 13 + 7 * kh) * 64 + lane) * 8;
     bf16x8 fb3[X ? 1 : 7];
-    sp_u32x4 fb3r[X ? BX_PF<NT> : 1][X ? NT : 1], bxr[X ? BX_PF<NT> : 1][X ? NT : 1];      // split modes: rings of BX_PF K blocks x NT planes
+    u32x4 fb3r[X ? BX_PF<NT> : 1][X ? NT : 1], bxr[X ? BX_PF<NT> : 1][X ? NT : 1];      // split modes: rings of BX_PF K blocks x NT planes
     if constexpr (!X) {
 #pragma unroll
         for (int u = 0; u < 7; ++u) fb3[u] = *reinterpret_cast<const bf16x8*>(brow3 + 512 * min(u, kh ? 5 : 6));
@@ -1187,7 +1146,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
 #pragma unroll
         for (int u = 0; u < BX_PF<NT>; ++u)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) fb3r[u][t] = *reinterpret_cast<const sp_u32x4*>(brow3 + t * p.qT_plane + 512 * min(u, kh ? 5 : 6));
+            for (int t = 0; t < NT; ++t) fb3r[u][t] = *reinterpret_cast<const u32x4*>(brow3 + t * p.qT_plane + 512 * min(u, kh ? 5 : 6));
     }
 
     const unsigned short* const brow5 = p.Wb + ((int64_t)(min(ct, CG_NT - 1) * 30 + 15 * kh) * 64 + lane) * 8;
@@ -1324,13 +1283,13 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
 #pragma unroll
                 for (int u = 0; u < 7; ++u) {
                     if (u < nkb3) {   // wave-uniform
-                        sp_u32x4 fa0[NT], fa1[NT], fb[NT];
+                        u32x4 fa0[NT], fa1[NT], fb[NT];
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {
-                            fa0[t] = *reinterpret_cast<const sp_u32x4*>(a0 + t * (BX_DQPLANE / 2) + 32 * u);
-                            fa1[t] = *reinterpret_cast<const sp_u32x4*>(a1 + t * (BX_DQPLANE / 2) + 32 * u);
+                            fa0[t] = *reinterpret_cast<const u32x4*>(a0 + t * (BX_DQPLANE / 2) + 32 * u);
+                            fa1[t] = *reinterpret_cast<const u32x4*>(a1 + t * (BX_DQPLANE / 2) + 32 * u);
                             fb[t] = fb3r[u % BX_PF<NT>][t];
-                            if (u + BX_PF<NT> < 7) fb3r[u % BX_PF<NT>][t] = *reinterpret_cast<const sp_u32x4*>(brow3 + t * p.qT_plane + 512 * min(u + BX_PF<NT>, nkb3 - 1));
+                            if (u + BX_PF<NT> < 7) fb3r[u % BX_PF<NT>][t] = *reinterpret_cast<const u32x4*>(brow3 + t * p.qT_plane + 512 * min(u + BX_PF<NT>, nkb3 - 1));
                         }
                         acc0 = sp_mfma<NT>(fa0, fb, acc0);
                         acc1 = sp_mfma<NT>(fa1, fb, acc1);
@@ -1342,7 +1301,7 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
 #pragma unroll
                 for (int u = 0; u < BX_PF<NT>; ++u)
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) bxr[u][t] = *reinterpret_cast<const sp_u32x4*>(brow5 + t * p.wb_plane + 512 * u);
+                    for (int t = 0; t < NT; ++t) bxr[u][t] = *reinterpret_cast<const u32x4*>(brow5 + t * p.wb_plane + 512 * u);
             }
             if (kh) {
                 float* dst = sPart3 + (ct * 64 + lane) * 8;
@@ -1544,14 +1503,14 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
                         const int cc = (int)(en & 0xffffu), need = (int)(en >> 16);
                         ad[hh] = (need == 0 || need == 1 + spk_r) ? rb + cc : BX_ZERO;
                     }
-                    sp_u32x4 fa[NT], fb[NT];
+                    u32x4 fa[NT], fb[NT];
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         const unsigned char* const pl = pbase + t * BX_DPPLANE;
                         const uint2 x0 = *reinterpret_cast<const uint2*>(pl + ad[0]), x1 = *reinterpret_cast<const uint2*>(pl + ad[1]);
-                        fa[t] = (sp_u32x4){x0.x, x0.y, x1.x, x1.y};
+                        fa[t] = (u32x4){x0.x, x0.y, x1.x, x1.y};
                         fb[t] = bxr[u % BX_PF<NT>][t];
-                        if (u + BX_PF<NT> < 15) bxr[u % BX_PF<NT>][t] = *reinterpret_cast<const sp_u32x4*>(brow5 + t * p.wb_plane + 512 * (u + BX_PF<NT>));
+                        if (u + BX_PF<NT> < 15) bxr[u % BX_PF<NT>][t] = *reinterpret_cast<const u32x4*>(brow5 + t * p.wb_plane + 512 * (u + BX_PF<NT>));
                     }
                     acc = sp_mfma<NT>(fa, fb, acc);
                 }

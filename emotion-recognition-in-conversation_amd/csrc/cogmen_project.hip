@@ -22,12 +22,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int PG_NB = 6;       // K blocks of 32 per wavefront (8 wavefronts: K <= 1536)
 constexpr int PG_BMAX = 2048;  // dialogues per batch (offsets in LDS)
 

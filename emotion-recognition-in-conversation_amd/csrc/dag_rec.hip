@@ -56,10 +56,7 @@ constexpr int SPIN_LIMIT = 4000000;
 #endif
 
 typedef unsigned long long u64;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ u64 ld64(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_tag(u64* p, float v, unsigned tag) {
     __hip_atomic_store(p, ((u64)tag << 32) | (u64)__builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -269,7 +266,6 @@ __global__ __launch_bounds__(256) void dag_meta_cap_kernel(const float* __restri
         if (label_out) label_out[i] = 0;
     }
 }
-
 
 // ----------------------------------------------------------------------------------------------- forward
 // The forward runs the LAYERS as a pipeline: layer l needs, at its step i, only h^{(l-1)}_{i+1} of the layer below, so
@@ -1103,7 +1099,6 @@ extern "C" int erc_dag_meta_cap(const float* speaker_onehot, const int64_t* spea
     ERC_LAUNCH_CHECK("dag_meta_cap");
     return ERC_OK;
 }
-
 
 // cfg[4] = {elements per workgroup, dialogues per group, groups per launch, layers per launch}
 extern "C" int erc_dag_rec_config(int dir, int B, int T, int n_layers, int epc_hint, int dg_hint, int lpl_hint, int* cfg) {

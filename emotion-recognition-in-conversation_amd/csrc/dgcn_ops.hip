@@ -211,23 +211,6 @@ __global__ __launch_bounds__(256) void brgcn_agg_fwd_kernel(const float* __restr
             if (lane + 64 * u < F) z[b * F + lane + 64 * u] = acc[b][u];
 }
 
-// Sum 16 per-lane values over the wavefront in 17 shuffles (instead of 16 x 6): halve the set of values and the lane
-// distance together.  Lane l ends up with the total of entry ((l>>5)&1)*8 + ((l>>4)&1)*4 + ((l>>3)&1)*2 + ((l>>2)&1).
-__device__ __forceinline__ float butterfly16_sum(const float (&a)[16], int lane) {
-    float b[8], c[4], d[2];
-    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8, h2 = lane & 4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (h5 ? a[8 + j] : a[j]) + __shfl_xor(h5 ? a[j] : a[8 + j], 32, 64);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = (h4 ? b[4 + j] : b[j]) + __shfl_xor(h4 ? b[j] : b[4 + j], 16, 64);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) d[j] = (h3 ? c[2 + j] : c[j]) + __shfl_xor(h3 ? c[j] : c[2 + j], 8, 64);
-    float e = (h2 ? d[1] : d[0]) + __shfl_xor(h2 ? d[0] : d[1], 4, 64);
-    e += __shfl_xor(e, 2, 64);
-    e += __shfl_xor(e, 1, 64);
-    return e;
-}
-
 // per target i, per in-edge e: T_e[b] = x_src . dZ[i, b, :]  ->  dnorm_e = sum_b att[type_e,b] T_e[b],
 // TT[e, b] = norm_e T_e[b]  (summed per relation by rel_sum_kernel -> d att).
 // The 30 dot products of an edge are reduced by two 16-value butterflies (34 shuffles; one full wave_sum per basis was
@@ -412,7 +395,6 @@ __global__ __launch_bounds__(256) void brgcn_bwd_source_kernel(const float* __re
 // tiles interleave the columns (column 64 h + 4 n + j belongs to MFMA (h, j), lane column n).
 constexpr int TF = 200, TO = 100, TG = 5, NGRP = NB / TG;      // features, outputs, bases per group, groups
 constexpr int TKP = (TG + 1) * TF + 4;          // LDS row of the Z tile (10 blocks + root block), 16-byte multiple
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 unsigned long long* g_brgcn_stamps = nullptr;      // diagnostic: 100 MHz stamps of one workgroup (erc_brgcn_set_stamps)
 #define BR_STAMP(slot)                                                                                              \
     do {                                                                                                            \
@@ -510,11 +492,11 @@ __global__ __launch_bounds__(512) void brgcn_fwd_tile_kernel(const float* __rest
     const int per = (nks + 7) / 8, ks0 = w * per, ks1 = min(nks, ks0 + per);
     const int r = lane & 15, kk = lane >> 4;
     const float* bg = basis + (int64_t)g * TG * TF * TO;
-    f32x4_t acc[2][4];
+    f32x4 acc[2][4];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[h][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int c0 = 4 * r, c1 = 64 + 4 * r;              // the lane's 4 columns in the two column halves
     const bool v1 = c1 < TO;                             // 64 + 4 r + 3 < 100  <=>  r < 9 (whole float4 inside)
     const int c1c = v1 ? c1 : 0;
@@ -671,9 +653,9 @@ __global__ __launch_bounds__(512) void brgcn_bwd_source_tile_kernel(const float*
     const int nblk = (with_root ? SKR + 8 : SKB + 12) / 16;      // 600 -> 38 blocks (608), 500 -> 32 blocks (512)
     const int r = lane & 15, kk = lane >> 4;
     const float* bg = basis + (int64_t)g * TG * TF * TO;
-    f32x4_t acc[SNT];
+    f32x4 acc[SNT];
 #pragma unroll
-    for (int t = 0; t < SNT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < SNT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int blk = w; blk < nblk; blk += 8) {
         const int k = 16 * blk + 4 * kk;                 // this lane's 4 consecutive k (one basis: 4 | 100)
         const int kc = min(k, (with_root ? SKR : SKB) - 4);
@@ -761,7 +743,7 @@ __global__ __launch_bounds__(512) void brgcn_bwd_target_tile_kernel(const float*
             for (int blk = 0; blk < DKB; ++blk) bv[blk] = *reinterpret_cast<const float4*>(bcol + min(16 * blk + 4 * kk, TO - 4));
         };
         auto tile = [&](int t, const float4 (&bv)[DKB]) {
-            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int blk = 0; blk < DKB; ++blk) {       // A is zero where k >= 100: the clamped B values do not matter
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[blk].x, bv[blk].x, acc, 0, 0, 0);

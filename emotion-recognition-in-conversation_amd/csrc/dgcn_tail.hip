@@ -12,21 +12,11 @@
 // All products are v_mfma_f32_16x16x4_f32 (exact fp32 multiply-adds, as the GEMMs they replace).  Operand access: the matrix
 // core sums over k whichever k sits in which slot, so k-step j of a group of 16 takes k = 16 S + 4 (lane >> 4) + j for A and B
 // alike -- a lane's four steps are ONE 16-byte load (LDS for the row tile, global / L2 for a weight row).
-#include "erc_common.h"
+#include "dgcn_tail_dev.h"      // tile geometry, mfma4 / wrow4 / tile_product (shared with dgcn_tail_eval.hip)
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TG = 200, TH = 100, TX = 300;     // features, hidden width, classifier input
-constexpr int TR = 16;                          // rows of a workgroup
-constexpr int THL = 10;                         // window the kernel is built for (wp, wf <= 10)
-constexpr int TW = TR + 2 * THL;                // 36 window rows
-constexpr int PX = 308;                         // LDS pitch of the [features | graph_out] tile (K = 304 used)
-constexpr int PH = 116;                         // LDS pitch of the 100-wide tiles (K = 112 used)
 constexpr int PD = 20;                          // LDS pitch of the dlogits tile (K = 16 used)
-constexpr int TMAXC = 8;
-constexpr int TNT = 7;                          // 16-column tiles over 100
 
 struct TailP {
     const float* slabs; int n_slabs; int64_t slab_stride;     // RGCN partial outputs [S][N * 100]
@@ -54,24 +44,7 @@ uint64_t* g_tail_stamps = nullptr;
         if (p.stamps && blockIdx.x == 0 && tid == 0) p.stamps[slot] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 
-
-__device__ __forceinline__ f32x4 mfma4(const float4& a, const float4& b, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-    return acc;
-}
-
-// B operand of one group for a weight stored [n][k] (nn.Linear layout, the product x W^T): 16 bytes of row n
-__device__ __forceinline__ float4 wrow4(const float* __restrict__ W, int ldw, int n, bool nv, int k0, int K) {
-    // (rows are 16-byte aligned: ldw % 4 == 0; K % 4 == 0, so a quad is inside the row or outside)
-    const bool v = nv && k0 < K;
-    const float4 w = *reinterpret_cast<const float4*>(W + (int64_t)n * ldw + (v ? k0 : 0));
-    const float m = v ? 1.f : 0.f;
-    return make_float4(w.x * m, w.y * m, w.z * m, w.w * m);
-}
-// ... for a weight stored [k][n] (the product dy W): four rows, one element each
+// B operand of one group, as wrow4, for a weight stored [k][n] (the product dy W): four rows, one element each
 __device__ __forceinline__ float4 wcol4(const float* __restrict__ W, int ldw, int n, bool nv, int k0, int K) {
     float v[4];
 #pragma unroll
@@ -81,20 +54,6 @@ __device__ __forceinline__ float4 wcol4(const float* __restrict__ W, int ldw, in
     }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
-
-// one 16 x 16 output tile over NG groups of 16 k: A rows from LDS (pitch pa, K padded with zeros), B fragments from registers
-template <int NG>
-__device__ __forceinline__ f32x4 tile_product(const float* sA, int pa, int l15, int kq, const float4 (&b)[NG], f32x4 acc) {
-#pragma unroll
-    for (int S = 0; S < NG; ++S) {
-        const float4 a = *reinterpret_cast<const float4*>(sA + l15 * pa + 16 * S + 4 * kq);
-        acc = mfma4(a, b[S], acc);
-    }
-    return acc;
-}
-
-constexpr int TNW = 8;              // wavefronts of a workgroup
-constexpr int TNTH = 64 * TNW;
 
 // The phases meet at lds_barrier() (erc_common.h), not __syncthreads(): the weight fragments of the NEXT phase are requested
 // before each barrier and must stay in flight across it (a phase would otherwise start with an L2 round trip per tile:

@@ -59,8 +59,6 @@ struct DrnnP {
     float* dREC;
 };
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // which: 0 g, 1 q[p], 2 e, 3 emotions
 __device__ __forceinline__ bool kept(uint64_t seed, uint64_t off, int64_t row, int which, int u, float p) {
     return erc_uniform(seed, off, ((uint64_t)row * 4 + which) * 160 + u) >= p;
@@ -69,8 +67,6 @@ __device__ __forceinline__ bool kept(uint64_t seed, uint64_t off, int64_t row, i
 __device__ __forceinline__ float* plane(float* base, int off, int w, int64_t N, int d, int64_t row) {
     return base + (int64_t)off * 2 * N + ((int64_t)d * N + row) * w;
 }
-
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 // rows 2 jp, 2 jp + 1 of the transposed block: out = sum_k WT[k * rows + 2 jp ..] x[k0 + k]  (8-byte loads; rows is even)
 __device__ __forceinline__ f2 dot_t2(const float* __restrict__ WT, int rows, int jp, const float* x, int k0, int nk) {

@@ -15,16 +15,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ float bf2f(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
-
 struct EgP0 { static constexpr int value = 0; };
 struct EgP1 { static constexpr int value = 1; };
 constexpr int EG_BM = 128, EG_BN = 128, EG_BK = 64;
@@ -171,21 +161,6 @@ __global__ __launch_bounds__(512, 4) void enc_gemm_kernel(const unsigned short* 
 
 // Attention of one (sequence, head) per workgroup slice: one wavefront per query row, keys in batches of 16 (butterfly
 // reduction of the 16 dot products), online softmax.  qkv bf16 [n_seq * S, 3 D] (q | k | v), out bf16 [n_seq * S, D].
-__device__ __forceinline__ float butterfly16_sum(const float (&a)[16], int lane) {
-    float b[8], c[4], d[2];
-    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8, h2 = lane & 4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) b[j] = (h5 ? a[8 + j] : a[j]) + __shfl_xor(h5 ? a[j] : a[8 + j], 32, 64);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = (h4 ? b[4 + j] : b[j]) + __shfl_xor(h4 ? b[j] : b[4 + j], 16, 64);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) d[j] = (h3 ? c[2 + j] : c[j]) + __shfl_xor(h3 ? c[j] : c[2 + j], 8, 64);
-    float e = (h2 ? d[1] : d[0]) + __shfl_xor(h2 ? d[0] : d[1], 4, 64);
-    e += __shfl_xor(e, 2, 64);
-    e += __shfl_xor(e, 1, 64);
-    return e;   // lane l: total of entry ((l>>5)&1)*8 + ((l>>4)&1)*4 + ((l>>3)&1)*2 + ((l>>2)&1)
-}
-
 __global__ __launch_bounds__(256) void enc_attn_kernel(const unsigned short* __restrict__ qkv, int S, int D, int heads,
                                                        float scale, unsigned short* __restrict__ out, int n_rows) {
     const int lane = threadIdx.x & 63;

@@ -17,16 +17,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ float bf2f(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
-
 // ------------------------------------------------------------------------------------------------ attention
 constexpr int AT_S = 128;     // positions per sequence (8 row tiles of 16)
 constexpr int AT_DC = 96;     // head-dim columns per staged chunk
@@ -47,12 +37,13 @@ struct AttnP {
     float scale, drop_p;
 };
 
-// reduce over the 16 lanes of a 16-lane row (the lanes that share l >> 4)
-__device__ __forceinline__ float row16_sum(float v) {
+// reduce over the 16 lanes of a 16-lane row (the lanes that share l >> 4), by shuffles at distance 8, 4, 2, 1: another order
+// of additions than erc_common.h's DPP row16_sum, hence other bits
+__device__ __forceinline__ float shfl16_sum(float v) {
     v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
     return v;
 }
-__device__ __forceinline__ float row16_max(float v) {
+__device__ __forceinline__ float shfl16_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 8, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
     v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 1, 64));
     return v;
@@ -168,7 +159,7 @@ __device__ __forceinline__ unsigned softmax_rows(const f32x4 (&acc)[8], float (&
         }
     float den[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) mx[q] = row16_max(mx[q]), den[q] = 0.f;
+    for (int q = 0; q < 4; ++q) mx[q] = shfl16_max(mx[q]), den[q] = 0.f;
 #pragma unroll
     for (int jt = 0; jt < 8; ++jt)
 #pragma unroll
@@ -177,7 +168,7 @@ __device__ __forceinline__ unsigned softmax_rows(const f32x4 (&acc)[8], float (&
             den[q] += p[jt][q];
         }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) den[q] = 1.0f / row16_sum(den[q]);
+    for (int q = 0; q < 4; ++q) den[q] = 1.0f / shfl16_sum(den[q]);
     unsigned keep = 0xffffffffu;
 #pragma unroll
     for (int jt = 0; jt < 8; ++jt)
@@ -275,7 +266,7 @@ __global__ __launch_bounds__(512) void enc_attn_bwd_kernel(AttnP P) {
                 acc[jt][q] = kf;
             }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) rs[q] = row16_sum(rs[q]);
+        for (int q = 0; q < 4; ++q) rs[q] = shfl16_sum(rs[q]);
 #pragma unroll
         for (int jt = 0; jt < 8; ++jt)
 #pragma unroll

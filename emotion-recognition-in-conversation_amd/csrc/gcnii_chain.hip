@@ -41,8 +41,6 @@ constexpr int MAXRW = 32;       // rows per workgroup (two 16-row MFMA tiles)
 constexpr int MAXT = 128;       // longest dialogue this kernel takes (LDS: MAXT x ZP gathered rows)
 constexpr int SPIN_LIMIT = 4000000;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
 struct Chain {

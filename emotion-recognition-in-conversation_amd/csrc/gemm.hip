@@ -19,10 +19,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
 struct GemmP {
     const void* A;
     const void* B;
@@ -339,11 +335,6 @@ __global__ __launch_bounds__(256) void gemm_f32_grouped_kernel(GemmP p, GroupP g
 // ---------------------------------------------------------------------------
 constexpr int BKH = 64;
 constexpr int KH_STRIDE = BKH + 8;  // in bf16 elements: 144-byte rows keep 16-B alignment, break the 128-B period
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-    const __bf16 h = (__bf16)f;  // plain cast: v_cvt_pk_bf16_f32, RNE, NaN stays NaN
-    return __builtin_bit_cast(unsigned short, h);
-}
 
 template <int A_KMAJOR, int B_KMAJOR, int X_IS_A, int NF>
 __global__ __launch_bounds__(256) void gemm_bf16x_kernel(GemmP p) {

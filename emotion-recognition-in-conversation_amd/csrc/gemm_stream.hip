@@ -15,10 +15,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
 struct T {
     static constexpr bool value = true;
 };
@@ -288,10 +284,6 @@ __global__ __launch_bounds__(64 * NW) void gemm_f32_stream_kernel(StreamP p) {
 
 // bf16 feature block as the A operand (rows K-contiguous, optional gather), fp32 B [N,K] rounded to bf16 on the fly:
 // the forward input projection.  v_mfma_f32_16x16x32_bf16: lane (r,g) holds k = kb*32 + 8g + j, j < 8.
-__device__ __forceinline__ short f2bf_s(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(short, h);
-}
 
 // Wave tile 32 rows x 32 columns (2 x 2 MFMA tiles: every B fragment is used for two row blocks, which halves the
 // W traffic through the per-CU L2 path -- the measured limiter of this kernel, ~70 GB/s per CU), 8 wavefronts
@@ -401,8 +393,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16a_stream_kernel(StreamP p) {
                         t[j] = (FULL || k + j < p.K) ? x : 0.f;
                     }
                 }
-                v = (bf16x8){f2bf_s(t[0]), f2bf_s(t[1]), f2bf_s(t[2]), f2bf_s(t[3]),
-                             f2bf_s(t[4]), f2bf_s(t[5]), f2bf_s(t[6]), f2bf_s(t[7])};
+                v = (bf16x8){(short)f2bf(t[0]), (short)f2bf(t[1]), (short)f2bf(t[2]), (short)f2bf(t[3]),
+                             (short)f2bf(t[4]), (short)f2bf(t[5]), (short)f2bf(t[6]), (short)f2bf(t[7])};
             }
             b[f] = n_ok[f] ? v : zero8;
         }

@@ -19,10 +19,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int XT = 128;          // tile rows / columns
 constexpr int XK = 32;           // K per chunk
 constexpr int XS = XK + 8;       // LDS row pitch (bf16 elements)
@@ -37,13 +33,12 @@ struct X3P {
 };
 
 typedef __bf16 bfx2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// two floats -> one packed bf16 pair (ONE v_cvt_pk_bf16_f32, round to nearest even) and back
+// two floats -> one packed bf16 pair (ONE v_cvt_pk_bf16_f32, round to nearest even); bf_lo / bf_hi (erc_common.h) take it apart.
+// The vector convert, not erc_common.h's bf_pack of two scalar casts: the same values, but hipcc builds this kernel (and, with
+// this form, the kernels that use bf_pack) differently around them.
 __device__ __forceinline__ unsigned pk_bf(float a, float b) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bfx2));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, bfx2));
 }
-__device__ __forceinline__ float lo_val(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float hi_val(unsigned pk) { return __builtin_bit_cast(float, pk & 0xffff0000u); }
 
 // four consecutive k of one row -> the three planes (8 bytes each): 13 VALU operations per pair of values
 __device__ __forceinline__ void split_store(unsigned short* dst, const f32x4 x) {
@@ -52,9 +47,9 @@ __device__ __forceinline__ void split_store(unsigned short* dst, const f32x4 x) 
     for (int t = 0; t < 2; ++t) {
         const float a = x[2 * t], b = x[2 * t + 1];
         h[t] = pk_bf(a, b);
-        const float ra = a - lo_val(h[t]), rb = b - hi_val(h[t]);
+        const float ra = a - bf_lo(h[t]), rb = b - bf_hi(h[t]);
         m[t] = pk_bf(ra, rb);
-        l[t] = pk_bf(ra - lo_val(m[t]), rb - hi_val(m[t]));
+        l[t] = pk_bf(ra - bf_lo(m[t]), rb - bf_hi(m[t]));
     }
     *reinterpret_cast<u32x2*>(dst) = (u32x2){h[0], h[1]};
     *reinterpret_cast<u32x2*>(dst + XPLANE) = (u32x2){m[0], m[1]};

@@ -49,8 +49,6 @@ struct GruP {
     int64_t zero_to;      // erc_gru_scan_bwd_cap: rows [node_off[B], zero_to) of dGX / dGH are written 0 (0: none)
 };
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __device__ __forceinline__ bool kept(const GruP& p, int m, int64_t row, int d, int u, uint64_t off, uint64_t seed) {
     return erc_uniform(seed ^ (p.rng_stream + (uint64_t)m), off, (uint64_t)row * (2 * H) + d * H + u) >= p.drop_p;
 }

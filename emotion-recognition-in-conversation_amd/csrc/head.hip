@@ -23,8 +23,6 @@ extern "C" int erc_head_fused_rows_per_workgroup(int n_rows);
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int HF_S = 108;      // LDS row pitch in floats: 16-byte aligned rows, 108 mod 64 = 44 -> conflict-free b128 rows
 constexpr int HF_ST = 116;     // pitch of the dZ row tiles: >= 112 (7 full column tiles are written), 116 mod 64 = 52
 constexpr int HF_NT = 7;       // column tiles of 16 (F <= 100 -> 7 tiles, the last one partial)
@@ -36,19 +34,6 @@ constexpr int HF_PART = 2 * 112 + 4;  // floats per workgroup partial record: co
 constexpr int HF_COUNTER = HF_PART - 1;
 constexpr int BS_G = 256;      // workgroups of the statistics pass: capacity of the partial records (one per CU for N > 8 192 rows)
 constexpr int BS_G_SMALL = 64; // ... up to 8 192 rows (the last arriver's sum over the partials is the longer part there)
-
-__device__ __forceinline__ float ld_sc1(const float* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_sc1d(const double* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1d(double* p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Training-mode BatchNorm statistics: column mean / rstd of x [N,F] into saved[2F], running statistics updated
@@ -167,31 +152,17 @@ struct HeadP {
         if (p.stamps && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) p.stamps[slot] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 
-__device__ __forceinline__ unsigned short hf_bf(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(unsigned short, h);
-}
-
-// DPP lane exchanges inside a row of 16 lanes (VALU, no LDS traffic)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-constexpr int DPP_X1 = 0xB1, DPP_X2 = 0x4E, DPP_HMIR = 0x141, DPP_MIR = 0x140;  // quad_perm xor 1 / xor 2, row_half_mirror, row_mirror
-__device__ __forceinline__ float row16_sum(float v) {  // total over the 16 lanes r, in every lane
-    v += dpp_f<DPP_X1>(v), v += dpp_f<DPP_X2>(v), v += dpp_f<DPP_HMIR>(v), v += dpp_f<DPP_MIR>(v);
-    return v;
-}
+// half-row forms of erc_common.h's row16_sum (DPP lane exchanges, no LDS traffic)
 __device__ __forceinline__ float row8_sum(float v) {  // total over each half row of 8 lanes
-    v += dpp_f<DPP_X1>(v), v += dpp_f<DPP_X2>(v), v += dpp_f<DPP_HMIR>(v);
+    v += dpp_mov<DPP_X1>(v), v += dpp_mov<DPP_X2>(v), v += dpp_mov<DPP_HMIR>(v);
     return v;
 }
 __device__ __forceinline__ float row8_max(float v) {
-    v = fmaxf(v, dpp_f<DPP_X1>(v)), v = fmaxf(v, dpp_f<DPP_X2>(v)), v = fmaxf(v, dpp_f<DPP_HMIR>(v));
+    v = fmaxf(v, dpp_mov<DPP_X1>(v)), v = fmaxf(v, dpp_mov<DPP_X2>(v)), v = fmaxf(v, dpp_mov<DPP_HMIR>(v));
     return v;
 }
 __device__ __forceinline__ float row8_min(float v) {
-    v = fminf(v, dpp_f<DPP_X1>(v)), v = fminf(v, dpp_f<DPP_X2>(v)), v = fminf(v, dpp_f<DPP_HMIR>(v));
+    v = fminf(v, dpp_mov<DPP_X1>(v)), v = fminf(v, dpp_mov<DPP_X2>(v)), v = fminf(v, dpp_mov<DPP_HMIR>(v));
     return v;
 }
 
@@ -334,7 +305,7 @@ __global__ __launch_bounds__(512) void head_fused_kernel(const HeadP p) {
         if ((RPW == 2 ? (kb & 3) : kb) == cq && mrow < N && kv) {
             if (p.H3) *reinterpret_cast<f32x4*>(p.H3 + (int64_t)mrow * F + k0) = h;
             if (p.H3b) *reinterpret_cast<uint2*>(p.H3b + (int64_t)mrow * p.ldb16 + k0) =
-                make_uint2((uint32_t)hf_bf(h[0]) | ((uint32_t)hf_bf(h[1]) << 16), (uint32_t)hf_bf(h[2]) | ((uint32_t)hf_bf(h[3]) << 16));
+                make_uint2((uint32_t)f2bf(h[0]) | ((uint32_t)f2bf(h[1]) << 16), (uint32_t)f2bf(h[2]) | ((uint32_t)f2bf(h[3]) << 16));
         }
     }
     // operands of the later phases, requested now so that their latency hides behind the first MFMA product
@@ -408,7 +379,7 @@ __global__ __launch_bounds__(512) void head_fused_kernel(const HeadP p) {
                 zreg[jn][q] = z;
                 if (row < N && 16 * nt + r < F) {
                     if (p.Z) p.Z[(int64_t)row * F + 16 * nt + r] = z;
-                    if (p.Zb) p.Zb[(int64_t)row * p.ldb16 + 16 * nt + r] = hf_bf(z);
+                    if (p.Zb) p.Zb[(int64_t)row * p.ldb16 + 16 * nt + r] = f2bf(z);
                 }
             }
         }
@@ -452,7 +423,7 @@ __global__ __launch_bounds__(512) void head_fused_kernel(const HeadP p) {
             if (rv && r < C) {
                 p.logits[(int64_t)row * C + r] = v;
                 if (p.dlogits) p.dlogits[(int64_t)row * p.lddl + r] = dq;
-                if (p.dlb) p.dlb[(int64_t)row * 8 + r] = hf_bf(dq);
+                if (p.dlb) p.dlb[(int64_t)row * 8 + r] = f2bf(dq);
             }
             if (rv && r == 0) lsum += wyq[q] * (lse - ly), hsum += ((int)am == y) ? 1.f : 0.f;
         }
@@ -483,7 +454,7 @@ __global__ __launch_bounds__(512) void head_fused_kernel(const HeadP p) {
                 const float dz = zreg[jn][q] > 0.f ? s * scale : 0.f;
                 if (row < N && 16 * nt + r < F) {
                     if (p.dZ) p.dZ[(int64_t)row * F + 16 * nt + r] = dz;
-                    if (p.dZb) p.dZb[(int64_t)row * p.ldb16 + 16 * nt + r] = hf_bf(dz);
+                    if (p.dZb) p.dZb[(int64_t)row * p.ldb16 + 16 * nt + r] = f2bf(dz);
                 }
                 tile[(4 * g + q) * HF_ST + 16 * nt + r] = dz;
             }
@@ -713,7 +684,7 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadP p) {
             if (mrow < N && kv) {
                 if (p.H3) *reinterpret_cast<f32x4*>(p.H3 + (int64_t)mrow * F + k0) = h;
                 if (p.H3b) *reinterpret_cast<uint2*>(p.H3b + (int64_t)mrow * p.ldb16 + k0) =
-                    make_uint2((uint32_t)hf_bf(h[0]) | ((uint32_t)hf_bf(h[1]) << 16), (uint32_t)hf_bf(h[2]) | ((uint32_t)hf_bf(h[3]) << 16));
+                    make_uint2((uint32_t)f2bf(h[0]) | ((uint32_t)f2bf(h[1]) << 16), (uint32_t)f2bf(h[2]) | ((uint32_t)f2bf(h[3]) << 16));
             }
         }
         int ylab[4];
@@ -764,7 +735,7 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadP p) {
             if (mrow < N && k0 < F) {
                 if (p.Z) *reinterpret_cast<f32x4*>(p.Z + (int64_t)mrow * F + k0) = zv;
                 if (p.Zb) *reinterpret_cast<uint2*>(p.Zb + (int64_t)mrow * p.ldb16 + k0) =
-                    make_uint2((uint32_t)hf_bf(zv[0]) | ((uint32_t)hf_bf(zv[1]) << 16), (uint32_t)hf_bf(zv[2]) | ((uint32_t)hf_bf(zv[3]) << 16));
+                    make_uint2((uint32_t)f2bf(zv[0]) | ((uint32_t)f2bf(zv[1]) << 16), (uint32_t)f2bf(zv[2]) | ((uint32_t)f2bf(zv[3]) << 16));
             }
         }
         HR_STAMP(3);
@@ -803,7 +774,7 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadP p) {
             if (rv && r < C) {
                 p.logits[(int64_t)row * C + r] = v;
                 if (p.dlogits) p.dlogits[(int64_t)row * p.lddl + r] = dq;
-                if (p.dlb) p.dlb[(int64_t)row * 8 + r] = hf_bf(dq);
+                if (p.dlb) p.dlb[(int64_t)row * 8 + r] = f2bf(dq);
             }
             if (rv && r == 0) lsum += wyq[q] * (lse - ly), hsum += ((int)am == y) ? 1.f : 0.f;
         }
@@ -843,7 +814,7 @@ __global__ __launch_bounds__(256, 2) void head_rows_kernel(const HeadP p) {
             if (mrow < N && k0 < F) {
                 if (p.dZ) *reinterpret_cast<f32x4*>(p.dZ + (int64_t)mrow * F + k0) = v;
                 if (p.dZb) *reinterpret_cast<uint2*>(p.dZb + (int64_t)mrow * p.ldb16 + k0) =
-                    make_uint2((uint32_t)hf_bf(v[0]) | ((uint32_t)hf_bf(v[1]) << 16), (uint32_t)hf_bf(v[2]) | ((uint32_t)hf_bf(v[3]) << 16));
+                    make_uint2((uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16), (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16));
             }
         }
 #pragma unroll

@@ -18,8 +18,6 @@ constexpr int TILE = 16;           // query / key rows per workgroup, and rows p
 constexpr int TPAD = 112;          // score row pitch in LDS (T <= 110)
 constexpr int MT = 256;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 template <int F>
 struct Att {
     static constexpr int F4 = F / 4;

@@ -53,15 +53,14 @@ struct P2PArgs {
     int32_t* health;               // local health word (raised on a poll timeout)
     int64_t n_pad;
 };
-typedef float p2p_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st_sys_x4(float* p, p2p_f4 v) {
+__device__ __forceinline__ void st_sys_x4(float* p, f4 v) {
     // (s_nop: a store of more than 64 bits needs wait states before its data registers may be overwritten, and the compiler's
     //  hazard recognizer does not look inside an asm statement -- without them a v_cndmask scheduled right behind the store
     //  replaced the last dword of lanes 12-15 of every 16: finding 44)
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
-__device__ __forceinline__ p2p_f4 ld_sys_x4(const float* p) {
-    p2p_f4 v;
+__device__ __forceinline__ f4 ld_sys_x4(const float* p) {
+    f4 v;
     asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v) : "v"(p) : "memory");
     return v;
 }
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         int64_t* const my_ep = p2p.epoch + b;
         const int ep = (int)(*my_ep + 1);
         const int64_t poff = (int64_t)(ep & 1) * p2p.n_pad + 4 * q0c;
-        if (q0 < nq) st_sys_x4(p2p.pub[p2p.rank] + poff, (p2p_f4){gv.x, gv.y, gv.z, gv.w});
+        if (q0 < nq) st_sys_x4(p2p.pub[p2p.rank] + poff, (f4){gv.x, gv.y, gv.z, gv.w});
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if ((int)threadIdx.x < p2p.world) {
@@ -129,10 +128,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         __syncthreads();
         if (threadIdx.x == 0) *my_ep = ep;
         if (s_p2p_skip) return;        // some rank's gradients are invalid: every rank leaves this step out
-        p2p_f4 acc = {0.f, 0.f, 0.f, 0.f};
-        p2p_f4 part[P2P_MAXW];
+        f4 acc = {0.f, 0.f, 0.f, 0.f};
+        f4 part[P2P_MAXW];
 #pragma unroll
-        for (int r = 0; r < P2P_MAXW; ++r) part[r] = r < p2p.world ? ld_sys_x4(p2p.pub[r] + poff) : (p2p_f4){0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < P2P_MAXW; ++r) part[r] = r < p2p.world ? ld_sys_x4(p2p.pub[r] + poff) : (f4){0.f, 0.f, 0.f, 0.f};
         asm volatile("s_waitcnt vmcnt(0)"
                      : "+v"(part[0]), "+v"(part[1]), "+v"(part[2]), "+v"(part[3]), "+v"(part[4]), "+v"(part[5]), "+v"(part[6]), "+v"(part[7])
                      :
@@ -230,9 +229,8 @@ __global__ __launch_bounds__(256) void norm_final_kernel(const double* __restric
 
 // Diagnostic only (bench.py --clock_probe): one wavefront runs a dependent MFMA chain and records shader cycles
 // (s_memtime) against the 100 MHz real-time counter, i.e. the clock the chip holds at that point of the stream.
-typedef float probe_f4 __attribute__((ext_vector_type(4)));
 __global__ void clock_probe_kernel(unsigned long long* out, int iters) {
-    probe_f4 acc = {0.f, 0.f, 0.f, 0.f};
+    f4 acc = {0.f, 0.f, 0.f, 0.f};
     const float a = (float)threadIdx.x, b = 1.0f;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     for (int i = 0; i < iters; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);

@@ -35,10 +35,6 @@ __device__ __forceinline__ int64_t shadow_dst(const ShadowDesc& d, int32_t n, in
     if (d.mode == 0) return d.dst_off + (int64_t)n * d.ld + k;
     return d.dst_off + ((((int64_t)(n >> 4) * d.ld + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (n & 15)) << 3) + (k & 7);
 }
-__device__ __forceinline__ unsigned short f2bf_u16(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(unsigned short, h);
-}
 // term t of the bf16 expansion of x (see ShadowDesc.terms); `r` carries the remainder from term to term
 __device__ __forceinline__ unsigned short bf_term_next(float& r) {
     const __bf16 h = (__bf16)r;

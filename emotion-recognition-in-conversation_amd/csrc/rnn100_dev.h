@@ -1,6 +1,6 @@
 // Device helpers shared by the hidden-100 weight-stationary scans (lstm.hip, gru100.hip): the row maps and step counts of a
-// (dialogue, direction) workgroup, the chunked LDS layout of the vectors every thread reads, the DPP moves and reductions of
-// the quad / 16-lane-row thread layout, the fast activations and the dropout uniform of an element.
+// (dialogue, direction) workgroup, the chunked LDS layout of the vectors every thread reads, the fast activations and the
+// dropout uniform of an element.  The DPP moves and reductions of the quad / 16-lane-row thread layout are erc_common.h's.
 // A scan file supplies its parameter struct (the fields named below), its cell math, its chunk load / store lambdas and its
 // entry points.
 #pragma once
@@ -21,8 +21,6 @@ constexpr int SC = 8;
 constexpr int CHK = 25, CHP = 28;
 constexpr int HP = 4 * CHP;        // hidden state
 __device__ __forceinline__ int chunk_pos(int k) { return (k / CHK) * CHP + k % CHK; }
-
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 // rows of a dialogue: row(t) = base + t * step
 struct RowMap {
@@ -58,28 +56,6 @@ __device__ __forceinline__ float fast_sigm(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x));
 }
 __device__ __forceinline__ float fast_tanh(float x) { return 2.0f * fast_sigm(2.0f * x) - 1.0f; }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// value of lane Q of the caller's quad (lanes 4u .. 4u+3), in every lane of the quad: one DPP move, no LDS
-template <int Q>
-__device__ __forceinline__ float quad_bcast(float v) { return dpp_mov<Q * 0x55>(v); }
-// sum over the quad, the same bits in its four lanes (xor 1, then xor 2: both orders add the same two pairs)
-__device__ __forceinline__ float quad_sum(float v) {
-    v += dpp_mov<0xB1>(v);
-    return v + dpp_mov<0x4E>(v);
-}
-// sum over the 16 lanes of a DPP row, in a fixed order: quad xor 1 / xor 2, half mirror, mirror.  By value, one sum a call: a
-// form that takes the backward's four sums as an array reference keeps the array in memory until after inlining, and the
-// compiler then schedules the whole step differently
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);
-    v += dpp_mov<0x4E>(v);
-    v += dpp_mov<0x141>(v);
-    return v + dpp_mov<0x140>(v);
-}
 
 // Inverted dropout of the layer's output rows [., 2H]: the uniform of element (row, d * H + u), the same forward and backward.
 // An element is kept, and scaled by 1 / (1 - p), when it is >= p; that select stays in the kernels (inside a helper the

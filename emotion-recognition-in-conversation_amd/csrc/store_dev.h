@@ -15,21 +15,19 @@
 int erc_store_mode(void);
 
 #ifdef __HIPCC__
-typedef float st_f32x4 __attribute__((ext_vector_type(4)));
-
 template <bool WT>
-__device__ __forceinline__ void st_out16(void* p, const st_f32x4 v) {
+__device__ __forceinline__ void st_out16(void* p, const f32x4 v) {
     if constexpr (WT) {
         // (s_nop: a store of more than 64 bits needs wait states before its data registers may be overwritten, and the compiler's
         //  hazard recognizer does not look inside an asm statement -- without them a v_cndmask scheduled right behind the store
         //  replaced the last dword of lanes 12-15 of every 16: finding 44)
         asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
     } else {
-        *(__attribute__((address_space(1))) st_f32x4*)p = v;
+        *(__attribute__((address_space(1))) f32x4*)p = v;
     }
 }
 // `wt` must be uniform over the wavefront (a field of the kernel's parameter struct): ONE scalar branch per store site
-__device__ __forceinline__ void st_out16(void* p, const st_f32x4 v, const int wt) {
+__device__ __forceinline__ void st_out16(void* p, const f32x4 v, const int wt) {
     if (wt) st_out16<true>(p, v);
     else st_out16<false>(p, v);
 }

@@ -19,9 +19,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // Pointers read from the descriptor table are generic to the compiler: without the explicit global address space it
 // emits flat_load, which also counts on lgkmcnt and so serialises with the LDS reads of the gather stage.
 #define ERC_GLOBAL __attribute__((address_space(1)))
@@ -52,20 +49,10 @@ struct WgDesc {  // 112 bytes; mirrored by engine.GemmPlanner.flush_wgrads ("<QQ
 // Cross-workgroup hand-off of the partial tiles WITHOUT fences (an agent-scope release/acquire fence pair costs
 // ~3.5 us per workgroup on MI355X: L2 write-back + invalidate): the slab is written with write-through (sc1) stores,
 // one full 256-byte run per wave instruction, drained with s_waitcnt vmcnt(0) before the workgroup's arrival
-// ticket; the last arriver reads it with sc1 loads.
-__device__ __forceinline__ float ld_sc1(const float* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// ticket; the last arriver reads it with sc1 loads (ld_sc1 / st_sc1, erc_common.h).
 
 // VEC (16-byte operand loads legal for BOTH operands) is compile-time: a runtime flag around a load makes hipcc
 // branch and drain vmcnt per load.
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    const __bf16 a = (__bf16)lo, b = (__bf16)hi;
-    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
 
 // MB: bf16 matrix cores.  v_mfma_f32_16x16x32_bf16 sums over 32 (g, slot) pairs, 8 slots per lane; the load pattern
 // stays the one above (one 16-byte load = four neighbouring output rows for ONE k), so a lane fills its 8 slots from 8
@@ -204,11 +191,11 @@ __device__ __forceinline__ void wgrad_body(const WgDesc& d, const int local, flo
                     const float x0 = xa[2 * dd][i] * xk[2 * dd], x1 = xa[2 * dd + 1][i] * xk[2 * dd + 1];
                     bsa[i] += x0 + x1;
                     split3(x0, h0, m0, l0), split3(x1, h1, m1, l1);
-                    ah[i][dd] = hi16(h0, h1), am[i][dd] = hi16(m0, m1), al[i][dd] = pack_bf16x2(l0, l1);
+                    ah[i][dd] = hi16(h0, h1), am[i][dd] = hi16(m0, m1), al[i][dd] = bf_pack(l0, l1);
                     const float y0 = xb[2 * dd][i] * xk[2 * dd], y1 = xb[2 * dd + 1][i] * xk[2 * dd + 1];
                     bsb[i] += y0 + y1;
                     split3(y0, h0, m0, l0), split3(y1, h1, m1, l1);
-                    bh[i][dd] = hi16(h0, h1), bm[i][dd] = hi16(m0, m1), bl[i][dd] = pack_bf16x2(l0, l1);
+                    bh[i][dd] = hi16(h0, h1), bm[i][dd] = hi16(m0, m1), bl[i][dd] = bf_pack(l0, l1);
                 }
             }
 #define ERC_MF(A_, B_) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A_[i]), __builtin_bit_cast(bf16x8, B_[j]), acc[i][j], 0, 0, 0)
@@ -245,8 +232,8 @@ __device__ __forceinline__ void wgrad_body(const WgDesc& d, const int local, flo
                 }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                fa[i][0] = pack_bf16x2(xa[0][i], xa[1][i]), fa[i][1] = pack_bf16x2(xa[2][i], xa[3][i]);
-                fb[i][0] = pack_bf16x2(xb[0][i], xb[1][i]), fb[i][1] = pack_bf16x2(xb[2][i], xb[3][i]);
+                fa[i][0] = bf_pack(xa[0][i], xa[1][i]), fa[i][1] = bf_pack(xa[2][i], xa[3][i]);
+                fb[i][0] = bf_pack(xb[0][i], xb[1][i]), fb[i][1] = bf_pack(xb[2][i], xb[3][i]);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -257,8 +244,8 @@ __device__ __forceinline__ void wgrad_body(const WgDesc& d, const int local, flo
                 }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                fa[i][2] = pack_bf16x2(ya[0][i], ya[1][i]), fa[i][3] = pack_bf16x2(ya[2][i], ya[3][i]);
-                fb[i][2] = pack_bf16x2(yb[0][i], yb[1][i]), fb[i][3] = pack_bf16x2(yb[2][i], yb[3][i]);
+                fa[i][2] = bf_pack(ya[0][i], ya[1][i]), fa[i][3] = bf_pack(ya[2][i], ya[3][i]);
+                fb[i][2] = bf_pack(yb[0][i], yb[1][i]), fb[i][3] = bf_pack(yb[2][i], yb[3][i]);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)

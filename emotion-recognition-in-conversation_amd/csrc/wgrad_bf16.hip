@@ -33,10 +33,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define ERC_GLOBAL __attribute__((address_space(1)))
 
 constexpr int W2_IDX_CAP = 4096;            // k per work item (row-gather stage in LDS)
@@ -90,8 +86,6 @@ struct W2Adam {
 };
 static_assert(sizeof(W2Desc) == 112, "W2Desc layout");
 
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // 16-byte write-through store (st_out16<true>, csrc/store_dev.h) / cache-bypassing load of a slab quad (sc0 sc1 = system scope: the
 // partial tiles cross XCDs, whose L2s are not coherent with each other).  The compiler does not count inline-asm loads: the
 // caller waits (vmcnt).
@@ -100,8 +94,6 @@ __device__ __forceinline__ f32x4 ld_sc1_x4(const float* p) {
     asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v) : "v"(p) : "memory");
     return v;
 }
-__device__ __forceinline__ float bf_lo(unsigned d) { return __builtin_bit_cast(float, d << 16); }
-__device__ __forceinline__ float bf_hi(unsigned d) { return __builtin_bit_cast(float, d & 0xffff0000u); }
 // {lo half of x, lo half of y} / {hi half of x, hi half of y} as one dword (x in the low 16 bits)
 __device__ __forceinline__ unsigned perm_lo(unsigned x, unsigned y) { return __builtin_amdgcn_perm(y, x, 0x05040100u); }
 __device__ __forceinline__ unsigned perm_hi(unsigned x, unsigned y) { return __builtin_amdgcn_perm(y, x, 0x07060302u); }
