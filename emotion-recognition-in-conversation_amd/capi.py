@@ -1131,13 +1131,22 @@ def dgcnv2_meta(onehot, S, lengths, B, T, n_cap, spk, node_row):
     _call("erc_dgcnv2_meta", onehot, S, lengths, B, T, n_cap, spk, node_row)
 
 
-def dgcnv2_edge_att_fwd(S, ldS, g, B, T, wp, wf, norm):
-    _call("erc_dgcnv2_edge_att_fwd", S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], norm)
+def dgcnv2_edge_att_fwd(S, ldS, g, B, T, wp, wf, norm, t_dev=None):
+    """``t_dev`` (device int32): capacity mode, B / T are capacities and the batch's longest dialogue is *t_dev (ercgraft.h)"""
+    args = (S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], norm)
+    if t_dev is None:
+        _call("erc_dgcnv2_edge_att_fwd", *args)
+    else:
+        _call("erc_dgcnv2_edge_att_fwd_cap", *args, t_dev)
 
 
-def dgcnv2_edge_att_bwd(S, ldS, g, B, T, wp, wf, dnorm, dS, dn_parts=1, dn_stride=0):
-    _call("erc_dgcnv2_edge_att_bwd", S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], dnorm,
-          dn_parts, dn_stride, dS)
+def dgcnv2_edge_att_bwd(S, ldS, g, B, T, wp, wf, dnorm, dS, dn_parts=1, dn_stride=0, t_dev=None):
+    """``t_dev``: capacity mode, every row of dS [B * T, 110] is written, rows t >= *t_dev as zeros (ercgraft.h)"""
+    args = (S, ldS, g["node_off"], B, T, wp, wf, g["out_ptr"], g["out_dst"], g["out_eid"], dnorm, dn_parts, dn_stride, dS)
+    if t_dev is None:
+        _call("erc_dgcnv2_edge_att_bwd", *args)
+    else:
+        _call("erc_dgcnv2_edge_att_bwd_cap", *args, t_dev)
 
 
 # --------------------------------------------------------------------------- matching attention 'general2' (csrc/match_att.hip)

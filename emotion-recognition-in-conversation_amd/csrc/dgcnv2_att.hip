@@ -9,6 +9,11 @@
 // (the softmax's own denominator cancels).  One wave per (dialogue, source position), lane t holding positions t and
 // t + 64 (T <= 110).  The backward writes dS [B*T, 110]: column p of dialogue b's rows belongs to source p alone, so every
 // element has one writer and no atomics are needed; columns p >= L_b are written as zeros.
+//
+// Capacity form (erc_dgcnv2_edge_att_*_cap, CAP = true): the launch is sized for (B_cap, T_cap) and the batch's own longest
+// dialogue arrives on the device; T_eff = clamp(*t_dev, 0, T_cap) takes T's place in the softmax, in the leak term and in the
+// rows that are read, so a wave does exactly the arithmetic of the exact launch with T = *t_dev.  The backward writes rows
+// t >= T_eff of dS as zeros (they belong to no position of this batch), still one writer per element.
 #include "erc_common.h"
 
 namespace {
@@ -68,13 +73,19 @@ __device__ __forceinline__ WinSoftmax win_softmax(const float* Sc, int ldS, int 
     return w;
 }
 
+// T of a capacity launch: the batch's longest dialogue, read from the device
+__device__ __forceinline__ int t_eff(const int32_t* __restrict__ t_dev, int T_cap) { return min(max(*t_dev, 0), T_cap); }
+
+template <bool CAP>
 __global__ __launch_bounds__(NT) void edge_att_fwd_kernel(const float* __restrict__ Sc, int ldS, const int32_t* __restrict__ node_off,
                                                           int B, int T, int wp, int wf, const int32_t* __restrict__ out_ptr,
                                                           const int32_t* __restrict__ out_dst,
-                                                          const int32_t* __restrict__ out_eid, float* __restrict__ norm) {
+                                                          const int32_t* __restrict__ out_eid, float* __restrict__ norm,
+                                                          const int32_t* __restrict__ t_dev) {
     const int lane = threadIdx.x & 63, p = blockIdx.x * (NT / 64) + (threadIdx.x >> 6), b = blockIdx.y;
     const int base = node_off[b], L = node_off[b + 1] - base;
     if (p >= L) return;
+    if constexpr (CAP) T = t_eff(t_dev, T);
     const WinSoftmax w = win_softmax(Sc, ldS, B, T, b, p, L, wp, wf, lane);
     const int j = base + p;
     // lane l writes out-edge l of the pass; u of its target comes from the lane that holds that position
@@ -83,22 +94,28 @@ __global__ __launch_bounds__(NT) void edge_att_fwd_kernel(const float* __restric
         const int e = eb + lane;
         const int i = e < e1 ? out_dst[e] - base : 0;
         const float ua = __shfl(w.u0, i & 63, 64), ub = __shfl(w.u1, i & 63, 64);
-        if (e < e1) norm[out_eid[e]] = (i < 64 ? ua : ub) / w.den;
+        // (CAP, T_eff == 0: no position was read, den is 0 -- the edge of a batch that claims no step gets weight 0, not 0 / 0)
+        if (e < e1) norm[out_eid[e]] = CAP && T == 0 ? 0.f : (i < 64 ? ua : ub) / w.den;
     }
 }
 
+template <bool CAP>
 __global__ __launch_bounds__(NT) void edge_att_bwd_kernel(const float* __restrict__ Sc, int ldS, const int32_t* __restrict__ node_off,
                                                           int B, int T, int wp, int wf, const int32_t* __restrict__ out_ptr,
                                                           const int32_t* __restrict__ out_dst,
                                                           const int32_t* __restrict__ out_eid, const float* __restrict__ dnorm,
-                                                          int dn_parts, int64_t dn_stride, float* __restrict__ dS) {
+                                                          int dn_parts, int64_t dn_stride, float* __restrict__ dS,
+                                                          const int32_t* __restrict__ t_dev) {
     const int lane = threadIdx.x & 63, p = blockIdx.x * (NT / 64) + (threadIdx.x >> 6), b = blockIdx.y;
     if (p >= NSCAL) return;
     const int base = node_off[b], L = node_off[b + 1] - base;
     const int t0 = lane, t1 = lane + 64;
-    if (p >= L) {       // no source at this position: its column of Wscalar receives nothing from dialogue b
-        if (t0 < T) dS[((int64_t)t0 * B + b) * ldS + p] = 0.f;
-        if (t1 < T) dS[((int64_t)t1 * B + b) * ldS + p] = 0.f;
+    const int T_cap = T;      // rows [T, T_cap) of a capacity launch: written 0
+    if constexpr (CAP) T = t_eff(t_dev, T);
+    // no source at this position: its column of Wscalar receives nothing from dialogue b (CAP, T == 0: nor from anything)
+    if (p >= L || (CAP && T == 0)) {
+        if (t0 < T_cap) dS[((int64_t)t0 * B + b) * ldS + p] = 0.f;
+        if (t1 < T_cap) dS[((int64_t)t1 * B + b) * ldS + p] = 0.f;
         return;
     }
     const WinSoftmax w = win_softmax(Sc, ldS, B, T, b, p, L, wp, wf, lane);
@@ -118,6 +135,10 @@ __global__ __launch_bounds__(NT) void edge_att_bwd_kernel(const float* __restric
     const float dot = wave_sum((in0 ? dn0 * n0 : 0.f) + (in1 ? dn1 * n1 : 0.f));
     if (t0 < T) dS[((int64_t)t0 * B + b) * ldS + p] = in0 ? n0 * (dn0 - dot) : -1e-10f * n0 * dot;
     if (t1 < T) dS[((int64_t)t1 * B + b) * ldS + p] = in1 ? n1 * (dn1 - dot) : -1e-10f * n1 * dot;
+    if constexpr (CAP) {
+        if (t0 >= T && t0 < T_cap) dS[((int64_t)t0 * B + b) * ldS + p] = 0.f;
+        if (t1 >= T && t1 < T_cap) dS[((int64_t)t1 * B + b) * ldS + p] = 0.f;
+    }
 }
 
 }  // namespace
@@ -134,29 +155,66 @@ extern "C" int erc_dgcnv2_meta(const float* onehot, int S, const int64_t* length
     return ERC_OK;
 }
 
+// The two entry points of each pass share their checks and their launch; t_dev == NULL is the exact form.
+static int edge_att_fwd(const char* name, const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                        const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* norm, const int32_t* t_dev,
+                        void* stream) {
+    ERC_REQUIRE(S && node_off && out_ptr && out_dst && out_eid && norm, "%s: null pointer", name);
+    ERC_REQUIRE(B > 0 && T > 0 && ldS >= NSCAL, "%s: bad sizes B=%d T=%d ldS=%d", name, B, T, ldS);
+    ERC_REQUIRE(T <= NSCAL, "%s: Wscalar has %d rows, dialogues of up to %d utterances (batch T=%d)", name, NSCAL, NSCAL, T);
+    const dim3 grid(erc_cdiv(T, NT / 64), B);
+    if (t_dev)
+        hipLaunchKernelGGL(edge_att_fwd_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B, T, wp, wf, out_ptr,
+                           out_dst, out_eid, norm, t_dev);
+    else
+        hipLaunchKernelGGL(edge_att_fwd_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B, T, wp, wf,
+                           out_ptr, out_dst, out_eid, norm, t_dev);
+    ERC_LAUNCH_CHECK(name);
+    return ERC_OK;
+}
+
+static int edge_att_bwd(const char* name, const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                        const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* dnorm, int dn_parts,
+                        int64_t dn_stride, float* dS, const int32_t* t_dev, void* stream) {
+    ERC_REQUIRE(S && node_off && out_ptr && out_dst && out_eid && dnorm && dS, "%s: null pointer", name);
+    ERC_REQUIRE(B > 0 && T > 0 && ldS >= NSCAL, "%s: bad sizes B=%d T=%d ldS=%d", name, B, T, ldS);
+    ERC_REQUIRE(T <= NSCAL, "%s: dialogues of up to %d utterances (batch T=%d)", name, NSCAL, T);
+    ERC_REQUIRE(dn_parts >= 1 && (dn_parts == 1 || dn_stride > 0), "%s: dn_parts=%d", name, dn_parts);
+    ERC_REQUIRE(S != dS, "%s: dS must not alias S", name);
+    const dim3 grid(erc_cdiv(NSCAL, NT / 64), B);
+    if (t_dev)
+        hipLaunchKernelGGL(edge_att_bwd_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B, T, wp, wf, out_ptr,
+                           out_dst, out_eid, dnorm, dn_parts, dn_stride, dS, t_dev);
+    else
+        hipLaunchKernelGGL(edge_att_bwd_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B, T, wp, wf,
+                           out_ptr, out_dst, out_eid, dnorm, dn_parts, dn_stride, dS, t_dev);
+    ERC_LAUNCH_CHECK(name);
+    return ERC_OK;
+}
+
 extern "C" int erc_dgcnv2_edge_att_fwd(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
                                        const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* norm,
                                        void* stream) {
-    ERC_REQUIRE(S && node_off && out_ptr && out_dst && out_eid && norm, "dgcnv2_edge_att_fwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && ldS >= NSCAL, "dgcnv2_edge_att_fwd: bad sizes B=%d T=%d ldS=%d", B, T, ldS);
-    ERC_REQUIRE(T <= NSCAL, "dgcnv2_edge_att_fwd: Wscalar has %d rows, dialogues of up to %d utterances (batch T=%d)", NSCAL, NSCAL,
-                T);
-    hipLaunchKernelGGL(edge_att_fwd_kernel, dim3(erc_cdiv(T, NT / 64), B), dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B, T,
-                       wp, wf, out_ptr, out_dst, out_eid, norm);
-    ERC_LAUNCH_CHECK("dgcnv2_edge_att_fwd");
-    return ERC_OK;
+    return edge_att_fwd("dgcnv2_edge_att_fwd", S, ldS, node_off, B, T, wp, wf, out_ptr, out_dst, out_eid, norm, nullptr, stream);
+}
+
+extern "C" int erc_dgcnv2_edge_att_fwd_cap(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                                           const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* norm,
+                                           const int32_t* t_dev, void* stream) {
+    return edge_att_fwd("dgcnv2_edge_att_fwd_cap", S, ldS, node_off, B, T, wp, wf, out_ptr, out_dst, out_eid, norm, t_dev, stream);
 }
 
 extern "C" int erc_dgcnv2_edge_att_bwd(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
                                        const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* dnorm,
                                        int dn_parts, int64_t dn_stride, float* dS, void* stream) {
-    ERC_REQUIRE(S && node_off && out_ptr && out_dst && out_eid && dnorm && dS, "dgcnv2_edge_att_bwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && ldS >= NSCAL, "dgcnv2_edge_att_bwd: bad sizes B=%d T=%d ldS=%d", B, T, ldS);
-    ERC_REQUIRE(T <= NSCAL, "dgcnv2_edge_att_bwd: dialogues of up to %d utterances (batch T=%d)", NSCAL, T);
-    ERC_REQUIRE(dn_parts >= 1 && (dn_parts == 1 || dn_stride > 0), "dgcnv2_edge_att_bwd: dn_parts=%d", dn_parts);
-    ERC_REQUIRE(S != dS, "dgcnv2_edge_att_bwd: dS must not alias S");
-    hipLaunchKernelGGL(edge_att_bwd_kernel, dim3(erc_cdiv(NSCAL, NT / 64), B), dim3(NT), 0, (hipStream_t)stream, S, ldS, node_off, B,
-                       T, wp, wf, out_ptr, out_dst, out_eid, dnorm, dn_parts, dn_stride, dS);
-    ERC_LAUNCH_CHECK("dgcnv2_edge_att_bwd");
-    return ERC_OK;
+    return edge_att_bwd("dgcnv2_edge_att_bwd", S, ldS, node_off, B, T, wp, wf, out_ptr, out_dst, out_eid, dnorm, dn_parts, dn_stride,
+                        dS, nullptr, stream);
+}
+
+extern "C" int erc_dgcnv2_edge_att_bwd_cap(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                                           const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid,
+                                           const float* dnorm, int dn_parts, int64_t dn_stride, float* dS, const int32_t* t_dev,
+                                           void* stream) {
+    return edge_att_bwd("dgcnv2_edge_att_bwd_cap", S, ldS, node_off, B, T, wp, wf, out_ptr, out_dst, out_eid, dnorm, dn_parts,
+                        dn_stride, dS, t_dev, stream);
 }

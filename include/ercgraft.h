@@ -1375,6 +1375,28 @@ int erc_dgcnv2_edge_att_fwd(const float* S, int ldS, const int32_t* node_off, in
 int erc_dgcnv2_edge_att_bwd(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
                             const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* dnorm,
                             int dn_parts, int64_t dn_stride, float* dS, void* stream);
+/* CAPACITY mode (t_dev == NULL: the two entry points above).  The launch is sized for B = B_cap dialogue slots (missing
+ * ones: length 0) and T = T_cap <= 110; t_dev (device int32) holds the batch's own longest dialogue and T_eff =
+ * clamp(*t_dev, 0, T_cap) takes T's place in the softmax over time, in the 1e-10 leak over the positions outside the window
+ * and in the rows (t * B + b) * ldS that are read: the reference softmaxes over the BATCH's padded length, padded rows
+ * included, so the bucket's T_cap must not enter the result.  norm[e] of every edge is bit-identical to
+ * erc_dgcnv2_edge_att_fwd launched with T = *t_dev on the same B (the same lanes hold the same positions and sum in the same
+ * order).  The backward writes EVERY row of dS [B_cap * T_cap, 110]: rows t < T_eff bit-identical to the exact launch, rows
+ * t >= T_eff +0 whatever was there, columns of absent sources +0 (all 110 columns of a length-0 slot), so dWscalar = dS^T M
+ * and dM += dS Wscalar may run over all B_cap * T_cap rows.  *t_dev == 0: norm of every edge and all of dS are written 0
+ * (no 0 / 0).  One wave per (dialogue, source), no LDS, no atomics, one writer per element, as the exact form.
+ *
+ * The step's batch tables in capacity mode need no entry point of their own: node_off, node_row (capacity nodes -> the zero
+ * row B*T), pad_node, x_row, label_out and counts = {n_dev, t_dev} are erc_bcrnn_meta_cap's (time-major, as here), the padded
+ * speaker ids of the bucket form erc_dgcnv2_meta's, and the resident form reads the store's speaker ids through
+ * erc_window_graph_build_desc.  The 300-wide nodal attention's backward is erc_match_att_bwd (it walks the dialogues through
+ * node_off; empty slots have length 0) followed by erc_mm_zero_tail over rows [node_off[B], n_cap) of dQ and dE. */
+int erc_dgcnv2_edge_att_fwd_cap(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                                const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* norm,
+                                const int32_t* t_dev, void* stream);
+int erc_dgcnv2_edge_att_bwd_cap(const float* S, int ldS, const int32_t* node_off, int B, int T, int wp, int wf,
+                                const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, const float* dnorm,
+                                int dn_parts, int64_t dn_stride, float* dS, const int32_t* t_dev, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------------------------------

@@ -16,6 +16,10 @@ class DGCNParams(ERCParams):
         self.optim = Group(name="Adam", lr=0.0003, weight_decay=0)                # dgcnv2.py:37
         self.loss_weights = True                                                  # dgcnv2.py:42
         self.speaker_onehot, self.batch_first = True, False                       # dgcnv2.py:43-44
+        self.dropout = 0.4                                                        # DGCNModule's default (dgcnv2.py:62)
+        # capacity buckets (one captured graph per padded (B, T, N) bucket instead of per exact shape) are opt-in here:
+        # --capacity_buckets=True, or --resident (with --device_collate), which implies them; --resident_eval with --resident
+        self.capacity_buckets = False
 
 
 ParamsType = DGCNParams
