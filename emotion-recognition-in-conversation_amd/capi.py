@@ -189,6 +189,25 @@ def gemm_f32(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, 
           bias_out, bias_slab, bias, act, aux, ldaux, act_scale, drop_p, rng_state, accumulate)
 
 
+def gemm_f32_stream(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k=1, c_slab=0,
+                    ones_col=0, bias_out=None, bias_slab=0, bias=None, act=0, aux=None, ldaux=0, act_scale=1.0,
+                    drop_p=0.0, rng_state=None, accumulate=0):
+    """the streaming kernel under its own name (erc_gemm_f32 hands it every N <= 1024)"""
+    _call("erc_gemm_f32_stream", A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k, c_slab,
+          ones_col, bias_out, bias_slab, bias, act, aux, ldaux, act_scale, drop_p, rng_state, accumulate)
+
+
+def gemm_f32_stream_form(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k=1, c_slab=0,
+                         ones_col=0, bias_out=None, bias_slab=0, bias=None, act=0, aux=None, ldaux=0, act_scale=1.0,
+                         drop_p=0.0, rng_state=None, accumulate=0):
+    """(a_mode, b_mode, nw, gather_a, gather_b, vec, rm, cf) of the kernel gemm_f32_stream runs for these arguments (ercgraft.h).
+    Nothing is launched or dereferenced: operands may be GPU tensors or plain integer addresses."""
+    form = (C.c_int32 * 8)()
+    _call("erc_gemm_f32_stream_form", A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, Cmat, ldc, M, N, K, split_k,
+          c_slab, ones_col, bias_out, bias_slab, bias, act, aux, ldaux, act_scale, drop_p, rng_state, accumulate, form)
+    return tuple(form)
+
+
 def gemm_bf16x(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, x_is_a, Cmat, ldc, M, N, K, split_k=1,
                c_slab=0, ones_col=0, bias_out=None, bias_slab=0):
     _call("erc_gemm_bf16x", A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, x_is_a, Cmat, ldc, M, N, K, split_k, c_slab,
@@ -207,6 +226,16 @@ def gemm_x3_grouped(A, lda, B, ldb, Cmat, pitch, node_off, n_dlg, n_mod, n_nodes
 
 def gemm_bf16a_stream(X, ldx, gather, W, ldw, Cm, ldc, M, N, K, bias=None, act=0):
     _call("erc_gemm_bf16a_stream", X, ldx, gather, W, ldw, int(W.dtype == torch.bfloat16), Cm, ldc, M, N, K, bias, act)
+
+
+def gemm_bf16a_stream_form(X, ldx, gather, W, ldw, Cm, ldc, M, N, K, bias=None, act=0, w_is_bf16=None):
+    """(kernel, nw, w_is_bf16, ub, a_vec, b_vec) of the kernel gemm_bf16a_stream runs for these arguments (ercgraft.h).  Nothing
+    is launched or dereferenced: operands may be GPU tensors or plain integer addresses (then ``w_is_bf16`` must be given)."""
+    if w_is_bf16 is None:
+        w_is_bf16 = W.dtype == torch.bfloat16
+    form = (C.c_int32 * 6)()
+    _call("erc_gemm_bf16a_stream_form", X, ldx, gather, W, ldw, int(w_is_bf16), Cm, ldc, M, N, K, bias, act, form)
+    return tuple(form)
 
 
 def slab_reduce(slabs, S, stride, bias, n_cols, act, out, numel, ld_out=0):

@@ -568,14 +568,20 @@ __global__ __launch_bounds__(512) void gemm_bf16a_persist_kernel(StreamP p) {
 
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-}  // namespace
+// ---- kernel selection.  The launchers and the *_form queries (ercgraft.h) both go through the two functions below: a
+// launcher switches on the form it gets back, so what a query reports is what a launch runs.
+struct F32Form {
+    int a_mode, b_mode, nw, gather_a, gather_b, vec, rm, cf;
+};
+struct Bf16aForm {
+    int kernel, nw, w_is_bf16, ub, a_vec, b_vec;
+};
 
-// Same contract as erc_gemm_f32 (ercgraft.h); selected by the host for skinny problems.
-extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const int32_t* a_gather, const float* B, int ldb,
-                                   int b_kmajor, const int32_t* b_gather, float* C, int ldc, int M, int N, int K,
-                                   int split_k, int64_t c_slab, int ones_col, float* bias_out, int64_t bias_slab,
-                                   const float* bias, int act, const float* aux, int ldaux, float act_scale, float drop_p,
-                                   const uint64_t* rng_state, int accumulate, void* stream) {
+// Argument checks of erc_gemm_f32_stream, the kernel parameters and the template instantiation for them.  Host only.
+int f32_stream_select(const float* A, int lda, int a_kmajor, const int32_t* a_gather, const float* B, int ldb, int b_kmajor,
+                      const int32_t* b_gather, float* C, int ldc, int M, int N, int K, int split_k, int64_t c_slab, int ones_col,
+                      float* bias_out, int64_t bias_slab, const float* bias, int act, const float* aux, int ldaux,
+                      float act_scale, float drop_p, const uint64_t* rng_state, int accumulate, StreamP& p, F32Form& f) {
     ERC_REQUIRE(A && B && C, "gemm_f32_stream: null operand");
     ERC_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_f32_stream: bad shape M=%d N=%d K=%d", M, N, K);
     ERC_REQUIRE(split_k >= 1, "gemm_f32_stream: split_k must be >= 1");
@@ -584,7 +590,7 @@ extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const 
     ERC_REQUIRE(act >= 0 && act <= 3 && (act != 2 || aux) && (act != 3 || rng_state), "gemm_f32_stream: bad epilogue");
     ERC_REQUIRE(!(a_gather && a_kmajor) && !(b_gather && !b_kmajor), "gemm_f32_stream: gather on a contiguous-K index only");
     ERC_REQUIRE(ones_col >= 0 && ones_col <= 2, "gemm_f32_stream: ones mode %d", ones_col);
-    StreamP p{};
+    p = StreamP{};
     p.A = A; p.B = B; p.C = C; p.a_gather = a_gather; p.b_gather = b_gather; p.bias = bias; p.aux = aux;
     p.bias_out = bias_out; p.rng = rng_state; p.c_slab = c_slab; p.bias_slab = bias_slab;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = ldaux; p.M = M; p.N = N; p.K = K;
@@ -604,8 +610,6 @@ extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const 
     // N=100): these products are bound by the length of the per-wavefront chain, not by fragment traffic.
     // Re-checked on every module's step (16x64 / 32x64 whenever >= 300..700 workgroups remain): MMGCN 8.18 -> 8.41..8.90 ms,
     // COGMEN 0.154 -> 0.160..0.169 ms, DialogueGCN 0.746 -> 0.749..0.874 ms.
-    dim3 grid(erc_cdiv(Nlog, 32), erc_cdiv(Mlog, 16), split_k);
-    hipStream_t st = (hipStream_t)stream;
     const bool ga = a_gather != nullptr, gb = b_gather != nullptr;
     const bool vec = (a_kmajor || p.a_vec) && (b_kmajor || p.b_vec);
     // Long K over many rows (MMGCN's dH0 = DG [6 300, 12 800] x U^T [12 800, 200]): with 16 x 32 wave tiles every workgroup
@@ -618,12 +622,67 @@ extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const 
         const char* e = getenv("ERC_GEMM_BIG_TILE");
         big_tile = e ? atoi(e) : 1;
     }
-    if (big_tile && !a_kmajor && !b_kmajor && !ga && !gb && vec && nw == 8 && K >= 4096 && Mlog >= 2048 && Nlog >= 64) {
+    if (big_tile && !a_kmajor && !b_kmajor && !ga && !gb && vec && nw == 8 && K >= 4096 && Mlog >= 2048 && Nlog >= 64)
+        f = F32Form{0, 0, 4, 0, 0, 1, 2, 4};
+    else   // the K-major A form (TN) is built with scalar loads only
+        f = F32Form{a_kmajor ? 1 : 0, b_kmajor ? 1 : 0, nw, ga, gb, a_kmajor ? 0 : (int)vec, 1, 2};
+    return ERC_OK;
+}
+
+// The same for erc_gemm_bf16a_stream.
+int bf16a_stream_select(const void* X, int ldx, const int32_t* gather, const void* W, int ldw, int w_is_bf16, float* C, int ldc,
+                        int M, int N, int K, const float* bias, int act, StreamP& p, Bf16aForm& f) {
+    ERC_REQUIRE(X && W && C && M > 0 && N > 0 && K > 0, "gemm_bf16a_stream: bad arguments");
+    ERC_REQUIRE(act == 0 || act == 1, "gemm_bf16a_stream: act %d", act);
+    p = StreamP{};
+    p.A = X; p.B = W; p.C = C; p.a_gather = gather; p.bias = bias; p.lda = ldx; p.ldb = ldw; p.ldc = ldc;
+    p.M = M; p.N = N; p.K = K; p.act = act;
+    const int nkb = erc_cdiv(K, 32);
+    p.kblocks_per_split = nkb;
+    // widest legal access per 8-element fragment: 2 = 16 B, 1 = 8 B, 4 = 4 B (bf16 operands); fp32 W: 1 = 16 B, 3 = 8 B
+    auto bvec = [](const void* q, int ld) { return !al16(q) ? 0 : (ld % 8 == 0 ? 2 : (ld % 4 == 0 ? 1 : (ld % 2 == 0 ? 4 : 0))); };
+    p.a_vec = bvec(X, ldx);
+    p.b_vec = w_is_bf16 ? bvec(W, ldw) : (!al16(W) ? 0 : (ldw % 4 == 0 ? 1 : (ldw % 2 == 0 ? 3 : 0)));
+    // weights resident in registers, every feature row read once (see the kernel); ERC_PERSIST_MIN_M overrides the
+    // row count from which it is used
+    static int persist_min_m = -1;
+    if (persist_min_m < 0) {
+        const char* e = getenv("ERC_PERSIST_MIN_M");
+        persist_min_m = e ? atoi(e) : 1024;   // measured crossover: the persistent kernel wins from ~2 k rows (6.9 vs 7.1 us) up
+    }
+    if (w_is_bf16 && M >= persist_min_m && N <= 32 * PJ_NT && K >= 32 && K <= 32 * 8 * PJ_NB && K % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0 &&
+        ((uintptr_t)X & 7) == 0 && ((uintptr_t)W & 7) == 0)
+        f = Bf16aForm{1, 8, 1, PJ_NB, 1, 1};   // this kernel reads both operands 8 bytes at a time whatever a_vec / b_vec say
+    else   // UB: see the launcher
+        f = Bf16aForm{0, nkb >= 16 ? 8 : (nkb >= 4 ? 4 : 1), w_is_bf16 ? 1 : 0, 6, p.a_vec, p.b_vec};
+    return ERC_OK;
+}
+
+}  // namespace
+
+// Same contract as erc_gemm_f32 (ercgraft.h); selected by the host for skinny problems.
+extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const int32_t* a_gather, const float* B, int ldb,
+                                   int b_kmajor, const int32_t* b_gather, float* C, int ldc, int M, int N, int K,
+                                   int split_k, int64_t c_slab, int ones_col, float* bias_out, int64_t bias_slab,
+                                   const float* bias, int act, const float* aux, int ldaux, float act_scale, float drop_p,
+                                   const uint64_t* rng_state, int accumulate, void* stream) {
+    StreamP p;
+    F32Form f;
+    const int rc = f32_stream_select(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, C, ldc, M, N, K, split_k, c_slab,
+                                     ones_col, bias_out, bias_slab, bias, act, aux, ldaux, act_scale, drop_p, rng_state,
+                                     accumulate, p, f);
+    if (rc != ERC_OK) return rc;
+    const int Nlog = N + (ones_col == 1 ? 1 : 0), Mlog = M + (ones_col == 2 ? 1 : 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (f.rm == 2) {
         dim3 grid2(erc_cdiv(Nlog, 64), erc_cdiv(Mlog, 32), split_k);
         hipLaunchKernelGGL((gemm_f32_stream_kernel<0, 0, 4, false, false, true, 2, 4>), grid2, dim3(256), 0, st, p);
         ERC_LAUNCH_CHECK("gemm_f32_stream");
         return ERC_OK;
     }
+    dim3 grid(erc_cdiv(Nlog, 32), erc_cdiv(Mlog, 16), split_k);
+    const int nw = f.nw;
+    const bool ga = f.gather_a, gb = f.gather_b, vec = f.vec;
 #define ERC_SL4(AM, BM_, NW_, GA_, GB_, V_) \
     hipLaunchKernelGGL((gemm_f32_stream_kernel<AM, BM_, NW_, GA_, GB_, V_, 1, 2>), grid, dim3(64 * NW_), 0, st, p)
 #define ERC_SL3(AM, BM_, GA_, GB_, V_)                        \
@@ -637,9 +696,9 @@ extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const 
         if (vec) ERC_SL3(AM, BM_, GA_, GB_, true); \
         else ERC_SL3(AM, BM_, GA_, GB_, false);    \
     } while (0)
-    if (!a_kmajor && !b_kmajor) {
+    if (f.a_mode == 0 && f.b_mode == 0) {
         if (ga) ERC_SL2(0, 0, true, false); else ERC_SL2(0, 0, false, false);
-    } else if (!a_kmajor && b_kmajor) {
+    } else if (f.a_mode == 0) {
         if (ga && gb) ERC_SL2(0, 1, true, true);
         else if (ga) ERC_SL2(0, 1, true, false);
         else if (gb) ERC_SL2(0, 1, false, true);
@@ -654,53 +713,69 @@ extern "C" int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const 
     return ERC_OK;
 }
 
+// The instantiation erc_gemm_f32_stream would launch for these arguments (ercgraft.h).  Nothing is launched or dereferenced.
+extern "C" int erc_gemm_f32_stream_form(const float* A, int lda, int a_kmajor, const int32_t* a_gather, const float* B, int ldb,
+                                        int b_kmajor, const int32_t* b_gather, float* C, int ldc, int M, int N, int K,
+                                        int split_k, int64_t c_slab, int ones_col, float* bias_out, int64_t bias_slab,
+                                        const float* bias, int act, const float* aux, int ldaux, float act_scale, float drop_p,
+                                        const uint64_t* rng_state, int accumulate, int32_t* form) {
+    ERC_REQUIRE(form, "gemm_f32_stream_form: null form");
+    StreamP p;
+    F32Form f;
+    const int rc = f32_stream_select(A, lda, a_kmajor, a_gather, B, ldb, b_kmajor, b_gather, C, ldc, M, N, K, split_k, c_slab,
+                                     ones_col, bias_out, bias_slab, bias, act, aux, ldaux, act_scale, drop_p, rng_state,
+                                     accumulate, p, f);
+    if (rc != ERC_OK) return rc;
+    const int v[8] = {f.a_mode, f.b_mode, f.nw, f.gather_a, f.gather_b, f.vec, f.rm, f.cf};
+    for (int i = 0; i < 8; ++i) form[i] = v[i];
+    return ERC_OK;
+}
+
 // C[M,N] = act(X[gather(m), :K] (bf16) * W[N,K]^T + bias), fp32 accumulate: forward input projection.
 // w_is_bf16 != 0: W is a bf16 copy [N, ldw] (kept in sync by erc_adam_step's shadow output), else fp32.
 extern "C" int erc_gemm_bf16a_stream(const void* X, int ldx, const int32_t* gather, const void* W, int ldw, int w_is_bf16,
                                      float* C, int ldc, int M, int N, int K, const float* bias, int act, void* stream) {
-    ERC_REQUIRE(X && W && C && M > 0 && N > 0 && K > 0, "gemm_bf16a_stream: bad arguments");
-    ERC_REQUIRE(act == 0 || act == 1, "gemm_bf16a_stream: act %d", act);
-    StreamP p{};
-    p.A = X; p.B = W; p.C = C; p.a_gather = gather; p.bias = bias; p.lda = ldx; p.ldb = ldw; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K; p.act = act;
-    const int nkb = erc_cdiv(K, 32);
-    p.kblocks_per_split = nkb;
-    // widest legal access per 8-element fragment: 2 = 16 B, 1 = 8 B, 4 = 4 B (bf16 operands); fp32 W: 1 = 16 B, 3 = 8 B
-    auto bvec = [](const void* q, int ld) { return !al16(q) ? 0 : (ld % 8 == 0 ? 2 : (ld % 4 == 0 ? 1 : (ld % 2 == 0 ? 4 : 0))); };
-    p.a_vec = bvec(X, ldx);
-    p.b_vec = w_is_bf16 ? bvec(W, ldw) : (!al16(W) ? 0 : (ldw % 4 == 0 ? 1 : (ldw % 2 == 0 ? 3 : 0)));
+    StreamP p;
+    Bf16aForm f;
+    const int rc = bf16a_stream_select(X, ldx, gather, W, ldw, w_is_bf16, C, ldc, M, N, K, bias, act, p, f);
+    if (rc != ERC_OK) return rc;
     dim3 grid(8 * erc_cdiv(erc_cdiv(M, 32), 8) * erc_cdiv(N, 32), 1, 1);  // see the XCD-aware mapping in the kernel
     hipStream_t st = (hipStream_t)stream;
-    // weights resident in registers, every feature row read once (see the kernel); ERC_PERSIST_MIN_M overrides the
-    // row count from which it is used
-    static int persist_min_m = -1;
-    if (persist_min_m < 0) {
-        const char* e = getenv("ERC_PERSIST_MIN_M");
-        persist_min_m = e ? atoi(e) : 1024;   // measured crossover: the persistent kernel wins from ~2 k rows (6.9 vs 7.1 us) up
-    }
-    if (w_is_bf16 && M >= persist_min_m && N <= 32 * PJ_NT && K >= 32 && K <= 32 * 8 * PJ_NB && K % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0 &&
-        ((uintptr_t)X & 7) == 0 && ((uintptr_t)W & 7) == 0) {
+    if (f.kernel == 1) {
         hipLaunchKernelGGL(gemm_bf16a_persist_kernel, dim3(256), dim3(512), 0, st, p);   // 128 pairs of workgroups
         ERC_LAUNCH_CHECK("gemm_bf16a_persist");
         return ERC_OK;
     }
     // UB = 3 with two workgroups per CU (<= 128 VGPRs) was tried for big grids: it spills (42 VGPRs) and ran 192 vs 118 us at
     // B = 512; with 173 VGPRs and one workgroup per CU 143 us.  The single 6-block batch is kept for every size.
-    const bool big = false;
+    const bool big = f.ub == 3;
 #define ERC_BA(NW_, WB_)                                                                                          \
     do {                                                                                                          \
         if (big) hipLaunchKernelGGL((gemm_bf16a_stream_kernel<NW_, WB_, 3>), grid, dim3(64 * NW_), 0, st, p);     \
         else hipLaunchKernelGGL((gemm_bf16a_stream_kernel<NW_, WB_, 6>), grid, dim3(64 * NW_), 0, st, p);         \
     } while (0)
-    if (nkb >= 16) {
-        if (w_is_bf16) ERC_BA(8, true); else ERC_BA(8, false);
-    } else if (nkb >= 4) {
-        if (w_is_bf16) ERC_BA(4, true); else ERC_BA(4, false);
+    if (f.nw == 8) {
+        if (f.w_is_bf16) ERC_BA(8, true); else ERC_BA(8, false);
+    } else if (f.nw == 4) {
+        if (f.w_is_bf16) ERC_BA(4, true); else ERC_BA(4, false);
     } else {
-        if (w_is_bf16) ERC_BA(1, true); else ERC_BA(1, false);
+        if (f.w_is_bf16) ERC_BA(1, true); else ERC_BA(1, false);
     }
 #undef ERC_BA
     ERC_LAUNCH_CHECK("gemm_bf16a_stream");
+    return ERC_OK;
+}
+
+// The kernel erc_gemm_bf16a_stream would launch for these arguments (ercgraft.h).  Nothing is launched or dereferenced.
+extern "C" int erc_gemm_bf16a_stream_form(const void* X, int ldx, const int32_t* gather, const void* W, int ldw, int w_is_bf16,
+                                          float* C, int ldc, int M, int N, int K, const float* bias, int act, int32_t* form) {
+    ERC_REQUIRE(form, "gemm_bf16a_stream_form: null form");
+    StreamP p;
+    Bf16aForm f;
+    const int rc = bf16a_stream_select(X, ldx, gather, W, ldw, w_is_bf16, C, ldc, M, N, K, bias, act, p, f);
+    if (rc != ERC_OK) return rc;
+    const int v[6] = {f.kernel, f.nw, f.w_is_bf16, f.ub, f.a_vec, f.b_vec};
+    for (int i = 0; i < 6; ++i) form[i] = v[i];
     return ERC_OK;
 }
 

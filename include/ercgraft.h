@@ -116,7 +116,7 @@ int erc_gemm_f32(const float* A, int lda, int a_kmajor, const int32_t* a_gather,
                  const float* bias, int act, const float* aux, int ldaux, float act_scale,
                  float drop_p, const uint64_t* rng_state, int accumulate, void* stream);
 
-/* erc_gemm_f32 dispatches on the output width: N <= 512 runs the register-streaming kernel (16x32 tile per
+/* erc_gemm_f32 dispatches on the output width: N <= 1024 runs the register-streaming kernel (16x32 tile per
  * wavefront, fragments loaded straight from global memory, K split over the wavefronts of a workgroup), wider
  * outputs the LDS-tiled kernel.  The streaming kernel is also exported under its own name (same contract). */
 int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const int32_t* a_gather,
@@ -125,6 +125,16 @@ int erc_gemm_f32_stream(const float* A, int lda, int a_kmajor, const int32_t* a_
                         int split_k, int64_t c_slab, int ones_col, float* bias_out, int64_t bias_slab,
                         const float* bias, int act, const float* aux, int ldaux, float act_scale,
                         float drop_p, const uint64_t* rng_state, int accumulate, void* stream);
+/* Which kernel erc_gemm_f32_stream runs for these arguments: the same argument checks and the same selection function as
+ * the launcher, but nothing is launched and no operand is dereferenced (only the pointers' alignment and NULL-ness count).
+ * form: HOST int32_t [8] = {a_mode (0 K-contiguous A, 1 K-major), b_mode (likewise), nw (wavefronts that split K: 1 | 4 | 8),
+ * gather_a, gather_b, vec (16-byte operand loads), rm, cf (wave tile 16 rm x 16 cf: 1, 2 or the big tile 2, 4)}. */
+int erc_gemm_f32_stream_form(const float* A, int lda, int a_kmajor, const int32_t* a_gather,
+                             const float* B, int ldb, int b_kmajor, const int32_t* b_gather,
+                             float* C, int ldc, int M, int N, int K,
+                             int split_k, int64_t c_slab, int ones_col, float* bias_out, int64_t bias_slab,
+                             const float* bias, int act, const float* aux, int ldaux, float act_scale,
+                             float drop_p, const uint64_t* rng_state, int accumulate, int32_t* form);
 /* Batched weight gradients (autograd of every nn.Linear / matmul weight behind loss.backward(),
  * track_mm/cogmen.py:187-189, dagerc.py:228-231, mmgcn.py:150-152, dgcn.py:127-129): n_desc independent products
  * C_i[M_i,N_i] = A_i^T B_i[gather_i] in ONE launch.  A_i [K,M_i] fp32 K-major; B_i [*,N_i] K-major, fp32 or bf16 (the
@@ -184,6 +194,12 @@ int erc_wgrad_max_k_per_split(void);
  * The HBM-dominant kernel of the COGMEN step (nn.Linear(D,100), track_mm/cogmen.py:103-105,147). */
 int erc_gemm_bf16a_stream(const void* X, int ldx, const int32_t* gather, const void* W, int ldw, int w_is_bf16,
                           float* C, int ldc, int M, int N, int K, const float* bias, int act, void* stream);
+/* Which kernel erc_gemm_bf16a_stream runs for these arguments (same checks and selection function as the launcher; nothing
+ * is launched or dereferenced).  form: HOST int32_t [6] = {kernel (0 streaming, 1 persistent), nw, w_is_bf16, ub (K blocks
+ * per load batch), a_vec, b_vec (access width per 8-element fragment: bf16 operand 2 = 16 B, 1 = 8 B, 4 = 4 B, 0 = by
+ * element; fp32 W 1 = 16 B, 3 = 8 B, 0 = by element)}.  The persistent kernel reports {1, 8, 1, 6, 1, 1}. */
+int erc_gemm_bf16a_stream_form(const void* X, int ldx, const int32_t* gather, const void* W, int ldw, int w_is_bf16,
+                               float* C, int ldc, int M, int N, int K, const float* bias, int act, int32_t* form);
 
 /* Same contract with bf16 operands for the big streamed operand (the padded
  * feature block): A or B given as bf16 (uint16 storage), the other operand is

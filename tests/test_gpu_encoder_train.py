@@ -13,19 +13,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.gemm_forms_ref import erc_uniform_np  # the one restatement of the generator (csrc/erc_common.h erc_uniform)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def erc_uniform_np(seed, offset, idx):
-    """csrc/erc_common.h erc_uniform on numpy uint64 arrays."""
-    u = np.uint64
-    with np.errstate(over="ignore"):
-        z = u(seed) ^ (u(offset) * u(0x9E3779B97F4A7C15)) ^ ((idx.astype(np.uint64) + u(0xD1B54A32D192ED03)) * u(0xBF58476D1CE4E5B9))
-        z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
-        z = z ^ (z >> u(31))
-    return (z >> u(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
 
 
 def keep_mask(shape, p, seed, offset, stream):

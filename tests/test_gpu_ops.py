@@ -111,6 +111,9 @@ def _gemm_ref(A, B):
                                    (64, 32, 32), (130, 900, 100), (2080, 100, 900)])
 @pytest.mark.parametrize("split", [1, 3])
 def test_gemm_nt_nn(capi, M, N, K, split):
+    """Workload shapes through erc_gemm_f32.  Every N <= 1024, so all of these land in the streaming kernel
+    (erc_gemm_f32_stream); which instantiation a shape reaches, and every other one, is tested on exact products in
+    tests/test_gpu_gemm_forms.py."""
     g = torch.Generator().manual_seed(M * 7 + N)
     A = torch.randn(M, K, generator=g)
     W = torch.randn(N, K, generator=g)  # nn.Linear layout
@@ -135,7 +138,8 @@ def test_gemm_nt_nn(capi, M, N, K, split):
 
 @pytest.mark.parametrize("rows,n_out,n_in", [(2080, 100, 1380), (61, 6, 100), (300, 400, 100), (5, 3, 7), (2080, 100, 100)])
 def test_gemm_wgrad_tn(capi, rows, n_out, n_in):
-    """dW = dY^T X (+ bias grad through the ones column), split-K slabs reduced by erc_slab_reduce."""
+    """dW = dY^T X (+ bias grad through the ones column), split-K slabs reduced by erc_slab_reduce.  These calls land in
+    the streaming kernel's TN forms (tests/test_gpu_gemm_forms.py runs every form and split on exact products)."""
     g = torch.Generator().manual_seed(rows + n_out)
     dY = torch.randn(rows, n_out, generator=g)
     X = torch.randn(rows, n_in, generator=g)
@@ -177,7 +181,8 @@ def test_gemm_wide_tiles(capi):
 
 
 def test_gemm_gather_and_unaligned(capi):
-    """fused gather of valid rows of the padded block; leading dimension not a multiple of 4 (MELD D=1242)."""
+    """fused gather of valid rows of the padded block; leading dimension not a multiple of 4 (MELD D=1242).  N = 100: the
+    streaming kernel's gather forms, vector (D = 1380) and scalar (see tests/test_gpu_gemm_forms.py for all of them)."""
     g = torch.Generator().manual_seed(9)
     for D in (1242, 1380, 37):
         Xpad = torch.randn(5 * 11, D, generator=g)
@@ -194,6 +199,8 @@ def test_gemm_gather_and_unaligned(capi):
 
 
 def test_gemm_relu_dropout_epilogues(capi):
+    """act 3 and act 2 at N = 100, i.e. in the streaming kernel's epilogue; tests/test_gpu_gemm_forms.py checks the kept set
+    against a restatement of the generator, in every layout."""
     g = torch.Generator().manual_seed(4)
     M, N, K = 300, 100, 100
     A, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g)
@@ -526,8 +533,10 @@ def test_wgrad_table(capi):
 @pytest.mark.parametrize("M,K,N,w_bf16", [(1982, 1380, 100, True), (500, 712, 100, False), (700, 1242, 37, True),
                                           (9000, 1380, 100, True), (8200, 712, 100, True), (8300, 96, 24, True)])
 def test_gemm_bf16a_projection(capi, M, K, N, w_bf16):
-    """Input projection on a bf16 feature block: C = relu(X[gather] W^T + b), fp32 accumulate.  Small row counts use the
-    streaming kernel, >= 8192 rows (bf16 W) the persistent kernel with the weights resident in registers."""
+    """Input projection on a bf16 feature block: C = relu(X[gather] W^T + b), fp32 accumulate.  Below 1024 rows, and with an
+    fp32 W, the streaming kernel runs; from 1024 rows on (bf16 W, N <= 128, K <= 1536) the persistent kernel with the weights
+    resident in registers: here the cases with M = 1982, 9000, 8200 and 8300.  tests/test_gpu_gemm_forms.py asserts which
+    kernel a call selects and checks both on exact products."""
     g = torch.Generator().manual_seed(M + K)
     X = torch.randn(M + 40, K, generator=g).bfloat16()
     Wf = (torch.randn(N, K, generator=g) / math.sqrt(K))
