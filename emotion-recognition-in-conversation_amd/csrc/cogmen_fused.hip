@@ -24,6 +24,7 @@
 // Everything else (means, softmax, BatchNorm) is fp32.  The graph is read through the CSR that erc_window_graph_build
 // wrote; the kernels only rely on |source - target| <= 5 (checked by the host wrapper through wp / wf).
 #include "erc_common.h"
+#include "record_chunks.h"
 #include "split_dev.h"
 #include "store_dev.h"
 
@@ -840,7 +841,7 @@ struct BxMap {
     static constexpr int BAND_OFF = SE_OFF + BX_SE_BYTES16;                                // band matrices; stage 3 on: the dH1 tile | K-split partials of stage 5
     static constexpr int BAND_BYTES = 2 * BW_ROWS * BW_BAND * 4;
     static constexpr int SV_OFF = BAND_OFF + BAND_BYTES;                                   // V row tile; from (c) on: the dQKVS planes
-    static constexpr int E_OFF = SV_OFF + BW_SK_BYTES;                                     // head records / K-split partials of the band product; dQKVS planes
+    static constexpr int E_OFF = SV_OFF + BW_SK_BYTES;                                     // stage 0: the means of the head records (sBnB; their fp64 partials live in the Q | G tiles); K-split partials of the band product; dQKVS planes
     static constexpr int E_BYTES = NT * BX_DQPLANE - BW_SK_BYTES > 24576 ? NT * BX_DQPLANE - BW_SK_BYTES : 24576;
     static constexpr int LUT_OFF = E_OFF + E_BYTES;
     static constexpr int LDS = LUT_OFF + 1024;
@@ -951,8 +952,10 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
         if (tid >= 64 && tid < 64 + CG_MID + 1) sOp[tid - 64] = p.out_ptr[min(max(mb + tid - 64, 0), N)];
     }
     if (tid >= 128 && tid < 128 + CG_TR) sSpkOwn[tid - 128] = p.node_spk[min(r0 + tid - 128, N - 1)];
-    double* const sHp = reinterpret_cast<double*>(lds + (X ? XM::E_OFF : BW_SDQ_OFF));                  // [4][256] partial sums of the head records
-    float* const sBnB = reinterpret_cast<float*>(lds + (X ? XM::E_OFF : BW_SDQ_OFF) + 4 * 256 * 8);     // [224] mean dY | mean dY * xhat
+    // [16][256] fp64 partial sums of the head records, one row per wavefront: 32 KB in the Q | G row tiles, which are written behind the combine
+    double* const sHp = reinterpret_cast<double*>(lds + (X ? XM::SQ_OFF : BW_SQ_OFF));
+    static_assert(XM::SG_OFF == XM::SQ_OFF + BW_SQ_BYTES && BW_SG_OFF == BW_SQ_OFF + BW_SQ_BYTES && CG_NW * 256 * 8 <= 2 * BW_SQ_BYTES, "head record partials");
+    float* const sBnB = reinterpret_cast<float*>(lds + (X ? XM::E_OFF : BW_SDQ_OFF));                   // [224] mean dY | mean dY * xhat (stage 0 only: sPartA follows)
     if constexpr (X) {
         // the K -> compact column table of the dH0 product (one entry per 4 k of the K = 960 = 9 blocks of 104 + padding): compact
         // BYTE offset | needed source speaker + 1 << 16 (0: any -- the self block; 3: none)
@@ -964,21 +967,28 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
             sLut[tid - 768] = e;
         }
     }
-    if (p.head_part) {   // (uniform) the head's workgroup records: slot = tid % 256, a quarter of the record list each
-        const int slot = tid & 255, part = tid >> 8;
-        const int G = p.head_parts, Gq = (G + 3) >> 2;
-        const int g_begin = min(part * Gq, G), g_end = min(G, g_begin + Gq);
-        double acc = 0.0;
-        if (slot < p.hp_floats) {
-            for (int g0 = g_begin; g0 < g_end; g0 += 16) {
-                float t[16];
+    if (p.head_part) {   // (uniform) the head's workgroup records: a record is hp_floats / 4 <= 64 contiguous float4, ONE wave instruction loads it
+        // (lane l its float4 l); wavefront w takes the chunk record_chunk(G, 16, w) of the record list (csrc/record_chunks.h): 124 records at
+        // B = 32 are one batch of 8 loads per thread (as 4-byte loads of one slot per thread the same bytes took four times the instructions)
+        const int G = p.head_parts, nq4 = p.hp_floats >> 2;
+        const RecordChunk ch = record_chunk(G, CG_NW, w);
+        const int l4 = min(lane, nq4 - 1);           // lanes at or beyond nq4 repeat the last float4 (loads stay unconditional)
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int g0 = ch.first; g0 < ch.last; g0 += 8) {   // (wave-uniform)
+            f32x4 t[8];
 #pragma unroll
-                for (int j = 0; j < 16; ++j) t[j] = p.head_part[(int64_t)min(g0 + j, G - 1) * p.hp_floats + slot];
+            for (int j = 0; j < 8; ++j)
+                t[j] = *reinterpret_cast<const f32x4*>(p.head_part + (int64_t)record_chunk_index(g0 + j, G) * p.hp_floats + 4 * l4);
 #pragma unroll
-                for (int j = 0; j < 16; ++j) acc += (double)t[j] * (g0 + j < g_end ? 1.0 : 0.0);
+            for (int j = 0; j < 8; ++j) {
+                const double mk = record_chunk_mask(g0 + j, ch);
+                a0 += (double)t[j][0] * mk, a1 += (double)t[j][1] * mk, a2 += (double)t[j][2] * mk, a3 += (double)t[j][3] * mk;
             }
         }
-        sHp[part * 256 + slot] = acc;
+        if (lane < nq4) {
+            double* const d = sHp + w * 256 + 4 * lane;
+            d[0] = a0, d[1] = a1, d[2] = a2, d[3] = a3;
+        }
     }
     {
         // K / V rows of the far range: 46 (+ 2 zero) rows x 50 float4
@@ -1030,13 +1040,19 @@ __global__ __launch_bounds__(CG_NTH) void cogmen_bwd_tile_kernel(const CgBwdP p)
     if (p.head_part) {
         __syncthreads();
         if (tid < 228) {
-            const double sv = ((sHp[tid] + sHp[256 + tid]) + sHp[512 + tid]) + sHp[768 + tid];
+            auto slot_sum = [&](int sl) {      // the sixteen chunks in wavefront order
+                double s = sHp[sl];
+#pragma unroll
+                for (int k = 1; k < CG_NW; ++k) s += sHp[k * 256 + sl];
+                return s;
+            };
+            const double sv = slot_sum(tid);
             if (tid < 224) sBnB[tid] = (float)(sv / (double)N);
             if (blockIdx.x == 0) {   // dbeta = sum dY, dgamma = sum dY * xhat (BatchNorm1d backward), loss / accuracy statistics
                 const int c = tid < 112 ? tid : tid - 112;
                 if (tid < 112 && c < CG_F) p.dbeta[c] = (float)sv, p.bn_bwd_out[c] = (float)(sv / (double)N);
                 if (tid >= 112 && tid < 224 && c < CG_F) p.dgamma[c] = (float)sv, p.bn_bwd_out[CG_F + c] = (float)(sv / (double)N);
-                const double wsum = ((sHp[226] + sHp[256 + 226]) + sHp[512 + 226]) + sHp[768 + 226];
+                const double wsum = slot_sum(226);
                 const double wmean = wsum / (double)p.head_parts;      // every record carries the same weight sum
                 if (tid == 224) p.stats[0] = (float)(sv / wmean), p.stats[2] = (float)wmean;
                 if (tid == 225) p.stats[1] = (float)sv;
@@ -1659,7 +1675,8 @@ static int bwd_tile_launch(int terms, const float* dY, const float* H2, int ldh2
                            const int32_t* node_spk, int n_speakers, const float* head_part, int head_parts,
                            int head_part_floats, float* dgamma, float* dbeta, float* stats, int grads_bf16, int lddh1,
                            const int32_t* n_dev, const int32_t* node_rec, void* stream) {
-    ERC_REQUIRE(!head_part || (head_parts > 0 && head_part_floats >= 227 && head_part_floats <= 256 && dgamma && dbeta && stats),
+    ERC_REQUIRE(!head_part || (head_parts > 0 && head_part_floats >= 228 && head_part_floats <= 256 && head_part_floats % 4 == 0 &&
+                               ((uintptr_t)head_part & 15) == 0 && dgamma && dbeta && stats),
                 "cogmen_bwd_tile: head record operands");
     ERC_REQUIRE(dY && H2 && gamma && saved && bn_bwd && QKVS && alpha && in_ptr && in_src && out_ptr && out_dst && out_typ &&
                     out_eid && inv_cnt && WqT && Wb && dQKVS && dH1 && dH0 && node_spk, "cogmen_bwd_tile: null pointer");

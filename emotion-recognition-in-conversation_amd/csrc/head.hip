@@ -17,6 +17,7 @@
 // Cross-workgroup sums (BatchNorm backward, loss, accuracy): per-workgroup partials written with write-through (sc1)
 // stores, an arrival counter, and the last workgroup adds them in workgroup order in fp64 -- deterministic, no fences.
 #include "erc_common.h"
+#include "record_chunks.h"
 #include <stdlib.h>
 
 extern "C" int erc_head_fused_rows_per_workgroup(int n_rows);
@@ -172,7 +173,7 @@ template <bool BNP, int RPW>
 __global__ __launch_bounds__(512) void head_fused_kernel(const HeadP p) {
     constexpr int NCW = 8 / RPW;   // wavefronts per row tile; each takes RPW of the 7 column tiles
     __shared__ __attribute__((aligned(16))) float sW[HF_MAXF * HF_S];  // W0, row pitch HF_S
-    __shared__ __attribute__((aligned(16))) float sT[RPW][16 * HF_ST > 2048 ? 16 * HF_ST : 2048];   // (>= 8 KB: the BatchNorm sums stage uses it first)    // dZ row tiles (transposition between the MFMA products); sT[0] first holds sLg
+    __shared__ __attribute__((aligned(16))) float sT[RPW][16 * HF_ST];   // dZ row tiles (transposition between the MFMA products); sT[0] first holds sLg
     __shared__ __attribute__((aligned(16))) float sD[RPW][16][8];  // dlogits of the two row tiles
     __shared__ float sCol[RPW][2][112];
     __shared__ float sLoss[RPW][2];
@@ -210,38 +211,44 @@ __global__ __launch_bounds__(512) void head_fused_kernel(const HeadP p) {
         // ---- BNP: training-mode BatchNorm statistics (torch.nn.BatchNorm1d, cogmen.py:67) from the per-tile column
         //      sums the forward tile kernel left behind: every workgroup adds the tiles in order (fp64) -- no last
         //      arriver, no extra launch; workgroup 0 publishes mean | rstd and updates the running statistics.
-        //      Thread (pair = tid % 128 < F, part = tid / 128) takes two columns and a quarter of the tile list: one
-        //      batch of 8-byte loads, in flight together with the W0 loads above.
+        //      A record is one contiguous run of 2F / 4 <= 50 float4: ONE wave instruction loads a whole record (lane l its
+        //      float4 l), wavefront w takes the chunk record_chunk(G, 8, w) of the tile list (csrc/record_chunks.h): one batch
+        //      of 16-byte loads, in flight together with the W0 loads above (a stage like this is priced per load
+        //      instruction: as 8-byte loads of two columns per thread the same bytes took twice as many).
         if (BNP) {
             // gamma / beta -> LDS (visible behind the barriers below): the A fragments then need no global operand but H2
             if (tid < 2 * (F / 4)) {
                 const int which = tid / (F / 4), q4 = tid - which * (F / 4);
                 *reinterpret_cast<f32x4*>(sGB + which * F + 4 * q4) = *reinterpret_cast<const f32x4*>((which ? p.beta : p.gamma) + 4 * q4);
             }
-            double* const sBn = reinterpret_cast<double*>(&sT[0][0]);   // [4][2][128] doubles = 8 KB of the tile area
-            const int pair = tid & 127, part = tid >> 7;
-            const int G = p.bn_tiles, Gq = (G + 3) >> 2;
-            const int g_begin = min(part * Gq, G), g_end = min(G, g_begin + Gq);
-            double ax = 0.0, ay = 0.0;
-            if (pair < F) {
-                for (int g0 = g_begin; g0 < g_end; g0 += 32) {
-                    float2 t[32];
+            double* const sBn = reinterpret_cast<double*>(sW);   // [8][2F] doubles = 12.8 KB of sW: W0 waits in registers until behind the barriers
+            const int G = p.bn_tiles, nq4 = F / 2;               // float4 slots of a record
+            const RecordChunk ch = record_chunk(G, 8, w);
+            const int l4 = min(lane, nq4 - 1);                    // lanes at or beyond nq4 repeat the last slot (loads stay unconditional)
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            for (int g0 = ch.first; g0 < ch.last; g0 += 16) {     // (wave-uniform) 124 tiles at B = 32: one batch of 16
+                f32x4 t[16];
 #pragma unroll
-                    for (int j = 0; j < 32; ++j) t[j] = *reinterpret_cast<const float2*>(p.bn_part + (int64_t)min(g0 + j, G - 1) * 2 * F + 2 * pair);
+                for (int j = 0; j < 16; ++j)
+                    t[j] = *reinterpret_cast<const f32x4*>(p.bn_part + (int64_t)record_chunk_index(g0 + j, G) * 2 * F + 4 * l4);
 #pragma unroll
-                    for (int j = 0; j < 32; ++j) {
-                        const double mk = g0 + j < g_end ? 1.0 : 0.0;
-                        ax += (double)t[j].x * mk, ay += (double)t[j].y * mk;
-                    }
+                for (int j = 0; j < 16; ++j) {
+                    const double mk = record_chunk_mask(g0 + j, ch);
+                    a0 += (double)t[j][0] * mk, a1 += (double)t[j][1] * mk, a2 += (double)t[j][2] * mk, a3 += (double)t[j][3] * mk;
                 }
             }
-            sBn[(part * 2 + 0) * 128 + pair] = ax, sBn[(part * 2 + 1) * 128 + pair] = ay;
+            if (lane < nq4) {
+                double* const d = sBn + w * 2 * F + 4 * lane;
+                d[0] = a0, d[1] = a1, d[2] = a2, d[3] = a3;
+            }
             __syncthreads();
             if (tid < F) {
-                // column c: sum x = slot c, sum x^2 = slot F + c of the 2F slots; slot s lives in pair s / 2, component s % 2
+                // column c: sum x = slot c, sum x^2 = slot F + c of the 2F slots; the eight chunks in wavefront order
                 auto slot_sum = [&](int sl) {
-                    const int pr = sl >> 1, cm = sl & 1;
-                    return ((sBn[(0 * 2 + cm) * 128 + pr] + sBn[(1 * 2 + cm) * 128 + pr]) + sBn[(2 * 2 + cm) * 128 + pr]) + sBn[(3 * 2 + cm) * 128 + pr];
+                    double s = sBn[sl];
+#pragma unroll
+                    for (int k = 1; k < 8; ++k) s += sBn[k * 2 * F + sl];
+                    return s;
                 };
                 const double sx = slot_sum(tid), sxx = slot_sum(F + tid);
                 const double m = sx / (double)N;
@@ -1181,6 +1188,7 @@ static int head_fused_launch(const float* H2, int ldh, int n_rows, int F, int C,
     ERC_REQUIRE(al16(H2) && al16(gamma) && al16(beta) && (!saved || al16(saved)) && al16(W0) && (!H3 || al16(H3)), "head_fused: 16-byte alignment");
     ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || rng_state), "head_fused: drop_p=%f", (double)drop_p);
     ERC_REQUIRE(!bn_part || (bn_tiles > 0 && saved_out && running_mean && running_var), "head_fused: BatchNorm partials operands");
+    ERC_REQUIRE(!bn_part || al16(bn_part), "head_fused: 16-byte alignment (bn_part: its records are loaded as float4)");
     HeadP p{};
     p.H2 = H2, p.gamma = gamma, p.beta = beta, p.saved = saved, p.W0 = W0, p.b0 = b0, p.W3 = W3, p.b3 = b3;
     p.labels = labels, p.weight = weight, p.rng = rng_state, p.H3 = H3, p.Z = Z, p.logits = logits, p.dlogits = dlogits;

@@ -430,6 +430,7 @@ int erc_head_fused(const float* H2, int ldh, int n_rows, int F, int C, const flo
 
 /* erc_head_fused with BatchNorm's batch statistics finalised inside (training mode of nn.BatchNorm1d, cogmen.py:67):
  * bn_part [bn_tiles][2F] floats = per-tile column sums (sum x | sum x^2) from erc_cogmen_fwd_tile (bn_fused = 2);
+ * 16-byte aligned (a record is loaded as 2F / 4 float4; refused otherwise); tiles at or beyond bn_tiles are never read;
  * every workgroup adds the tiles in order, workgroup 0 writes saved [2F] = mean | rstd (an OUTPUT here) and updates
  * running_mean / running_var (momentum, unbiased variance).  defer_reduce != 0: no last arriver -- bn_bwd, dgamma, dbeta and
  * stats are NOT written here; the consumer adds the workgroup records of ws itself (erc_cogmen_bwd_tile, head_part). */
@@ -549,7 +550,9 @@ int erc_cogmen_fwd_tile(const float* H0, int ldh0, int n_nodes, int wp, int wf, 
  * the operands of the weight gradients (cogmen.py:187-188).
  * head_part != NULL (with erc_head_fused_bn's defer_reduce): bn_bwd is an OUTPUT -- every workgroup adds the head
  * kernel's head_parts workgroup records (head_part_floats = erc_head_fused_part_floats() each) itself, in the same order,
- * and workgroup 0 writes bn_bwd, dgamma (= sum dY * xhat), dbeta (= sum dY) and stats {mean loss, #correct, weight sum}. */
+ * and workgroup 0 writes bn_bwd, dgamma (= sum dY * xhat), dbeta (= sum dY) and stats {mean loss, #correct, weight sum}.
+ * The records are loaded as float4: head_part 16-byte aligned and head_part_floats in [228, 256] a multiple of 4 (refused
+ * otherwise; erc_head_fused_part_floats() = 228); records at or beyond head_parts are never read. */
 int erc_cogmen_bwd_tile(const float* dY, const float* H2, int ldh2, int n_nodes, int wp, int wf, const float* gamma,
                         const float* saved, const float* bn_bwd, const float* QKVS, const float* alpha,
                         const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
