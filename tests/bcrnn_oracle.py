@@ -12,19 +12,20 @@ import torch.nn.functional as F
 MAX_T = 110
 
 
-def gru_scan(gx, W_hh, b_hh, eps=None):
+def gru_scan(gx, W_hh, b_hh, eps=None, ops=torch):
     """dialogues in scan order: gx [L, 300] or [L, n, 300] (n dialogues of the same length) = x W_ih^T + b_ih -> h [L, (n,) 100];
     torch.nn.GRU, gate order r|z|n, h0 = 0.  ``eps`` (zeros, shaped as gx) is added to the recurrent pre-activations
-    W_hh h + b_hh: its gradient is what the backward kernel calls dGH."""
+    W_hh h + b_hh: its gradient is what the backward kernel calls dGH.  ``ops`` supplies matmul, sigmoid and tanh
+    (tests/rnn_scan_ref.py passes ones whose float32 results do not depend on the machine's math libraries)."""
     h, out = gx.new_zeros(gx.shape[1:-1] + (W_hh.shape[1],)), []
     for s in range(gx.shape[0]):
-        gh = h @ W_hh.t() + b_hh
+        gh = ops.matmul(h, W_hh.t()) + b_hh
         if eps is not None:
             gh = gh + eps[s]
         ir, iz, inn = gx[s].chunk(3, -1)
         hr, hz, hn = gh.chunk(3, -1)
-        r, z = torch.sigmoid(ir + hr), torch.sigmoid(iz + hz)
-        n = torch.tanh(inn + r * hn)
+        r, z = ops.sigmoid(ir + hr), ops.sigmoid(iz + hz)
+        n = ops.tanh(inn + r * hn)
         h = (1 - z) * n + z * h
         out.append(h)
     return torch.stack(out)

@@ -20,6 +20,7 @@ import torch
 
 from erc_amd import capi
 from tests import bcrnn_oracle as O
+from tests.rnn_scan_ref import lstm_scan
 from tests.util_cases import fill_params
 
 pytestmark = pytest.mark.gpu
@@ -106,18 +107,6 @@ def test_scan_with_device_step_count_equals_the_exact_launch(cell, drop, t_dev):
             assert bool((got[k][:, 2 * H:] == STALE).all()), k      # nothing past the 200 columns
 
 
-def _lstm_scan(gx, W_hh, b_hh):
-    """float64 chain, scan order: gx [L, n, 400] -> h [L, n, 100]; torch.nn.LSTM, gate order i|f|g|o, h0 = c0 = 0"""
-    h = c = gx.new_zeros(gx.shape[1], W_hh.shape[1])
-    out = []
-    for s in range(gx.shape[0]):
-        i, f, g, o = (gx[s] + h @ W_hh.t() + b_hh).chunk(4, -1)
-        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-        h = torch.sigmoid(o) * torch.tanh(c)
-        out.append(h)
-    return torch.stack(out)
-
-
 @pytest.mark.parametrize("cell", CELLS)
 def test_scan_with_device_step_count_matches_the_float64_chain(cell):
     """*t_dev = 37 of T_cap = 110, B = 5, dropped copy on: outputs < 1e-5, gate gradients <= 1e-4 of the chain's largest entry
@@ -135,7 +124,7 @@ def test_scan_with_device_step_count_matches_the_float64_chain(cell):
         ix = rows if d == 0 else rows.flip(0)
         gx = G64[ix][..., d * G:(d + 1) * G]
         if cell == "lstm":
-            h = _lstm_scan(gx + eps[ix][..., d * G:(d + 1) * G], W64[d], b64[d])
+            h = lstm_scan(gx + eps[ix][..., d * G:(d + 1) * G], W64[d], b64[d])[0]
         else:
             h = O.gru_scan(gx, W64[d], b64[d], eps[ix][..., d * G:(d + 1) * G])
         halves.append(h if d == 0 else h.flip(0))
