@@ -63,7 +63,7 @@ struct W2Desc {  // 112 bytes; mirrored by engine.GemmPlanner.flush_wgrads_bf16 
 // parameter / moment buffers (same layout as the gradient), bf16 shadows included.  The update is spread over all work items,
 // the slab sums over S times as many threads, and the optimizer launch (9.8 us + a launch gap of a 96 us step) is gone.
 // Every workgroup keeps private copies of the step count (state[4 + b], as adam_kernel) and of the launch sequence number.
-struct W2Adam {
+struct W2AdamBase {
     int decoupled, spin_limit;     // spin_limit: bound of the wait for a tile's splits (test hook: erc_wgrad_bf16_set_spin_limit)
     float lr, b1, b2, eps, wd, grad_scale;
     float *data, *grad, *m, *v;
@@ -79,6 +79,14 @@ struct W2Adam {
     // item of every rank and continues with the RANK-ORDERED sum: bit-identical replicas, no RCCL call, no optimizer launch.
     int x_world, x_rank, x_spin;
     int wt;                // != 0: the finished gradient / parameter / moment quads leave as write-through stores (store_dev.h)
+};
+// the single-rank form of the bf16 launch: no exchange (x_world <= 1) -- its code (rendezvous, publish stores, rank-ordered sums) is
+// compiled out and the 16 peer pointers are not kernel arguments (on this kernel code size is time: see the update loop)
+struct W2AdamLocal : W2AdamBase {
+    static constexpr bool XCH = false;
+};
+struct W2Adam : W2AdamBase {      // (the layout this struct had before the single-rank form existed)
+    static constexpr bool XCH = true;
     float* x_pub[8];
     int32_t* x_flags[8];
     int64_t* x_epoch;      // [512] one exchange counter per work item (private to its workgroup)
@@ -109,11 +117,13 @@ __device__ __forceinline__ unsigned perm_hi(unsigned x, unsigned y) { return __b
 // of the record over the same k-steps -- they request the same A rows at about the same time, so the 256 B of an A row per
 // k reach the CU once instead of once per column tile (at N = 33 k the A operand, 6.6 MB per record, does not fit a 4 MB L2 and
 // was streamed through the fabric 22 times for the 22 column tiles of the projection gradient: 397 of the launch's 595 MB).
-template <bool ADAM, bool WIDE, int NT>
+template <bool ADAM, bool WIDE, int NT, class AD>
 __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float* red, float* bred, int* idx, int* s_flag,
-                                        float* slabs, int* counters, uint64_t* stamps_item, uint64_t* stamps_tile, const W2Adam& ad) {
+                                        float* slabs, int* counters, uint64_t* stamps_item, uint64_t* stamps_tile, const AD& ad) {
     uint64_t* stamps = stamps_item;
     W2_STAMP(0);
+    bool xch = false;      // (uniform) this launch exchanges gradients with its peers; AD = W2AdamLocal: never
+    if constexpr (AD::XCH) xch = ad.x_world > 1;
     // fused optimizer: the step's skip decision and this workgroup's private step count, requested before the K loop
     bool adam_on = false;
     int64_t adam_step = 0;
@@ -201,8 +211,13 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
     // ---- the exchange of one work item (see W2Adam): `publish` has stored this item's finished gradient elements into the publish
     //      buffer at poff + their flat offsets; returns false when any rank flagged its step invalid (or a peer never arrived)
     __shared__ int s_x_skip;
-    auto x_poff = [&]() __attribute__((always_inline)) -> int64_t { return (int64_t)((ad.x_epoch[blockIdx.x] + 1) & 1) * ad.x_npad; };
+    auto x_poff = [&]() __attribute__((always_inline)) -> int64_t {
+        if constexpr (AD::XCH) return (int64_t)((ad.x_epoch[blockIdx.x] + 1) & 1) * ad.x_npad;
+        else return 0;
+    };
     auto x_rendezvous = [&](const bool local_skip) __attribute__((always_inline)) -> bool {
+        if constexpr (!AD::XCH) return true;
+        else {
         const int b = blockIdx.x, nblk = gridDim.x;
         const int ep = (int)(ad.x_epoch[b] + 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's publish stores are out
@@ -232,9 +247,12 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
         __syncthreads();
         if (threadIdx.x == 0) ad.x_epoch[b] = ep;
         return s_x_skip == 0;
+        }
     };
     auto x_sum4 = [&](const int64_t poff_off) __attribute__((always_inline)) -> f32x4 {      // rank-ordered sum of one published quad
         f32x4 part[8];
+        if constexpr (!AD::XCH) return (f32x4){0.f, 0.f, 0.f, 0.f};
+        else {
 #pragma unroll
         for (int r = 0; r < 8; ++r) part[r] = r < ad.x_world ? ld_sc1_x4(ad.x_pub[r] + poff_off) : (f32x4){0.f, 0.f, 0.f, 0.f};
         asm volatile("s_waitcnt vmcnt(0)"
@@ -246,29 +264,38 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
         for (int r = 0; r < 8; ++r)
             if (r < ad.x_world) acc += part[r];
         return acc;
+        }
     };
     auto x_sum1 = [&](const int64_t poff_off) __attribute__((always_inline)) -> float {
         float acc = 0.f;
-        for (int r = 0; r < ad.x_world; ++r) {
-            const float* pb = nullptr;
+        if constexpr (AD::XCH) {
+            for (int r = 0; r < ad.x_world; ++r) {
+                const float* pb = nullptr;
 #pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (q == r) pb = ad.x_pub[q];
-            acc += __hip_atomic_load(pb + poff_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                for (int q = 0; q < 8; ++q)
+                    if (q == r) pb = ad.x_pub[q];
+                acc += __hip_atomic_load(pb + poff_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
         }
         return acc;
+    };
+    auto x_mypub = [&]() __attribute__((always_inline)) -> float* {      // this rank's publish buffer
+        float* mypub = nullptr;
+        if constexpr (AD::XCH) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r == ad.x_rank) mypub = ad.x_pub[r];
+        }
+        return mypub;
     };
     if (ADAM && d.kind == 1) {   // plain range of finished gradients: d.C[0, M)
         if (threadIdx.x == 64) copy_tab();
         __syncthreads();
         const int64_t base = d.C - ad.grad;
         int64_t xoff = 0;
-        if (ad.x_world > 1) {      // (uniform) exchange the range first: every element published, then summed in rank order
+        if (xch) {      // (uniform) exchange the range first: every element published, then summed in rank order
             xoff = x_poff() + base;
-            float* mypub = nullptr;
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-                if (r == ad.x_rank) mypub = ad.x_pub[r];
+            float* const mypub = x_mypub();
             for (int e = (int)threadIdx.x; e < d.M; e += 256) __hip_atomic_store(mypub + xoff + e, d.C[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             adam_on = x_rendezvous(!adam_on) && adam_on;
         }
@@ -280,7 +307,7 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
                     float4 pn[8];
                     const bool isq[8] = {true};
                     f32x4 gq = *(const ERC_GLOBAL f32x4*)(d.C + e);
-                    if (ad.x_world > 1) {
+                    if (xch) {
                         gq = x_sum4(xoff + e);
                         *(ERC_GLOBAL f32x4*)(d.C + e) = gq;
                     }
@@ -290,7 +317,7 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
                 } else {
                     for (int t = e; t < min(e + 4, d.M); ++t) {
                         float gv = d.C[t];
-                        if (ad.x_world > 1) d.C[t] = gv = x_sum1(xoff + t);
+                        if (xch) d.C[t] = gv = x_sum1(xoff + t);
                         adam_one(base + t, gv);
                     }
                 }
@@ -425,25 +452,26 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
                 }
             }
         };
-        // ring of four groups: a group's buffers are refilled (unconditionally: past the end the clamped rows are re-read and
-        // never multiplied) as soon as its products are issued
+        // ring of four groups: a group's buffers are refilled as soon as its products are issued -- if the next pass multiplies
+        // them (uniform: a refill nobody multiplies is 16 wave loads of a clamped row that the slab stores and the wait in front
+        // of the arrival ticket queue behind; at N = 1982, where a wavefront's 31 steps are one pass, that was all 64 of them)
         for (int s0 = 0; s0 < ns; s0 += 32) {
             __builtin_amdgcn_sched_barrier(0);
             mma_group(s0, ga0, gb0);
             __builtin_amdgcn_sched_barrier(0);
-            load_a(s0 + 32, ga0), load_b(s0 + 32, gb0);
+            if (s0 + 32 < ns) load_a(s0 + 32, ga0), load_b(s0 + 32, gb0);
             __builtin_amdgcn_sched_barrier(0);
             if (s0 + 8 < ns) mma_group(s0 + 8, ga1, gb1);     // (uniform)
             __builtin_amdgcn_sched_barrier(0);
-            load_a(s0 + 40, ga1), load_b(s0 + 40, gb1);
+            if (s0 + 40 < ns) load_a(s0 + 40, ga1), load_b(s0 + 40, gb1);
             __builtin_amdgcn_sched_barrier(0);
             if (s0 + 16 < ns) mma_group(s0 + 16, ga2, gb2);
             __builtin_amdgcn_sched_barrier(0);
-            load_a(s0 + 48, ga2), load_b(s0 + 48, gb2);
+            if (s0 + 48 < ns) load_a(s0 + 48, ga2), load_b(s0 + 48, gb2);
             __builtin_amdgcn_sched_barrier(0);
             if (s0 + 24 < ns) mma_group(s0 + 24, ga3, gb3);
             __builtin_amdgcn_sched_barrier(0);
-            load_a(s0 + 56, ga3), load_b(s0 + 56, gb3);
+            if (s0 + 56 < ns) load_a(s0 + 56, ga3), load_b(s0 + 56, gb3);
         }
     } else {
         // ---- split compute modes: A [K, lda] and B [K or gathered rows, ldb] are FP32 in memory (lda, ldb multiples of 4, 16-byte
@@ -728,7 +756,7 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
             }
             __syncthreads();
             W2_STAMP(5);
-            if (ad.x_world <= 1) bump_step();      // (every thread read the step count in front of the barriers; with the
+            if (!xch) bump_step();                 // (every thread read the step count in front of the barriers; with the
             if (!*s_flag) return;                  //  gradient exchange the count moves behind it: a peer may veto the step)
             stamps = stamps_tile ? stamps_tile : stamps;
             W2_STAMP(8);
@@ -767,12 +795,9 @@ __device__ __forceinline__ void w2_body(const W2Desc& d, const int local, float*
             float bsum = 0.f;      // bias strip element of this thread (split 0 of the tile)
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) bsum += bt[jj] * (jj < S ? 1.f : 0.f);
-            if (ad.x_world > 1) {      // (uniform) the gradient exchange of this work item: its owned quads + its bias strip elements
+            if (xch) {      // (uniform) the gradient exchange of this work item: its owned quads + its bias strip elements
                 const int64_t poff = x_poff();
-                float* mypub = nullptr;
-#pragma unroll
-                for (int r = 0; r < 8; ++r)
-                    if (r == ad.x_rank) mypub = ad.x_pub[r];
+                float* const mypub = x_mypub();
 #pragma unroll
                 for (int o = 0; o < 8; ++o)
                     if (o < owned && valid[o] == 4) st_out16<true>(mypub + poff + off[o], res[o]);
@@ -921,9 +946,9 @@ struct W2Bases {  // first work item of every descriptor, passed by value (no de
     int v[W2_MAX_DESC];
 };
 
-template <bool ADAM, bool WIDE, int NT>
+template <bool ADAM, bool WIDE, int NT, class AD>
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const W2Desc* __restrict__ table, const int n_desc, const W2Bases bases,
-                                                         float* slabs, int* counters, uint64_t* stamps, int stamp_item, const W2Adam ad) {
+                                                         float* slabs, int* counters, uint64_t* stamps, int stamp_item, int stamp_di, int stamp_local, const AD ad) {
     __shared__ __attribute__((aligned(16))) float red[4 * 4096];   // 64 KB: two reduction passes
     __shared__ float bred[4 * 192];
     __shared__ int idx[W2_IDX_CAP];
@@ -936,16 +961,21 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const W2Desc* __restric
     const W2Desc d = table[di];
     const int local = L - bases.v[di];      // (WIDE: a workgroup covers four column tiles -- item_base counts slabs, bases workgroups)
     if (local >= d.n_items) return;
-    // (stamp_item is a work item of record 0)
-    const bool st_item = stamps && L == stamp_item, st_tile = stamps && di == 0 && local / d.splits == stamp_item / d.splits;
-    w2_body<ADAM, WIDE, NT>(d, local, red, bred, idx, &s_flag, slabs, counters, st_item ? stamps : nullptr, st_tile ? stamps : nullptr, ad);
+    // the stamped work item is item `stamp_local` of record `stamp_di` (any item of the launch; found on the host, which holds the
+    // records' bases): it writes slots 0..7, the splits of its tile slots 8..13.  With stamps off this is one null test.
+    const bool st_item = stamps && L == stamp_item;
+    const bool st_tile = stamps && di == stamp_di && local / d.splits == stamp_local / d.splits;
+    // (slot 14: when work item 0 started, the reference for the dispatch spread -- bf16 forms only: in the split forms, which sit at
+    //  256 VGPRs, the extra test moved their spilled-SGPR counts)
+    if (NT == 1 && stamps && L == 0 && threadIdx.x == 0) stamps[14] = __builtin_amdgcn_s_memrealtime();
+    w2_body<ADAM, WIDE, NT, AD>(d, local, red, bred, idx, &s_flag, slabs, counters, st_item ? stamps : nullptr, st_tile ? stamps : nullptr, ad);
 }
 
 }  // namespace
 
 static uint64_t* g_w2_stamps = nullptr;
 static int g_w2_stamp_item = 0;
-// diagnostic: 16 x uint64 phase stamps (10 ns ticks) of work item `item` (a work item of record 0) of the following launches
+// diagnostic: 16 x uint64 phase stamps (10 ns ticks) of work item `item` (any work item; blockIdx.x) of the following launches
 extern "C" int erc_wgrad_bf16_set_stamps(uint64_t* stamps, int item) {
     g_w2_stamps = stamps, g_w2_stamp_item = item;
     return ERC_OK;
@@ -974,25 +1004,35 @@ static int w2_launch(int mode, const void* table, int n_desc, const int32_t* ite
                     "wgrad_bf16: item_base[%d] = %d", t, item_base[t]);
         bases.v[t] = item_base[t];
     }
+    int stamp_di = 0;      // the record of the stamped work item, and the item's index within it
+    for (int t = 1; t < n_desc; ++t)
+        if (g_w2_stamp_item >= item_base[t]) stamp_di = t;
+    const int stamp_local = g_w2_stamp_item - item_base[stamp_di];
     ERC_REQUIRE(terms >= 1 && terms <= 3 && (terms == 1 || mode != 2), "wgrad_split: terms = %d (1 .. 3; the wide form is bf16 only)", terms);
 #define W2_GO(ADAM_, NT_)                                                                                                              \
-    hipLaunchKernelGGL((wgrad_bf16_kernel<ADAM_, false, NT_>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, \
-                       n_desc, bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, ad)
+    hipLaunchKernelGGL((wgrad_bf16_kernel<ADAM_, false, NT_, W2Adam>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, \
+                       n_desc, bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, stamp_di, stamp_local, ad)
     if (terms == 2) {
         if (mode == 1) W2_GO(true, 2);
         else W2_GO(false, 2);
     } else if (terms == 3) {
         if (mode == 1) W2_GO(true, 3);
         else W2_GO(false, 3);
-    } else if (mode == 1)
-        hipLaunchKernelGGL((wgrad_bf16_kernel<true, false, 1>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, n_desc,
-                           bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, ad);
+    } else if (mode == 1 && ad.x_world > 1)
+        hipLaunchKernelGGL((wgrad_bf16_kernel<true, false, 1, W2Adam>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, n_desc,
+                           bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, stamp_di, stamp_local, ad);
+    else if (mode == 1) {      // single rank: the instance without the exchange
+        W2AdamLocal al;
+        static_cast<W2AdamBase&>(al) = ad;
+        hipLaunchKernelGGL((wgrad_bf16_kernel<true, false, 1, W2AdamLocal>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table,
+                           n_desc, bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, stamp_di, stamp_local, al);
+    }
     else if (mode == 2)
-        hipLaunchKernelGGL((wgrad_bf16_kernel<false, true, 1>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, n_desc,
-                           bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, ad);
+        hipLaunchKernelGGL((wgrad_bf16_kernel<false, true, 1, W2Adam>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, n_desc,
+                           bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, stamp_di, stamp_local, ad);
     else
-        hipLaunchKernelGGL((wgrad_bf16_kernel<false, false, 1>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, n_desc,
-                           bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, ad);
+        hipLaunchKernelGGL((wgrad_bf16_kernel<false, false, 1, W2Adam>), dim3(n_items), dim3(256), 0, (hipStream_t)stream, (const W2Desc*)table, n_desc,
+                           bases, slabs, counters, g_w2_stamps, g_w2_stamp_item, stamp_di, stamp_local, ad);
 #undef W2_GO
     ERC_LAUNCH_CHECK("wgrad_bf16");
     return ERC_OK;

@@ -180,8 +180,9 @@ int erc_wgrad_bf16_set_spin_limit(int limit);
 int erc_wgrad_bf16_wide(const void* table, int n_desc, const int32_t* wg_base, int n_wgs, float* slabs, int32_t* counters,
                         void* stream);
 int64_t erc_wgrad_bf16_slab_floats(void);
-/* diagnostic: phase stamps (10 ns ticks) of work item `item` (of record 0) of the following erc_wgrad_bf16 launches,
- * 16 x uint64 device memory; NULL switches them off (tools/wgrad_stamps.py) */
+/* diagnostic: phase stamps (10 ns ticks) of work item `item` (any work item of any record) of the following
+ * erc_wgrad_bf16 launches, 16 x uint64 device memory: slots 0..5 the item's own phases, 8..13 those of its tile behind the
+ * split-K hand-off, 14 the start of work item 0 (bf16 forms only); NULL switches them off (tools/wgrad_stamps.py) */
 int erc_wgrad_bf16_set_stamps(uint64_t* stamps, int item);
 int erc_wgrad_bf16_max_k_per_split(void);
 int erc_wgrad_max_k_per_split(void);
