@@ -1246,9 +1246,22 @@ def dialogrnn_scan_fwd(GX, ldgx, WT, params, offs, D_m, node_off, node_spk, B, T
 
 
 def dialogrnn_scan_bwd(GX, ldgx, WT, params, offs, D_m, node_off, node_spk, B, T, S, N, drop_p, drop_rec, rng, rng_stream, save,
-                       dEmo, ldde, dGX, lddgx, dREC):
-    _call("erc_dialogrnn_scan_bwd", GX, ldgx, WT, params, C.addressof(offs), D_m, node_off, node_spk, B, T, S, N, float(drop_p),
-          float(drop_rec), rng, rng_stream, save, dEmo, ldde, dGX, lddgx, dREC)
+                       dEmo, ldde, dGX, lddgx, dREC, n_dev=None):
+    """``n_dev`` (device int32): capacity form -- N is the capacity, rows [*n_dev, N) of dGX and dREC are written +0 (ercgraft.h)"""
+    args = (GX, ldgx, WT, params, C.addressof(offs), D_m, node_off, node_spk, B, T, S, N, float(drop_p), float(drop_rec), rng,
+            rng_stream, save, dEmo, ldde, dGX, lddgx, dREC)
+    if n_dev is None:
+        _call("erc_dialogrnn_scan_bwd", *args)
+    else:
+        _call("erc_dialogrnn_scan_bwd_cap", *args, n_dev)
+
+
+def dialogrnn_meta_cap(onehot, S, lengths, desc, store_speaker, store_label, zero_store_row, B, T, n_cap, node_off, node_row,
+                       node_spk, label_out, counts):
+    """index tables of a DialogueRNN step in capacity mode, bucket form (onehot + lengths) or resident form (desc + the store's
+    speaker ids and labels); counts = [n_dev, longest dialogue] (ercgraft.h)"""
+    _call("erc_dialogrnn_meta_cap", onehot, S, lengths, desc, store_speaker, store_label, zero_store_row, B, T, n_cap, node_off,
+          node_row, node_spk, label_out, counts)
 
 
 def bcrnn_meta_cap(lengths, desc, store_label, zero_store_row, B, T, n_cap, node_off, node_row, pad_node, x_row, label_out, counts):

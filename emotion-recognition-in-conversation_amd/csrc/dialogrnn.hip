@@ -57,6 +57,7 @@ struct DrnnP {
     const float* dEmo; int ldde;
     float* dGX; int lddgx;
     float* dREC;
+    const int32_t* n_dev;      // capacity form of the backward: the batch's node count (device); N is then the capacity
 };
 
 // which: 0 g, 1 q[p], 2 e, 3 emotions
@@ -262,7 +263,49 @@ __global__ __launch_bounds__(NT) void drnn_fwd_kernel(DrnnP p) {
 
 constexpr int BWD_LDS_FLOATS = 2 * MAXT * DG + 1352 + 304 + 304 + 4 * 452 + 1800 + 152 + 152 + 112 + 112 + 112;   // 157 KB
 
+// +0 over n floats at p (4-byte aligned), by thread t of nt: single floats up to the first 16-byte boundary and behind the
+// last, 16-byte stores between
+__device__ __forceinline__ void zero_range(float* p, int64_t n, int64_t t, int64_t nt) {
+    const int64_t head = min(n, (int64_t)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2));
+    const int64_t n4 = (n - head) >> 2;
+    if (t < head) p[t] = 0.f;
+    float4* q = reinterpret_cast<float4*>(p + head);
+    for (int64_t i = t; i < n4; i += nt) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t done = head + 4 * n4;
+    if (t < n - done) p[done + t] = 0.f;
+}
+
+constexpr int TAIL_WG = 16;            // the capacity form's tails are owned by this many workgroups, whatever B is
+
+// +0 to the rows [*n_dev, N) of dGX (columns [0, 2100)) and of the four dREC planes of both directions: one contiguous range per
+// (plane, direction), dGX too when its pitch is 2100.  Thread t of nt.
+__device__ __forceinline__ void drnn_zero_tails(float* dGX, int lddgx, float* dREC, int64_t N, const int32_t* n_dev, int64_t t,
+                                                int64_t nt) {
+    const int64_t n = min(max((int64_t)n_dev[0], (int64_t)0), N), rows = N - n;
+    if (rows <= 0) return;
+    constexpr int DR_OFF[4] = {DR_GH_G, DR_GH_P, DR_GI_E, DR_GH_E}, DR_W[4] = {G3, G3, E3, E3};
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) zero_range(plane(dREC, DR_OFF[f], DR_W[f], N, d, n), rows * DR_W[f], t, nt);
+    if (lddgx == 2 * GXW) {
+        zero_range(dGX + n * lddgx, rows * 2 * GXW, t, nt);
+    } else {
+        for (int64_t r = n; r < N; ++r) zero_range(dGX + r * lddgx, 2 * GXW, t, nt);
+    }
+}
+
+// CAP (erc_dialogrnn_scan_bwd_cap): p.N is the capacity, *p.n_dev the batch's node count.  The grid is B x (2 + k), k =
+// ceil(TAIL_WG / B): of the workgroups blockIdx.y >= 2 the first TAIL_WG own the tails (drnn_zero_tails) and the others (B - 16 of
+// them where B > 16: a grid is a product) end at their first branch; the B x 2 scanning workgroups run the code of the exact
+// form (the test on blockIdx.y reads no kernel argument: this form compiles to the exact form's registers and scratch).
+template <bool CAP>
 __global__ __launch_bounds__(NT) void drnn_bwd_kernel(DrnnP p) {
+    if (CAP && blockIdx.y >= 2) {
+        const int w = (blockIdx.y - 2) * gridDim.x + blockIdx.x;
+        if (w < TAIL_WG) drnn_zero_tails(p.dGX, p.lddgx, p.dREC, p.N, p.n_dev, (int64_t)w * NT + threadIdx.x, (int64_t)TAIL_WG * NT);
+        return;
+    }
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* dHist = sm;                 // [MAXT][DG]  gradient wrt g'_j
     float* hist = dHist + MAXT * DG;   // [MAXT][DG]  g'_j (scan order), read back from the forward's save
@@ -508,6 +551,62 @@ __global__ void drnn_meta_kernel(const float* onehot, int S, const int64_t* leng
     }
 }
 
+// DialogueRNN in capacity mode (dialogrnn.py): the tables of drnn_meta_kernel for a step whose launches are sized for (B, T, n_cap)
+// while the batch's own counts live on the device.  lengths [B] (int64) + onehot [T, B, S], or desc [2 B] (int32: lengths | first
+// store rows; RESIDENT) + the store's speaker ids and labels [zero_store_row].  The rows are compact, so nothing but the capacity
+// rows i >= n needs a filler: node_row 0 (a row of the static block) or zero_store_row, speaker 0, label 0.
+__global__ void drnn_meta_cap_kernel(const float* onehot, int S, const int64_t* lengths, const int32_t* desc,
+                                     const int64_t* store_speaker, const int64_t* store_label, int zero_store_row, int B, int T,
+                                     int n_cap, int32_t* node_off, int32_t* node_row, int32_t* node_spk, int64_t* label_out,
+                                     int32_t* counts) {
+    __shared__ int s_off[1025];
+    if (threadIdx.x == 0) {
+        int acc = 0, tmax = 0;
+        for (int b = 0; b < B; ++b) {
+            s_off[b] = acc;
+            const int L = (int)min(max(desc ? (int64_t)desc[b] : lengths[b], (int64_t)0), (int64_t)T);
+            const int Lc = min(L, n_cap - acc);       // never past the capacity (the host sizes n_cap >= sum(lengths))
+            acc += Lc;
+            tmax = max(tmax, Lc);
+        }
+        s_off[B] = acc;
+        counts[0] = acc;       // n_dev
+        counts[1] = tmax;      // the longest dialogue
+    }
+    __syncthreads();
+    const int n = s_off[B];
+    for (int b = threadIdx.x; b <= B; b += blockDim.x) node_off[b] = s_off[b];
+    for (int i = threadIdx.x; i < n_cap; i += blockDim.x) {
+        int row = desc ? zero_store_row : 0, spk = 0;
+        int64_t lab = 0;
+        if (i < n) {
+            int lo = 0, hi = B;                       // the dialogue of node i: the first b with s_off[b + 1] > i
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_off[mid + 1] <= i) lo = mid + 1; else hi = mid;
+            }
+            const int b = min(lo, B - 1), t = i - s_off[b];
+            if (desc) {
+                const int64_t r = (int64_t)desc[B + b] + t;
+                if (r >= 0 && r < zero_store_row) {   // a row outside the store reads the zero row, speaker 0, label 0
+                    row = (int)r;
+                    spk = (int)min(max(store_speaker[r], (int64_t)0), (int64_t)(S - 1));
+                    if (store_label) lab = store_label[r];
+                }
+            } else {
+                const float* r = onehot + ((int64_t)t * B + b) * S;
+                int best = 0;
+                for (int k = 1; k < S; ++k)
+                    if (r[k] > r[best]) best = k;
+                row = t * B + b, spk = best;
+            }
+        }
+        node_row[i] = row;
+        node_spk[i] = spk;
+        if (label_out) label_out[i] = lab;
+    }
+}
+
 // bc-LSTM / bc-GRU in capacity mode (bcrnn.py): the index tables of a step whose launches are sized for (B, T, n_cap) while the
 // batch's own counts live on the device.  lengths [B] (int64) or desc [2 B] (int32: lengths | first store rows; RESIDENT).
 __global__ void bcrnn_meta_kernel(const int64_t* lengths, const int32_t* desc, const int64_t* store_label, int zero_store_row,
@@ -641,30 +740,74 @@ extern "C" int erc_dialogrnn_scan_fwd(const float* GX, int ldgx, const float* WT
     return ERC_OK;
 }
 
+namespace {
+
+// both forms of the backward scan: n_dev == nullptr is the exact one (grid B x 2), else the grid has ceil(TAIL_WG / B) more rows of B
+// workgroups, of which TAIL_WG own the tails
+int scan_bwd_launch(const char* what, const float* GX, int ldgx, const float* WT, const float* params, const int64_t* offs_host,
+                    int D_m, const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N, float drop_p,
+                    float drop_rec, const uint64_t* rng_state, uint64_t rng_stream, const float* save, const float* dEmo, int ldde,
+                    float* dGX, int lddgx, float* dREC, const int32_t* n_dev, void* stream) {
+    ERC_REQUIRE(GX && WT && params && offs_host && node_off && node_spk && save && dEmo && dGX && dREC, "%s: null pointer", what);
+    ERC_REQUIRE(B > 0 && T > 0 && N > 0 && D_m > 0, "%s: bad sizes B=%d T=%d N=%lld D_m=%d", what, B, T, (long long)N, D_m);
+    ERC_REQUIRE(T <= MAXT, "%s: dialogues of up to %d utterances (batch T=%d)", what, MAXT, T);
+    ERC_REQUIRE(S >= 1 && S <= MAXS, "%s: n_speakers=%d (1..%d are built)", what, S, MAXS);
+    ERC_REQUIRE(ldgx >= 2 * GXW && lddgx >= 2 * GXW && ldde >= 2 * DE, "%s: row pitches ldgx=%d lddgx=%d ldde=%d", what, ldgx, lddgx,
+                ldde);
+    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f && drop_rec >= 0.f && drop_rec < 1.f, "%s: drop_p %f / %f", what, drop_p, drop_rec);
+    ERC_REQUIRE(!(drop_p > 0.f || drop_rec > 0.f) || rng_state, "%s: dropout needs rng_state", what);
+    ERC_REQUIRE(dGX != GX, "%s: dGX must not alias GX", what);
+    DrnnP p{};
+    p.GX = GX; p.ldgx = ldgx; p.WT = WT; p.params = params; p.Dm = D_m; p.node_off = node_off; p.node_spk = node_spk;
+    p.B = B; p.T = T; p.S = S; p.N = N; p.drop_p = drop_p; p.drop_rec = drop_rec; p.rng = rng_state; p.rng_stream = rng_stream;
+    p.save = const_cast<float*>(save); p.dEmo = dEmo; p.ldde = ldde; p.dGX = dGX; p.lddgx = lddgx; p.dREC = dREC; p.n_dev = n_dev;
+    ERC_REQUIRE(fill_offsets(p, offs_host), "%s: negative parameter offset", what);
+    const int64_t bytes = (int64_t)BWD_LDS_FLOATS * 4;
+    const void* kernel = n_dev ? (const void*)drnn_bwd_kernel<true> : (const void*)drnn_bwd_kernel<false>;
+    ERC_REQUIRE(set_lds(kernel, bytes), "%s: %lld bytes of LDS refused", what, (long long)bytes);
+    if (n_dev)
+        hipLaunchKernelGGL(drnn_bwd_kernel<true>, dim3(B, 2 + erc_cdiv(TAIL_WG, B)), dim3(NT), bytes, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(drnn_bwd_kernel<false>, dim3(B, 2), dim3(NT), bytes, (hipStream_t)stream, p);
+    ERC_LAUNCH_CHECK(what);
+    return ERC_OK;
+}
+
+}  // namespace
+
 extern "C" int erc_dialogrnn_scan_bwd(const float* GX, int ldgx, const float* WT, const float* params, const int64_t* offs_host, int D_m,
                                       const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N,
                                       float drop_p, float drop_rec, const uint64_t* rng_state, uint64_t rng_stream,
                                       const float* save, const float* dEmo, int ldde, float* dGX, int lddgx, float* dREC,
                                       void* stream) {
-    ERC_REQUIRE(GX && WT && params && offs_host && node_off && node_spk && save && dEmo && dGX && dREC, "dialogrnn_scan_bwd: null pointer");
-    ERC_REQUIRE(B > 0 && T > 0 && N > 0 && D_m > 0, "dialogrnn_scan_bwd: bad sizes B=%d T=%d N=%lld D_m=%d", B, T, (long long)N, D_m);
-    ERC_REQUIRE(T <= MAXT, "dialogrnn_scan_bwd: dialogues of up to %d utterances (batch T=%d)", MAXT, T);
-    ERC_REQUIRE(S >= 1 && S <= MAXS, "dialogrnn_scan_bwd: n_speakers=%d (1..%d are built)", S, MAXS);
-    ERC_REQUIRE(ldgx >= 2 * GXW && lddgx >= 2 * GXW && ldde >= 2 * DE, "dialogrnn_scan_bwd: row pitches ldgx=%d lddgx=%d ldde=%d", ldgx,
-                lddgx, ldde);
-    ERC_REQUIRE(drop_p >= 0.f && drop_p < 1.f && drop_rec >= 0.f && drop_rec < 1.f, "dialogrnn_scan_bwd: drop_p %f / %f", drop_p,
-                drop_rec);
-    ERC_REQUIRE(!(drop_p > 0.f || drop_rec > 0.f) || rng_state, "dialogrnn_scan_bwd: dropout needs rng_state");
-    ERC_REQUIRE(dGX != GX, "dialogrnn_scan_bwd: dGX must not alias GX");
-    DrnnP p{};
-    p.GX = GX; p.ldgx = ldgx; p.WT = WT; p.params = params; p.Dm = D_m; p.node_off = node_off; p.node_spk = node_spk;
-    p.B = B; p.T = T; p.S = S; p.N = N; p.drop_p = drop_p; p.drop_rec = drop_rec; p.rng = rng_state; p.rng_stream = rng_stream;
-    p.save = const_cast<float*>(save); p.dEmo = dEmo; p.ldde = ldde; p.dGX = dGX; p.lddgx = lddgx; p.dREC = dREC;
-    ERC_REQUIRE(fill_offsets(p, offs_host), "dialogrnn_scan_bwd: negative parameter offset");
-    const int64_t bytes = (int64_t)BWD_LDS_FLOATS * 4;
-    ERC_REQUIRE(set_lds((const void*)drnn_bwd_kernel, bytes), "dialogrnn_scan_bwd: %lld bytes of LDS refused", (long long)bytes);
-    hipLaunchKernelGGL(drnn_bwd_kernel, dim3(B, 2), dim3(NT), bytes, (hipStream_t)stream, p);
-    ERC_LAUNCH_CHECK("dialogrnn_scan_bwd");
+    return scan_bwd_launch("dialogrnn_scan_bwd", GX, ldgx, WT, params, offs_host, D_m, node_off, node_spk, B, T, S, N, drop_p, drop_rec,
+                           rng_state, rng_stream, save, dEmo, ldde, dGX, lddgx, dREC, nullptr, stream);
+}
+
+extern "C" int erc_dialogrnn_scan_bwd_cap(const float* GX, int ldgx, const float* WT, const float* params, const int64_t* offs_host,
+                                          int D_m, const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N,
+                                          float drop_p, float drop_rec, const uint64_t* rng_state, uint64_t rng_stream,
+                                          const float* save, const float* dEmo, int ldde, float* dGX, int lddgx, float* dREC,
+                                          const int32_t* n_dev, void* stream) {
+    ERC_REQUIRE(n_dev, "dialogrnn_scan_bwd_cap: null n_dev");
+    return scan_bwd_launch("dialogrnn_scan_bwd_cap", GX, ldgx, WT, params, offs_host, D_m, node_off, node_spk, B, T, S, N, drop_p,
+                           drop_rec, rng_state, rng_stream, save, dEmo, ldde, dGX, lddgx, dREC, n_dev, stream);
+}
+
+extern "C" int erc_dialogrnn_meta_cap(const float* onehot, int S, const int64_t* lengths, const int32_t* desc,
+                                      const int64_t* store_speaker, const int64_t* store_label, int zero_store_row, int B, int T,
+                                      int n_cap, int32_t* node_off, int32_t* node_row, int32_t* node_spk, int64_t* label_out,
+                                      int32_t* counts, void* stream) {
+    ERC_REQUIRE(node_off && node_row && node_spk && counts, "dialogrnn_meta_cap: null pointer");
+    ERC_REQUIRE((lengths && onehot && !desc) || (desc && store_speaker && !lengths && !onehot),
+                "dialogrnn_meta_cap: lengths + onehot (bucket form) or desc + store_speaker (resident form)");
+    ERC_REQUIRE(!store_label || (desc && label_out), "dialogrnn_meta_cap: store_label needs desc and label_out");
+    ERC_REQUIRE(!desc || zero_store_row >= 0, "dialogrnn_meta_cap: zero_store_row=%d", zero_store_row);
+    ERC_REQUIRE(B > 0 && B <= 1024 && T > 0 && S > 0 && n_cap > 0, "dialogrnn_meta_cap: bad sizes B=%d T=%d S=%d n_cap=%d", B, T, S,
+                n_cap);
+    hipLaunchKernelGGL(drnn_meta_cap_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, onehot, S, lengths, desc, store_speaker,
+                       store_label, zero_store_row, B, T, n_cap, node_off, node_row, node_spk, label_out, counts);
+    ERC_LAUNCH_CHECK("dialogrnn_meta_cap");
     return ERC_OK;
 }
 

@@ -212,7 +212,7 @@ class StepGraphs:
     """Captured HIP graphs of the whole training step, least-recently-used eviction.
 
     * CAPACITY BUCKETS (trainers with capacity.CapacityBuckets: COGMEN in the bf16 compute mode, DialogueGCN on its default
-      path, bc-LSTM / bc-GRU and DAG-ERC with ``--capacity_buckets=True`` or ``--resident``).  The reference reshuffles
+      path, bc-LSTM / bc-GRU, DialogueRNN and DAG-ERC with ``--capacity_buckets=True`` or ``--resident``).  The reference reshuffles
       the dialogues every epoch and its last batch is smaller (lumo/trainer/trainer.py:429-442, mmbase.py:468), so (B, T, N)
       almost never repeats.  A bucket is a set of static capacity-sized input buffers -- ``batch_size`` dialogues (missing
       ones get length 0), the longest training dialogue of every rank, N rounded up to the trainer's N_BUCKET (COGMEN 256,
@@ -412,7 +412,8 @@ class ResidentEpochs(ResidentLoop):
     descriptor buffer and replays the bucket's captured graph -- the projection launch reads feature rows, speakers and labels
     straight from the store (csrc/cogmen_project.hip, resident mode).  Host work per step: one 256-byte device copy + one
     graph launch.  Trainers with ``resident_batch``: COGMEN, DialogueGCN, bc-LSTM / bc-GRU (their layer-0 input projection
-    reads the store through the row map of erc_bcrnn_meta_cap), DAG-ERC (the row map of erc_dag_meta_cap)."""
+    reads the store through the row map of erc_bcrnn_meta_cap), DialogueRNN (its hoisted products gather the store's rows
+    through node_row of erc_dialogrnn_meta_cap), DAG-ERC (the row map of erc_dag_meta_cap)."""
 
     def __init__(self, trainer, store, batch_size, seed, capture=True):
         super().__init__(trainer, store, batch_size, capture)

@@ -1495,6 +1495,42 @@ int erc_dialogrnn_scan_bwd(const float* GX, int ldgx, const float* WT, const flo
                            const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N, float drop_p,
                            float drop_rec, const uint64_t* rng_state, uint64_t rng_stream, const float* save,
                            const float* dEmo, int ldde, float* dGX, int lddgx, float* dREC, void* stream);
+/* DialogueRNN in CAPACITY mode: one captured step per bucket (B dialogue slots -- missing ones: length 0 --, T = T_cap, n_cap
+ * nodes) serves every batch the reshuffling loader draws (lumo/trainer/trainer.py:429-442, mmbase.py:468), the batch's node
+ * count n living on the device.
+ *
+ * erc_dialogrnn_meta_cap (the tables erc_dialogrnn_meta derives from qmask / umask, dgcnv2_models.py:275 and :445-457, plus the
+ * counts): one launch, one workgroup, B <= 1024.  Bucket form: lengths [B] (int64) + onehot [T, B, S] (fp32), desc =
+ * store_speaker = store_label = label_out = NULL.  Resident form: desc [2 B] (int32: lengths | first store rows) +
+ * store_speaker [U] (int64 ids) + store_label [U] (or NULL) with zero_store_row = U, lengths = onehot = NULL.
+ *   node_off [B+1]  prefix sums of the lengths clamped to [0, T] and to the capacity that is left: nothing is written at or
+ *                   past n_cap
+ *   node_row [n_cap]  t*B + b of node node_off[b] + t (bucket form) or its store row desc[B + b] + t (resident form)
+ *   node_spk [n_cap]  first index of the one-hot maximum (erc_dialogrnn_meta's rule) or the store's id clamped to [0, S)
+ *   label_out [n_cap] (resident form)  store_label of the node's store row
+ *   counts [2] = {n = node_off[B], the longest dialogue}
+ * On rows < n node_off / node_row / node_spk are bit-equal to erc_dialogrnn_meta's for the same batch.  Capacity rows i in
+ * [n, n_cap): node_row 0 (a row inside the static block) or zero_store_row, node_spk 0, label 0; a store row outside [0, U)
+ * is treated like them.
+ *
+ * The forward needs no capacity entry point: erc_dialogrnn_scan_fwd takes B = the slots (a slot of length 0 runs no step; the
+ * extents come from node_off on the device), T and N are only the strides of alpha and of the planes, and the dropout masks are
+ * keyed by the compact row, not by B, T or N: rows < n are bit-equal to the exact-size launch from the same rng_state.
+ *
+ * erc_dialogrnn_scan_bwd_cap: erc_dialogrnn_scan_bwd with N = n_cap (the plane stride) and n_dev (device int32, clamped to
+ * [0, n_cap]; the caller passes node_off[B], counts[0] above).  Rows < *n_dev of dGX and dREC are bit-identical to
+ * erc_dialogrnn_scan_bwd called with the same strides (the B x 2 scanning workgroups run the same code); rows [*n_dev, n_cap)
+ * are written +0 -- columns [0, 2100) of dGX and both directions of dgh_g, dgh_p, dgi_e, dgh_e -- in the same launch by 16 more
+ * workgroups whatever B is (the grid gets ceil(16 / B) more rows of B; the surplus ends at once), one contiguous range per (plane, direction) in 16-byte stores between its aligned ends, so that the caller's
+ * weight-gradient products may run over all n_cap rows whatever an earlier batch left in the saved states. */
+int erc_dialogrnn_meta_cap(const float* onehot, int S, const int64_t* lengths, const int32_t* desc, const int64_t* store_speaker,
+                           const int64_t* store_label, int zero_store_row, int B, int T, int n_cap, int32_t* node_off,
+                           int32_t* node_row, int32_t* node_spk, int64_t* label_out, int32_t* counts, void* stream);
+int erc_dialogrnn_scan_bwd_cap(const float* GX, int ldgx, const float* WT, const float* params, const int64_t* offs_host, int D_m,
+                               const int32_t* node_off, const int32_t* node_spk, int B, int T, int S, int64_t N, float drop_p,
+                               float drop_rec, const uint64_t* rng_state, uint64_t rng_stream, const float* save,
+                               const float* dEmo, int ldde, float* dGX, int lddgx, float* dREC, const int32_t* n_dev,
+                               void* stream);
 /* bc-LSTM / bc-GRU (LSTMModel / GRUModel, dgcnv2_models.py:389-425 / :350-386) in CAPACITY mode: the index tables of a step
  * whose launches are sized for B dialogue slots (missing ones: length 0), T = T_cap and n_cap nodes, from lengths [B] (int64)
  * or, RESIDENT, from desc [2 B] (int32: lengths | first store rows).  Rows are time-major (t*B + b, batch_first=False).

@@ -18,6 +18,9 @@ class DialogRNNParams(ERCParams):
         self.loss_weights = True                                                  # dgcnv2.py:42
         self.speaker_onehot, self.batch_first = True, False                       # dgcnv2.py:43-44
         self.dropout_rec, self.dropout = 0.5, 0.5                                 # dgcnv2_models.py:430-431
+        # capacity buckets (one captured graph per padded (B, T, N) bucket instead of per exact shape) are opt-in here:
+        # --capacity_buckets=True, or --resident (with --device_collate), which implies them; --resident_eval with --resident
+        self.capacity_buckets = False
 
 
 ParamsType = DialogRNNParams
