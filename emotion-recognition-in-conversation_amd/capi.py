@@ -1316,3 +1316,70 @@ def chain_run(chain):
 
 def chain_free(chain):
     _check(lib().erc_chain_free(chain), "erc_chain_free")
+
+
+# --------------------------------------------------------------------------- MMIN base model (csrc/lstm128.hip, textcnn.hip, ema.hip)
+class ErcLstm128Job(C.Structure):
+    """host mirror of ErcLstm128Job (ercgraft.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("GX", "W_hh", "b_hh", "pool", "arg", "gates", "Cst", "Hprev", "dpool", "dGX")] + \
+               [(n, C.c_int32) for n in ("B", "T", "ldp", "lddp")]
+
+
+def lstm128_hidden():
+    return int(lib().erc_lstm128_hidden())
+
+
+def lstm128_max_jobs():
+    return int(lib().erc_lstm128_max_jobs())
+
+
+def lstm128_jobs(jobs):
+    """ErcLstm128Job array of ``jobs``: dicts of the struct's fields, tensors (on the GPU) or None for the pointers"""
+    arr = (ErcLstm128Job * max(1, len(jobs)))()
+    for dst, job in zip(arr, jobs):
+        for name, ctype in ErcLstm128Job._fields_:
+            v = job.get(name)
+            if isinstance(v, torch.Tensor):
+                if not v.is_cuda:
+                    raise ErcGraftError("lstm128 job: %s must live on the GPU (got a %s tensor)" % (name, v.device))
+                v = v.data_ptr()
+            setattr(dst, name, v if ctype is C.c_void_p else int(v or 0))
+    return arr
+
+
+def lstm128_pool_fwd(jobs, n_jobs=None):
+    """``jobs``: a list of job dicts, or the array lstm128_jobs made of one (a step keeps it: nothing is rebuilt per launch)"""
+    arr = jobs if isinstance(jobs, C.Array) else lstm128_jobs(jobs)
+    _call("erc_lstm128_pool_fwd", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs)
+
+
+def lstm128_pool_bwd(jobs, n_jobs=None):
+    arr = jobs if isinstance(jobs, C.Array) else lstm128_jobs(jobs)
+    _call("erc_lstm128_pool_bwd", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs)
+
+
+def textcnn_min_t():
+    return int(lib().erc_textcnn_min_t())
+
+
+def textcnn_channels():
+    return int(lib().erc_textcnn_channels())
+
+
+def textcnn_conv_floats(B, T):
+    return int(lib().erc_textcnn_conv_floats(B, T))
+
+
+def textcnn_pool_fwd(x, B, T, D, Ws, bs, conv, pooled, ldp, arg):
+    """``Ws`` / ``bs``: the weights [128, k*D] and biases [128] of k = 3, 4, 5; ``conv``: textcnn_conv_floats(B, T) of scratch"""
+    if conv.numel() < textcnn_conv_floats(B, T):
+        raise ErcGraftError("textcnn_pool_fwd: conv holds %d floats, B=%d T=%d needs %d" % (conv.numel(), B, T, textcnn_conv_floats(B, T)))
+    _call("erc_textcnn_pool_fwd", x, B, T, D, *Ws, *bs, conv, pooled, ldp, arg)
+
+
+def textcnn_pool_bwd(x, B, T, D, pooled, ldp, arg, dpooled, lddp, dWs, dbs):
+    _call("erc_textcnn_pool_bwd", x, B, T, D, pooled, ldp, arg, dpooled, lddp, *dWs, *dbs)
+
+
+def ema_step(ema, p, n, alpha):
+    _call("erc_ema_step", ema, p, n, alpha)

@@ -1,0 +1,472 @@
+"""MMIN's full-modality base model on the MI355X hot path (drop-in for MMINBaseModule, track_mm/mmin_models.py:202-240, and the
+trainer of track_mm/mmin_base.py): an utterance classifier over three encoders -- a hidden-128 LSTM with a max-pool over time
+for the audio frames and one for the visual frames (LSTMEncoder 'maxpool', :43-95), a text CNN over the BERT token rows
+(TextCNN, :8-40) -- and a three-layer classifier over their concatenation (Classifier, :98-130).  ``mmin_miss`` / ``mmin_miss2``
+(not built) start from this model's checkpoint and reuse its encoders through ``encode``.
+
+``MMINBaseModule`` keeps the reference's constructor signature, its ``state_dict`` key for key and shape for shape (22 tensors,
+2 063 620 parameters at 342 / 1024 / 130 / 4, all live) and ``forward(**batch) -> (logits [B, C], feat [B, 128])``.  Built: fp32,
+all three modalities, text of at least erc_textcnn_min_t() = 5 tokens; anything else raises ``ErcGraftError`` naming the argument.
+
+Batches are batch-first: audio [B, Ta, 130] zero-padded to the batch's longest utterance (the LSTM runs over ALL padded steps
+and they take part in the maximum, as in the reference, which packs nothing), visual [B, 50, 342], text [B, 22, 1024].
+
+Launches of a training step:
+  forward   GX_a = x_a W_ih^T + b (GEMM) | GX_v (GEMM) | erc_lstm128_pool_fwd (both encoders, one launch) -> fused[:, 0:256]
+            erc_textcnn_pool_fwd (3 GEMMs over overlapping rows, K cut in 8, + pool) | erc_dropout_fwd 0.5 | embd GEMM + ReLU -> fused[:, 256:384]
+            netC.module.0 GEMM + ReLU + dropout 0.3 | netC.module.3 likewise -> feat | fc_out GEMM | erc_cross_entropy
+  backward  3 GEMMs with the ReLU / dropout mask in the epilogue down to dfused | the text slice's GEMM (ReLU mask) | dpooled GEMM
+            | erc_dropout_fwd on the gradient (same mask) | erc_textcnn_pool_bwd | erc_lstm128_pool_bwd (one launch)
+            | erc_wgrad_table: every Linear / LSTM weight gradient and bias sum, one launch
+  update    erc_adam_step | erc_ema_step
+"""
+import json
+import os
+import time
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import capi
+from .engine import FlatParams, FusedAdam, GemmPlanner, WorkspaceCache, linear_fwd, linear_wgrad
+
+HID, EMB = 128, 384
+AUDIO_DIM, VISUAL_DIM, TEXT_DIM = 130, 342, 1024     # mmin_base.py:86-91: constants of the trainer
+STREAM_TEXT = 0x7E770                                  # dropout stream of the pooled text (erc_dropout_fwd)
+SALT_C0, SALT_C1 = 0xC0 << 32, 0xC1 << 32             # seeds of the two classifier dropouts (the GEMM epilogue has no stream)
+EMA_ALPHA = 0.999                                      # mmin_base.py:99
+
+
+# parameter holders with the reference's attribute names (state_dict keys); the math is in libercgraft
+class _TextCNN(nn.Module):
+    def __init__(self, input_dim):
+        super().__init__()
+        self.conv1 = nn.Conv2d(1, HID, (3, input_dim))
+        self.conv2 = nn.Conv2d(1, HID, (4, input_dim))
+        self.conv3 = nn.Conv2d(1, HID, (5, input_dim))
+        self.embd = nn.Sequential(nn.Linear(3 * HID, HID), nn.ReLU(inplace=True))
+
+
+class _LSTMEncoder(nn.Module):
+    def __init__(self, input_size):
+        super().__init__()
+        self.rnn = nn.LSTM(input_size, HID, batch_first=True)
+
+
+class _Classifier(nn.Module):
+    def __init__(self, input_dim, n_classes):
+        super().__init__()
+        # creation order of the reference (the hidden layers, then fc_out), registration order of its state_dict (fc_out first)
+        layers = [nn.Linear(input_dim, HID), nn.ReLU(), nn.Dropout(0.3), nn.Linear(HID, HID), nn.ReLU(), nn.Dropout(0.3)]
+        self.fc_out = nn.Linear(HID, n_classes)
+        self.module = nn.Sequential(*layers)
+
+
+class MMINBaseModule(nn.Module):
+    DROP_TEXT, DROP_C = 0.5, 0.3
+
+    def __init__(self, visual_dim=0, text_dim=0, audio_dim=0, n_classes=4, compute="f32", seed=1):
+        super().__init__()
+        if compute != "f32":
+            raise capi.ErcGraftError("mmin_base runs in fp32 only (the reference is fp32); compute=%r is not supported" % (compute, ))
+        for name, d in (("visual_dim", visual_dim), ("text_dim", text_dim), ("audio_dim", audio_dim)):
+            if int(d) < 1:
+                raise capi.ErcGraftError("mmin_base: %s=%r: the classifier reads all three encoders (its input is %d wide)" % (name, d, EMB))
+        if int(n_classes) < 2:
+            raise capi.ErcGraftError("mmin_base: n_classes=%r" % (n_classes, ))
+        self.visual_dim, self.text_dim, self.audio_dim = int(visual_dim), int(text_dim), int(audio_dim)
+        self.n_classes, self.compute = int(n_classes), compute
+        self.netL = _TextCNN(self.text_dim)
+        self.netA = _LSTMEncoder(self.audio_dim)
+        self.netV = _LSTMEncoder(self.visual_dim)
+        self.netC = _Classifier(EMB, self.n_classes)
+        self.flat, self._ws, self._seed = None, WorkspaceCache(), seed
+
+    # ------------------------------------------------------------------------------------------------------------ set-up
+    def finalize(self, device):
+        self.to(device)
+        self.flat = FlatParams([[(n, p)] for n, p in self.named_parameters()], device)
+        self.rng_state = torch.tensor([0, self._seed], dtype=torch.int64, device=device)
+        self._salt = torch.tensor([[0, SALT_C0], [0, SALT_C1]], dtype=torch.int64, device=device)
+        self._rng2 = torch.zeros(2, 2, dtype=torch.int64, device=device)
+        return self
+
+    @property
+    def _last_ws(self):
+        return self._ws.last
+
+    def _w(self, name):
+        return self.flat.w(name)
+
+    def _off(self, name):
+        return self.flat.offsets[name]
+
+    def _make_workspace(self, B, Ta, Tv, Tt, device):
+        # zeros, not empty: a stale NaN must never reach a weight-gradient GEMM through a row the step did not touch
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        C = self.n_classes
+        ws = dict(fused=f32(B, EMB), dfused=f32(B, EMB), z0=f32(B, HID), feat=f32(B, HID), logits=f32(B, C), dlogits=f32(B, C),
+                  dfeat=f32(B, HID), dz0=f32(B, HID), dtext=f32(B, HID), stats=f32(256))
+        for tag, T in (("A", Ta), ("V", Tv)):
+            if T:
+                ws[tag] = dict(T=T, GX=f32(B * T, 4 * HID), gates=f32(B * T, 4 * HID), Cst=f32(B * T, HID), Hprev=f32(B * T, HID),
+                               dGX=f32(B * T, 4 * HID), arg=i32(B, HID))
+        if Tt:
+            ws["L"] = dict(T=Tt, conv=f32(capi.textcnn_conv_floats(B, Tt)), pooled=f32(B, EMB), pd=f32(B, EMB), arg=i32(B, EMB), dpd=f32(B, EMB),
+                           dpooled=f32(B, EMB))
+        jobs = []
+        for n, (tag, net) in enumerate((("A", "netA"), ("V", "netV"))):
+            if tag in ws:
+                e = ws[tag]
+                jobs.append(dict(GX=e["GX"], W_hh=self._w(net + ".rnn.weight_hh_l0"), b_hh=self._w(net + ".rnn.bias_hh_l0"),
+                                 pool=ws["fused"][:, n * HID:], arg=e["arg"], gates=e["gates"], Cst=e["Cst"], Hprev=e["Hprev"],
+                                 dpool=ws["dfused"][:, n * HID:], dGX=e["dGX"], B=B, T=e["T"], ldp=EMB, lddp=EMB))
+        ws["n_jobs"], ws["jobs"] = len(jobs), capi.lstm128_jobs(jobs)
+        ws["planner"] = GemmPlanner(device, 1 << 16, grad=self.flat.grad)
+        return ws
+
+    def _inputs(self, audio, visual, text, need_all):
+        got = dict(audio_feature=(audio, self.audio_dim), visual_feature=(visual, self.visual_dim), text_feature=(text, self.text_dim))
+        B = None
+        for name, (x, d) in got.items():
+            if x is None:
+                if need_all:
+                    raise capi.ErcGraftError("mmin_base: %s is missing: the classifier reads all three encoders (its input is %d "
+                                             "wide)" % (name, EMB))
+                continue
+            if x.dim() != 3 or int(x.shape[2]) != d or x.dtype != torch.float32 or int(x.shape[1]) < 1:
+                raise capi.ErcGraftError("mmin_base: %s must be fp32 [B, T >= 1, %d], got %s %s" % (name, d, x.dtype, tuple(x.shape)))
+            if B is not None and int(x.shape[0]) != B:
+                raise capi.ErcGraftError("mmin_base: %s has %d samples, the batch %d" % (name, int(x.shape[0]), B))
+            B = int(x.shape[0])
+        if B is None:
+            raise capi.ErcGraftError("mmin_base: encode needs at least one of audio_feature, visual_feature, text_feature")
+        if text is not None and int(text.shape[1]) < capi.textcnn_min_t():
+            raise capi.ErcGraftError("mmin_base: text_feature has %d tokens, the widest convolution needs %d"
+                                     % (int(text.shape[1]), capi.textcnn_min_t()))
+        return B
+
+    # ----------------------------------------------------------------------------------------------------------- forward
+    def _encode(self, audio, visual, text, training, need_all=False):
+        """the encoders that have an input, into their column ranges of ws["fused"]"""
+        if self.flat is None:
+            raise capi.ErcGraftError("call MMINBaseModule.finalize(device) before forward")
+        B = self._inputs(audio, visual, text, need_all)
+        T = [0 if x is None else int(x.shape[1]) for x in (audio, visual, text)]
+        dev = next(x for x in (audio, visual, text) if x is not None).device
+        ws = self._ws.get((B, *T), lambda: self._make_workspace(B, *T, dev))
+        pl = ws["planner"]
+        pl.reset()
+        for tag, net, x in (("A", "netA", audio), ("V", "netV", visual)):
+            if x is not None:
+                e = ws[tag]
+                e["x"] = x = x.contiguous()
+                linear_fwd(pl, x, int(x.shape[2]), None, self._w(net + ".rnn.weight_ih_l0"), self._w(net + ".rnn.bias_ih_l0"), e["GX"],
+                           4 * HID, B * e["T"], 4 * HID, int(x.shape[2]))
+        if ws["n_jobs"]:
+            capi.lstm128_pool_fwd(ws["jobs"], ws["n_jobs"])
+        if text is not None:
+            e = ws["L"]
+            e["x"] = x = text.contiguous()
+            capi.textcnn_pool_fwd(x, B, e["T"], self.text_dim, [self._w("netL.conv%d.weight" % k) for k in (1, 2, 3)],
+                                  [self._w("netL.conv%d.bias" % k) for k in (1, 2, 3)], e["conv"], e["pooled"], EMB, e["arg"])
+            e["p"] = self.DROP_TEXT if training else 0.0
+            if e["p"] > 0:
+                capi.dropout_fwd(e["pooled"], B * EMB, e["p"], self.rng_state, STREAM_TEXT, e["pd"])
+            e["in"] = e["pd"] if e["p"] > 0 else e["pooled"]
+            linear_fwd(pl, e["in"], EMB, None, self._w("netL.embd.0.weight"), self._w("netL.embd.0.bias"), ws["fused"][:, 2 * HID:], EMB,
+                       B, HID, EMB, act=1)
+        return ws, B
+
+    def encode(self, audio_feature=None, visual_feature=None, text_feature=None, *args, **kwargs):
+        """the [B, 128] features of the modalities given, in the order audio, visual, text (mmin_models.py:213-226)"""
+        ws, _ = self._encode(audio_feature, visual_feature, text_feature, self.training)
+        return [ws["fused"][:, n * HID:(n + 1) * HID] for n, x in enumerate((audio_feature, visual_feature, text_feature)) if x is not None]
+
+    def _forward_impl(self, audio, visual, text, training):
+        ws, B = self._encode(audio, visual, text, training, need_all=True)
+        pl, C = ws["planner"], self.n_classes
+        p = ws["p_c"] = self.DROP_C if training else 0.0
+        if p > 0:
+            torch.add(self.rng_state.unsqueeze(0), self._salt, out=self._rng2)
+        for n, (name, xin, k, out) in enumerate((("netC.module.0", ws["fused"], EMB, ws["z0"]), ("netC.module.3", ws["z0"], HID, ws["feat"]))):
+            linear_fwd(pl, xin, k, None, self._w(name + ".weight"), self._w(name + ".bias"), out, HID, B, HID, k,
+                       act=3 if p > 0 else 1, drop_p=p, rng=self._rng2[n] if p > 0 else None)
+        linear_fwd(pl, ws["feat"], HID, None, self._w("netC.fc_out.weight"), self._w("netC.fc_out.bias"), ws["logits"], C, B, C, HID)
+        return ws, B
+
+    def forward(self, audio_feature=None, visual_feature=None, text_feature=None, *args, **kwargs):
+        ws, _ = self._forward_impl(audio_feature, visual_feature, text_feature, self.training)
+        return ws["logits"], ws["feat"]
+
+    # ---------------------------------------------------------------------------------------------------------- backward
+    def loss_and_grads(self, batch):
+        """mean cross entropy of the logits (mmin_base.py:131) and every gradient into flat.grad; returns the device stats
+        (stats[0] = loss, stats[1] = #correct)"""
+        ws, B = self._forward_impl(batch.get("audio_feature"), batch.get("visual_feature"), batch.get("text_feature"), self.training)
+        pl, C, p = ws["planner"], self.n_classes, ws["p_c"]
+        scale = 1.0 / (1.0 - p)
+        capi.cross_entropy(ws["logits"], C, C, B, None, batch["label"], None, 1.0, ws["dlogits"], C, ws["stats"])
+        # the classifier: each layer's weight gradient joins the step's one batched launch; the gradient wrt its input goes
+        # through the ReLU / dropout mask of the layer below in the GEMM epilogue (aux = that layer's output)
+        W0 = self._w("netC.module.0.weight")
+        linear_wgrad(pl, ws["dlogits"], C, ws["feat"], HID, None, C, HID, B, self._off("netC.fc_out.weight"), self._off("netC.fc_out.bias"),
+                     defer=True)
+        capi.gemm_f32(ws["dlogits"], C, 0, None, self._w("netC.fc_out.weight"), HID, 1, None, ws["dfeat"], HID, B, HID, C, act=2,
+                      aux=ws["feat"], ldaux=HID, act_scale=scale)
+        linear_wgrad(pl, ws["dfeat"], HID, ws["z0"], HID, None, HID, HID, B, self._off("netC.module.3.weight"),
+                     self._off("netC.module.3.bias"), defer=True)
+        capi.gemm_f32(ws["dfeat"], HID, 0, None, self._w("netC.module.3.weight"), HID, 1, None, ws["dz0"], HID, B, HID, HID, act=2,
+                      aux=ws["z0"], ldaux=HID, act_scale=scale)
+        linear_wgrad(pl, ws["dz0"], HID, ws["fused"], EMB, None, HID, EMB, B, self._off("netC.module.0.weight"),
+                     self._off("netC.module.0.bias"), defer=True)
+        # dfused: the audio | visual columns as they are (dpool of the two scans), the text columns through embd's ReLU
+        capi.gemm_f32(ws["dz0"], HID, 0, None, W0, EMB, 1, None, ws["dfused"], EMB, B, 2 * HID, HID)
+        capi.gemm_f32(ws["dz0"], HID, 0, None, W0[:, 2 * HID:], EMB, 1, None, ws["dtext"], HID, B, HID, HID, act=2,
+                      aux=ws["fused"][:, 2 * HID:], ldaux=EMB, act_scale=1.0)
+        e = ws["L"]
+        linear_wgrad(pl, ws["dtext"], HID, e["in"], EMB, None, HID, EMB, B, self._off("netL.embd.0.weight"), self._off("netL.embd.0.bias"),
+                     defer=True)
+        capi.gemm_f32(ws["dtext"], HID, 0, None, self._w("netL.embd.0.weight"), EMB, 1, None, e["dpd"], EMB, B, EMB, HID)
+        if e["p"] > 0:      # the forward's mask: same counter, same stream, same element index
+            capi.dropout_fwd(e["dpd"], B * EMB, e["p"], self.rng_state, STREAM_TEXT, e["dpooled"])
+        g = self.flat.g
+        capi.textcnn_pool_bwd(e["x"], B, e["T"], self.text_dim, e["pooled"], EMB, e["arg"], e["dpooled"] if e["p"] > 0 else e["dpd"], EMB,
+                              [g("netL.conv%d.weight" % k) for k in (1, 2, 3)], [g("netL.conv%d.bias" % k) for k in (1, 2, 3)])
+        capi.lstm128_pool_bwd(ws["jobs"], ws["n_jobs"])
+        for tag, net in (("A", "netA"), ("V", "netV")):
+            s, rows = ws[tag], B * ws[tag]["T"]
+            d = int(s["x"].shape[2])
+            linear_wgrad(pl, s["dGX"], 4 * HID, s["x"], d, None, 4 * HID, d, rows, self._off(net + ".rnn.weight_ih_l0"),
+                         self._off(net + ".rnn.bias_ih_l0"), defer=True)
+            linear_wgrad(pl, s["dGX"], 4 * HID, s["Hprev"], HID, None, 4 * HID, HID, rows, self._off(net + ".rnn.weight_hh_l0"),
+                         self._off(net + ".rnn.bias_hh_l0"), defer=True)
+        pl.reduce_into(ws, self.flat.grad)
+        return ws["stats"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- training
+class PlateauLR:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau(optim, "min") with torch's defaults (factor 0.1, patience 10, relative
+    threshold 1e-4, no cooldown, min_lr 0, eps 1e-8) on a host scalar"""
+
+    def __init__(self, lr, factor=0.1, patience=10, threshold=1e-4, eps=1e-8):
+        self.lr, self.factor, self.patience, self.threshold, self.eps = lr, factor, patience, threshold, eps
+        self.best, self.bad = float("inf"), 0
+
+    def step(self, metric):
+        """-> the learning rate after this epoch's metric"""
+        metric = float(metric)
+        if metric < self.best * (1.0 - self.threshold):
+            self.best, self.bad = metric, 0
+        else:
+            self.bad += 1
+        if self.bad > self.patience:
+            new = self.lr * self.factor
+            if self.lr - new > self.eps:
+                self.lr = new
+            self.bad = 0
+        return self.lr
+
+
+class MMINBaseTrainer:
+    """``--module=mmin_base``: mean cross entropy, Adam (lr 2e-4, no weight decay), the EMA copy stepped after every optimizer
+    step, ReduceLROnPlateau on the validation loss, the best checkpoint by test accuracy (mmin_base.py:63-217)."""
+    NAME = "mmin_base"
+
+    def __init__(self, params, device):
+        self.params, self.device = params, torch.device(device)
+        torch.manual_seed(params.seed)
+        self.model = MMINBaseModule(visual_dim=VISUAL_DIM, text_dim=TEXT_DIM, audio_dim=AUDIO_DIM, n_classes=params.n_classes,
+                                    compute=params.get("compute", "f32"), seed=params.seed).finalize(self.device)
+        o = params.optim
+        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0), decoupled=(o.name == "AdamW"),
+                               seed=params.seed)
+        self.model.rng_state = self.optim.rng_state      # the dropout offset advances with the optimizer step
+        self.use_ema = bool(params.get("ema", True))
+        self.ema = self.model.flat.data.clone() if self.use_ema else None      # EMA(model): a deep copy of the parameters
+        self.sched = PlateauLR(o.lr)
+        self.accuracy, self.global_steps = 0.0, 0
+        self._swap = None
+
+    def prepare_batch(self, batch):
+        return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+    def train_step(self, batch):
+        self.model.train()
+        stats = self.model.loss_and_grads(batch)
+        self.optim.step()
+        if self.use_ema:
+            capi.ema_step(self.ema, self.model.flat.data, self.model.flat.numel, EMA_ALPHA)
+        self.global_steps += 1
+        return stats
+
+    def to_logits(self, batch):
+        return self.model(**batch)[0]
+
+    class _EmaWeights:
+        """the model computing with the EMA weights: the flat buffer's contents are exchanged on entry and exit (the kernels'
+        operands stay where they are)"""
+
+        def __init__(self, trainer):
+            self.t = trainer
+
+        def __enter__(self):
+            flat, t = self.t.model.flat, self.t
+            t._swap = flat.data.clone()
+            flat.data.copy_(t.ema)
+
+        def __exit__(self, *exc):
+            self.t.model.flat.data.copy_(self.t._swap)
+            self.t._swap = None
+            return False
+
+    def ema_weights(self):
+        return self._EmaWeights(self)
+
+    def eval_epoch(self, loader):
+        """one pass with the model and one with the EMA model over ``loader``; logits stay on the device, one copy per epoch.
+        -> dict(Lall = sum over batches of the batch-mean CE (meter.sum), Acc, Acc2, C, true, pred)"""
+        self.model.eval()
+        batches = [self.prepare_batch(b) for b in loader]
+        ys = torch.cat([b["label"] for b in batches])
+        run = lambda: [self.to_logits(b).clone() for b in batches]
+        logits = run()
+        losses = torch.stack([torch.nn.functional.cross_entropy(lg, b["label"]) for lg, b in zip(logits, batches)]).sum()
+        pred = torch.cat(logits).argmax(-1)
+        out = dict(C=int(ys.shape[0]))
+        if self.use_ema:
+            with self.ema_weights():
+                pred2 = torch.cat(run()).argmax(-1)
+            host = torch.stack([pred, pred2, ys]).cpu()
+            out["Acc2"] = float((host[1] == host[2]).sum()) / out["C"]
+        else:
+            host = torch.stack([pred, ys]).cpu()
+        out.update(Lall=float(losses), Acc=float((host[0] == host[-1]).sum()) / out["C"], true=host[-1].tolist(), pred=host[0].tolist())
+        return out
+
+    def on_eval_end(self, rec):
+        """the plateau scheduler on the validation epoch's accumulated loss (mmin_base.py:171-177); -> True when the learning
+        rate changed (a captured step holds it as a launch argument and must be dropped)"""
+        lr = self.sched.step(rec["Lall"])
+        changed = lr != self.optim.lr
+        self.optim.lr = lr
+        return changed
+
+    def on_test_end(self, rec, save_dir=None):
+        """best checkpoint by test Acc, last checkpoint always (mmin_base.py:198-201); -> True when this epoch is the best"""
+        best = self.accuracy < rec["Acc"]
+        if best:
+            self.accuracy = rec["Acc"]
+        if save_dir:
+            os.makedirs(save_dir, exist_ok=True)
+            for tag in (("best_model", ) if best else ()) + ("last_model", ):
+                save(self, os.path.join(save_dir, tag + ".ckpt"))
+                with open(os.path.join(save_dir, tag + ".json"), "w") as fh:
+                    fh.write(json.dumps({"global_steps": self.global_steps, "accuracy": self.accuracy}))
+        return best
+
+
+def state_dict(trainer):
+    """the reference trainer's envelope with both registered models: {'models': {'model', 'ema_model'}, 'optims': {'optim'}}"""
+    from . import checkpoint
+    sd = checkpoint.state_dict(trainer)
+    if trainer.use_ema:
+        flat = trainer.model.flat
+        sd["models"]["ema_model"] = {k: flat.view(trainer.ema, k).detach().cpu().clone() for k in trainer.model.state_dict()}
+    return sd
+
+
+def save(trainer, path):
+    torch.save(state_dict(trainer), path)
+    return path
+
+
+def load(trainer, path, with_optimizer=True):
+    """``--pretrain_path``: a checkpoint written by ``save`` or by the reference's trainer; the EMA weights follow the file's
+    ``ema_model`` (the loaded model's where the file has none)"""
+    from . import checkpoint
+    ckpt = checkpoint.load(trainer, path, with_optimizer=with_optimizer)
+    if trainer.use_ema:
+        flat = trainer.model.flat
+        trainer.ema.copy_(flat.data)
+        ema = ckpt.get("models", {}).get("ema_model") if isinstance(ckpt, dict) else None
+        for k, v in (ema or {}).items():
+            flat.view(trainer.ema, k).copy_(v.to(flat.device, torch.float32))
+    trainer.sched.lr = trainer.optim.lr
+    return ckpt
+
+
+def mmin_collate(samples):
+    """MMINBaseCollate (mmin_base.py:224-251): audio zero-padded to the batch's longest utterance, batch-first"""
+    from torch.nn.utils.rnn import pad_sequence
+    audio = [torch.as_tensor(s["audio_feature"], dtype=torch.float32) for s in samples]
+    return dict(audio_feature=pad_sequence(audio, batch_first=True, padding_value=0.0),
+                audio_feature_length=[int(a.shape[0]) for a in audio],
+                visual_feature=torch.as_tensor(np.stack([s["visual_feature"] for s in samples]), dtype=torch.float32),
+                text_feature=torch.as_tensor(np.stack([s["text_feature"] for s in samples]), dtype=torch.float32),
+                label=torch.tensor([int(s["label"]) for s in samples], dtype=torch.long), name=[s["name"] for s in samples])
+
+
+def make_loaders(params):
+    from torch.utils.data import DataLoader
+    from .synthetic import make_mmin_samples
+    if not params.get("synthetic", True):
+        raise SystemExit("dataset %s: the .h5 feature readers of the reference need h5py, which this build cannot test against; "
+                         "only --synthetic=True is built for --module=mmin_base" % params.dataset)
+    lo, hi = params.get("mmin_frames", (50, 400))
+    out = []
+    for split, n, grp in (("train", params.n_train, params.train), ("val", params.get("n_val", params.n_test), params.val),
+                          ("test", params.n_test, params.test)):
+        data = make_mmin_samples(n, split, seed=params.seed, frames=(int(lo), int(hi)), n_classes=params.n_classes)
+        gen = torch.Generator().manual_seed(params.seed)
+        out.append(DataLoader(data, batch_size=grp.batch_size, shuffle=(split == "train"), collate_fn=mmin_collate, generator=gen))
+    return out
+
+
+def run(trainer_cls, params_cls, argv=None):
+    """the epoch loop of --module=mmin_base: training steps (EMA after each), the validation epoch (plateau scheduler), the test
+    epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
+    from .trainer import classification_report, fix_seed
+    params = params_cls()
+    params.from_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("the ERC hot path runs on an MI355X through libercgraft.so; no GPU is visible (there is no CPU fallback)")
+    device = torch.device(params.device if params.device not in (None, "cuda") else "cuda:0")
+    torch.cuda.set_device(device)
+    train_loader, val_loader, test_loader = make_loaders(params)
+    fix_seed(params.seed)
+    trainer = trainer_cls(params, device)
+    if params.get("pretrain_path"):
+        load(trainer, params.pretrain_path)
+    ring = torch.zeros(max(1, len(train_loader)), 4, dtype=torch.float32, device=device)
+    last = {}
+    for epoch in range(params.epoch):
+        t0, counts = time.perf_counter(), []
+        for i, item in enumerate(train_loader):
+            stats = trainer.train_step(trainer.prepare_batch(item))
+            ring[i].copy_(stats[:4], non_blocking=True)
+            counts.append(int(item["label"].shape[0]))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        trainer.model.flat.check_health("mmin_base")
+        rows = ring[:len(counts)].cpu().tolist()
+        if params.log_every:
+            for i, (row, n_b) in enumerate(zip(rows, counts)):
+                if (i + 1) % params.log_every == 0:
+                    print(json.dumps({"epoch": epoch, "step": i, "Lall": row[0], "Acc": row[1] / max(1, n_b)}), flush=True)
+        val = trainer.eval_epoch(val_loader)
+        trainer.on_eval_end(val)
+        test = trainer.eval_epoch(test_loader)
+        best = trainer.on_test_end(test, params.get("save_dir"))
+        rep = classification_report(test["true"], test["pred"], params.n_classes) if params.get("confuse_matrix", True) else {}
+        last = {"epoch": epoch, "train_utt_per_s": sum(counts) / dt, "lr": trainer.optim.lr,
+                "val": {k: val[k] for k in ("Lall", "Acc", "Acc2") if k in val}, "test": {k: test[k] for k in ("Lall", "Acc", "Acc2") if k in test},
+                "report": {k: rep[k] for k in rep if k != "cm"}, "class_names": list(params.class_names), "best_acc": trainer.accuracy,
+                "is_best": best}
+        print(json.dumps(last), flush=True)
+    if params.get("save"):
+        save(trainer, params.save)
+    return last

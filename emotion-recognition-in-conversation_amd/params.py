@@ -35,7 +35,10 @@ DATASETS = tuple(
 # labels, trained by --module=cim only.  The MOSEI.adpated.pkl names (sbert / fbank / is10) and the raw-audio tracks
 # are out of scope.
 MOSEI_DATASETS = ("mosei-cim-2",)
-ALL_DATASETS = DATASETS + MOSEI_DATASETS
+# MMIN's IEMOCAP utterance features (:31: ComParE audio frames, DenseFace visual frames, BERT token rows; four classes), read by
+# --module=mmin_base only
+MMIN_DATASETS = ("iemocap-mmin-4",)
+ALL_DATASETS = DATASETS + MOSEI_DATASETS + MMIN_DATASETS
 
 
 class Group(dict):

@@ -63,3 +63,28 @@ def make_mosei_dialogues(n, dims, min_len=1, max_len=98, seed=1, force_max=False
             "senti2_label": senti,
         })
     return out
+
+
+MMIN_SPLIT_SALT = {"train": 0, "val": 1, "test": 2}
+
+
+def make_mmin_samples(n, split="train", seed=1, frames=(50, 400), n_classes=4, dims=None):
+    """Utterance samples in the shapes of the reference's MMIN readers (mmdatasets/datas/mm/iemocap_feature.py:304-357): visual
+    [50, 342] (DenseFace frames), text [22, 1024] (BERT token rows), audio [t, 130] (ComParE frames), ``label`` in
+    [0, n_classes), ``name``.  The real ComParE frame counts are not known here: ``t`` is drawn uniformly from ``frames``
+    (inclusive) -- an ASSUMPTION behind the flag --mmin_frames.  ``split`` (train / val / test) salts the seed, so the three
+    splits are disjoint draws; the same (n, split, seed, frames) gives the same samples."""
+    dims = dims or dict(a=130, t=1024, v=342)
+    rng = np.random.RandomState((seed * 3 + MMIN_SPLIT_SALT[split]) % (1 << 31))
+    lo, hi = int(frames[0]), int(frames[1])
+    out = []
+    for i in range(n):
+        t = int(rng.randint(lo, hi + 1))
+        out.append({
+            "audio_feature": rng.standard_normal((t, dims["a"])).astype(np.float32),
+            "visual_feature": rng.standard_normal((50, dims["v"])).astype(np.float32),
+            "text_feature": rng.standard_normal((22, dims["t"])).astype(np.float32),
+            "label": int(rng.randint(0, n_classes)),
+            "name": "%s_%05d" % (split, i),
+        })
+    return out

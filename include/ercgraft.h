@@ -1547,6 +1547,72 @@ int erc_log_softmax_rows(const float* x, int ldx, int C, int n_rows, float* y, i
 
 
 /* ------------------------------------------------------------------------
+ * MMIN full-modality base model (track_mm/mmin_models.py:8-130,202-240; track_mm/mmin_base.py): the hidden-128 LSTM
+ * encoders with a max-pool over time, the text CNN, and the EMA copy of the parameters.
+ *
+ * erc_lstm128_pool_fwd / _bwd replace LSTMEncoder(d, 128, 'maxpool') (mmin_models.py:43-95: nn.LSTM(batch_first=True), gate
+ * order i|f|g|o, then F.max_pool1d over all T steps) and its autograd.  A JOB is one encoder over one batch; up to
+ * erc_lstm128_max_jobs() = 2 jobs (audio and visual: they are independent) share a launch, one workgroup per (sample, job).
+ * Rows are batch-first: row(b, t) = b * T + t.  Hidden size erc_lstm128_hidden() = 128.
+ *   GX     [B*T, 512]  the caller's hoisted x W_ih^T + b_ih (one GEMM)           forward in
+ *   W_hh   [512, 128], b_hh [512]                                                 forward in (W_hh: backward too)
+ *   pool   [B, ldp >= 128]  max over t in [0, T) of h_t -- padded steps included  forward out
+ *   arg    [B, 128] int32   the first step attaining it                            forward out, backward in
+ *   gates  [B*T, 512] post-activation i|f|g|o; Cst [B*T, 128] cell state;
+ *   Hprev  [B*T, 128] h_{t-1} (the operand of the W_hh gradient GEMM)              forward out, backward in (gates, Cst)
+ *   dpool  [B, lddp >= 128] gradient wrt pool                                      backward in
+ *   dGX    [B*T, 512] gradient wrt the gate pre-activations, EVERY row written     backward out
+ * Step t of unit u receives dpool[b, u] iff arg[b, u] == t.  dW_ih = dGX^T x, dW_hh = dGX^T Hprev and both bias gradients (the
+ * column sums of dGX) are the caller's (erc_wgrad_table).  No dx.  Every sample runs all T steps (padding = zero rows of x).
+ * Write sets are exactly the buffers above; a repeated launch is bit-identical.  Bad arguments (null pointer, B or T <= 0,
+ * ldp / lddp < 128, n_jobs outside [1, 2]) give ERC_E_ARG before anything is launched. */
+typedef struct ErcLstm128Job {
+    const float* GX;
+    const float* W_hh;
+    const float* b_hh;
+    float* pool;
+    int32_t* arg;
+    float* gates;
+    float* Cst;
+    float* Hprev;
+    const float* dpool;
+    float* dGX;
+    int32_t B, T, ldp, lddp;
+} ErcLstm128Job;
+int erc_lstm128_hidden(void);
+int erc_lstm128_max_jobs(void);
+int erc_lstm128_pool_fwd(const ErcLstm128Job* jobs_host, int n_jobs, void* stream);
+int erc_lstm128_pool_bwd(const ErcLstm128Job* jobs_host, int n_jobs, void* stream);
+
+/* erc_textcnn_pool_fwd / _bwd replace TextCNN's three conv blocks (mmin_models.py:15-17,24-37: Conv2d(1, 128, (k, D)) for
+ * k = 3, 4, 5, ReLU, F.max_pool1d over the T - k + 1 windows, the results side by side) and their autograd; the dropout and the
+ * `embd` layer behind them stay the caller's (erc_dropout_fwd, erc_gemm_f32).
+ *   x [B*T, D] (contiguous rows), Wk [128, k*D] (= Conv2d weight [128, 1, k, D]), bk [128]
+ *   conv   erc_textcnn_conv_floats(B, T) = 8 * B*T * 384 floats of scratch: the three exact-fp32 products (erc_gemm_f32 with row
+ *          pitch D and K = k*D over overlapping rows), each cut into 8 pieces of K that the pooling launch sums in index order
+ *          (shorter fp32 accumulation chains, 8 times the workgroups); D >= 43
+ *   pooled [B, ldp >= 384], arg [B, 384] int32: max over t in [0, T-k] of relu(conv + bias) and the FIRST window attaining it; a
+ *          channel whose every window is <= 0 pools to 0 (arg 0) and has gradient 0
+ *   backward: dWk[ch, j, :] = sum_b g[b, ch] x[b, arg[b, ch] + j, :], dbk[ch] = sum_b g[b, ch], g = dpooled where pooled > 0;
+ *          summed over b in index order in registers (deterministic, no atomics); the gradients are WRITTEN, not added.
+ * T >= erc_textcnn_min_t() = 5 (the widest kernel), erc_textcnn_channels() = 128; anything else is ERC_E_ARG before any launch. */
+int erc_textcnn_min_t(void);
+int erc_textcnn_channels(void);
+int64_t erc_textcnn_conv_floats(int B, int T);
+int erc_textcnn_pool_fwd(const float* x, int B, int T, int D, const float* W3, const float* W4, const float* W5,
+                         const float* b3, const float* b4, const float* b5, float* conv, float* pooled, int ldp,
+                         int32_t* arg, void* stream);
+int erc_textcnn_pool_bwd(const float* x, int B, int T, int D, const float* pooled, int ldp, const int32_t* arg,
+                         const float* dpooled, int lddp, float* dW3, float* dW4, float* dW5, float* db3, float* db4,
+                         float* db5, void* stream);
+
+/* ema[i] = alpha * ema[i] + (1 - alpha) * p[i], i < n: the step of lumo's EMA copy (lumo/contrib/module/ema.py:51-61) over the
+ * flat parameter buffer, one launch; two rounded products and a rounded sum, in the order of the reference's tensor expression.
+ * 1 - alpha is formed from the float alpha in double and rounded: an element differs from a torch run of `alpha * ema + (1 - alpha) * p`
+ * with a Python-float alpha by at most 2^-25 |p| and one unit in the last place.  alpha outside [0, 1], n <= 0 or a null pointer: ERC_E_ARG. */
+int erc_ema_step(float* ema, const float* p, int64_t n, float alpha, void* stream);
+
+/* ------------------------------------------------------------------------
  * Launch chain: a captured step replayed as PLAIN kernel launches from native code.
  * A training step captured into a HIP graph (one stream, kernels only) is a simple path of kernel nodes.  Replaying the
  * graph leaves the queue idle between two replays (DESIGN.md findings 48, 64); the same kernels launched one by one on a
