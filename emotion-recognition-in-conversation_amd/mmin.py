@@ -29,7 +29,8 @@ import torch
 from torch import nn
 
 from . import capi
-from .engine import FlatParams, FusedAdam, GemmPlanner, WorkspaceCache, linear_fwd, linear_wgrad
+from .capacity import TrainerBase
+from .engine import FlatParams, GemmPlanner, WorkspaceCache, linear_fwd, linear_wgrad
 
 HID, EMB = 128, 384
 AUDIO_DIM, VISUAL_DIM, TEXT_DIM = 130, 342, 1024     # mmin_base.py:86-91: constants of the trainer
@@ -271,30 +272,28 @@ class PlateauLR:
         return self.lr
 
 
-class MMINBaseTrainer:
+class MMINBaseTrainer(TrainerBase):
     """``--module=mmin_base``: mean cross entropy, Adam (lr 2e-4, no weight decay), the EMA copy stepped after every optimizer
-    step, ReduceLROnPlateau on the validation loss, the best checkpoint by test accuracy (mmin_base.py:63-217)."""
+    step, ReduceLROnPlateau on the validation loss, the best checkpoint by test accuracy (mmin_base.py:63-217).
+    ``prepare_batch``, ``to_logits`` and the optimizer set-up are TrainerBase's (a batch of this module has no ``text_length``:
+    no ``n_nodes`` is added)."""
     NAME = "mmin_base"
+    CLASS_WEIGHTED = False
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
         torch.manual_seed(params.seed)
         self.model = MMINBaseModule(visual_dim=VISUAL_DIM, text_dim=TEXT_DIM, audio_dim=AUDIO_DIM, n_classes=params.n_classes,
                                     compute=params.get("compute", "f32"), seed=params.seed).finalize(self.device)
-        o = params.optim
-        self.optim = FusedAdam(self.model.flat, lr=o.lr, weight_decay=o.get("weight_decay", 0.0), decoupled=(o.name == "AdamW"),
-                               seed=params.seed)
-        self.model.rng_state = self.optim.rng_state      # the dropout offset advances with the optimizer step
+        self._make_optim()
         self.use_ema = bool(params.get("ema", True))
         self.ema = self.model.flat.data.clone() if self.use_ema else None      # EMA(model): a deep copy of the parameters
-        self.sched = PlateauLR(o.lr)
+        self.sched = PlateauLR(params.optim.lr)
         self.accuracy, self.global_steps = 0.0, 0
         self._swap = None
 
-    def prepare_batch(self, batch):
-        return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-
     def train_step(self, batch):
+        """TrainerBase's step with the EMA step behind the optimizer's (one rank: no gradient all-reduce)"""
         self.model.train()
         stats = self.model.loss_and_grads(batch)
         self.optim.step()
@@ -302,9 +301,6 @@ class MMINBaseTrainer:
             capi.ema_step(self.ema, self.model.flat.data, self.model.flat.numel, EMA_ALPHA)
         self.global_steps += 1
         return stats
-
-    def to_logits(self, batch):
-        return self.model(**batch)[0]
 
     class _EmaWeights:
         """the model computing with the EMA weights: the flat buffer's contents are exchanged on entry and exit (the kernels'
@@ -429,7 +425,7 @@ def make_loaders(params):
 def run(trainer_cls, params_cls, argv=None):
     """the epoch loop of --module=mmin_base: training steps (EMA after each), the validation epoch (plateau scheduler), the test
     epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
-    from .trainer import classification_report, fix_seed
+    from .trainer import classification_report, fix_seed, print_step_lines, train_epoch_loader
     params = params_cls()
     params.from_args(argv)
     if not torch.cuda.is_available():
@@ -444,19 +440,13 @@ def run(trainer_cls, params_cls, argv=None):
     ring = torch.zeros(max(1, len(train_loader)), 4, dtype=torch.float32, device=device)
     last = {}
     for epoch in range(params.epoch):
-        t0, counts = time.perf_counter(), []
-        for i, item in enumerate(train_loader):
-            stats = trainer.train_step(trainer.prepare_batch(item))
-            ring[i].copy_(stats[:4], non_blocking=True)
-            counts.append(int(item["label"].shape[0]))
+        t0 = time.perf_counter()
+        counts = train_epoch_loader(train_loader, None, trainer, ring)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         trainer.model.flat.check_health("mmin_base")
-        rows = ring[:len(counts)].cpu().tolist()
         if params.log_every:
-            for i, (row, n_b) in enumerate(zip(rows, counts)):
-                if (i + 1) % params.log_every == 0:
-                    print(json.dumps({"epoch": epoch, "step": i, "Lall": row[0], "Acc": row[1] / max(1, n_b)}), flush=True)
+            print_step_lines(params, epoch, ring, counts)
         val = trainer.eval_epoch(val_loader)
         trainer.on_eval_end(val)
         test = trainer.eval_epoch(test_loader)

@@ -615,21 +615,9 @@ def _setup_resident(params, trainer, train_loader, test_loader, rank, world):
     return resident, res_eval
 
 
-# -- one training epoch, in three forms.  The step forms return the batches' utterance counts; a step's stats go into its row
-#    of ``ring`` (no device->host synchronisation inside the epoch)
-def _train_epoch_resident(resident, t0, acc_prev, epoch, log):
-    """--resident: returns (#utterances, seconds, the running totals); prints the epoch's mean loss / accuracy"""
-    n_utt, n_st = resident.epoch()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    tot = resident.acc.cpu().tolist()                           # running totals: this epoch = the difference
-    acc = [a - b for a, b in zip(tot, acc_prev)]
-    if log:
-        print(json.dumps({"epoch": epoch, "steps": n_st, "Lall": acc[0] / n_st, "Acc": acc[1] / max(1, n_utt)}), flush=True)
-    return n_utt, dt, tot
-
-
-def _train_epoch_fixed(fixed, graphs, trainer, ring):
+# -- one training epoch over batches, in two forms (the third, --resident, is ResidentEpochs.epoch).  They return the batches'
+#    utterance counts; a step's stats go into its row of ``ring`` (no device->host synchronisation inside the epoch)
+def train_epoch_fixed(fixed, graphs, trainer, ring):
     """--fixed_batches: the device batches collated once, in a fresh order; each one's graph binds to its own buffers"""
     counts = []
     for i, (bid, (n_b, dev_batch)) in enumerate(fixed):
@@ -639,7 +627,7 @@ def _train_epoch_fixed(fixed, graphs, trainer, ring):
     return counts
 
 
-def _train_epoch_loader(loader, graphs, trainer, ring):
+def train_epoch_loader(loader, graphs, trainer, ring):
     """the default: the loader's reshuffled batches, through StepGraphs where there is one"""
     counts = []
     for i, item in enumerate(loader):
@@ -650,7 +638,8 @@ def _train_epoch_loader(loader, graphs, trainer, ring):
     return counts
 
 
-def _print_step_lines(params, epoch, ring, counts, multitask):
+def print_step_lines(params, epoch, ring, counts, multitask=False):
+    """every ``log_every``-th step's JSON line, from one device -> host copy of the ring"""
     rows = ring[:len(counts)].cpu().tolist()
     for i, (row, n_b) in enumerate(zip(rows, counts)):
         if (i + 1) % params.log_every == 0:
@@ -660,17 +649,8 @@ def _print_step_lines(params, epoch, ring, counts, multitask):
             print(json.dumps(line), flush=True)
 
 
-# -- one test epoch (after every training epoch: mmbase.py:136,180-201), in two forms
-def _test_epoch_resident(res_eval):
-    """--resident_eval: graph replays over the resident test store, one device -> host copy (the training epoch ended with a
-    synchronisation).  Returns (confusion matrix on the host, seconds)."""
-    t1 = time.perf_counter()
-    cm_host = res_eval.epoch()
-    torch.cuda.synchronize()
-    return cm_host, time.perf_counter() - t1
-
-
-def _test_epoch_loader(trainer, test_loader, multiemo):
+# -- one test epoch (after every training epoch: mmbase.py:136,180-201) over batches (--resident_eval: ResidentEval.epoch)
+def test_epoch_loader(trainer, test_loader, multiemo=False):
     """returns (true, pred, true_multi, prob_multi); the last two are filled under ``multiemo``"""
     true, pred, true_multi, prob_multi = [], [], [], []
     for batch in test_loader:
@@ -687,6 +667,53 @@ def _test_epoch_loader(trainer, test_loader, multiemo):
         pred.extend(logits.argmax(-1).cpu().tolist())
         true.extend(batch["label"].tolist())
     return true, pred, true_multi, prob_multi
+
+
+@dataclasses.dataclass
+class EvalEpoch:
+    """what ``EpochLoop.test_epoch`` returns: ``cm`` is the confusion matrix of a ResidentEval epoch (host int64 [C, C]) and
+    None after the host loop, whose lists follow (the last two are filled under ``multiemo``)"""
+    cm: object = None
+    true: list = dataclasses.field(default_factory=list)
+    pred: list = dataclasses.field(default_factory=list)
+    true_multi: list = dataclasses.field(default_factory=list)
+    prob_multi: list = dataclasses.field(default_factory=list)
+
+
+class EpochLoop:
+    """One epoch as train_mm.py runs it, for ``run`` and for tools/epoch_bench.py.  The constructor does what lies between
+    "trainer constructed" and "first epoch", in this order (FixedBatches draws from the loader, ``resident.plan`` draws the
+    permutations of every epoch): the loaders, StepGraphs / FixedBatches, the per-step stats ring, the resident loops.
+    ``train_epoch`` and ``test_epoch`` launch an epoch in the form the flags select; they do not synchronise, take no host
+    clock, print nothing and leave the model's mode alone -- ``model.train()`` / ``model.eval()``, which walk every submodule,
+    are the caller's part like the clock, and ``run`` keeps them outside its timed spans.  ``counters``: the ResidentEpochs
+    or StepGraphs of the run (their ``replays`` / ``eager`` / ``captures``), None for the plain eager loop."""
+
+    def __init__(self, params, trainer, device, rank=0, world=1):
+        self.params, self.trainer = params, trainer
+        self.train_loader, self.test_loader = make_loaders(params, rank, world, device)
+        self.graphs, self.fixed = _setup_graphs(params, trainer, self.train_loader, rank, world, device)
+        self.n_steps = len(self.fixed) if self.fixed is not None else len(self.train_loader)
+        # per-step {loss, #correct, ...}: read once per epoch
+        self.ring = torch.zeros(max(1, self.n_steps), 4, dtype=torch.float32, device=device)
+        self.resident, self.res_eval = _setup_resident(params, trainer, self.train_loader, self.test_loader, rank, world)
+        self.counters = self.resident or self.graphs
+
+    def train_epoch(self):
+        """(#utterances, the steps' utterance counts: [] under --resident, whose steps are never materialised)"""
+        if self.resident is not None:
+            return self.resident.epoch()[0], []
+        if self.fixed is not None:
+            counts = train_epoch_fixed(self.fixed, self.graphs, self.trainer, self.ring)
+        else:
+            counts = train_epoch_loader(self.train_loader, self.graphs, self.trainer, self.ring)
+        return sum(counts), counts
+
+    def test_epoch(self, multiemo=False):
+        """an ``EvalEpoch``; call it with the model in eval mode"""
+        if self.res_eval is not None:
+            return EvalEpoch(cm=self.res_eval.epoch())
+        return EvalEpoch(None, *test_epoch_loader(self.trainer, self.test_loader, multiemo))
 
 
 def _epoch_line(epoch, utt_per_s, rep, best, counters, n_steps, test_s, multiemo_rep):
@@ -726,43 +753,40 @@ def run(trainer_cls, params_cls, argv=None):
     if params.get("load"):      # checkpoint in the reference's envelope (checkpoint.py)
         from . import checkpoint
         checkpoint.load(trainer, params.load)
-    train_loader, test_loader = make_loaders(params, rank, world, device)
-    graphs, fixed = _setup_graphs(params, trainer, train_loader, rank, world, device)
-    n_steps = len(fixed) if fixed is not None else len(train_loader)
-    ring = torch.zeros(max(1, n_steps), 4, dtype=torch.float32, device=device)    # per-step {loss, #correct, ...}: read once per epoch
-    resident, res_eval = _setup_resident(params, trainer, train_loader, test_loader, rank, world)
+    loop = EpochLoop(params, trainer, device, rank, world)
     best, acc_prev = {}, [0.0] * 4
     log = rank == 0 and params.log_every
     multiemo = params.get("mosei_metric", "") == "multiemo"
     check_cluster = getattr(trainer.model, "check_cluster", lambda: None)
     for epoch in range(params.epoch):
         trainer.model.train()
-        t0, counts = time.perf_counter(), []
-        if resident is not None:
-            n_utt, dt, acc_prev = _train_epoch_resident(resident, t0, acc_prev, epoch, log)
-        elif fixed is not None:
-            counts = _train_epoch_fixed(fixed, graphs, trainer, ring)
-        else:
-            counts = _train_epoch_loader(train_loader, graphs, trainer, ring)
+        t0 = time.perf_counter()
+        n_utt, counts = loop.train_epoch()
         torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if loop.resident is not None:      # no step lines: the epoch's mean loss / accuracy from the running totals
+            tot = loop.resident.acc.cpu().tolist()
+            acc, acc_prev = [a - b for a, b in zip(tot, acc_prev)], tot
+            if log:
+                print(json.dumps({"epoch": epoch, "steps": loop.n_steps, "Lall": acc[0] / loop.n_steps,
+                                  "Acc": acc[1] / max(1, n_utt)}), flush=True)
         check_cluster()
-        if resident is None:
-            n_utt, dt = sum(counts), time.perf_counter() - t0
         if log:
-            _print_step_lines(params, epoch, ring, counts, getattr(trainer, "multitask", False))
+            print_step_lines(params, epoch, loop.ring, counts, getattr(trainer, "multitask", False))
         trainer.model.eval()
-        cm_host = test_s = None
-        if res_eval is not None:
-            cm_host, test_s = _test_epoch_resident(res_eval)
-        else:
-            true, pred, true_multi, prob_multi = _test_epoch_loader(trainer, test_loader, multiemo)
+        t1 = time.perf_counter()
+        res = loop.test_epoch(multiemo)
+        test_s = None
+        if res.cm is not None:             # (the host loop synchronises per batch and reports no time of its own)
+            torch.cuda.synchronize()
+            test_s = time.perf_counter() - t1
         check_cluster()      # a timeout inside to_logits would make the metrics below meaningless
         if rank == 0:
-            rep = classification_report(true, pred, params.n_classes) if cm_host is None else report_from_cm(cm_host.numpy())
+            rep = classification_report(res.true, res.pred, params.n_classes) if res.cm is None else report_from_cm(res.cm.numpy())
             for k in ("acc", "wa", "f1", "mif1", "maf1", "pre", "rec"):
                 best[k] = max(best.get(k, 0.0), rep[k])
-            multiemo_rep = multiemo_report(np.concatenate(true_multi), np.concatenate(prob_multi)) if multiemo else None
-            print(json.dumps(_epoch_line(epoch, n_utt / dt, rep, best, resident or graphs, len(counts), test_s, multiemo_rep)),
+            multiemo_rep = multiemo_report(np.concatenate(res.true_multi), np.concatenate(res.prob_multi)) if multiemo else None
+            print(json.dumps(_epoch_line(epoch, n_utt / dt, rep, best, loop.counters, len(counts), test_s, multiemo_rep)),
                   flush=True)
     if params.get("save") and rank == 0:
         from . import checkpoint
@@ -770,7 +794,7 @@ def run(trainer_cls, params_cls, argv=None):
     if world > 1:
         # the captured step graphs hold RCCL work: they go before the process group does (bench.py saw an abort at interpreter
         # exit, once in a while, with the group torn down under live graphs)
-        graphs = resident = None
+        loop = None
         import gc
         gc.collect()
         torch.cuda.synchronize()

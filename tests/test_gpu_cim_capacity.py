@@ -567,11 +567,11 @@ def test_eval_scores_is_numpy_s_confusion_matrix_of_the_exact_step():
 def test_a_resident_test_epoch_equals_the_default_test_loop():
     """ResidentEval over the 10-dialogue store at B = 4 (three steps, the last with two empty slots) against the host loop's
     confusion matrix, twice: the second epoch is replays alone"""
-    from erc_amd.trainer import ResidentEval, StoreLoader, _test_epoch_loader
+    from erc_amd.trainer import ResidentEval, StoreLoader, test_epoch_loader
     tr, p = _trainer(extra=["--device_collate", "--resident", "--resident_eval"])
     _, store = _store(p, False)
     tr.model.eval()
-    true, pred, _, _ = _test_epoch_loader(tr, StoreLoader(store, 4, False, 0), False)
+    true, pred, _, _ = test_epoch_loader(tr, StoreLoader(store, 4, False, 0), False)
     want = np.zeros((6, 6), dtype=np.int64)
     np.add.at(want, (np.asarray(true), np.asarray(pred)), 1)
     ev = ResidentEval(tr, store, 4)

@@ -151,9 +151,9 @@ def _min_gap():
 
 def _host_cm(tr, store, C):
     """the default test loop of trainer.run on this trainer: its confusion matrix (true x predicted)"""
-    from erc_amd.trainer import StoreLoader, _test_epoch_loader
+    from erc_amd.trainer import StoreLoader, test_epoch_loader
     tr.model.eval()
-    true, pred, _, _ = _test_epoch_loader(tr, StoreLoader(store, 4, False, 0), False)
+    true, pred, _, _ = test_epoch_loader(tr, StoreLoader(store, 4, False, 0), False)
     cm = torch.zeros(C, C, dtype=torch.int64)
     for t, q in zip(true, pred):
         cm[t, q] += 1

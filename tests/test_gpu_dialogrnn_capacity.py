@@ -733,8 +733,8 @@ def test_the_cli_configurations_test_epochs_replay_one_evaluation_graph():
     p = _cli_params(FLAGS)
     T.fix_seed(p.seed)
     tr = DialogRNNTrainer(p, torch.device(DEV))
-    train_loader, test_loader = T.make_loaders(p, 0, 1, torch.device(DEV))
-    resident, ev = T._setup_resident(p, tr, train_loader, test_loader, 0, 1)
+    loop = T.EpochLoop(p, tr, torch.device(DEV))
+    resident, ev, test_loader = loop.resident, loop.res_eval, loop.test_loader
     assert type(ev) is T.ResidentEval and ev.steps == 1 and len(set(ev.caps)) == 1
     tr.model.eval()
     cms = []

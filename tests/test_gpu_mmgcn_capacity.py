@@ -662,7 +662,7 @@ def test_resident_test_epoch_confusion_matrix_equals_the_host_loops(mods, S, C):
     """ResidentEval over the six test dialogues at batch 4 (two steps, the second with two empty slots; a first visit and a
     replay of the one bucket) against the default host loop (StoreLoader batches through to_logits, argmax on the host) and
     against the float64 oracle, whose top-two gap exceeds 1e-3 in every row -- so no row is left out"""
-    from erc_amd.trainer import ResidentEval, StoreLoader, _test_epoch_loader
+    from erc_amd.trainer import ResidentEval, StoreLoader, test_epoch_loader
     pseed, dseed = CM_SEEDS[mods]
     ref = _new_oracle(mods, S, C, pseed)
     tr, p = _trainer(mods, S, C, extra=["--device_collate", "--resident", "--resident_eval"], ref=ref)
@@ -682,7 +682,7 @@ def test_resident_test_epoch_confusion_matrix_equals_the_host_loops(mods, S, C):
     tr.model.eval()
     cms = [ev.epoch().numpy(), ev.epoch().numpy()]            # the second epoch is replays alone
     assert (ev.captures, ev.eager, ev.replays) == (1, 1, 3)
-    true, pred, _, _ = _test_epoch_loader(tr, StoreLoader(store, 4, False, 0), False)
+    true, pred, _, _ = test_epoch_loader(tr, StoreLoader(store, 4, False, 0), False)
     host_cm = np.zeros((C, C), dtype=np.int64)
     np.add.at(host_cm, (np.asarray(true), np.asarray(pred)), 1)
     assert int(host_cm.sum()) == sum(TEST_LENGTHS)
