@@ -1383,3 +1383,99 @@ def textcnn_pool_bwd(x, B, T, D, pooled, ldp, arg, dpooled, lddp, dWs, dbs):
 
 def ema_step(ema, p, n, alpha):
     _call("erc_ema_step", ema, p, n, alpha)
+
+
+# --------------------------------------------------------------------------- MMIN missing-modality model (csrc/resae.hip)
+RESAE_LAYERS = 32
+
+
+class ErcResaeJob(C.Structure):
+    """host mirror of ErcResaeJob (ercgraft.h)"""
+    _fields_ = [("W", C.c_void_p * RESAE_LAYERS), ("b", C.c_void_p * RESAE_LAYERS)] + \
+               [(n, C.c_void_p) for n in ("x", "recon", "latents", "act", "d_recon", "d_latents", "dx", "dY")] + \
+               [(n, C.c_int32) for n in ("B", "ldx", "ldr", "ldl", "lddr", "lddl", "lddx", "reserved")]
+
+
+def resae_input():
+    return int(lib().erc_resae_input())
+
+
+def resae_latent():
+    return int(lib().erc_resae_latent())
+
+
+def resae_max_jobs():
+    return int(lib().erc_resae_max_jobs())
+
+
+def resae_max_blocks():
+    return int(lib().erc_resae_max_blocks())
+
+
+def resae_rows_per_group():
+    return int(lib().erc_resae_rows_per_group())
+
+
+def resae_act_floats(B, n_blocks):
+    return int(lib().erc_resae_act_floats(B, n_blocks))
+
+
+def resae_layer_names(n_blocks):
+    """the chain's Linear layers in the kernels' order, as state_dict prefixes of a ResidualAE"""
+    names = []
+    for i in range(n_blocks):
+        names += ["encoder_%d.%d" % (i, k) for k in (0, 2, 4)] + ["decoder_%d.%d" % (i, k) for k in (0, 2, 4)]
+    return names + ["transition.0", "transition.2"]
+
+
+def resae_layer_dims(n_blocks):
+    """(out, in) of every layer, in the kernels' order"""
+    return [(256, 384), (128, 256), (64, 128), (128, 64), (256, 128), (384, 256)] * n_blocks + [(384, 384), (384, 384)]
+
+
+def _gpu_ptr(what, name, v):
+    if isinstance(v, torch.Tensor):
+        if not v.is_cuda:
+            raise ErcGraftError("%s: %s must live on the GPU (got a %s tensor)" % (what, name, v.device))
+        return v.data_ptr()
+    return v
+
+
+def resae_jobs(jobs):
+    """ErcResaeJob array of ``jobs``: dicts of the struct's fields; ``W`` / ``b`` are lists of up to 32 tensors in the chain's
+    order, the other pointers tensors (on the GPU) or None"""
+    arr = (ErcResaeJob * max(1, len(jobs)))()
+    for dst, job in zip(arr, jobs):
+        for name, ctype in ErcResaeJob._fields_:
+            v = job.get(name)
+            if name in ("W", "b"):
+                v = list(v or [])
+                if len(v) > RESAE_LAYERS:
+                    raise ErcGraftError("resae job: %s has %d entries, the chain at most %d" % (name, len(v), RESAE_LAYERS))
+                for l in range(RESAE_LAYERS):
+                    getattr(dst, name)[l] = _gpu_ptr("resae job", "%s[%d]" % (name, l), v[l]) if l < len(v) else None
+            elif ctype is C.c_void_p:
+                setattr(dst, name, _gpu_ptr("resae job", name, v))
+            else:
+                setattr(dst, name, int(v or 0))
+    return arr
+
+
+def resae_fwd(jobs, n_blocks, n_jobs=None):
+    """``jobs``: a list of job dicts, or the array resae_jobs made of one (a step keeps it)"""
+    arr = jobs if isinstance(jobs, C.Array) else resae_jobs(jobs)
+    _call("erc_resae_fwd", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs, n_blocks)
+
+
+def resae_bwd(jobs, n_blocks, n_jobs=None):
+    arr = jobs if isinstance(jobs, C.Array) else resae_jobs(jobs)
+    _call("erc_resae_bwd", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs, n_blocks)
+
+
+def mse_grad(a, lda, b, ldb, B, n_cols, weight, d, ldd, loss_out):
+    """loss_out[0] = mean((a - b)^2); d = weight * 2 (a - b) / (B n_cols)"""
+    _call("erc_mse_grad", a, lda, b, ldb, B, n_cols, weight, d, ldd, loss_out)
+
+
+def mmin_miss_combine(dx0, dx1, dcyc, feat, ldf, B, dfeat, lddf, dtext, lddt, ce_stats, w_mse, w_cyc, stats):
+    _call("erc_mmin_miss_combine", dx0, dx1, dcyc, feat, ldf, B, dfeat, lddf, dtext, lddt, ce_stats, w_mse, w_cyc, stats)

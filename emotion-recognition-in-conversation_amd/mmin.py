@@ -2,7 +2,8 @@
 trainer of track_mm/mmin_base.py): an utterance classifier over three encoders -- a hidden-128 LSTM with a max-pool over time
 for the audio frames and one for the visual frames (LSTMEncoder 'maxpool', :43-95), a text CNN over the BERT token rows
 (TextCNN, :8-40) -- and a three-layer classifier over their concatenation (Classifier, :98-130).  ``mmin_miss`` / ``mmin_miss2``
-(not built) start from this model's checkpoint and reuse its encoders through ``encode``.
+start from this model's checkpoint and reuse its encoders through ``encode``: ``mmin_miss`` is erc_amd/mmin_miss.py,
+``mmin_miss2`` is not built.
 
 ``MMINBaseModule`` keeps the reference's constructor signature, its ``state_dict`` key for key and shape for shape (22 tensors,
 2 063 620 parameters at 342 / 1024 / 130 / 4, all live) and ``forward(**batch) -> (logits [B, C], feat [B, 128])``.  Built: fp32,
@@ -65,24 +66,29 @@ class _Classifier(nn.Module):
 
 
 class MMINBaseModule(nn.Module):
+    NAME = "mmin_base"
     DROP_TEXT, DROP_C = 0.5, 0.3
 
     def __init__(self, visual_dim=0, text_dim=0, audio_dim=0, n_classes=4, compute="f32", seed=1):
         super().__init__()
         if compute != "f32":
-            raise capi.ErcGraftError("mmin_base runs in fp32 only (the reference is fp32); compute=%r is not supported" % (compute, ))
+            raise capi.ErcGraftError("%s runs in fp32 only (the reference is fp32); compute=%r is not supported" % (self.NAME, compute))
         for name, d in (("visual_dim", visual_dim), ("text_dim", text_dim), ("audio_dim", audio_dim)):
             if int(d) < 1:
-                raise capi.ErcGraftError("mmin_base: %s=%r: the classifier reads all three encoders (its input is %d wide)" % (name, d, EMB))
+                raise capi.ErcGraftError("%s: %s=%r: all three encoders are read (their outputs side by side are %d wide)" % (self.NAME, name, d, EMB))
         if int(n_classes) < 2:
-            raise capi.ErcGraftError("mmin_base: n_classes=%r" % (n_classes, ))
+            raise capi.ErcGraftError("%s: n_classes=%r" % (self.NAME, n_classes))
         self.visual_dim, self.text_dim, self.audio_dim = int(visual_dim), int(text_dim), int(audio_dim)
         self.n_classes, self.compute = int(n_classes), compute
         self.netL = _TextCNN(self.text_dim)
         self.netA = _LSTMEncoder(self.audio_dim)
         self.netV = _LSTMEncoder(self.visual_dim)
-        self.netC = _Classifier(EMB, self.n_classes)
+        self._build_head()
         self.flat, self._ws, self._seed = None, WorkspaceCache(), seed
+
+    def _build_head(self):
+        """what follows the encoders, in the reference's registration order (MMINMissModule: the autoencoders come first)"""
+        self.netC = _Classifier(EMB, self.n_classes)
 
     # ------------------------------------------------------------------------------------------------------------ set-up
     def finalize(self, device):
@@ -134,26 +140,26 @@ class MMINBaseModule(nn.Module):
         for name, (x, d) in got.items():
             if x is None:
                 if need_all:
-                    raise capi.ErcGraftError("mmin_base: %s is missing: the classifier reads all three encoders (its input is %d "
-                                             "wide)" % (name, EMB))
+                    raise capi.ErcGraftError("%s: %s is missing: all three encoders are read (their outputs side by side are %d "
+                                             "wide)" % (self.NAME, name, EMB))
                 continue
             if x.dim() != 3 or int(x.shape[2]) != d or x.dtype != torch.float32 or int(x.shape[1]) < 1:
-                raise capi.ErcGraftError("mmin_base: %s must be fp32 [B, T >= 1, %d], got %s %s" % (name, d, x.dtype, tuple(x.shape)))
+                raise capi.ErcGraftError("%s: %s must be fp32 [B, T >= 1, %d], got %s %s" % (self.NAME, name, d, x.dtype, tuple(x.shape)))
             if B is not None and int(x.shape[0]) != B:
-                raise capi.ErcGraftError("mmin_base: %s has %d samples, the batch %d" % (name, int(x.shape[0]), B))
+                raise capi.ErcGraftError("%s: %s has %d samples, the batch %d" % (self.NAME, name, int(x.shape[0]), B))
             B = int(x.shape[0])
         if B is None:
-            raise capi.ErcGraftError("mmin_base: encode needs at least one of audio_feature, visual_feature, text_feature")
+            raise capi.ErcGraftError("%s: encode needs at least one of audio_feature, visual_feature, text_feature" % self.NAME)
         if text is not None and int(text.shape[1]) < capi.textcnn_min_t():
-            raise capi.ErcGraftError("mmin_base: text_feature has %d tokens, the widest convolution needs %d"
-                                     % (int(text.shape[1]), capi.textcnn_min_t()))
+            raise capi.ErcGraftError("%s: text_feature has %d tokens, the widest convolution needs %d"
+                                     % (self.NAME, int(text.shape[1]), capi.textcnn_min_t()))
         return B
 
     # ----------------------------------------------------------------------------------------------------------- forward
     def _encode(self, audio, visual, text, training, need_all=False):
         """the encoders that have an input, into their column ranges of ws["fused"]"""
         if self.flat is None:
-            raise capi.ErcGraftError("call MMINBaseModule.finalize(device) before forward")
+            raise capi.ErcGraftError("call %s.finalize(device) before forward" % type(self).__name__)
         B = self._inputs(audio, visual, text, need_all)
         T = [0 if x is None else int(x.shape[1]) for x in (audio, visual, text)]
         dev = next(x for x in (audio, visual, text) if x is not None).device
@@ -186,16 +192,20 @@ class MMINBaseModule(nn.Module):
         ws, _ = self._encode(audio_feature, visual_feature, text_feature, self.training)
         return [ws["fused"][:, n * HID:(n + 1) * HID] for n, x in enumerate((audio_feature, visual_feature, text_feature)) if x is not None]
 
-    def _forward_impl(self, audio, visual, text, training):
-        ws, B = self._encode(audio, visual, text, training, need_all=True)
+    def _classifier_fwd(self, ws, B, xin, k_in, training):
+        """netC on ``xin`` [B, k_in]: two Linear + ReLU + dropout 0.3 layers (the mask in the GEMM epilogue) -> feat, fc_out -> logits"""
         pl, C = ws["planner"], self.n_classes
         p = ws["p_c"] = self.DROP_C if training else 0.0
         if p > 0:
             torch.add(self.rng_state.unsqueeze(0), self._salt, out=self._rng2)
-        for n, (name, xin, k, out) in enumerate((("netC.module.0", ws["fused"], EMB, ws["z0"]), ("netC.module.3", ws["z0"], HID, ws["feat"]))):
-            linear_fwd(pl, xin, k, None, self._w(name + ".weight"), self._w(name + ".bias"), out, HID, B, HID, k,
+        for n, (name, x, k, out) in enumerate((("netC.module.0", xin, k_in, ws["z0"]), ("netC.module.3", ws["z0"], HID, ws["feat"]))):
+            linear_fwd(pl, x, k, None, self._w(name + ".weight"), self._w(name + ".bias"), out, HID, B, HID, k,
                        act=3 if p > 0 else 1, drop_p=p, rng=self._rng2[n] if p > 0 else None)
         linear_fwd(pl, ws["feat"], HID, None, self._w("netC.fc_out.weight"), self._w("netC.fc_out.bias"), ws["logits"], C, B, C, HID)
+
+    def _forward_impl(self, audio, visual, text, training):
+        ws, B = self._encode(audio, visual, text, training, need_all=True)
+        self._classifier_fwd(ws, B, ws["fused"], EMB, training)
         return ws, B
 
     def forward(self, audio_feature=None, visual_feature=None, text_feature=None, *args, **kwargs):
@@ -203,16 +213,13 @@ class MMINBaseModule(nn.Module):
         return ws["logits"], ws["feat"]
 
     # ---------------------------------------------------------------------------------------------------------- backward
-    def loss_and_grads(self, batch):
-        """mean cross entropy of the logits (mmin_base.py:131) and every gradient into flat.grad; returns the device stats
-        (stats[0] = loss, stats[1] = #correct)"""
-        ws, B = self._forward_impl(batch.get("audio_feature"), batch.get("visual_feature"), batch.get("text_feature"), self.training)
+    def _classifier_bwd(self, ws, B, xin, k_in, labels, stats):
+        """mean cross entropy of the logits into ``stats`` and netC's backward down to ws["dz0"] (the gradient wrt the first
+        layer's pre-activation).  Each layer's weight gradient joins the step's batched launch; the gradient wrt its input goes
+        through the ReLU / dropout mask of the layer below in the GEMM epilogue (aux = that layer's output)"""
         pl, C, p = ws["planner"], self.n_classes, ws["p_c"]
         scale = 1.0 / (1.0 - p)
-        capi.cross_entropy(ws["logits"], C, C, B, None, batch["label"], None, 1.0, ws["dlogits"], C, ws["stats"])
-        # the classifier: each layer's weight gradient joins the step's one batched launch; the gradient wrt its input goes
-        # through the ReLU / dropout mask of the layer below in the GEMM epilogue (aux = that layer's output)
-        W0 = self._w("netC.module.0.weight")
+        capi.cross_entropy(ws["logits"], C, C, B, None, labels, None, 1.0, ws["dlogits"], C, stats)
         linear_wgrad(pl, ws["dlogits"], C, ws["feat"], HID, None, C, HID, B, self._off("netC.fc_out.weight"), self._off("netC.fc_out.bias"),
                      defer=True)
         capi.gemm_f32(ws["dlogits"], C, 0, None, self._w("netC.fc_out.weight"), HID, 1, None, ws["dfeat"], HID, B, HID, C, act=2,
@@ -221,13 +228,13 @@ class MMINBaseModule(nn.Module):
                      self._off("netC.module.3.bias"), defer=True)
         capi.gemm_f32(ws["dfeat"], HID, 0, None, self._w("netC.module.3.weight"), HID, 1, None, ws["dz0"], HID, B, HID, HID, act=2,
                       aux=ws["z0"], ldaux=HID, act_scale=scale)
-        linear_wgrad(pl, ws["dz0"], HID, ws["fused"], EMB, None, HID, EMB, B, self._off("netC.module.0.weight"),
+        linear_wgrad(pl, ws["dz0"], HID, xin, k_in, None, HID, k_in, B, self._off("netC.module.0.weight"),
                      self._off("netC.module.0.bias"), defer=True)
-        # dfused: the audio | visual columns as they are (dpool of the two scans), the text columns through embd's ReLU
-        capi.gemm_f32(ws["dz0"], HID, 0, None, W0, EMB, 1, None, ws["dfused"], EMB, B, 2 * HID, HID)
-        capi.gemm_f32(ws["dz0"], HID, 0, None, W0[:, 2 * HID:], EMB, 1, None, ws["dtext"], HID, B, HID, HID, act=2,
-                      aux=ws["fused"][:, 2 * HID:], ldaux=EMB, act_scale=1.0)
-        e = ws["L"]
+
+    def _encoders_bwd(self, ws, B):
+        """from ws["dfused"][:, 0:256] (the two scans' dpool) and ws["dtext"] (the gradient wrt embd's pre-activation) down to
+        every encoder gradient"""
+        pl, e = ws["planner"], ws["L"]
         linear_wgrad(pl, ws["dtext"], HID, e["in"], EMB, None, HID, EMB, B, self._off("netL.embd.0.weight"), self._off("netL.embd.0.bias"),
                      defer=True)
         capi.gemm_f32(ws["dtext"], HID, 0, None, self._w("netL.embd.0.weight"), EMB, 1, None, e["dpd"], EMB, B, EMB, HID)
@@ -244,7 +251,19 @@ class MMINBaseModule(nn.Module):
                          self._off(net + ".rnn.bias_ih_l0"), defer=True)
             linear_wgrad(pl, s["dGX"], 4 * HID, s["Hprev"], HID, None, 4 * HID, HID, rows, self._off(net + ".rnn.weight_hh_l0"),
                          self._off(net + ".rnn.bias_hh_l0"), defer=True)
-        pl.reduce_into(ws, self.flat.grad)
+
+    def loss_and_grads(self, batch):
+        """mean cross entropy of the logits (mmin_base.py:131) and every gradient into flat.grad; returns the device stats
+        (stats[0] = loss, stats[1] = #correct)"""
+        ws, B = self._forward_impl(batch.get("audio_feature"), batch.get("visual_feature"), batch.get("text_feature"), self.training)
+        self._classifier_bwd(ws, B, ws["fused"], EMB, batch["label"], ws["stats"])
+        # dfused: the audio | visual columns as they are (dpool of the two scans), the text columns through embd's ReLU
+        W0 = self._w("netC.module.0.weight")
+        capi.gemm_f32(ws["dz0"], HID, 0, None, W0, EMB, 1, None, ws["dfused"], EMB, B, 2 * HID, HID)
+        capi.gemm_f32(ws["dz0"], HID, 0, None, W0[:, 2 * HID:], EMB, 1, None, ws["dtext"], HID, B, HID, HID, act=2,
+                      aux=ws["fused"][:, 2 * HID:], ldaux=EMB, act_scale=1.0)
+        self._encoders_bwd(ws, B)
+        ws["planner"].reduce_into(ws, self.flat.grad)
         return ws["stats"]
 
 
@@ -278,13 +297,14 @@ class MMINBaseTrainer(TrainerBase):
     ``prepare_batch``, ``to_logits`` and the optimizer set-up are TrainerBase's (a batch of this module has no ``text_length``:
     no ``n_nodes`` is added)."""
     NAME = "mmin_base"
+    MODULE = MMINBaseModule
     CLASS_WEIGHTED = False
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
         torch.manual_seed(params.seed)
-        self.model = MMINBaseModule(visual_dim=VISUAL_DIM, text_dim=TEXT_DIM, audio_dim=AUDIO_DIM, n_classes=params.n_classes,
-                                    compute=params.get("compute", "f32"), seed=params.seed).finalize(self.device)
+        self.model = self.MODULE(visual_dim=VISUAL_DIM, text_dim=TEXT_DIM, audio_dim=AUDIO_DIM, n_classes=params.n_classes,
+                                 compute=params.get("compute", "f32"), seed=params.seed).finalize(self.device)
         self._make_optim()
         self.use_ema = bool(params.get("ema", True))
         self.ema = self.model.flat.data.clone() if self.use_ema else None      # EMA(model): a deep copy of the parameters
@@ -343,6 +363,18 @@ class MMINBaseTrainer(TrainerBase):
         out.update(Lall=float(losses), Acc=float((host[0] == host[-1]).sum()) / out["C"], true=host[-1].tolist(), pred=host[0].tolist())
         return out
 
+    def load_pretrained(self, path):
+        """``--pretrain_path``: the whole trainer state of a ``mmin_base`` checkpoint"""
+        return load(self, path)
+
+    def extra_models(self):
+        """further entries of the checkpoint's ``models`` (MMINMissTrainer: the pretrained model)"""
+        return {}
+
+    @staticmethod
+    def make_loaders(params):
+        return make_loaders(params)
+
     def on_eval_end(self, rec):
         """the plateau scheduler on the validation epoch's accumulated loss (mmin_base.py:171-177); -> True when the learning
         rate changed (a captured step holds it as a launch argument and must be dropped)"""
@@ -372,6 +404,7 @@ def state_dict(trainer):
     if trainer.use_ema:
         flat = trainer.model.flat
         sd["models"]["ema_model"] = {k: flat.view(trainer.ema, k).detach().cpu().clone() for k in trainer.model.state_dict()}
+    sd["models"].update(trainer.extra_models())
     return sd
 
 
@@ -406,24 +439,42 @@ def mmin_collate(samples):
                 label=torch.tensor([int(s["label"]) for s in samples], dtype=torch.long), name=[s["name"] for s in samples])
 
 
-def make_loaders(params):
+class _Transformed(torch.utils.data.Dataset):
+    """samples with an output transform, applied at every read (one draw per sample per epoch)"""
+
+    def __init__(self, data, fn):
+        self.data, self.fn = data, fn
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, i):
+        return self.fn(dict(self.data[i]))
+
+
+def make_loaders(params, collate=None, transform=None, name="mmin_base"):
+    """the synthetic train / val / test loaders; ``collate``: stage -> collate function (default: mmin_collate everywhere),
+    ``transform``: applied to every TRAINING sample each time it is read (MMINMissDM's output transform)"""
     from torch.utils.data import DataLoader
     from .synthetic import make_mmin_samples
     if not params.get("synthetic", True):
         raise SystemExit("dataset %s: the .h5 feature readers of the reference need h5py, which this build cannot test against; "
-                         "only --synthetic=True is built for --module=mmin_base" % params.dataset)
+                         "only --synthetic=True is built for --module=%s" % (params.dataset, name))
     lo, hi = params.get("mmin_frames", (50, 400))
     out = []
     for split, n, grp in (("train", params.n_train, params.train), ("val", params.get("n_val", params.n_test), params.val),
                           ("test", params.n_test, params.test)):
         data = make_mmin_samples(n, split, seed=params.seed, frames=(int(lo), int(hi)), n_classes=params.n_classes)
+        if transform is not None and split == "train":
+            data = _Transformed(data, transform)
         gen = torch.Generator().manual_seed(params.seed)
-        out.append(DataLoader(data, batch_size=grp.batch_size, shuffle=(split == "train"), collate_fn=mmin_collate, generator=gen))
+        out.append(DataLoader(data, batch_size=grp.batch_size, shuffle=(split == "train"),
+                              collate_fn=mmin_collate if collate is None else collate(split), generator=gen))
     return out
 
 
 def run(trainer_cls, params_cls, argv=None):
-    """the epoch loop of --module=mmin_base: training steps (EMA after each), the validation epoch (plateau scheduler), the test
+    """the epoch loop of --module=mmin_base and --module=mmin_miss: training steps (EMA after each), the validation epoch (plateau scheduler), the test
     epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
     from .trainer import classification_report, fix_seed, print_step_lines, train_epoch_loader
     params = params_cls()
@@ -432,11 +483,11 @@ def run(trainer_cls, params_cls, argv=None):
         raise RuntimeError("the ERC hot path runs on an MI355X through libercgraft.so; no GPU is visible (there is no CPU fallback)")
     device = torch.device(params.device if params.device not in (None, "cuda") else "cuda:0")
     torch.cuda.set_device(device)
-    train_loader, val_loader, test_loader = make_loaders(params)
+    train_loader, val_loader, test_loader = trainer_cls.make_loaders(params)
     fix_seed(params.seed)
     trainer = trainer_cls(params, device)
     if params.get("pretrain_path"):
-        load(trainer, params.pretrain_path)
+        trainer.load_pretrained(params.pretrain_path)
     ring = torch.zeros(max(1, len(train_loader)), 4, dtype=torch.float32, device=device)
     last = {}
     for epoch in range(params.epoch):
@@ -444,7 +495,7 @@ def run(trainer_cls, params_cls, argv=None):
         counts = train_epoch_loader(train_loader, None, trainer, ring)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        trainer.model.flat.check_health("mmin_base")
+        trainer.model.flat.check_health(trainer.NAME)
         if params.log_every:
             print_step_lines(params, epoch, ring, counts)
         val = trainer.eval_epoch(val_loader)

@@ -36,7 +36,7 @@ DATASETS = tuple(
 # are out of scope.
 MOSEI_DATASETS = ("mosei-cim-2",)
 # MMIN's IEMOCAP utterance features (:31: ComParE audio frames, DenseFace visual frames, BERT token rows; four classes), read by
-# --module=mmin_base only
+# --module=mmin_base and --module=mmin_miss only
 MMIN_DATASETS = ("iemocap-mmin-4",)
 ALL_DATASETS = DATASETS + MOSEI_DATASETS + MMIN_DATASETS
 

@@ -1613,6 +1613,77 @@ int erc_textcnn_pool_bwd(const float* x, int B, int T, int D, const float* poole
 int erc_ema_step(float* ema, const float* p, int64_t n, float alpha, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MMIN missing-modality model (track_mm/mmin_miss.py:68-107,191-223): the residual autoencoders and the MSE pair.
+ *
+ * erc_resae_fwd / _bwd replace ResidualAE.forward (mmin_models.py:187-199) and its autograd for layers = [256, 128, 64],
+ * input_dim = erc_resae_input() = 384, use_bn = False, dropout = 0 (the only settings MMINMissModule uses, mmin_miss.py:79-80;
+ * the host refuses anything else), n_blocks in [1, erc_resae_max_blocks() = 5], LeakyReLU slope 0.01.  A JOB is one autoencoder
+ * over one batch; up to erc_resae_max_jobs() = 2 jobs (netAE and netAE_cycle) share a launch, and a job's results do not depend
+ * on the other job.  A workgroup owns erc_resae_rows_per_group() = 16 rows of one job and runs the whole chain for them; the
+ * workgroups of a launch never wait for each other.  Any B >= 1.  Exact fp32 products (v_mfma_f32_16x16x4_f32).
+ *   W[l], b[l]  layer l of the chain, weight [out, in] (16-byte aligned) and bias [out], in the order of the state_dict:
+ *               block i: l = 6i + {0,1,2} = encoder_i.{0,2,4} (384->256->128->64, LeakyReLU after the first two),
+ *               6i + {3,4,5} = decoder_i.{0,2,4} (64->128->256->384, ReLU after the first two); 6 n_blocks + {0,1} =
+ *               transition.{0,2} (384->384, ReLU, 384->384)
+ *   x       [B, ldx >= 384]                                                      forward in
+ *   recon   [B, ldr >= 384] = transition(x_in + x_out) of the last block         forward out
+ *   latents [B, ldl >= 64 n_blocks]: block i's latent in columns [64i, 64i + 64)  forward out
+ *   act     erc_resae_act_floats(B, n_blocks) = B (1216 n_blocks + 768) floats, 16-byte aligned: the INPUT rows of every layer,
+ *           each a dense [B, width] matrix (the operand of that layer's weight-gradient product), block i at float offset
+ *           1216 B i: x_in [B,384] at +0, h1 [B,256] at +384 B, h2 [B,128] at +640 B, latent [B,64] at +768 B, g1 [B,128] at
+ *           +832 B, g2 [B,256] at +960 B (x_in_0 = x, x_in_i = x_in_{i-1} + x_out_{i-1}); then t_in [B,384] | t1 [B,384].
+ *           h*, g*, t1 are POST-activation: out > 0 is the ReLU / LeakyReLU mask of the backward      forward out, backward in
+ *   d_recon   [B, lddr >= 384]; d_latents [B, lddl >= 64 n_blocks] or NULL (= zero)                    backward in
+ *   dx      [B, lddx >= 384] gradient wrt x, written (not accumulated)                                 backward out
+ *   dY      erc_resae_act_floats(B, n_blocks) floats, 16-byte aligned: the gradient wrt the PRE-activation output of every
+ *           layer, dense [B, width], block i at 1216 B i: encoder_i.0 [B,256] at +0, .2 [B,128] at +256 B, .4 [B,64] at +384 B,
+ *           decoder_i.0 [B,128] at +448 B, .2 [B,256] at +576 B, .4 [B,384] at +832 B; then transition.0 [B,384] |
+ *           transition.2 [B,384] (a copy of d_recon)                                                     backward out
+ * dW_l = dY_l^T (layer l's input rows) and db_l = column sums of dY_l are the caller's (erc_wgrad_table).  Write sets are
+ * exactly the buffers above; a repeated launch is bit-identical.  Bad arguments (null pointer, B <= 0, a pitch below its
+ * width, n_blocks or n_jobs out of range, a weight / act / dY that is not 16-byte aligned) give ERC_E_ARG before any launch. */
+typedef struct ErcResaeJob {
+    const float* W[32];
+    const float* b[32];
+    const float* x;
+    float* recon;
+    float* latents;
+    float* act;
+    const float* d_recon;
+    const float* d_latents;
+    float* dx;
+    float* dY;
+    int32_t B, ldx, ldr, ldl, lddr, lddl, lddx, reserved;
+} ErcResaeJob;
+int erc_resae_input(void);
+int erc_resae_latent(void);
+int erc_resae_max_jobs(void);
+int erc_resae_max_blocks(void);
+int erc_resae_rows_per_group(void);
+int64_t erc_resae_act_floats(int B, int n_blocks);
+int erc_resae_fwd(const ErcResaeJob* jobs_host, int n_jobs, int n_blocks, void* stream);
+int erc_resae_bwd(const ErcResaeJob* jobs_host, int n_jobs, int n_blocks, void* stream);
+
+/* F.mse_loss(a, b) (mmin_miss.py:207-208) over [B, n_cols] with its gradient: loss_out[0] = mean((a - b)^2) (unweighted; a
+ * slot of the step's stats), d [B, ldd] = weight * 2 (a - b) / (B n_cols): the gradient of weight * loss wrt a, its negative
+ * wrt b.  One workgroup; the sum is taken in double in a fixed order (deterministic).  Null pointer, B or n_cols <= 0, a pitch
+ * below n_cols: ERC_E_ARG. */
+int erc_mse_grad(const float* a, int lda, const float* b, int ldb, int B, int n_cols, float weight, float* d, int ldd,
+                 float* loss_out, void* stream);
+
+/* The feature gradient of MMINMissTrainer.train_step (mmin_miss.py:196-213) and the step's loss slots, one launch.
+ * netAE_cycle reads `features` (mmin_miss.py:104) and Lcycle = mse(features, fusion_cycle) reads them again, so
+ *   dfeat [B, lddf >= 384] = dx0 + dx1 - dcyc   (dx0 / dx1: erc_resae_bwd's dx of netAE / netAE_cycle, dcyc: erc_mse_grad's d
+ *                                                with a = fusion_cycle, b = features; all three dense [B, 384])
+ *   dtext [B, lddt >= 128] = dfeat[:, 256:384] where feat[:, 256:384] > 0, else 0 (the ReLU of TextCNN.embd, mmin_models.py:19-22)
+ *   stats[0] = ce_stats[0] + w_mse stats[2] + w_cyc stats[3] (Lall), stats[1] = ce_stats[1] (#correct), stats[4] = ce_stats[0]
+ *   (Lce); stats[2] / stats[3] are the two erc_mse_grad losses the caller put there.  feat [B, ldf >= 384].
+ * Null pointer, B <= 0 or a pitch below its width: ERC_E_ARG. */
+int erc_mmin_miss_combine(const float* dx0, const float* dx1, const float* dcyc, const float* feat, int ldf, int B,
+                          float* dfeat, int lddf, float* dtext, int lddt, const float* ce_stats, float w_mse, float w_cyc,
+                          float* stats, void* stream);
+
+/* ------------------------------------------------------------------------
  * Launch chain: a captured step replayed as PLAIN kernel launches from native code.
  * A training step captured into a HIP graph (one stream, kernels only) is a simple path of kernel nodes.  Replaying the
  * graph leaves the queue idle between two replays (DESIGN.md findings 48, 64); the same kernels launched one by one on a

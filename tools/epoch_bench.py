@@ -61,9 +61,13 @@ PRESETS = {
                  "mosei": ["--dataset=mosei-cim-2", "--modality=atv", "--n_train=2240", "--n_test=672"]}),
     "dagerc": (16, {"bf16": IEMOCAP + ["--compute=bf16"], "f32": IEMOCAP + ["--compute=f32"]}),
     "mmgcn": (16, {"iemocap": IEMOCAP + ["--modality=atv"]}),
+    # listed so that the plugin resolves here; every mode is skipped (below): tools/mmin_miss_bench.py times this module
+    "mmin_miss": (32, {"iemocap": ["--dataset=iemocap-mmin-4", "--n_train=120", "--n_test=31"]}),
 }
 # the multi-label metrics of CMU-MOSEI are no function of a confusion matrix; bc-LSTM / bc-GRU have no scored test step
-SKIPPED = {("cim", "mosei"): {"resident_eval"}, ("bclstm", None): {"resident_eval"}, ("bcgru", None): {"resident_eval"}}
+# mmin_miss runs mmin_base's loop (three loaders, no graphs, none of these modes)
+SKIPPED = {("cim", "mosei"): {"resident_eval"}, ("bclstm", None): {"resident_eval"}, ("bcgru", None): {"resident_eval"},
+           ("mmin_miss", None): set(MODES) | {"steps"}}
 
 
 def skipped(module, config, mode):
@@ -276,6 +280,8 @@ def main(argv=None):
     if a.module not in PRESETS:
         plugin(a.module)          # (mmin_base: refused with its message)
         raise SystemExit("--module=%s has no preset; known: %s" % (a.module, ", ".join(sorted(PRESETS))))
+    if all(skipped(a.module, None, m) for m in MODES):
+        raise SystemExit("--module=%s has none of these modes (it runs mmin_base's loop): tools/%s_bench.py" % (a.module, a.module))
     if a.child:
         return child(a)
     for config in [c for c in a.config.split(",") if c] or list(PRESETS[a.module][1]):
