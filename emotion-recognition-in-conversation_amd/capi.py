@@ -1358,6 +1358,42 @@ def lstm128_pool_bwd(jobs, n_jobs=None):
     _call("erc_lstm128_pool_bwd", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs)
 
 
+def lstm128_pool_fwd_tcap(jobs, counts, dyn_mask, n_jobs=None):
+    """capacity form: the jobs' B / T are capacities, ``counts`` = {B, Ta} int32 on the device, bit i of ``dyn_mask``: job i
+    runs counts[1] steps (ercgraft.h)"""
+    arr = jobs if isinstance(jobs, C.Array) else lstm128_jobs(jobs)
+    _call("erc_lstm128_pool_fwd_tcap", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs, counts, dyn_mask)
+
+
+def lstm128_pool_bwd_tcap(jobs, counts, dyn_mask, n_jobs=None):
+    arr = jobs if isinstance(jobs, C.Array) else lstm128_jobs(jobs)
+    _call("erc_lstm128_pool_bwd_tcap", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs, counts, dyn_mask)
+
+
+def mmin_collate_width(modality):
+    return int(lib().erc_mmin_collate_width(modality))
+
+
+def mmin_collate(desc, store_audio, store_visual, store_text, store_label, B_cap, T_cap, frames_max, audio, visual, text, label,
+                 counts):
+    """``store_*``: the split in HBM (audio [n_frames, 130] ragged, visual [n, Tv, 342], text [n, Tt, 1024], label [n]); ``desc``
+    int32 [3 B_cap] on the device: frames | first frame row | sample index; writes every element of the five outputs"""
+    for name, x, dt in (("desc", desc, torch.int32), ("store_label", store_label, torch.int64), ("label", label, torch.int64),
+                        ("counts", counts, torch.int32), ("store_audio", store_audio, torch.float32),
+                        ("store_visual", store_visual, torch.float32), ("store_text", store_text, torch.float32),
+                        ("audio", audio, torch.float32), ("visual", visual, torch.float32), ("text", text, torch.float32)):
+        if x is not None and (x.dtype != dt or not x.is_contiguous()):
+            raise ErcGraftError("mmin_collate: %s must be a contiguous %s tensor" % (name, dt))
+    n, Tv, Tt = (int(store_visual.shape[0]), int(store_visual.shape[1]), int(store_text.shape[1])) \
+        if store_visual is not None and store_text is not None else (0, 0, 0)
+    need = dict(desc=3 * B_cap, audio=B_cap * T_cap * 130, visual=B_cap * Tv * 342, text=B_cap * Tt * 1024, label=B_cap, counts=2)
+    for name, x in (("desc", desc), ("audio", audio), ("visual", visual), ("text", text), ("label", label), ("counts", counts)):
+        if x is not None and B_cap > 0 and T_cap > 0 and x.numel() < need[name]:
+            raise ErcGraftError("mmin_collate: %s holds %d elements, B_cap=%d T_cap=%d needs %d" % (name, x.numel(), B_cap, T_cap, need[name]))
+    _call("erc_mmin_collate", desc, store_audio, 0 if store_audio is None else int(store_audio.shape[0]), store_visual, store_text,
+          store_label, n, Tv, Tt, B_cap, T_cap, frames_max, audio, visual, text, label, counts)
+
+
 def textcnn_min_t():
     return int(lib().erc_textcnn_min_t())
 

@@ -19,8 +19,13 @@
 // lanes = 4 units; lane `part` of the row multiplies gate gradients [32 part, 32 part + 32) into the row's 4 units) and
 // writes dGX on every row; all weight gradients are the caller's GEMMs over dGX, x and Hprev.
 //
-// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): forward 202 VGPRs, backward 210 VGPRs, no AGPRs,
-// no scratch, no spills, occupancy 2 wavefronts per SIMD (= the 512 threads of one workgroup: up to 256 registers per lane).
+// Capacity forms (erc_lstm128_pool_fwd_tcap / _bwd_tcap: one captured step for every batch of a bucket): the same kernels
+// instantiated with MODE = Capacity read the batch's sample count and audio length from device memory; a job's B and T then
+// size the launch and pitch the rows.  Per sample the code is the exact form's.
+//
+// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), both modes alike: forward 202 VGPRs, backward 210
+// VGPRs, no AGPRs, no scratch, no spills, occupancy 2 wavefronts per SIMD (= the 512 threads of one workgroup: up to 256
+// registers per lane).
 #include "rnn100_dev.h"
 
 namespace {
@@ -36,11 +41,37 @@ struct Jobs {
     ErcLstm128Job j[MAX_JOBS];
 };
 
-__global__ __launch_bounds__(NTH) void lstm128_fwd_kernel(Jobs P) {
+// T and B capacity (erc_lstm128_pool_*_tcap): the job's B and T size the launch and pitch the rows, counts = {B, Ta} of the
+// batch is read on the device.  Job i runs counts[1] steps when bit i of dyn_mask is set (audio), its own T otherwise (visual).
+struct Exact {
+    static constexpr bool CAP = false;
+};
+struct Capacity {
+    static constexpr bool CAP = true;
+    const int32_t* counts;
+    int dyn_mask;
+    __device__ __forceinline__ int B(const ErcLstm128Job& p) const { return min(max(counts[0], 0), p.B); }
+    __device__ __forceinline__ int T(const ErcLstm128Job& p) const {
+        return (dyn_mask >> blockIdx.y) & 1 ? min(max(counts[1], 1), p.T) : p.T;
+    }
+};
+
+// MODE = Exact: every sample runs the job's T steps.  MODE = Capacity: T steps of rows pitched p.T steps apart per sample; a
+// slot the batch does not have pools to zero and writes nothing else.
+template <class MODE>
+__global__ __launch_bounds__(NTH) void lstm128_fwd_kernel(Jobs P, MODE mode) {
     const ErcLstm128Job& p = P.j[blockIdx.y];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (b >= p.B) return;      // uniform: the grid is sized for the larger job
-    const int T = p.T;
+    int T = p.T;
+    if constexpr (MODE::CAP) {
+        if (b >= mode.B(p)) {  // uniform
+            if (tid < H) p.pool[(int64_t)b * p.ldp + tid] = 0.f;
+            return;
+        }
+        T = mode.T(p);
+    }
+    const int TP = p.T;
     __shared__ __attribute__((aligned(16))) float s_h[2][4 * KP];
     const int u = tid >> 2, q = tid & 3;
     const int gcol = q * H + u;       // the gate this thread activates: its column of GX / gates
@@ -60,7 +91,7 @@ __global__ __launch_bounds__(NTH) void lstm128_fwd_kernel(Jobs P) {
     float c = 0.f, hprev = 0.f, best = -2.f;    // |h| < 1
     int best_t = 0;
     __syncthreads();
-    const int64_t row0 = (int64_t)b * T;
+    const int64_t row0 = (int64_t)b * TP;
     const float* const gx0 = p.GX + row0 * G4 + gcol;
     float* const gate0 = p.gates + row0 * G4 + gcol;
     // the unit's per-step outputs: lane 0 stores c, lane 1 h_{t-1}
@@ -130,11 +161,23 @@ __global__ __launch_bounds__(NTH) void lstm128_fwd_kernel(Jobs P) {
     }
 }
 
-__global__ __launch_bounds__(NTH) void lstm128_bwd_kernel(Jobs P) {
+// MODE = Capacity: dGX rows the scan does not reach (t >= T, and every row of a slot the batch does not have) are written
+// zero, 16 bytes a store (a dGX row is 2048 bytes), before the scan starts: the weight-gradient products over all B * T rows
+// then add exact zeros.
+template <class MODE>
+__global__ __launch_bounds__(NTH) void lstm128_bwd_kernel(Jobs P, MODE mode) {
     const ErcLstm128Job& p = P.j[blockIdx.y];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (b >= p.B) return;      // uniform
-    const int T = p.T;
+    int T = p.T;
+    if constexpr (MODE::CAP) {
+        T = b >= mode.B(p) ? 0 : mode.T(p);
+        f4* const tail = reinterpret_cast<f4*>(p.dGX + ((int64_t)b * p.T + T) * G4);
+        const int n4 = (p.T - T) * (G4 / 4);
+        for (int i = tid; i < n4; i += NTH) tail[i] = f4{0.f, 0.f, 0.f, 0.f};
+        if (T == 0) return;    // uniform
+    }
+    const int TP = p.T;
     __shared__ __attribute__((aligned(16))) float s_dp[2][16 * KP];     // gate gradients of the step, entry q*H + u chunked
     const int u = tid >> 2, q = tid & 3;
     const int part = tid & 15, u0 = (tid >> 4) * 4, myr = (tid >> 2) & 3;
@@ -146,7 +189,7 @@ __global__ __launch_bounds__(NTH) void lstm128_bwd_kernel(Jobs P) {
         wt23[i] = f2{src[2], src[3]};
     }
     const int gcol = q * H + u;
-    const int64_t row0 = (int64_t)b * T;
+    const int64_t row0 = (int64_t)b * TP;
     const float* const gate0 = p.gates + row0 * G4 + gcol;
     const float* const c0p = p.Cst + row0 * H + u;
     float* const dgx0 = p.dGX + row0 * G4 + gcol;
@@ -248,7 +291,7 @@ extern "C" int erc_lstm128_pool_fwd(const ErcLstm128Job* jobs_host, int n_jobs, 
     Jobs P;
     int max_b = 0;
     if (int e = fill("lstm128_pool_fwd", P, jobs_host, n_jobs, false, max_b)) return e;
-    hipLaunchKernelGGL(lstm128_fwd_kernel, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(lstm128_fwd_kernel<Exact>, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P, Exact{});
     ERC_LAUNCH_CHECK("lstm128_pool_fwd");
     return ERC_OK;
 }
@@ -257,7 +300,37 @@ extern "C" int erc_lstm128_pool_bwd(const ErcLstm128Job* jobs_host, int n_jobs, 
     Jobs P;
     int max_b = 0;
     if (int e = fill("lstm128_pool_bwd", P, jobs_host, n_jobs, true, max_b)) return e;
-    hipLaunchKernelGGL(lstm128_bwd_kernel, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(lstm128_bwd_kernel<Exact>, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P, Exact{});
     ERC_LAUNCH_CHECK("lstm128_pool_bwd");
+    return ERC_OK;
+}
+
+static int tcap_args(const char* name, const int32_t* counts, int dyn_mask, int n_jobs) {
+    ERC_REQUIRE(counts, "%s: null counts", name);
+    ERC_REQUIRE(dyn_mask >= 0 && dyn_mask < (1 << n_jobs), "%s: dyn_mask=%d names a job beyond n_jobs=%d", name, dyn_mask, n_jobs);
+    return ERC_OK;
+}
+
+extern "C" int erc_lstm128_pool_fwd_tcap(const ErcLstm128Job* jobs_host, int n_jobs, const int32_t* counts, int dyn_mask,
+                                         void* stream) {
+    Jobs P;
+    int max_b = 0;
+    if (int e = fill("lstm128_pool_fwd_tcap", P, jobs_host, n_jobs, false, max_b)) return e;
+    if (int e = tcap_args("lstm128_pool_fwd_tcap", counts, dyn_mask, n_jobs)) return e;
+    hipLaunchKernelGGL(lstm128_fwd_kernel<Capacity>, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P, Capacity{counts, dyn_mask});
+    ERC_LAUNCH_CHECK("lstm128_pool_fwd_tcap");
+    return ERC_OK;
+}
+
+extern "C" int erc_lstm128_pool_bwd_tcap(const ErcLstm128Job* jobs_host, int n_jobs, const int32_t* counts, int dyn_mask,
+                                         void* stream) {
+    Jobs P;
+    int max_b = 0;
+    if (int e = fill("lstm128_pool_bwd_tcap", P, jobs_host, n_jobs, true, max_b)) return e;
+    if (int e = tcap_args("lstm128_pool_bwd_tcap", counts, dyn_mask, n_jobs)) return e;
+    for (int i = 0; i < n_jobs; ++i)
+        ERC_REQUIRE(((uintptr_t)jobs_host[i].dGX & 15) == 0, "lstm128_pool_bwd_tcap: job %d: dGX is not 16-byte aligned", i);
+    hipLaunchKernelGGL(lstm128_bwd_kernel<Capacity>, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P, Capacity{counts, dyn_mask});
+    ERC_LAUNCH_CHECK("lstm128_pool_bwd_tcap");
     return ERC_OK;
 }

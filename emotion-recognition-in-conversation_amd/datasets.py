@@ -205,3 +205,62 @@ class DeviceDialogueStore:
         out.update(seq)
         assert out["label"].shape[0] == N
         return out
+
+
+# --------------------------------------------------------------------------------------------- MMIN utterances in HBM
+MMIN_T_BUCKET = 64      # audio frame capacities are multiples of this
+
+
+def mmin_t_cap(ta, t_max):
+    """T capacity of a batch whose longest utterance has ``ta`` audio frames: ``ta`` rounded up to a multiple of MMIN_T_BUCKET,
+    at most ``t_max`` (the split's longest utterance; 0 or None: no limit)"""
+    cap = -(-int(ta) // MMIN_T_BUCKET) * MMIN_T_BUCKET
+    return min(cap, int(t_max)) if t_max else cap
+
+
+class MMINDeviceStore:
+    """One split of MMIN utterance samples (synthetic.make_mmin_samples, or the reference readers' dicts) on ``device``: the
+    audio frames of all utterances as one ragged matrix ``audio`` [sum t_i, 130] with ``lengths`` / ``offsets`` (host int64, as
+    DeviceDialogueStore's), ``visual`` [n, 50, 342], ``text`` [n, 22, 1024], ``label`` [n] int64.  A batch is never
+    materialised on the host: ``desc`` gives the 3 B_cap int32 erc_mmin_collate reads (frames | first frame row | sample index,
+    empty slots last).  ``device=None`` keeps everything on the host (tests of the tables)."""
+
+    def __init__(self, samples, device=None):
+        f32 = lambda key: [np.asarray(s[key], dtype=np.float32) for s in samples]
+        audio = f32("audio_feature")
+        self.device = torch.device("cpu") if device is None else torch.device(device)
+        self.lengths = torch.tensor([a.shape[0] for a in audio], dtype=torch.int64)
+        self.offsets = torch.zeros(len(audio) + 1, dtype=torch.int64)
+        self.offsets[1:] = torch.cumsum(self.lengths, 0)
+        self.t_max = int(self.lengths.max()) if len(audio) else 0
+        self.audio = torch.from_numpy(np.concatenate(audio, 0)).to(self.device)
+        self.visual = torch.from_numpy(np.stack(f32("visual_feature"))).to(self.device)
+        self.text = torch.from_numpy(np.stack(f32("text_feature"))).to(self.device)
+        self.label = torch.tensor([int(s["label"]) for s in samples], dtype=torch.int64).to(self.device)
+        self._lens32, self._offs32 = self.lengths.to(torch.int32).numpy(), self.offsets[:-1].to(torch.int32).numpy()
+
+    def __len__(self):
+        return int(self.lengths.numel())
+
+    def desc(self, indices, B_cap):
+        """host int32 [3 B_cap] of the batch ``indices`` (at most B_cap of them)"""
+        return self.table([list(indices)], B_cap)[0][0]
+
+    def table(self, batches, B_cap):
+        """(int32 array [len(batches), 3 B_cap], the batches' T capacities) of an epoch's batches (lists of sample indices)"""
+        tab = np.zeros((len(batches), 3, B_cap), dtype=np.int32)
+        caps = []
+        for row, idx in zip(tab, batches):
+            idx = np.asarray(idx, dtype=np.int64)
+            if idx.size > B_cap:
+                raise ValueError("a batch of %d samples does not fit B_cap=%d" % (idx.size, B_cap))
+            row[0, :idx.size], row[1, :idx.size], row[2, :idx.size] = self._lens32[idx], self._offs32[idx], idx
+            caps.append(mmin_t_cap(row[0].max(), self.t_max))
+        return tab.reshape(len(batches), 3 * B_cap), caps
+
+
+def index_batches(n, batch_size, shuffle, generator=None):
+    """the sample indices of one epoch's batches exactly as ``DataLoader(data, batch_size, shuffle, generator=generator)``
+    visits them (it IS a DataLoader, over the indices: same sampler, same draws from ``generator``, a short last batch)"""
+    from torch.utils.data import DataLoader
+    return [list(b) for b in DataLoader(range(n), batch_size=batch_size, shuffle=shuffle, generator=generator, collate_fn=list)]

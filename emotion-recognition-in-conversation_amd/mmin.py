@@ -20,6 +20,13 @@ Launches of a training step:
             | erc_dropout_fwd on the gradient (same mask) | erc_textcnn_pool_bwd | erc_lstm128_pool_bwd (one launch)
             | erc_wgrad_table: every Linear / LSTM weight gradient and bias sum, one launch
   update    erc_adam_step | erc_ema_step
+
+From HBM (opt-in): in capacity mode a batch that carries ``counts`` (device int32 {B, Ta}) is a BUCKET --
+fixed buffers of train.batch_size slots and an audio capacity of a multiple of 64 frames -- and the step above runs on it with
+erc_lstm128_pool_fwd_tcap / _bwd_tcap and erc_cross_entropy_cap + erc_mm_zero_tail; every other launch is the same.
+``--capacity_buckets=True`` feeds host-collated batches through trainer.StepGraphs, ``--device_collate --resident`` keeps the
+training split in a datasets.MMINDeviceStore and replays erc_mmin_collate + step + Adam + EMA per 3 B int32
+(``MMINResidentEpochs``), ``--resident_eval`` scores the validation and test epochs on the device (``MMINResidentEval``).
 """
 import json
 import os
@@ -31,7 +38,9 @@ from torch import nn
 
 from . import capi
 from .capacity import TrainerBase
-from .engine import FlatParams, GemmPlanner, WorkspaceCache, linear_fwd, linear_wgrad
+from .datasets import MMINDeviceStore, index_batches, mmin_t_cap
+from .engine import FlatParams, GemmPlanner, WorkspaceCache, _world_size, linear_fwd, linear_wgrad
+from .trainer import ResidentLoop, StepGraphs, dynamic_n, report_from_cm
 
 HID, EMB = 128, 384
 AUDIO_DIM, VISUAL_DIM, TEXT_DIM = 130, 342, 1024     # mmin_base.py:86-91: constants of the trainer
@@ -68,6 +77,7 @@ class _Classifier(nn.Module):
 class MMINBaseModule(nn.Module):
     NAME = "mmin_base"
     DROP_TEXT, DROP_C = 0.5, 0.3
+    dynamic_n = False      # capacity mode (trainer.dynamic_n): a batch with ``counts`` is a bucket, its sizes are capacities
 
     def __init__(self, visual_dim=0, text_dim=0, audio_dim=0, n_classes=4, compute="f32", seed=1):
         super().__init__()
@@ -131,6 +141,7 @@ class MMINBaseModule(nn.Module):
                                  pool=ws["fused"][:, n * HID:], arg=e["arg"], gates=e["gates"], Cst=e["Cst"], Hprev=e["Hprev"],
                                  dpool=ws["dfused"][:, n * HID:], dGX=e["dGX"], B=B, T=e["T"], ldp=EMB, lddp=EMB))
         ws["n_jobs"], ws["jobs"] = len(jobs), capi.lstm128_jobs(jobs)
+        ws["dyn_mask"] = 1 if "A" in ws else 0      # capacity mode: the audio job (the first) reads its length from the device
         ws["planner"] = GemmPlanner(device, 1 << 16, grad=self.flat.grad)
         return ws
 
@@ -156,14 +167,19 @@ class MMINBaseModule(nn.Module):
         return B
 
     # ----------------------------------------------------------------------------------------------------------- forward
-    def _encode(self, audio, visual, text, training, need_all=False):
-        """the encoders that have an input, into their column ranges of ws["fused"]"""
+    def _encode(self, audio, visual, text, training, need_all=False, counts=None):
+        """the encoders that have an input, into their column ranges of ws["fused"].  ``counts`` (device int32 {B, Ta}, written
+        by erc_mmin_collate or by the bucket's fill): the inputs are a bucket's, B and the audio length are capacities, and the
+        scans and the loss read the batch's own sizes from it; a bucket has workspaces of its own, one
+        for training and one for evaluation"""
         if self.flat is None:
             raise capi.ErcGraftError("call %s.finalize(device) before forward" % type(self).__name__)
         B = self._inputs(audio, visual, text, need_all)
         T = [0 if x is None else int(x.shape[1]) for x in (audio, visual, text)]
         dev = next(x for x in (audio, visual, text) if x is not None).device
-        ws = self._ws.get((B, *T), lambda: self._make_workspace(B, *T, dev))
+        key = (B, *T) if counts is None else (B, *T, "capacity", bool(training))
+        ws = self._ws.get(key, lambda: self._make_workspace(B, *T, dev))
+        ws["counts"] = counts
         pl = ws["planner"]
         pl.reset()
         for tag, net, x in (("A", "netA", audio), ("V", "netV", visual)):
@@ -172,8 +188,10 @@ class MMINBaseModule(nn.Module):
                 e["x"] = x = x.contiguous()
                 linear_fwd(pl, x, int(x.shape[2]), None, self._w(net + ".rnn.weight_ih_l0"), self._w(net + ".rnn.bias_ih_l0"), e["GX"],
                            4 * HID, B * e["T"], 4 * HID, int(x.shape[2]))
-        if ws["n_jobs"]:
+        if ws["n_jobs"] and counts is None:
             capi.lstm128_pool_fwd(ws["jobs"], ws["n_jobs"])
+        elif ws["n_jobs"]:
+            capi.lstm128_pool_fwd_tcap(ws["jobs"], counts, ws["dyn_mask"], ws["n_jobs"])
         if text is not None:
             e = ws["L"]
             e["x"] = x = text.contiguous()
@@ -203,14 +221,29 @@ class MMINBaseModule(nn.Module):
                        act=3 if p > 0 else 1, drop_p=p, rng=self._rng2[n] if p > 0 else None)
         linear_fwd(pl, ws["feat"], HID, None, self._w("netC.fc_out.weight"), self._w("netC.fc_out.bias"), ws["logits"], C, B, C, HID)
 
-    def _forward_impl(self, audio, visual, text, training):
-        ws, B = self._encode(audio, visual, text, training, need_all=True)
+    def _forward_impl(self, audio, visual, text, training, counts=None):
+        ws, B = self._encode(audio, visual, text, training, need_all=True, counts=counts)
         self._classifier_fwd(ws, B, ws["fused"], EMB, training)
         return ws, B
 
+    def _counts(self, batch):
+        """the bucket's {B, Ta} in capacity mode, None for an exact-shape batch"""
+        return batch.get("counts") if self.dynamic_n else None
+
     def forward(self, audio_feature=None, visual_feature=None, text_feature=None, *args, **kwargs):
-        ws, _ = self._forward_impl(audio_feature, visual_feature, text_feature, self.training)
+        ws, _ = self._forward_impl(audio_feature, visual_feature, text_feature, self.training, self._counts(kwargs))
         return ws["logits"], ws["feat"]
+
+    def eval_scores(self, batch, cm, loss_sum):
+        """one evaluation step of a bucket scored on the device: the forward in eval mode (its own workspace; neither the
+        training flag nor the dropout counter is touched), the batch-mean cross entropy ADDED to ``loss_sum`` (float64 [1]) and
+        the batch's confusion matrix added to ``cm`` (int64 [C, C], true x predicted).  No host sync.  -> the workspace"""
+        C, cnt = self.n_classes, batch["counts"]
+        ws, B = self._forward_impl(batch["audio_feature"], batch["visual_feature"], batch["text_feature"], False, cnt)
+        capi.cross_entropy_cap(ws["logits"], C, C, B, cnt, None, batch["label"], None, 1.0, None, C, ws["stats"])
+        loss_sum.add_(ws["stats"][:1])
+        capi.rows_score(ws["logits"], C, B, C, B, cnt, None, batch["label"], cm)
+        return ws
 
     # ---------------------------------------------------------------------------------------------------------- backward
     def _classifier_bwd(self, ws, B, xin, k_in, labels, stats):
@@ -219,7 +252,11 @@ class MMINBaseModule(nn.Module):
         through the ReLU / dropout mask of the layer below in the GEMM epilogue (aux = that layer's output)"""
         pl, C, p = ws["planner"], self.n_classes, ws["p_c"]
         scale = 1.0 / (1.0 - p)
-        capi.cross_entropy(ws["logits"], C, C, B, None, labels, None, 1.0, ws["dlogits"], C, stats)
+        if ws["counts"] is None:
+            capi.cross_entropy(ws["logits"], C, C, B, None, labels, None, 1.0, ws["dlogits"], C, stats)
+        else:      # the mean over the batch's own samples; dlogits rows beyond them are zero, and so is every gradient row below
+            capi.cross_entropy_cap(ws["logits"], C, C, B, ws["counts"], None, labels, None, 1.0, ws["dlogits"], C, stats)
+            capi.mm_zero_tail(ws["dlogits"], C, C, 1, B, ws["counts"])
         linear_wgrad(pl, ws["dlogits"], C, ws["feat"], HID, None, C, HID, B, self._off("netC.fc_out.weight"), self._off("netC.fc_out.bias"),
                      defer=True)
         capi.gemm_f32(ws["dlogits"], C, 0, None, self._w("netC.fc_out.weight"), HID, 1, None, ws["dfeat"], HID, B, HID, C, act=2,
@@ -243,7 +280,10 @@ class MMINBaseModule(nn.Module):
         g = self.flat.g
         capi.textcnn_pool_bwd(e["x"], B, e["T"], self.text_dim, e["pooled"], EMB, e["arg"], e["dpooled"] if e["p"] > 0 else e["dpd"], EMB,
                               [g("netL.conv%d.weight" % k) for k in (1, 2, 3)], [g("netL.conv%d.bias" % k) for k in (1, 2, 3)])
-        capi.lstm128_pool_bwd(ws["jobs"], ws["n_jobs"])
+        if ws["counts"] is None:
+            capi.lstm128_pool_bwd(ws["jobs"], ws["n_jobs"])
+        else:
+            capi.lstm128_pool_bwd_tcap(ws["jobs"], ws["counts"], ws["dyn_mask"], ws["n_jobs"])
         for tag, net in (("A", "netA"), ("V", "netV")):
             s, rows = ws[tag], B * ws[tag]["T"]
             d = int(s["x"].shape[2])
@@ -255,7 +295,8 @@ class MMINBaseModule(nn.Module):
     def loss_and_grads(self, batch):
         """mean cross entropy of the logits (mmin_base.py:131) and every gradient into flat.grad; returns the device stats
         (stats[0] = loss, stats[1] = #correct)"""
-        ws, B = self._forward_impl(batch.get("audio_feature"), batch.get("visual_feature"), batch.get("text_feature"), self.training)
+        ws, B = self._forward_impl(batch.get("audio_feature"), batch.get("visual_feature"), batch.get("text_feature"), self.training,
+                                   self._counts(batch))
         self._classifier_bwd(ws, B, ws["fused"], EMB, batch["label"], ws["stats"])
         # dfused: the audio | visual columns as they are (dpool of the two scans), the text columns through embd's ReLU
         W0 = self._w("netC.module.0.weight")
@@ -299,9 +340,17 @@ class MMINBaseTrainer(TrainerBase):
     NAME = "mmin_base"
     MODULE = MMINBaseModule
     CLASS_WEIGHTED = False
+    CAPACITY_MODES = True      # --capacity_buckets, --device_collate --resident, --resident_eval are built (mmin_miss: refused)
+    capacity = False           # --capacity_buckets / --resident: host batches go through buckets (StepGraphs.capacity_bucket)
+    t_cap = 0                  # the training split's longest utterance: no bucket is longer (set by ``run``)
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
+        if self.CAPACITY_MODES:
+            if max(_world_size(), int(os.environ.get("WORLD_SIZE", "1"))) > 1 and any(params.get(k) for k in CAPACITY_FLAGS):
+                raise capi.ErcGraftError("--module=%s: %s are built for one rank; data-parallel runs keep the default loop"
+                                         % (self.NAME, ", ".join("--" + k for k in CAPACITY_FLAGS)))
+            self.capacity = bool(params.get("capacity_buckets", False) or params.get("resident", False))
         torch.manual_seed(params.seed)
         self.model = self.MODULE(visual_dim=VISUAL_DIM, text_dim=TEXT_DIM, audio_dim=AUDIO_DIM, n_classes=params.n_classes,
                                  compute=params.get("compute", "f32"), seed=params.seed).finalize(self.device)
@@ -313,8 +362,11 @@ class MMINBaseTrainer(TrainerBase):
         self._swap = None
 
     def train_step(self, batch):
-        """TrainerBase's step with the EMA step behind the optimizer's (one rank: no gradient all-reduce)"""
+        """TrainerBase's step with the EMA step behind the optimizer's (one rank: no gradient all-reduce).  A resident batch
+        (``resident_batch``) is collated on the device first, from its store and descriptor"""
         self.model.train()
+        if batch.get("desc") is not None:
+            device_collate(batch)
         stats = self.model.loss_and_grads(batch)
         self.optim.step()
         if self.use_ema:
@@ -341,6 +393,48 @@ class MMINBaseTrainer(TrainerBase):
 
     def ema_weights(self):
         return self._EmaWeights(self)
+
+    # ------------------------------------------------------------------------------------------------- capacity mode
+    def make_bucket(self, B_cap, T_cap, Tv, Tt):
+        """the static input buffers of bucket (B_cap, T_cap): what ``mmin_collate`` returns at capacity shape, and counts = {B, Ta}"""
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)
+        return dict(audio_feature=f32(B_cap, T_cap, AUDIO_DIM), visual_feature=f32(B_cap, Tv, VISUAL_DIM), text_feature=f32(B_cap, Tt, TEXT_DIM),
+                    label=torch.zeros(B_cap, dtype=torch.int64, device=self.device),
+                    counts=torch.zeros(2, dtype=torch.int32, device=self.device))
+
+    @staticmethod
+    def fill_bucket(static, batch):
+        """a host-collated batch (on the device already) into its bucket: rows and slots the batch does not have are zero"""
+        B, Ta = (int(v) for v in batch["audio_feature"].shape[:2])
+        static["audio_feature"].zero_()
+        static["audio_feature"][:B, :Ta].copy_(batch["audio_feature"], non_blocking=True)
+        for k in ("visual_feature", "text_feature", "label"):
+            static[k][:B].copy_(batch[k], non_blocking=True)
+            static[k][B:].zero_()
+        static["counts"].copy_(torch.tensor([B, Ta], dtype=torch.int32), non_blocking=True)
+
+    def capacity_bucket(self, batch):
+        """trainer.StepGraphs: (key, make_static, fill) of the bucket of a prepared batch -- B_cap = train.batch_size, T_cap =
+        the batch's audio length rounded up (datasets.mmin_t_cap) -- or None with the mode off or for a batch larger than
+        train.batch_size"""
+        B_cap = int(self.params.train.batch_size)
+        if not self.capacity or "counts" in batch or int(batch["audio_feature"].shape[0]) > B_cap:
+            return None
+        T_cap = mmin_t_cap(int(batch["audio_feature"].shape[1]), self.t_cap)
+        Tv, Tt = int(batch["visual_feature"].shape[1]), int(batch["text_feature"].shape[1])
+        return ("capacity", B_cap, T_cap, Tv, Tt), lambda: self.make_bucket(B_cap, T_cap, Tv, Tt), self.fill_bucket
+
+    def resident_batch(self, store, cur_desc, B_cap, T_cap):
+        """the "batch" of a step whose samples stay in ``store`` (datasets.MMINDeviceStore): the bucket's buffers, which the
+        step's first launch fills from the store through the 3 B_cap int32 of ``cur_desc`` (erc_mmin_collate)"""
+        batch = self.make_bucket(B_cap, T_cap, int(store.visual.shape[1]), int(store.text.shape[1]))
+        batch.update(store=store, desc=cur_desc)
+        return batch
+
+    def resident_eval_step(self, batch, cm, loss_sum):
+        """one evaluation step from the store, scored on the device (``MMINBaseModule.eval_scores``); -> the step's workspace"""
+        device_collate(batch)
+        return self.model.eval_scores(batch, cm, loss_sum)
 
     def eval_epoch(self, loader):
         """one pass with the model and one with the EMA model over ``loader``; logits stay on the device, one copy per epoch.
@@ -395,6 +489,17 @@ class MMINBaseTrainer(TrainerBase):
                 with open(os.path.join(save_dir, tag + ".json"), "w") as fh:
                     fh.write(json.dumps({"global_steps": self.global_steps, "accuracy": self.accuracy}))
         return best
+
+
+CAPACITY_FLAGS = ("capacity_buckets", "device_collate", "resident", "resident_eval")
+
+
+def device_collate(batch):
+    """erc_mmin_collate of a resident batch: its descriptor's samples from the store into the bucket's buffers, one launch"""
+    st, a = batch["store"], batch["audio_feature"]
+    B_cap, T_cap = int(a.shape[0]), int(a.shape[1])
+    capi.mmin_collate(batch["desc"], st.audio, st.visual, st.text, st.label, B_cap, T_cap, min(T_cap, st.t_max), a, batch["visual_feature"],
+                      batch["text_feature"], batch["label"], batch["counts"])
 
 
 def state_dict(trainer):
@@ -473,10 +578,160 @@ def make_loaders(params, collate=None, transform=None, name="mmin_base"):
     return out
 
 
+class MMINResidentEpochs(ResidentLoop):
+    """``--device_collate --resident`` of --module=mmin_base: the training split stays in a datasets.MMINDeviceStore.  Per epoch
+    the host draws the batches' sample indices exactly as the default loop's DataLoader does (datasets.index_batches: the same
+    sampler on the same generator, a short last batch) and uploads ONE int32 table [steps, 3 B]; a step copies its 3 B int32
+    into the fixed descriptor and replays the graph of its bucket -- collate, forward, backward, Adam, EMA.  ResidentLoop's
+    visit / capture / counters, keyed by the batch's T capacity (datasets.mmin_t_cap) instead of a node capacity."""
+
+    def __init__(self, trainer, store, batch_size, generator, capture=True):
+        super().__init__(trainer, store, batch_size, capture)
+        self.T = store.t_max
+        self.cur_desc = torch.zeros(3 * self.B, dtype=torch.int32, device=store.device)
+        self.gen = generator
+        self.acc = torch.zeros(4, dtype=torch.float64, device=store.device)      # sums of the steps' {loss, #correct, -, -}
+
+    def _batch(self, cap):
+        return self.trainer.resident_batch(self.store, self.cur_desc, self.B, cap)
+
+    def _step(self, batch):
+        self.acc.add_(self.trainer.train_step(batch)[:4])
+        return self.trainer.model._last_ws
+
+    def tables(self):
+        """(host int32 table [steps, 3 B], T capacity per step, utterances per step) of the NEXT epoch: draws from the generator"""
+        batches = index_batches(len(self.store), self.B, True, self.gen)
+        table, caps = self.store.table(batches, self.B)
+        return table, caps, [len(b) for b in batches]
+
+    def drop_graphs(self):
+        """the learning rate is an argument of the captured optimizer launch: after a change every bucket runs one eager step
+        on its buffers again and is captured anew"""
+        self.graphs = {cap: (None, batch, ws) for cap, (_, batch, ws) in self.graphs.items()}
+
+    def epoch(self):
+        """one pass over the store; returns the steps' utterance counts"""
+        table, caps, counts = self.tables()
+        with dynamic_n(self.trainer.model):
+            self._steps(torch.from_numpy(table).to(self.store.device), caps)
+        return counts
+
+
+class MMINResidentEval(ResidentLoop):
+    """``--resident_eval``: a validation or test split in a datasets.MMINDeviceStore, visited in its fixed order (the table is
+    uploaded once, here).  One graph per T capacity: collate, the forward in eval mode, erc_cross_entropy_cap into a float64
+    accumulator (Lall = the sum of the batch means, the plateau scheduler's metric) and erc_rows_score into a confusion matrix.
+    ``epoch`` runs the pass with the model's weights and, under EMA, again with the EMA weights swapped in, and copies ONE
+    tensor to the host: both matrices and both sums."""
+
+    def __init__(self, trainer, store, batch_size, capture=True):
+        super().__init__(trainer, store, batch_size, capture)
+        self.T = store.t_max
+        self.cur_desc = torch.zeros(3 * self.B, dtype=torch.int32, device=store.device)
+        table, self.caps = store.table(index_batches(len(store), self.B, False), self.B)
+        self.table_dev = torch.from_numpy(table).to(store.device)
+        C = self.C = int(trainer.params.n_classes)
+        self.cm = torch.zeros(C, C, dtype=torch.int64, device=store.device)
+        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=store.device)
+        self.out = torch.zeros(2, C * C + 1, dtype=torch.float64, device=store.device)     # per pass: the matrix (exact in float64) | Lall
+
+    def _batch(self, cap):
+        return self.trainer.resident_batch(self.store, self.cur_desc, self.B, cap)
+
+    def _step(self, batch):
+        return self.trainer.resident_eval_step(batch, self.cm, self.loss_sum)
+
+    def _pass(self, k):
+        self.cm.zero_()
+        self.loss_sum.zero_()
+        with dynamic_n(self.trainer.model):
+            self._steps(self.table_dev, self.caps)
+        self.out[k, :-1].copy_(self.cm.reshape(-1))
+        self.out[k, -1:].copy_(self.loss_sum)
+
+    def epoch(self):
+        """``eval_epoch``'s dict without the per-sample lists: Lall, Acc, C, cm (host int64 [C, C], true x predicted) and, under
+        EMA, Acc2 and cm2"""
+        tr, C = self.trainer, self.C
+        self._pass(0)
+        if tr.use_ema:
+            with tr.ema_weights():
+                self._pass(1)
+        host = self.out.cpu()
+        cms = host[:, :-1].round().to(torch.int64).reshape(2, C, C)
+        n = int(cms[0].sum())
+        out = dict(C=n, Lall=float(host[0, -1]), Acc=float(cms[0].diagonal().sum()) / max(1, n), cm=cms[0].numpy())
+        if tr.use_ema:
+            out.update(Acc2=float(cms[1].diagonal().sum()) / max(1, n), cm2=cms[1].numpy())
+        return out
+
+
+class CapacityLoops:
+    """what ``run`` builds from the capacity flags of --module=mmin_base (all None without them: the default loop):
+    ``graphs`` (--capacity_buckets: trainer.StepGraphs over host-collated batches), ``resident`` (--device_collate --resident),
+    ``val`` / ``test`` (--resident_eval).  A combination that is not built exits here, before the first epoch."""
+
+    def __init__(self, params, trainer, loaders):
+        self.graphs = self.resident = self.val = self.test = None
+        flags = {k: bool(params.get(k, False)) for k in CAPACITY_FLAGS}
+        if not trainer.CAPACITY_MODES or not any(flags.values()):
+            return
+        if flags["resident"] != flags["device_collate"]:
+            raise SystemExit("--module=%s: --resident runs from the device store of --device_collate; give both or neither" % trainer.NAME)
+        if flags["resident_eval"] and not flags["resident"]:
+            raise SystemExit("--module=%s: --resident_eval needs --device_collate --resident" % trainer.NAME)
+        capture = params.get("graph_capture", True)
+        train, val, test = (ld.dataset for ld in loaders)
+        trainer.t_cap = max(int(s["audio_feature"].shape[0]) for s in train)
+        if flags["resident"]:
+            self.resident = MMINResidentEpochs(trainer, MMINDeviceStore(train, trainer.device), params.train.batch_size,
+                                               loaders[0].generator, capture=capture)
+        else:
+            self.graphs = StepGraphs(trainer, maxsize=64, capture=capture)
+        if flags["resident_eval"]:
+            self.val = MMINResidentEval(trainer, MMINDeviceStore(val, trainer.device), params.val.batch_size, capture=capture)
+            self.test = MMINResidentEval(trainer, MMINDeviceStore(test, trainer.device), params.test.batch_size, capture=capture)
+
+    def on_lr_change(self):
+        if self.resident is not None:
+            self.resident.drop_graphs()
+        if self.graphs is not None:
+            for ent in self.graphs.cache.values():
+                ent.graph = ent.out = None
+
+    def counter_keys(self):
+        """the epoch line's counters (trainer._epoch_line's names), {} for the default loop"""
+        tot = [c for c in (self.resident or self.graphs, self.val, self.test) if c is not None]
+        if not tot:
+            return {}
+        return {"graph_replays": sum(c.replays for c in tot), "eager_steps": sum(c.eager for c in tot),
+                "graphs_captured": sum(c.captures for c in tot)}
+
+
+def train_epoch(trainer, loops, train_loader, ring):
+    """one training epoch in the form the flags select (``loops``: CapacityLoops); no clock, no synchronisation -> the steps'
+    utterance counts"""
+    from .trainer import train_epoch_loader
+    if loops.resident is not None:
+        return loops.resident.epoch()
+    return train_epoch_loader(train_loader, loops.graphs, trainer, ring)
+
+
+def eval_epochs(trainer, loops, val_loader, test_loader):
+    """the validation epoch, the plateau scheduler on its loss (captured steps are dropped when the learning rate changes)
+    and the test epoch -> (val, test)"""
+    val = loops.val.epoch() if loops.val is not None else trainer.eval_epoch(val_loader)
+    if trainer.on_eval_end(val):
+        loops.on_lr_change()
+    test = loops.test.epoch() if loops.test is not None else trainer.eval_epoch(test_loader)
+    return val, test
+
+
 def run(trainer_cls, params_cls, argv=None):
     """the epoch loop of --module=mmin_base and --module=mmin_miss: training steps (EMA after each), the validation epoch (plateau scheduler), the test
     epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
-    from .trainer import classification_report, fix_seed, print_step_lines, train_epoch_loader
+    from .trainer import classification_report, fix_seed, print_step_lines
     params = params_cls()
     params.from_args(argv)
     if not torch.cuda.is_available():
@@ -489,24 +744,29 @@ def run(trainer_cls, params_cls, argv=None):
     if params.get("pretrain_path"):
         trainer.load_pretrained(params.pretrain_path)
     ring = torch.zeros(max(1, len(train_loader)), 4, dtype=torch.float32, device=device)
+    loops = CapacityLoops(params, trainer, (train_loader, val_loader, test_loader))
     last = {}
     for epoch in range(params.epoch):
         t0 = time.perf_counter()
-        counts = train_epoch_loader(train_loader, None, trainer, ring)
+        counts = train_epoch(trainer, loops, train_loader, ring)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         trainer.model.flat.check_health(trainer.NAME)
-        if params.log_every:
+        if params.log_every and loops.resident is None:      # (a resident step leaves no row in the ring)
             print_step_lines(params, epoch, ring, counts)
-        val = trainer.eval_epoch(val_loader)
-        trainer.on_eval_end(val)
-        test = trainer.eval_epoch(test_loader)
+        val, test = eval_epochs(trainer, loops, val_loader, test_loader)
         best = trainer.on_test_end(test, params.get("save_dir"))
-        rep = classification_report(test["true"], test["pred"], params.n_classes) if params.get("confuse_matrix", True) else {}
+        if not params.get("confuse_matrix", True):
+            rep = {}
+        elif "cm" in test:
+            rep = report_from_cm(test["cm"])
+        else:
+            rep = classification_report(test["true"], test["pred"], params.n_classes)
         last = {"epoch": epoch, "train_utt_per_s": sum(counts) / dt, "lr": trainer.optim.lr,
                 "val": {k: val[k] for k in ("Lall", "Acc", "Acc2") if k in val}, "test": {k: test[k] for k in ("Lall", "Acc", "Acc2") if k in test},
                 "report": {k: rep[k] for k in rep if k != "cm"}, "class_names": list(params.class_names), "best_acc": trainer.accuracy,
                 "is_best": best}
+        last.update(loops.counter_keys())
         print(json.dumps(last), flush=True)
     if params.get("save"):
         save(trainer, params.save)

@@ -173,6 +173,7 @@ class MMINMissTrainer(MMINBaseTrainer):
     loop are MMINBaseTrainer's."""
     NAME = "mmin_miss"
     MODULE = MMINMissModule
+    CAPACITY_MODES = False
 
     def __init__(self, params, device):
         for key, what in (("capacity_buckets", "capacity buckets"), ("resident", "--resident"), ("resident_eval", "--resident_eval")):

@@ -1583,6 +1583,41 @@ int erc_lstm128_hidden(void);
 int erc_lstm128_max_jobs(void);
 int erc_lstm128_pool_fwd(const ErcLstm128Job* jobs_host, int n_jobs, void* stream);
 int erc_lstm128_pool_bwd(const ErcLstm128Job* jobs_host, int n_jobs, void* stream);
+/* T AND B CAPACITY of the same (as erc_lstm_scan_fwd_tcap / _bwd_tcap): the launch is sized for the job's B (= B_cap) and the
+ * rows are pitched by the job's T (= T_cap), row(b, t) = b * T + t; the batch's own sizes are read on the device from
+ * counts = {B, Ta} int32 (erc_mmin_collate writes it): Bdev = clamp(counts[0], 0, B) for every job, Tdev = clamp(counts[1], 1, T)
+ * for job i when bit i of dyn_mask is set (the audio encoder) and the job's own T otherwise (the visual encoder).  Sample
+ * b < Bdev runs Tdev steps with the code of the exact form: pool, arg, and rows (b < Bdev, t < Tdev) of gates, Cst, Hprev and dGX
+ * carry the bits of erc_lstm128_pool_fwd / _bwd launched at T = Tdev on the same GX values.
+ *   forward write set   pool, arg rows b < Bdev; gates, Cst, Hprev rows (b < Bdev, t < Tdev); pool rows Bdev <= b < B = 0.
+ *                       Nothing else: arg rows b >= Bdev and every other row of gates, Cst, Hprev keep what they held.
+ *   backward write set  EVERY row of dGX: the scan's gradient on rows (b < Bdev, t < Tdev), zero on all others (a slot the batch
+ *                       does not have zeroes its T rows and returns), so that dGX^T x and dGX^T Hprev over all B * T rows add
+ *                       exact zeros whatever x and Hprev hold there (finite values: the caller's buffers start as zeros).
+ * Refused with ERC_E_ARG before any launch: what the exact forms refuse, null counts, a dyn_mask bit at or beyond n_jobs, and
+ * (backward) a dGX that is not 16-byte aligned.  A repeated launch is bit-identical. */
+int erc_lstm128_pool_fwd_tcap(const ErcLstm128Job* jobs_host, int n_jobs, const int32_t* counts, int dyn_mask, void* stream);
+int erc_lstm128_pool_bwd_tcap(const ErcLstm128Job* jobs_host, int n_jobs, const int32_t* counts, int dyn_mask, void* stream);
+
+/* Device collate of an MMIN batch (MMINBaseCollate, mmin_base.py:224-251) from a split that lives in device memory, one launch.
+ *   store   store_audio [n_frames, 130]: the frames of all utterances, one ragged matrix; store_visual [n_samples, Tv, 342];
+ *           store_text [n_samples, Tt, 1024]; store_label [n_samples] int64.  Widths: erc_mmin_collate_width(0 | 1 | 2).
+ *   desc    [3 B_cap] int32 on the device: frames | first frame row | sample index of every slot; frames == 0 is an empty slot
+ *           (empty slots come last: the scans run slots [0, counts[0])).
+ *   audio   [B_cap * T_cap, 130], row(b, t) = b * T_cap + t: the slot's frame t, zero where t >= frames or the slot is empty
+ *   visual  [B_cap * Tv, 342], text [B_cap * Tt, 1024]: the sample's rows, zero for an empty slot
+ *   label   [B_cap] int64, 0 for an empty slot;  counts [2] int32 = {number of non-empty slots, max frames}
+ * EVERY element of the five outputs is written by every launch (nothing of an earlier batch survives); nothing else is
+ * written.  Workgroups never wait for each other.  Rows are 8-byte aligned (520, 1368, 4096 bytes) and every access is 8 bytes
+ * wide.  frames_max is the host's upper bound of desc's frames.  Refused with ERC_E_ARG before any launch: frames_max > T_cap
+ * (or < 0), a null pointer, B_cap / T_cap / Tv / Tt <= 0, an empty store, a feature buffer that is not 8-byte aligned.
+ * What only the device knows is clamped there: frames to [0, T_cap], first frame row to [0, n_frames - frames], sample index to
+ * [0, n_samples). */
+int erc_mmin_collate_width(int modality);
+int erc_mmin_collate(const int32_t* desc, const float* store_audio, int64_t n_frames, const float* store_visual,
+                     const float* store_text, const int64_t* store_label, int n_samples, int Tv, int Tt, int B_cap,
+                     int T_cap, int frames_max, float* audio, float* visual, float* text, int64_t* label,
+                     int32_t* counts, void* stream);
 
 /* erc_textcnn_pool_fwd / _bwd replace TextCNN's three conv blocks (mmin_models.py:15-17,24-37: Conv2d(1, 128, (k, D)) for
  * k = 3, 4, 5, ReLU, F.max_pool1d over the T - k + 1 windows, the results side by side) and their autograd; the dropout and the
