@@ -153,10 +153,13 @@ class DeviceDialogueStore:
     padded batch dict as ``ERCCollate`` with a handful of device gathers (no DataLoader worker, no host copy per step).
     Layout switches follow the params like ERCCollate's (mmbase.py:344-455)."""
 
+    DESC_INTS = 2      # int32 per batch slot of a resident step's descriptor (trainer.batch_table: length | first row)
+
     def __init__(self, dialogues, params, device, dtype=torch.float32):
         self.params, self.device = params, device
         lens = [len(d["label"]) for d in dialogues]
         self.lengths = torch.tensor(lens, dtype=torch.int64)
+        self.t_max = max(lens)      # the longest dialogue
         self.offsets = torch.zeros(len(lens) + 1, dtype=torch.int64)
         self.offsets[1:] = torch.cumsum(self.lengths, 0)
         order = {"t": "text", "a": "audio", "v": "visual"}
@@ -224,6 +227,8 @@ class MMINDeviceStore:
     DeviceDialogueStore's), ``visual`` [n, 50, 342], ``text`` [n, 22, 1024], ``label`` [n] int64.  A batch is never
     materialised on the host: ``desc`` gives the 3 B_cap int32 erc_mmin_collate reads (frames | first frame row | sample index,
     empty slots last).  ``device=None`` keeps everything on the host (tests of the tables)."""
+
+    DESC_INTS = 3      # int32 per batch slot of a resident step's descriptor (``desc``)
 
     def __init__(self, samples, device=None):
         f32 = lambda key: [np.asarray(s[key], dtype=np.float32) for s in samples]

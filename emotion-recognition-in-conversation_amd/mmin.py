@@ -40,7 +40,8 @@ from . import capi
 from .capacity import TrainerBase
 from .datasets import MMINDeviceStore, index_batches, mmin_t_cap
 from .engine import FlatParams, GemmPlanner, WorkspaceCache, _world_size, linear_fwd, linear_wgrad
-from .trainer import ResidentLoop, StepGraphs, dynamic_n, report_from_cm
+from .trainer import (ResidentLoop, StepGraphs, classification_report, dynamic_n, epoch_loop_class, fix_seed, print_step_lines,
+                      report_from_cm, setup_device, train_epoch_loader)
 
 HID, EMB = 128, 384
 AUDIO_DIM, VISUAL_DIM, TEXT_DIM = 130, 342, 1024     # mmin_base.py:86-91: constants of the trainer
@@ -341,8 +342,9 @@ class MMINBaseTrainer(TrainerBase):
     MODULE = MMINBaseModule
     CLASS_WEIGHTED = False
     CAPACITY_MODES = True      # --capacity_buckets, --device_collate --resident, --resident_eval are built (mmin_miss: refused)
+    # EPOCH_LOOP = MMINEpochLoop: assigned below the loop's definition, at the end of this file (trainer.epoch_loop_class)
     capacity = False           # --capacity_buckets / --resident: host batches go through buckets (StepGraphs.capacity_bucket)
-    t_cap = 0                  # the training split's longest utterance: no bucket is longer (set by ``run``)
+    t_cap = 0                  # the training split's longest utterance: no bucket is longer (set by MMINEpochLoop)
 
     def __init__(self, params, device):
         self.params, self.device = params, torch.device(device)
@@ -587,8 +589,6 @@ class MMINResidentEpochs(ResidentLoop):
 
     def __init__(self, trainer, store, batch_size, generator, capture=True):
         super().__init__(trainer, store, batch_size, capture)
-        self.T = store.t_max
-        self.cur_desc = torch.zeros(3 * self.B, dtype=torch.int32, device=store.device)
         self.gen = generator
         self.acc = torch.zeros(4, dtype=torch.float64, device=store.device)      # sums of the steps' {loss, #correct, -, -}
 
@@ -604,11 +604,6 @@ class MMINResidentEpochs(ResidentLoop):
         batches = index_batches(len(self.store), self.B, True, self.gen)
         table, caps = self.store.table(batches, self.B)
         return table, caps, [len(b) for b in batches]
-
-    def drop_graphs(self):
-        """the learning rate is an argument of the captured optimizer launch: after a change every bucket runs one eager step
-        on its buffers again and is captured anew"""
-        self.graphs = {cap: (None, batch, ws) for cap, (_, batch, ws) in self.graphs.items()}
 
     def epoch(self):
         """one pass over the store; returns the steps' utterance counts"""
@@ -627,8 +622,6 @@ class MMINResidentEval(ResidentLoop):
 
     def __init__(self, trainer, store, batch_size, capture=True):
         super().__init__(trainer, store, batch_size, capture)
-        self.T = store.t_max
-        self.cur_desc = torch.zeros(3 * self.B, dtype=torch.int32, device=store.device)
         table, self.caps = store.table(index_batches(len(store), self.B, False), self.B)
         self.table_dev = torch.from_numpy(table).to(store.device)
         C = self.C = int(trainer.params.n_classes)
@@ -667,94 +660,95 @@ class MMINResidentEval(ResidentLoop):
         return out
 
 
-class CapacityLoops:
-    """what ``run`` builds from the capacity flags of --module=mmin_base (all None without them: the default loop):
-    ``graphs`` (--capacity_buckets: trainer.StepGraphs over host-collated batches), ``resident`` (--device_collate --resident),
-    ``val`` / ``test`` (--resident_eval).  A combination that is not built exits here, before the first epoch."""
+class _CounterSum:
+    """the epoch line's counters of a capacity run: ``replays`` / ``eager`` / ``captures`` summed over its training, validation
+    and test loops"""
 
-    def __init__(self, params, trainer, loaders):
-        self.graphs = self.resident = self.val = self.test = None
+    def __init__(self, parts):
+        self.parts = parts
+
+    replays = property(lambda self: sum(c.replays for c in self.parts))
+    eager = property(lambda self: sum(c.eager for c in self.parts))
+    captures = property(lambda self: sum(c.captures for c in self.parts))
+
+
+class MMINEpochLoop:
+    """trainer.EpochLoop's surface for --module=mmin_base and --module=mmin_miss (one rank), whose epoch has three loaders, a
+    second pass under the EMA weights and the plateau scheduler between the validation and the test epoch.  The constructor
+    does what lies between "trainer constructed" and "first epoch": the loaders, ``trainer.t_cap``, what the capacity flags
+    select -- ``graphs`` (--capacity_buckets: trainer.StepGraphs over host-collated batches) or ``resident`` (--device_collate
+    --resident), ``res_val`` / ``res_eval`` (--resident_eval: the validation and the test split) -- and the stats ring; a
+    combination that is not built exits here.  ``fixed`` is always None.  ``counters``: None for the default loop.  Like
+    EpochLoop's, ``train_epoch`` and ``test_epoch`` do not synchronise, take no clock and print nothing."""
+
+    def __init__(self, params, trainer, device, rank=0, world=1):
+        self.params, self.trainer = params, trainer
+        self.train_loader, self.val_loader, self.test_loader = trainer.make_loaders(params)
+        self.graphs = self.fixed = self.resident = self.res_val = self.res_eval = self.counters = None
         flags = {k: bool(params.get(k, False)) for k in CAPACITY_FLAGS}
-        if not trainer.CAPACITY_MODES or not any(flags.values()):
-            return
-        if flags["resident"] != flags["device_collate"]:
-            raise SystemExit("--module=%s: --resident runs from the device store of --device_collate; give both or neither" % trainer.NAME)
-        if flags["resident_eval"] and not flags["resident"]:
-            raise SystemExit("--module=%s: --resident_eval needs --device_collate --resident" % trainer.NAME)
-        capture = params.get("graph_capture", True)
-        train, val, test = (ld.dataset for ld in loaders)
-        trainer.t_cap = max(int(s["audio_feature"].shape[0]) for s in train)
-        if flags["resident"]:
-            self.resident = MMINResidentEpochs(trainer, MMINDeviceStore(train, trainer.device), params.train.batch_size,
-                                               loaders[0].generator, capture=capture)
-        else:
-            self.graphs = StepGraphs(trainer, maxsize=64, capture=capture)
-        if flags["resident_eval"]:
-            self.val = MMINResidentEval(trainer, MMINDeviceStore(val, trainer.device), params.val.batch_size, capture=capture)
-            self.test = MMINResidentEval(trainer, MMINDeviceStore(test, trainer.device), params.test.batch_size, capture=capture)
+        if trainer.CAPACITY_MODES and any(flags.values()):
+            if flags["resident"] != flags["device_collate"]:
+                raise SystemExit("--module=%s: --resident runs from the device store of --device_collate; give both or neither" % trainer.NAME)
+            if flags["resident_eval"] and not flags["resident"]:
+                raise SystemExit("--module=%s: --resident_eval needs --device_collate --resident" % trainer.NAME)
+            capture = params.get("graph_capture", True)
+            store = lambda loader: MMINDeviceStore(loader.dataset, device)
+            trainer.t_cap = max(int(s["audio_feature"].shape[0]) for s in self.train_loader.dataset)
+            if flags["resident"]:
+                self.resident = MMINResidentEpochs(trainer, store(self.train_loader), params.train.batch_size,
+                                                   self.train_loader.generator, capture=capture)
+            else:
+                self.graphs = StepGraphs(trainer, maxsize=64, capture=capture)
+            if flags["resident_eval"]:
+                self.res_val = MMINResidentEval(trainer, store(self.val_loader), params.val.batch_size, capture=capture)
+                self.res_eval = MMINResidentEval(trainer, store(self.test_loader), params.test.batch_size, capture=capture)
+            self.counters = _CounterSum([c for c in (self.resident or self.graphs, self.res_val, self.res_eval) if c is not None])
+        self.n_steps = len(self.train_loader)
+        self.ring = torch.zeros(max(1, self.n_steps), 4, dtype=torch.float32, device=device)
 
-    def on_lr_change(self):
+    def train_epoch(self):
+        """(#utterances, the steps' utterance counts); a resident step leaves no row in the ring"""
         if self.resident is not None:
-            self.resident.drop_graphs()
-        if self.graphs is not None:
-            for ent in self.graphs.cache.values():
-                ent.graph = ent.out = None
+            counts = self.resident.epoch()
+        else:
+            counts = train_epoch_loader(self.train_loader, self.graphs, self.trainer, self.ring)
+        return sum(counts), counts
 
-    def counter_keys(self):
-        """the epoch line's counters (trainer._epoch_line's names), {} for the default loop"""
-        tot = [c for c in (self.resident or self.graphs, self.val, self.test) if c is not None]
-        if not tot:
-            return {}
-        return {"graph_replays": sum(c.replays for c in tot), "eager_steps": sum(c.eager for c in tot),
-                "graphs_captured": sum(c.captures for c in tot)}
-
-
-def train_epoch(trainer, loops, train_loader, ring):
-    """one training epoch in the form the flags select (``loops``: CapacityLoops); no clock, no synchronisation -> the steps'
-    utterance counts"""
-    from .trainer import train_epoch_loader
-    if loops.resident is not None:
-        return loops.resident.epoch()
-    return train_epoch_loader(train_loader, loops.graphs, trainer, ring)
+    def test_epoch(self, multiemo=False):
+        """the validation epoch, the plateau scheduler on its loss (captured training steps are dropped when the learning rate
+        changes) and the test epoch -> (val, test), ``eval_epoch``'s dicts"""
+        tr = self.trainer
+        val = self.res_val.epoch() if self.res_val is not None else tr.eval_epoch(self.val_loader)
+        if tr.on_eval_end(val) and self.counters is not None:
+            (self.resident or self.graphs).drop_graphs()
+        test = self.res_eval.epoch() if self.res_eval is not None else tr.eval_epoch(self.test_loader)
+        return val, test
 
 
-def eval_epochs(trainer, loops, val_loader, test_loader):
-    """the validation epoch, the plateau scheduler on its loss (captured steps are dropped when the learning rate changes)
-    and the test epoch -> (val, test)"""
-    val = loops.val.epoch() if loops.val is not None else trainer.eval_epoch(val_loader)
-    if trainer.on_eval_end(val):
-        loops.on_lr_change()
-    test = loops.test.epoch() if loops.test is not None else trainer.eval_epoch(test_loader)
-    return val, test
+MMINBaseTrainer.EPOCH_LOOP = MMINEpochLoop      # (trainer.epoch_loop_class; MMINMissTrainer inherits it)
 
 
 def run(trainer_cls, params_cls, argv=None):
-    """the epoch loop of --module=mmin_base and --module=mmin_miss: training steps (EMA after each), the validation epoch (plateau scheduler), the test
-    epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
-    from .trainer import classification_report, fix_seed, print_step_lines
+    """--module=mmin_base and --module=mmin_miss: training steps (EMA after each), the validation epoch (plateau scheduler), the
+    test epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
     params = params_cls()
     params.from_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("the ERC hot path runs on an MI355X through libercgraft.so; no GPU is visible (there is no CPU fallback)")
-    device = torch.device(params.device if params.device not in (None, "cuda") else "cuda:0")
-    torch.cuda.set_device(device)
-    train_loader, val_loader, test_loader = trainer_cls.make_loaders(params)
+    device = setup_device(params)
     fix_seed(params.seed)
     trainer = trainer_cls(params, device)
     if params.get("pretrain_path"):
         trainer.load_pretrained(params.pretrain_path)
-    ring = torch.zeros(max(1, len(train_loader)), 4, dtype=torch.float32, device=device)
-    loops = CapacityLoops(params, trainer, (train_loader, val_loader, test_loader))
+    loop = epoch_loop_class(trainer_cls)(params, trainer, device)
     last = {}
     for epoch in range(params.epoch):
         t0 = time.perf_counter()
-        counts = train_epoch(trainer, loops, train_loader, ring)
+        n_utt, counts = loop.train_epoch()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         trainer.model.flat.check_health(trainer.NAME)
-        if params.log_every and loops.resident is None:      # (a resident step leaves no row in the ring)
-            print_step_lines(params, epoch, ring, counts)
-        val, test = eval_epochs(trainer, loops, val_loader, test_loader)
+        if params.log_every and loop.resident is None:
+            print_step_lines(params, epoch, loop.ring, counts)
+        val, test = loop.test_epoch()
         best = trainer.on_test_end(test, params.get("save_dir"))
         if not params.get("confuse_matrix", True):
             rep = {}
@@ -762,11 +756,13 @@ def run(trainer_cls, params_cls, argv=None):
             rep = report_from_cm(test["cm"])
         else:
             rep = classification_report(test["true"], test["pred"], params.n_classes)
-        last = {"epoch": epoch, "train_utt_per_s": sum(counts) / dt, "lr": trainer.optim.lr,
+        last = {"epoch": epoch, "train_utt_per_s": n_utt / dt, "lr": trainer.optim.lr,
                 "val": {k: val[k] for k in ("Lall", "Acc", "Acc2") if k in val}, "test": {k: test[k] for k in ("Lall", "Acc", "Acc2") if k in test},
                 "report": {k: rep[k] for k in rep if k != "cm"}, "class_names": list(params.class_names), "best_acc": trainer.accuracy,
                 "is_best": best}
-        last.update(loops.counter_keys())
+        c = loop.counters
+        if c is not None:
+            last.update(graph_replays=c.replays, eager_steps=c.eager, graphs_captured=c.captures)
         print(json.dumps(last), flush=True)
     if params.get("save"):
         save(trainer, params.save)

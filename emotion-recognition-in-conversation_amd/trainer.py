@@ -315,6 +315,12 @@ class StepGraphs:
             model.refresh_shadows()          # the bf16 copies follow the restored parameters
         self.maxsize = max(self.maxsize, len(self.cache) + 2)
 
+    def drop_graphs(self):
+        """A launch argument of the captured step changed (the learning rate): every entry keeps its static buffers and
+        workspace, runs one eager step on them when its key comes up again and is captured anew"""
+        for ent in self.cache.values():
+            ent.graph = ent.out = None
+
     def step(self, batch, key=None, resident=False):
         """``resident``: ``batch`` lives in fixed device buffers of its own (FixedBatches) -- the graph binds to them."""
         bucket = None
@@ -352,9 +358,10 @@ class StepGraphs:
 
 
 class ResidentLoop:
-    """What ``--resident`` and ``--resident_eval`` share: the dialogues stay in a DeviceDialogueStore and a step's batch is
-    never materialised.  A step is 2 B int32 (a row of ``batch_table``) copied into the fixed descriptor ``cur_desc`` plus its
-    node capacity -- the batch's node count rounded up to N_BUCKET, at most B * T, T the store's own longest dialogue.  The
+    """What ``--resident`` and ``--resident_eval`` share: the items stay in a device store (DeviceDialogueStore; MMIN's
+    utterances: MMINDeviceStore) and a step's batch is never materialised.  A step is ``store.DESC_INTS`` B int32 (2 B, a row of
+    ``batch_table``; MMIN: 3 B) copied into the fixed descriptor ``cur_desc`` plus its capacity -- here the batch's node count
+    rounded up to N_BUCKET, at most B * T, T the store's own longest item (``store.t_max``); MMIN's loops key by a T capacity.  The
     first visit of a capacity runs the subclass's ``_step`` eagerly on the trainer's resident batch of that capacity and then
     captures it; every later step of that capacity is one copy, one dict lookup, one replay.  A trainer whose step does not
     scale with N names its own node bucket (``RESIDENT_N_BUCKET``, clipped to B * T: DAG-ERC, one capacity per store)."""
@@ -363,13 +370,18 @@ class ResidentLoop:
 
     def __init__(self, trainer, store, batch_size, capture=True):
         self.trainer, self.store, self.B = trainer, store, int(batch_size)
-        self.T = int(store.lengths.max())
+        self.T = int(store.t_max)
         named = getattr(trainer, "RESIDENT_N_BUCKET", None)
         if named:
             self.N_BUCKET = max(1, min(int(named), self.B * self.T))
-        self.cur_desc = torch.zeros(2 * self.B, dtype=torch.int32, device=store.device)
-        self.graphs, self.capture = {}, capture      # node capacity -> (graph or None, batch, workspace kept alive)
+        self.cur_desc = torch.zeros(store.DESC_INTS * self.B, dtype=torch.int32, device=store.device)
+        self.graphs, self.capture = {}, capture      # capacity -> (graph or None, batch, workspace kept alive)
         self.replays = self.eager = self.captures = 0
+
+    def drop_graphs(self):
+        """A launch argument of the captured step changed (the learning rate): every capacity keeps its buffers and workspace,
+        runs one eager step on them when it comes up again and is captured anew"""
+        self.graphs = {cap: (None, batch, ws) for cap, (_, batch, ws) in self.graphs.items()}
 
     # -- the one place that touches the HIP runtime (a test replaces it with a recorder that does not execute what it records)
     def _capture(self, fn):
@@ -716,6 +728,21 @@ class EpochLoop:
         return EvalEpoch(None, *test_epoch_loader(self.trainer, self.test_loader, multiemo))
 
 
+def epoch_loop_class(trainer_cls):
+    """the epoch-loop class of a trainer class: the one it names (``EPOCH_LOOP``: the MMIN trainers), else ``EpochLoop``"""
+    return getattr(trainer_cls, "EPOCH_LOOP", None) or EpochLoop
+
+
+def setup_device(params, local=0):
+    """the process's GPU: ``--device``, else cuda:<local rank>, made current"""
+    if not torch.cuda.is_available():
+        raise RuntimeError("the ERC hot path runs on an MI355X through libercgraft.so; no GPU is visible "
+                           "(there is no CPU fallback)")
+    device = torch.device(params.device if params.device not in (None, "cuda") else "cuda:%d" % local)
+    torch.cuda.set_device(device)
+    return device
+
+
 def _epoch_line(epoch, utt_per_s, rep, best, counters, n_steps, test_s, multiemo_rep):
     """the epoch's JSON line; ``counters``: the ResidentEpochs or StepGraphs of the run, None for a plain eager loop"""
     line = {"epoch": epoch, "train_utt_per_s": utt_per_s, "test": {k: rep[k] for k in rep if k != "cm"}, "best": best,
@@ -738,12 +765,7 @@ def run(trainer_cls, params_cls, argv=None):
                          "CMU-MOSEI" % params.dataset)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise RuntimeError("the ERC hot path runs on an MI355X through libercgraft.so; no GPU is visible "
-                           "(there is no CPU fallback)")
-    device = torch.device(params.device if params.device not in (None, "cuda") else "cuda:%d" % local)
-    torch.cuda.set_device(device)
+    device = setup_device(params, int(os.environ.get("LOCAL_RANK", "0")))
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

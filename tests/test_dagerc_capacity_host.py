@@ -250,6 +250,8 @@ def test_without_the_flags_the_run_builds_neither(monkeypatch):
 
 class _LenStore(types.SimpleNamespace):
     """what the resident loops read of a DeviceDialogueStore"""
+    DESC_INTS = 2
+    t_max = property(lambda self: int(self.lengths.max()))
 
     def __len__(self):
         return int(self.lengths.numel())
@@ -298,7 +300,7 @@ def test_a_resident_epoch_is_one_capture_and_otherwise_replays():
 def test_resident_loop_takes_the_trainers_node_bucket_and_keeps_128_otherwise():
     from erc_amd.trainer import ResidentLoop
     lens = torch.tensor([50, 60, 70], dtype=torch.int64)
-    store = types.SimpleNamespace(lengths=lens, device="cpu")
+    store = types.SimpleNamespace(lengths=lens, t_max=70, DESC_INTS=2, device="cpu")
     plain = ResidentLoop(types.SimpleNamespace(), store, 4)
     assert plain.N_BUCKET == 128 and plain._caps_of([1, 128, 129, 280]) == [128, 128, 256, 280]
     named = ResidentLoop(types.SimpleNamespace(RESIDENT_N_BUCKET=64), store, 4)

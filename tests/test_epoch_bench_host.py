@@ -28,16 +28,12 @@ CASES = [(m, c, mode) for m, (_, configs) in sorted(EB.PRESETS.items()) for c in
          if not EB.skipped(m, c, mode)]
 
 
-def test_every_plugin_but_mmin_base_has_a_preset_and_resolves_to_trainer_and_params():
-    assert sorted(EB.PRESETS) == [m for m in PLUGINS if m != "mmin_base"]
+def test_every_plugin_has_a_preset_and_resolves_to_trainer_and_params():
+    assert sorted(EB.PRESETS) == PLUGINS
     for module in EB.PRESETS:
         trainer_cls, params_cls = EB.plugin(module)
         assert callable(getattr(trainer_cls, "train_step", None)) and hasattr(params_cls(), "from_args")
         assert (trainer_cls, params_cls) == importlib.import_module("track_mm." + module).main.args
-    with pytest.raises(SystemExit, match="mmin_bench.py"):
-        EB.plugin("mmin_base")
-    with pytest.raises(SystemExit, match="mmin_bench.py"):
-        EB.main(["--module=mmin_base"])
 
 
 @pytest.mark.parametrize("module,config,mode", CASES, ids=["-".join(c) for c in CASES])
@@ -48,7 +44,7 @@ def test_preset_parses_with_the_modules_own_params(module, config, mode):
     assert isinstance(p.dims(), dict) and all(int(v) > 0 for v in p.dims().values())        # a dataset params.dims() knows
     assert p.dataset == [f for f in argv if f.startswith("--dataset=")][-1].split("=", 1)[1]
     assert int(p.train.batch_size) == int(p.test.batch_size) == EB.PRESETS[module][0]
-    assert (int(p.n_train), int(p.n_test)) in ((120, 31), (1039, 280), (2240, 672))
+    assert (int(p.n_train), int(p.n_test)) in ((120, 31), (1039, 280), (2240, 672), (1024, 64))
     for flag in EB.MODES[mode]:
         key, _, value = flag[2:].partition("=")
         assert p.get(key) == {"": True, "True": True, "False": False}[value], flag
@@ -58,6 +54,8 @@ def test_skipped_cells_and_overrides():
     assert EB.skipped("cim", "mosei", "resident_eval") and not EB.skipped("cim", "iemocap", "resident_eval")
     assert EB.skipped("bcgru", "meld", "resident_eval") and EB.skipped("bclstm", "iemocap", "resident_eval")
     assert not EB.skipped("bcgru", "meld", "resident")
+    assert EB.skipped("mmin_miss", "f50_400", "resident") and not EB.skipped("mmin_base", "f50_400", "resident")
+    assert EB.skipped("mmin_miss", "f100_100", "exact") and EB.skipped("mmin_base", "f100_100", "exact")
     argv = EB.flags("bcgru", "iemocap", "default", sets=["n_train=10", "train.batch_size=4", "syn_min_len=1"], collate_on_device=True)
     assert argv.count("--n_train=10") == 1 and "--n_train=120" not in argv and "--n_test=31" in argv
     assert "--train.batch_size=4" in argv and "--train.batch_size=32" not in argv and "--test.batch_size=32" in argv
@@ -118,6 +116,10 @@ def test_skipped_modes_start_no_child(monkeypatch, capsys):
     monkeypatch.setattr(EB.subprocess, "run", rec)
     EB.main(["--module=cim", "--config=mosei", "--modes=resident,resident_eval", "--steps"])
     assert [[a for a in cmd if a.startswith("--modes=")][0] for cmd in rec.calls] == ["--modes=resident", "--modes=steps"]
+    rec = _Recorder([0])
+    monkeypatch.setattr(EB.subprocess, "run", rec)
+    EB.main(["--module=mmin_miss", "--config=f50_400", "--modes=default,resident", "--steps"])
+    assert [[a for a in cmd if a.startswith("--modes=")][0] for cmd in rec.calls] == ["--modes=default"]
 
 
 def test_the_summary_is_the_hand_computed_one():

@@ -118,3 +118,21 @@ def test_resident_without_device_collate_exits_before_the_first_epoch():
     with pytest.raises(SystemExit) as exc:
         _loop(["--resident"])
     assert str(exc.value) == "--resident needs --device_collate, one rank and a trainer with resident batches (capacity mode)"
+
+
+def test_resident_loops_on_a_dialogue_store_take_two_ints_per_slot_and_the_stores_longest_dialogue():
+    """the descriptor width and T are the store's (``DESC_INTS``, ``t_max``): a DeviceDialogueStore gives 2 B int32 and its
+    longest dialogue, MMIN's utterance store 3 B (tests/test_mmin_cap_ref.py)"""
+    from erc_amd.datasets import DeviceDialogueStore, MMINDeviceStore
+    p = _params()
+    train, test = T.load_dialogues(p)
+    assert (DeviceDialogueStore.DESC_INTS, MMINDeviceStore.DESC_INTS) == (2, 3)
+    for dialogs, B in ((train, 4), (test, 3)):
+        store = DeviceDialogueStore(dialogs, p, CPU)
+        longest = max(len(d["label"]) for d in dialogs)
+        assert store.t_max == longest == int(store.lengths.max())
+        for loop in (T.ResidentEpochs(_Stub(), store, B, seed=3), T.ResidentEval(_Stub(), store, B, n_classes=6)):
+            assert loop.cur_desc.shape == (2 * B, ) and loop.cur_desc.dtype == torch.int32
+            assert loop.T == longest and loop.B == B and loop.graphs == {}
+            loop.drop_graphs()                                          # nothing captured yet: nothing to drop
+            assert loop.graphs == {}

@@ -89,6 +89,12 @@ def _trainer(*argv):
     return mmin.MMINBaseTrainer(p, "cpu")
 
 
+def _loop(*argv):
+    """the epoch loop on the CPU over real tiny splits -> (loop, trainer)"""
+    t = _trainer("--n_train=5", "--n_val=5", "--n_test=5", "--mmin_frames=3,150", *argv)
+    return mmin.MMINEpochLoop(t.params, t, torch.device("cpu")), t
+
+
 def test_flags():
     from track_mm.mmin_base import MMINBaseParams
     p = MMINBaseParams().from_args([])
@@ -98,16 +104,24 @@ def test_flags():
     assert tr.capacity is False and tr.model.dynamic_n is False and tr.CAPACITY_MODES
     assert tr.capacity_bucket(mmin.mmin_collate(_samples(3))) is None
     assert _trainer("--capacity_buckets=True").capacity and _trainer("--device_collate", "--resident").capacity
-    loaders = [types.SimpleNamespace(dataset=_samples(5), generator=None)] * 3
-    none = mmin.CapacityLoops(tr.params, tr, loaders)
-    assert (none.graphs, none.resident, none.val, none.test) == (None, None, None, None) and none.counter_keys() == {}
-    for argv in (("--resident", ), ("--device_collate", ), ("--resident_eval", ), ("--resident_eval", "--capacity_buckets=True")):
-        t = _trainer(*argv)
-        with pytest.raises(SystemExit):
-            mmin.CapacityLoops(t.params, t, loaders)
-    t = _trainer("--capacity_buckets=True")
-    loops = mmin.CapacityLoops(t.params, t, loaders)
-    assert loops.graphs is not None and loops.resident is None and t.t_cap == max(s["audio_feature"].shape[0] for s in loaders[0].dataset)
+    from erc_amd.trainer import epoch_loop_class
+    from erc_amd.mmin_miss import MMINMissTrainer
+    assert epoch_loop_class(mmin.MMINBaseTrainer) is epoch_loop_class(MMINMissTrainer) is mmin.MMINEpochLoop
+    none, t = _loop()
+    assert (none.graphs, none.fixed, none.resident, none.res_val, none.res_eval) == (None, ) * 5 and none.counters is None
+    assert t.t_cap == 0 and none.n_steps == 2 and tuple(none.ring.shape) == (2, 4)
+    assert [len(ld.dataset) for ld in (none.train_loader, none.val_loader, none.test_loader)] == [5, 5, 5]
+    both = "--module=mmin_base: --resident runs from the device store of --device_collate; give both or neither"
+    needs = "--module=mmin_base: --resident_eval needs --device_collate --resident"
+    for argv, wording in ((("--resident", ), both), (("--device_collate", ), both), (("--resident_eval", ), needs),
+                          (("--resident_eval", "--capacity_buckets=True"), needs)):
+        t = _trainer("--n_train=5", "--n_val=5", "--n_test=5", "--mmin_frames=3,150", *argv)      # the trainer takes the flags ...
+        with pytest.raises(SystemExit) as exc:                                                    # ... the loop refuses them
+            mmin.MMINEpochLoop(t.params, t, torch.device("cpu"))
+        assert str(exc.value) == wording
+    loops, t = _loop("--capacity_buckets=True")
+    assert loops.graphs is not None and loops.resident is None
+    assert t.t_cap == max(s["audio_feature"].shape[0] for s in loops.train_loader.dataset) > 0
 
 
 def test_data_parallel_runs_stay_refused(monkeypatch):
@@ -225,20 +239,33 @@ def test_resident_epochs_one_eager_visit_per_t_cap_then_replays_and_recapture_af
 
 
 def test_capacity_loops_drop_the_graphs_when_the_learning_rate_changes():
-    tr = _trainer("--capacity_buckets=True")
-    loaders = [types.SimpleNamespace(dataset=_samples(5), generator=None)] * 3
-    loops = mmin.CapacityLoops(tr.params, tr, loaders)
+    """``test_epoch`` with the trainer's two evaluation hooks replaced (no library here): validation, the scheduler, the test
+    epoch, in this order; the graphs go exactly when ``on_eval_end`` reports a change"""
     from erc_amd.trainer import GraphEntry
-    ent = loops.graphs.cache["k"] = GraphEntry({}, None, True, seen=3, graph=object(), out=object())
-    loops.on_lr_change()
+    loops, tr = _loop("--capacity_buckets=True")
+    log, changed = [], [False]
+    tr.eval_epoch = lambda loader: log.append(loader) or {"Lall": float(len(log))}
+    tr.on_eval_end = lambda rec: log.append(rec) or changed[0]
+    graph, out = object(), object()
+    ent = loops.graphs.cache["k"] = GraphEntry({}, None, True, seen=3, graph=graph, out=out, workspace="ws")
+    assert loops.test_epoch() == ({"Lall": 1.0}, {"Lall": 3.0})
+    assert log == [loops.val_loader, {"Lall": 1.0}, loops.test_loader]
+    assert ent.graph is graph and ent.out is out                      # the learning rate stayed: nothing is dropped
+    changed[0] = True
+    loops.test_epoch()
     assert ent.graph is None and ent.out is None and loops.graphs.cache["k"] is ent
-    assert loops.counter_keys() == {"graph_replays": 0, "eager_steps": 0, "graphs_captured": 0}
+    assert (ent.static, ent.seen, ent.workspace) == ({}, 3, "ws")     # the static buffers and the workspace stay
+    c = loops.counters
+    assert (c.replays, c.eager, c.captures) == (0, 0, 0)
+    loops.graphs.replays, loops.graphs.eager, loops.graphs.captures = 5, 2, 1
+    assert (c.replays, c.eager, c.captures) == (5, 2, 1)
 
 
 def test_resident_eval_fixed_order_two_passes_one_result():
     samples = _samples(n=7, frames=(3, 150))
     store, B, tr, calls = R.host_store(samples), 4, _Trainer(), []
     ev = _recorder(mmin.MMINResidentEval(tr, store, B), calls)
+    assert ev.cur_desc.shape == (3 * B, ) and ev.cur_desc.dtype == torch.int32 and ev.T == store.t_max
     table, caps = store.table([[0, 1, 2, 3], [4, 5, 6]], B)
     assert ev.table_dev.tolist() == table.tolist() and ev.caps == caps
     out = ev.epoch()

@@ -11,8 +11,11 @@ B = 4
 
 
 class _Store:
+    DESC_INTS = 2
+
     def __init__(self, lengths):
         self.lengths = torch.tensor(lengths, dtype=torch.int64)
+        self.t_max = max(lengths)
         self.offsets = torch.zeros(len(lengths) + 1, dtype=torch.int64)
         self.offsets[1:] = torch.cumsum(self.lengths, 0)
         self.device = "cpu"

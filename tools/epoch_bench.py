@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Whole reshuffled epochs of any ``--module`` -- the training epoch AND the test epoch behind it, as train_mm.py runs them
-(trainer.EpochLoop) -- on the synthetic presets below, in these modes:
+(trainer.EpochLoop, or the loop class the module's trainer names: trainer.epoch_loop_class) -- on the synthetic presets
+below, in these modes:
 
   eager          --graph_capture=False: every step launched from Python (capacity buckets' static buffers, no replay)
   default        no flag: the module's default loop (exact shapes, captured when a shape repeats; capacity buckets where
                  the trainer has them on by default: COGMEN bf16, DialogueGCN)
   exact          --fixed_batches: the opt-in sampling whose batch shapes repeat, so every step replays an exact-shape graph
   buckets        --capacity_buckets=True: one captured graph per capacity bucket, every batch a copy-in + replay
-  resident       --device_collate --resident: dialogues in HBM, a step's input is 2 B int32
+  resident       --device_collate --resident: dialogues in HBM, a step's input is 2 B int32 (MMIN: utterances, 3 B int32)
   resident_eval  ... --resident_eval: the test epoch from HBM too, scored on the device
+
+The MMIN modules' "test epoch" is their validation epoch (with the plateau scheduler behind it) plus their test epoch:
+``test_ms`` of an ``mmin_base`` / ``mmin_miss`` record covers both, and ``eval_captures_total`` counts both evaluation loops.
 
 Every (config, mode) runs in a fresh child process of this tool under its own ``timeout -k 10``, one at a time; the first
 child that ends with a non-zero status ends the tool with that status after one error line, and nothing more is started.
@@ -46,6 +50,9 @@ MODES = {"eager": ["--graph_capture=False"], "default": [], "exact": ["--fixed_b
 IEMOCAP = ["--dataset=iemocap-cogmen-6", "--n_train=120", "--n_test=31"]
 MELD = ["--dataset=meld-mmgcn-7", "--modality=atv", "--loss_weights=False", "--n_train=1039", "--n_test=280"]
 BCRNN = (32, {"iemocap": IEMOCAP, "meld": MELD})
+# utterances of 50..400 audio frames (two T capacities at B = 32) and of exactly 100 (one)
+MMIN_SPLITS = ["--dataset=iemocap-mmin-4", "--n_train=1024", "--n_val=64", "--n_test=64", "--val.batch_size=32"]
+MMIN = (32, {"f50_400": MMIN_SPLITS + ["--mmin_frames=50,400"], "f100_100": MMIN_SPLITS + ["--mmin_frames=100,100"]})
 # module -> (batch size, {config: flags})
 PRESETS = {
     "cogmen": (32, {"iemocap": IEMOCAP + ["--compute=bf16"],
@@ -61,13 +68,15 @@ PRESETS = {
                  "mosei": ["--dataset=mosei-cim-2", "--modality=atv", "--n_train=2240", "--n_test=672"]}),
     "dagerc": (16, {"bf16": IEMOCAP + ["--compute=bf16"], "f32": IEMOCAP + ["--compute=f32"]}),
     "mmgcn": (16, {"iemocap": IEMOCAP + ["--modality=atv"]}),
-    # listed so that the plugin resolves here; every mode is skipped (below): tools/mmin_miss_bench.py times this module
-    "mmin_miss": (32, {"iemocap": ["--dataset=iemocap-mmin-4", "--n_train=120", "--n_test=31"]}),
+    "mmin_base": MMIN,
+    "mmin_miss": MMIN,
 }
-# the multi-label metrics of CMU-MOSEI are no function of a confusion matrix; bc-LSTM / bc-GRU have no scored test step
-# mmin_miss runs mmin_base's loop (three loaders, no graphs, none of these modes)
+# the multi-label metrics of CMU-MOSEI are no function of a confusion matrix; bc-LSTM / bc-GRU have no scored test step; the
+# MMIN modules have no --fixed_batches and no node buckets, and without a capacity flag their --graph_capture=False is the
+# default loop; mmin_miss's trainer refuses the capacity modes
+MMIN_UNBUILT = {"exact", "eager", "steps"}
 SKIPPED = {("cim", "mosei"): {"resident_eval"}, ("bclstm", None): {"resident_eval"}, ("bcgru", None): {"resident_eval"},
-           ("mmin_miss", None): set(MODES) | {"steps"}}
+           ("mmin_base", None): MMIN_UNBUILT, ("mmin_miss", None): MMIN_UNBUILT | {"buckets", "resident", "resident_eval"}}
 
 
 def skipped(module, config, mode):
@@ -76,8 +85,6 @@ def skipped(module, config, mode):
 
 def plugin(module):
     """(trainer class, params class) of ``--module``: every plugin is ``partial(run, Trainer, ParamsType)``"""
-    if module == "mmin_base":
-        raise SystemExit("--module=mmin_base has none of these modes (its loop has three loaders and no graphs): tools/mmin_bench.py")
     return importlib.import_module("track_mm." + module).main.args
 
 
@@ -150,7 +157,8 @@ def child(a):
             "dataset": params.dataset, "batch_size": int(params.train.batch_size)}
     if steps:
         return print(json.dumps(dict(head, **step_times(T, tr, params, a.iters))), flush=True)
-    loop = T.EpochLoop(params, tr, device)
+    loop = T.epoch_loop_class(trainer_cls)(params, tr, device)
+    evals = [e for e in (getattr(loop, "res_val", None), loop.res_eval) if e is not None]      # (res_val: the MMIN loop's)
     multiemo = params.get("mosei_metric", "") == "multiemo"
     c = loop.counters
     seen = lambda: (c.replays, c.eager, c.captures) if c is not None else (0, 0, 0)
@@ -183,7 +191,7 @@ def child(a):
     print(json.dumps(dict(head, device_collate=bool(params.get("device_collate", False)), steps_per_epoch=loop.n_steps,
                           utterances_per_epoch=n_utt, **summarise(train_ms, epoch_ms, counts, warmup),
                           captures_total=c.captures if c is not None else 0,
-                          eval_captures_total=loop.res_eval.captures if loop.res_eval is not None else 0,
+                          eval_captures_total=sum(e.captures for e in evals),
                           launches_per_eager_step=len(calls), kernel_launches_per_eager_step=launches, loss_finite=loss == loss and abs(loss) != float("inf"))), flush=True)
 
 
@@ -278,10 +286,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     a.repo = os.path.abspath(a.repo)
     if a.module not in PRESETS:
-        plugin(a.module)          # (mmin_base: refused with its message)
         raise SystemExit("--module=%s has no preset; known: %s" % (a.module, ", ".join(sorted(PRESETS))))
-    if all(skipped(a.module, None, m) for m in MODES):
-        raise SystemExit("--module=%s has none of these modes (it runs mmin_base's loop): tools/%s_bench.py" % (a.module, a.module))
     if a.child:
         return child(a)
     for config in [c for c in a.config.split(",") if c] or list(PRESETS[a.module][1]):

@@ -7,19 +7,12 @@ the baseline.  One JSON line per (batch size, Ta).
 
     python tools/mmin_bench.py [--batch 32] [--ta 100,400] [--replays 50] [--cpu_steps 1]
 
-``--epochs N`` measures whole epochs instead -- training + validation + test, as ``train_mm.py --module=mmin_base`` runs them -- in
-four forms: the default loop, ``--capacity_buckets=True``, ``--device_collate --resident`` and the latter with
-``--resident_eval``.  Each form runs in a fresh child process under its own ``timeout -k 10``; an epoch is timed with device
-events around it; the run stops at the first child that fails.  One JSON line per (frames, form): min / median / max over the
-N epochs behind one untimed epoch, utterances per second of the median, and the replay counters.
-
-    python tools/mmin_bench.py --epochs 5 [--frames 50,400:100,100] [--batch 32] [--n_train 1024] [--child_timeout 240]
+Whole epochs (training + validation + test, in every loop form) are timed by tools/epoch_bench.py --module=mmin_base.
 """
 import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
@@ -103,54 +96,6 @@ def cpu_time(B, Ta, steps):
     return statistics.median(times[1:])
 
 
-FORMS = {"default": [], "buckets": ["--capacity_buckets=True"], "resident": ["--device_collate", "--resident"],
-         "resident_eval": ["--device_collate", "--resident", "--resident_eval"]}
-
-
-def epochs_child(form, frames, batch, n_train, n_epochs):
-    """one form in this process: an untimed epoch (allocations, first visits, captures), then ``n_epochs`` timed ones"""
-    from erc_amd import mmin
-    from erc_amd.trainer import fix_seed
-    from track_mm.mmin_base import MMINBaseParams
-    p = MMINBaseParams().from_args(["--mmin_frames=%s" % frames, "--n_train=%d" % n_train, "--train.batch_size=%d" % batch,
-                                    "--val.batch_size=%d" % batch, "--test.batch_size=%d" % batch, "--log_every=0"] + FORMS[form])
-    loaders = mmin.MMINBaseTrainer.make_loaders(p)
-    fix_seed(p.seed)
-    tr = mmin.MMINBaseTrainer(p, "cuda:0")
-    ring = torch.zeros(len(loaders[0]), 4, device="cuda:0")
-    loops = mmin.CapacityLoops(p, tr, loaders)
-    times, n_utt = [], 0
-    for epoch in range(n_epochs + 1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        n_utt = sum(mmin.train_epoch(tr, loops, loaders[0], ring))
-        val, test = mmin.eval_epochs(tr, loops, loaders[1], loaders[2])
-        e1.record()
-        e1.synchronize()
-        if epoch:
-            times.append(e0.elapsed_time(e1))
-    tr.model.flat.check_health(tr.NAME)
-    med = statistics.median(times)
-    res = {"form": form, "mmin_frames": frames, "B": batch, "n_train": n_train, "n_val": p.n_val, "n_test": p.n_test, "epochs": n_epochs,
-           "epoch_ms_min": min(times), "epoch_ms_median": med, "epoch_ms_max": max(times), "train_utt_per_epoch_s": n_utt / med * 1e3,
-           "val_Lall": val["Lall"], "test_Acc": test["Acc"]}
-    res.update(loops.counter_keys())
-    print(json.dumps(res), flush=True)
-
-
-def epochs_parent(args):
-    for frames in args.frames.split(":"):
-        for form in FORMS:
-            cmd = ["timeout", "-k", "10", str(args.child_timeout), sys.executable, os.path.abspath(__file__), "--epochs", str(args.epochs),
-                   "--form", form, "--frames", frames, "--batch", args.batch, "--n_train", str(args.n_train)]
-            res = subprocess.run(cmd, capture_output=True, text=True)
-            sys.stdout.write(res.stdout)
-            sys.stdout.flush()
-            if res.returncode != 0:
-                sys.stderr.write(res.stderr[-4000:])
-                raise SystemExit("mmin_bench --epochs: form %s at frames %s ended with status %d; stopping" % (form, frames, res.returncode))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="32")
@@ -158,18 +103,7 @@ def main():
     ap.add_argument("--replays", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--cpu_steps", type=int, default=1)
-    ap.add_argument("--epochs", type=int, default=0)
-    ap.add_argument("--frames", default="50,400:100,100")
-    ap.add_argument("--n_train", type=int, default=1024)
-    ap.add_argument("--child_timeout", type=int, default=240)
-    ap.add_argument("--form", default=None, choices=sorted(FORMS))
     args = ap.parse_args()
-    if args.epochs > 0:
-        if args.form:
-            epochs_child(args.form, args.frames, int(args.batch), args.n_train, args.epochs)
-        else:
-            epochs_parent(args)
-        return
     for B in (int(v) for v in args.batch.split(",")):
         for Ta in (int(v) for v in args.ta.split(",")):
             res = gpu_time(B, Ta, args.replays, args.warmup)
