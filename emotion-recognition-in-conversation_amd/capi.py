@@ -1508,6 +1508,31 @@ def resae_bwd(jobs, n_blocks, n_jobs=None):
     _call("erc_resae_bwd", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs, n_blocks)
 
 
+def resae_latents(job, n_blocks):
+    """the latents of ONE job alone (inference): ``job`` a job dict, or the array resae_jobs made of one"""
+    arr = job if isinstance(job, C.Array) else resae_jobs([job])
+    _call("erc_resae_latents", C.addressof(arr), n_blocks)
+
+
+def mmin_miss_max_cond():
+    return int(lib().erc_mmin_miss_max_cond())
+
+
+def mmin_miss_patterns(missing_types):
+    """host int32 array of erc_mmin_miss_expand's patterns from rows (visual, text, audio) of 0 / 1, 1 = kept (MISSING_TYPES)"""
+    return (C.c_int32 * len(missing_types))(*[int(v) | int(t) << 1 | int(a) << 2 for v, t, a in missing_types])
+
+
+def mmin_miss_expand(feat, ldf, zfeat, patterns, B, out, ldo):
+    """``patterns``: mmin_miss_patterns' array (or None: refused by the library)"""
+    _call("erc_mmin_miss_expand", feat, ldf, zfeat, None if patterns is None else C.addressof(patterns),
+          0 if patterns is None else len(patterns), B, out, ldo)
+
+
+def mmin_miss_score(logits, ld, labels, B, n_cond, Cn, cm, loss_sum):
+    _call("erc_mmin_miss_score", logits, ld, labels, B, n_cond, Cn, cm, loss_sum)
+
+
 def mse_grad(a, lda, b, ldb, B, n_cols, weight, d, ldd, loss_out):
     """loss_out[0] = mean((a - b)^2); d = weight * 2 (a - b) / (B n_cols)"""
     _call("erc_mse_grad", a, lda, b, ldb, B, n_cols, weight, d, ldd, loss_out)

@@ -728,6 +728,36 @@ class MMINEpochLoop:
 MMINBaseTrainer.EPOCH_LOOP = MMINEpochLoop      # (trainer.epoch_loop_class; MMINMissTrainer inherits it)
 
 
+def missing_records(missing, with_report):
+    """the epoch line's entries of ``eval_epoch``'s ``missing`` dict (MMINMissTrainer, --eval_missing), in its order: Lall, Acc,
+    Acc2 under EMA, C = the utterances counted, and with ``with_report`` report_from_cm's block (the matrix included)"""
+    out = {}
+    for key, rec in missing.items():
+        out[key] = {k: rec[k] for k in ("Lall", "Acc", "Acc2") if k in rec}
+        out[key]["C"] = int(rec["cm"].sum())
+        if with_report:
+            out[key]["report"] = report_from_cm(rec["cm"])
+    return out
+
+
+def epoch_line(params, epoch, utt_per_s, lr, val, test, best_acc, is_best):
+    """the epoch's JSON record from ``eval_epoch``'s dicts of the validation and the test split"""
+    if not params.get("confuse_matrix", True):
+        rep = {}
+    elif "cm" in test:
+        rep = report_from_cm(test["cm"])
+    else:
+        rep = classification_report(test["true"], test["pred"], params.n_classes)
+    last = {"epoch": epoch, "train_utt_per_s": utt_per_s, "lr": lr,
+            "val": {k: val[k] for k in ("Lall", "Acc", "Acc2") if k in val}, "test": {k: test[k] for k in ("Lall", "Acc", "Acc2") if k in test},
+            "report": {k: rep[k] for k in rep if k != "cm"}, "class_names": list(params.class_names), "best_acc": best_acc,
+            "is_best": is_best}
+    if "missing" in test:      # --module=mmin_miss --eval_missing: both splits under the six missing-modality patterns
+        last["missing"] = {split: missing_records(rec["missing"], params.get("confuse_matrix", True))
+                           for split, rec in (("val", val), ("test", test))}
+    return last
+
+
 def run(trainer_cls, params_cls, argv=None):
     """--module=mmin_base and --module=mmin_miss: training steps (EMA after each), the validation epoch (plateau scheduler), the
     test epoch (Acc, Acc2, report, best / last checkpoints); one JSON line per epoch"""
@@ -750,16 +780,7 @@ def run(trainer_cls, params_cls, argv=None):
             print_step_lines(params, epoch, loop.ring, counts)
         val, test = loop.test_epoch()
         best = trainer.on_test_end(test, params.get("save_dir"))
-        if not params.get("confuse_matrix", True):
-            rep = {}
-        elif "cm" in test:
-            rep = report_from_cm(test["cm"])
-        else:
-            rep = classification_report(test["true"], test["pred"], params.n_classes)
-        last = {"epoch": epoch, "train_utt_per_s": n_utt / dt, "lr": trainer.optim.lr,
-                "val": {k: val[k] for k in ("Lall", "Acc", "Acc2") if k in val}, "test": {k: test[k] for k in ("Lall", "Acc", "Acc2") if k in test},
-                "report": {k: rep[k] for k in rep if k != "cm"}, "class_names": list(params.class_names), "best_acc": trainer.accuracy,
-                "is_best": best}
+        last = epoch_line(params, epoch, n_utt / dt, trainer.optim.lr, val, test, trainer.accuracy, best)
         c = loop.counters
         if c is not None:
             last.update(graph_replays=c.replays, eager_steps=c.eager, graphs_captured=c.captures)

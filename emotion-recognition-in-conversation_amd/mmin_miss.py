@@ -27,6 +27,13 @@ after the checkpoint was loaded, so the pretrained text CNN's convolutions are r
 (``--pretrain_reinit=False`` keeps the loaded weights); the pretrained model is in training mode during training steps (its text
 dropout is live, drawing from its own counter); missing modalities are zeroed inputs that still run through their encoders;
 validation and test batches are full-modality.
+
+``--eval_missing`` (default off; the reference has no counterpart) also scores the validation and test epochs
+under the six patterns of ``MISSING_TYPES`` (mmin_miss.py:345-360), masked as MMINMissCollate masks a training batch
+(mmin_miss.py:328-337), WITHOUT six more passes: a masked modality's 128 feature columns are those of an all-zero sample, so behind
+every batch's unchanged forward ``score_missing`` launches erc_mmin_miss_expand (the batch's features against the zero-input row,
+6 B rows) | erc_resae_latents (netAE's latents alone) | the three classifier GEMMs | erc_mmin_miss_score (six confusion matrices
+and loss sums, kept on the device until the epoch's one copy).
 """
 import math
 import random
@@ -35,7 +42,7 @@ import torch
 from torch import nn
 
 from . import capi, mmin
-from .engine import _world_size, linear_wgrad
+from .engine import WorkspaceCache, _world_size, linear_wgrad
 from .mmin import EMB, HID, MMINBaseModule, MMINBaseTrainer
 
 AE_LAYERS, N_BLOCKS = (256, 128, 64), 5                  # mmin_miss.py:77-78
@@ -44,6 +51,9 @@ W_MSE, W_CYCLE = 4.0, 2.0                                # :210
 PRETRAINED_SEED_SALT = 0x5EED                            # the pretrained model's dropout counter stream is its own
 MISSING_TYPES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1))     # :348-353, columns visual, text, audio
 MODAL_KEYS = ("visual_feature", "text_feature", "audio_feature")                        # :354, :332
+# --eval_missing: a pattern's name is the modalities that REMAIN, in the project's a t v letters: "v", "t", "a", "tv", "av", "at"
+MISSING_KEYS = tuple("".join(c for c, i in (("a", 2), ("t", 1), ("v", 0)) if m[i]) for m in MISSING_TYPES)
+MISSING_PATTERNS = capi.mmin_miss_patterns(MISSING_TYPES)
 
 
 class _ResidualAE(nn.Module):
@@ -133,6 +143,77 @@ class MMINMissModule(MMINBaseModule):
         pl.reduce_into(ws, self.flat.grad)
         return stats
 
+    # --------------------------------------------------------------------------------- evaluation under missing modalities
+    def begin_missing_pass(self):
+        """forget the zero-input features: they are constants of the weights, so a pass over other weights (the EMA copy swapped
+        in, a training step in between) starts with this"""
+        self._zero_feat, self._zero_vt = {}, {}
+
+    def _zero_encode(self, audio, visual, text):
+        """the encoders on zero inputs of one sample, in workspaces of their own (the batch's workspace and ``_last_ws`` stay)"""
+        if not hasattr(self, "_zero_ws"):
+            self._zero_ws = WorkspaceCache(maxsize=8)
+        batch_ws, self._ws = self._ws, self._zero_ws
+        try:
+            ws, _ = self._encode(audio, visual, text, False)
+        finally:
+            self._ws = batch_ws
+        return ws["fused"][0]
+
+    def zero_features(self, Ta, Tv, Tt, device):
+        """[384]: what the encoders make of a sample whose three inputs are zero (MMINMissCollate's masking: a missing modality is
+        a zero input that still runs through its encoder), audio padded to ``Ta`` frames.  The visual and text columns are computed
+        once per pass, the audio columns once per pass and distinct ``Ta`` (``zero_scans`` counts those scans)"""
+        if not hasattr(self, "_zero_feat"):
+            self.begin_missing_pass()
+        z = self._zero_feat.get((Ta, Tv, Tt))
+        if z is None:
+            zeros = lambda T, d: torch.zeros(1, T, d, dtype=torch.float32, device=device)
+            if (Tv, Tt) not in self._zero_vt:
+                self._zero_vt[Tv, Tt] = self._zero_encode(None, zeros(Tv, self.visual_dim), zeros(Tt, self.text_dim))[HID:].clone()
+            z = torch.cat([self._zero_encode(zeros(Ta, self.audio_dim), None, None)[:HID], self._zero_vt[Tv, Tt]])
+            self._zero_feat[Ta, Tv, Tt] = z
+            self.zero_scans += 1
+        return z
+
+    zero_scans = 0      # audio zero-input scans so far (tests count them per pass)
+
+    def _missing_workspace(self, B, device):
+        if not hasattr(self, "_miss_ws"):
+            self._miss_ws = WorkspaceCache(maxsize=4)
+
+        def make():
+            K, C = len(MISSING_TYPES), self.n_classes
+            f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+            m = dict(x=f32(K * B, EMB), latents=f32(K * B, LAT), z0=f32(K * B, HID), feat=f32(K * B, HID), logits=f32(K * B, C))
+            names = capi.resae_layer_names(N_BLOCKS)
+            m["job"] = capi.resae_jobs([dict(W=[self._w("netAE.%s.weight" % n) for n in names], b=[self._w("netAE.%s.bias" % n) for n in names],
+                                             x=m["x"], latents=m["latents"], B=K * B, ldx=EMB, ldl=LAT)])
+            return m
+        return self._miss_ws.get(B, make)
+
+    def score_missing(self, labels, cm, loss_sum):
+        """the batch of the forward just run (eval mode), scored under the six patterns of MISSING_TYPES without a second pass
+        over its inputs: its features (``fused`` of that forward) expanded against the zero-input features (1 launch), netAE's
+        latents of the 6 B rows (erc_resae_latents, 1 launch), the classifier (3 GEMMs) and erc_mmin_miss_score, which adds the
+        confusion matrices to ``cm`` (int64 [6, C, C]) and the batch-mean cross entropies to ``loss_sum`` (float64 [6]).
+        Nothing is copied to the host; no random draw, no state changes.  -> the logits [6 B, C] (a workspace buffer)"""
+        ws = self._last_ws
+        if ws is None or self.training:
+            raise capi.ErcGraftError("mmin_miss: score_missing follows a forward in eval mode")
+        B, C, K, dev = int(ws["fused"].shape[0]), self.n_classes, len(MISSING_TYPES), ws["fused"].device
+        if tuple(labels.shape) != (B, ) or labels.dtype != torch.int64:
+            raise capi.ErcGraftError("mmin_miss: score_missing: labels must be int64 [%d], got %s %s" % (B, labels.dtype, tuple(labels.shape)))
+        z = self.zero_features(ws["A"]["T"], ws["V"]["T"], ws["L"]["T"], dev)
+        m = self._missing_workspace(B, dev)
+        capi.mmin_miss_expand(ws["fused"], EMB, z, MISSING_PATTERNS, B, m["x"], EMB)
+        capi.resae_latents(m["job"], N_BLOCKS)
+        for name, x, k, out, n, act in (("netC.module.0", m["latents"], LAT, m["z0"], HID, 1), ("netC.module.3", m["z0"], HID, m["feat"], HID, 1),
+                                        ("netC.fc_out", m["feat"], HID, m["logits"], C, 0)):
+            capi.gemm_f32(x, k, 0, None, self._w(name + ".weight"), k, 0, None, out, n, K * B, n, k, bias=self._w(name + ".bias"), act=act)
+        capi.mmin_miss_score(m["logits"], C, labels, B, K, C, cm, loss_sum)
+        return m["logits"]
+
     @staticmethod
     def _act_offsets(B, n_blocks=N_BLOCKS):
         """float offset of every layer's INPUT rows in erc_resae_fwd's ``act`` buffer (ercgraft.h), in the chain's order"""
@@ -169,8 +250,8 @@ def efficiency_init(module):
 
 # ---------------------------------------------------------------------------------------------------------------- training
 class MMINMissTrainer(MMINBaseTrainer):
-    """``--module=mmin_miss`` (mmin_miss.py:110-296).  Evaluation, the plateau scheduler, best / last checkpoints and the epoch
-    loop are MMINBaseTrainer's."""
+    """``--module=mmin_miss`` (mmin_miss.py:110-296).  Evaluation (with ``--eval_missing``: ``eval_epoch`` below), the plateau
+    scheduler, best / last checkpoints and the epoch loop are MMINBaseTrainer's."""
     NAME = "mmin_miss"
     MODULE = MMINMissModule
     CAPACITY_MODES = False
@@ -190,6 +271,7 @@ class MMINMissTrainer(MMINBaseTrainer):
         self.finetune = bool(params.get("finetune", False))
         self.reinit = bool(params.get("pretrain_reinit", True))
         self._model_initialised = False
+        self.eval_missing = bool(params.get("eval_missing", False))
         if not params.get("pretrain_path"):      # otherwise the epoch loop's load_pretrained runs it behind the load
             self._efficiency_init()
 
@@ -234,6 +316,51 @@ class MMINMissTrainer(MMINBaseTrainer):
             capi.ema_step(self.ema, self.model.flat.data, self.model.flat.numel, mmin.EMA_ALPHA)
         self.global_steps += 1
         return stats
+
+    def eval_epoch(self, loader):
+        """MMINBaseTrainer.eval_epoch; under ``--eval_missing`` the same two passes (the same launches in the same order, so the
+        full-modality figures are the ones without the flag) with ``MMINMissModule.score_missing`` behind every batch's forward.
+        The dict gains ``missing``: {"v" | "t" | "a" | "tv" | "av" | "at": dict(Lall, Acc, cm [C, C] true x predicted, and
+        under EMA Acc2, cm2)} in MISSING_TYPES' order; the six matrices and sums of both passes reach the host in ONE copy"""
+        if not self.eval_missing:
+            return super().eval_epoch(loader)
+        self.model.eval()
+        batches = [self.prepare_batch(b) for b in loader]
+        ys = torch.cat([b["label"] for b in batches])
+        K, C, n_pass = len(MISSING_TYPES), int(self.model.n_classes), 2 if self.use_ema else 1
+        cm = torch.zeros(n_pass, K, C, C, dtype=torch.int64, device=self.device)
+        sums = torch.zeros(n_pass, K, dtype=torch.float64, device=self.device)
+
+        def run(k):
+            self.model.begin_missing_pass()
+            out = []
+            for b in batches:
+                out.append(self.to_logits(b).clone())
+                self.model.score_missing(b["label"], cm[k], sums[k])
+            return out
+        logits = run(0)
+        losses = torch.stack([torch.nn.functional.cross_entropy(lg, b["label"]) for lg, b in zip(logits, batches)]).sum()
+        pred = torch.cat(logits).argmax(-1)
+        out = dict(C=int(ys.shape[0]))
+        if self.use_ema:
+            with self.ema_weights():
+                pred2 = torch.cat(run(1)).argmax(-1)
+            host = torch.stack([pred, pred2, ys]).cpu()
+            out["Acc2"] = float((host[1] == host[2]).sum()) / out["C"]
+        else:
+            host = torch.stack([pred, ys]).cpu()
+        self.model.begin_missing_pass()      # the next user of the zero-input features starts from the weights of that time
+        out.update(Lall=float(losses), Acc=float((host[0] == host[-1]).sum()) / out["C"], true=host[-1].tolist(), pred=host[0].tolist())
+        packed = torch.cat([cm.reshape(n_pass, -1).to(torch.float64), sums], 1).cpu()      # counts are exact in float64
+        cms = packed[:, :K * C * C].round().to(torch.int64).reshape(n_pass, K, C, C).numpy()
+        out["missing"] = {}
+        for i, key in enumerate(MISSING_KEYS):
+            n = max(1, int(cms[0, i].sum()))
+            rec = dict(Lall=float(packed[0, K * C * C + i]), Acc=float(cms[0, i].trace()) / n, cm=cms[0, i])
+            if self.use_ema:
+                rec.update(Acc2=float(cms[1, i].trace()) / n, cm2=cms[1, i])
+            out["missing"][key] = rec
+        return out
 
     @staticmethod
     def make_loaders(params):

@@ -1698,6 +1698,13 @@ int erc_resae_rows_per_group(void);
 int64_t erc_resae_act_floats(int B, int n_blocks);
 int erc_resae_fwd(const ErcResaeJob* jobs_host, int n_jobs, int n_blocks, void* stream);
 int erc_resae_bwd(const ErcResaeJob* jobs_host, int n_jobs, int n_blocks, void* stream);
+/* The inference form of erc_resae_fwd for ONE job: what MMINMissModule's classifier reads (mmin_miss.py:103-106).  Reads x, W, b
+ * and writes latents [B, ldl >= 64 n_blocks] alone: no saved activation, no decoder behind the last latent, no transition.
+ * recon, act, d_recon, d_latents, dx and dY of the job are never dereferenced (all may be NULL).  The same kernel in another mode:
+ * every latent carries the bits of erc_resae_fwd's on the same x.  Any B >= 1; no workgroup waits for another; a repeated launch
+ * is bit-identical.  Null job / x / latents, B <= 0, ldx < 384, ldl < 64 n_blocks, n_blocks outside [1, 5], a null bias or a
+ * weight that is null or not 16-byte aligned (all 6 n_blocks + 2, as for the forward): ERC_E_ARG before any launch. */
+int erc_resae_latents(const ErcResaeJob* job_host, int n_blocks, void* stream);
 
 /* F.mse_loss(a, b) (mmin_miss.py:207-208) over [B, n_cols] with its gradient: loss_out[0] = mean((a - b)^2) (unweighted; a
  * slot of the step's stats), d [B, ldd] = weight * 2 (a - b) / (B n_cols): the gradient of weight * loss wrt a, its negative
@@ -1717,6 +1724,31 @@ int erc_mse_grad(const float* a, int lda, const float* b, int ldb, int B, int n_
 int erc_mmin_miss_combine(const float* dx0, const float* dx1, const float* dcyc, const float* feat, int ldf, int B,
                           float* dfeat, int lddf, float* dtext, int lddt, const float* ce_stats, float w_mse, float w_cyc,
                           float* stats, void* stream);
+
+/* Evaluation under missing modalities (the patterns of track_mm/mmin_miss.py:345-360, masked as MMINMissCollate masks a training
+ * batch, track_mm/mmin_miss.py:328-337; the reference evaluates full-modality only).  A masked modality is a zero input that
+ * still runs through its encoder, so its 128 feature columns are one row of constants of the weights (audio: and of the padded
+ * length): the features of a batch under a pattern are a column-block selection.
+ *
+ * erc_mmin_miss_expand: out [n_cond * B, ldo >= 384], row c * B + b = per 128-column block (audio 0:128, visual 128:256, text
+ *   256:384) feat[b] [B, ldf >= 384] where pattern c keeps that modality, zfeat [384] elsewhere.  patterns_host: n_cond <=
+ *   erc_mmin_miss_max_cond() = 8 HOST ints, bit 0 = visual kept, bit 1 = text kept, bit 2 = audio kept (the columns of a
+ *   MISSING_TYPES row).  Columns [0, 384) of all n_cond * B rows are written, in 16-byte pieces; nothing else is.  ERC_E_ARG before
+ *   any launch: null pointer, n_cond outside [1, 8], B <= 0, a pattern outside [0, 8), a pitch below 384 or no multiple of 4,
+ *   feat / zfeat / out not 16-byte aligned.
+ * erc_mmin_miss_score: logits [n_cond * B, ld >= C] read as n_cond blocks of B rows, labels [B] (the same for every block).
+ *   cm [n_cond, C, C] int64 (true x predicted), ADDED TO: cm[c, label, pred] += 1, pred = the first index of the maximum
+ *   (erc_rows_score's rule; as there a label outside [0, C) and a row of nothing but NaN are not counted).  loss_sum [n_cond]
+ *   float64, ADDED TO: the mean over block c's counted rows of logsumexp(z) - z[label], every term and the sum in double in a
+ *   fixed order (nothing is added for a block without a counted row).  One workgroup per block owns its matrix and its sum: no
+ *   atomics on global memory, a repeated run gives the same bits.  C <= erc_rows_score_max_classes().  Writes nothing else.
+ *   ERC_E_ARG before any launch: null pointer, n_cond outside [1, 8], B <= 0, C out of range, ld < C, labels / cm / loss_sum not
+ *   8-byte aligned. */
+int erc_mmin_miss_max_cond(void);
+int erc_mmin_miss_expand(const float* feat, int ldf, const float* zfeat, const int32_t* patterns_host, int n_cond, int B,
+                         float* out, int ldo, void* stream);
+int erc_mmin_miss_score(const float* logits, int ld, const int64_t* labels, int B, int n_cond, int C, int64_t* cm,
+                        double* loss_sum, void* stream);
 
 /* ------------------------------------------------------------------------
  * Launch chain: a captured step replayed as PLAIN kernel launches from native code.

@@ -14,6 +14,20 @@ The fused launches and the per-layer graph are timed --visits times in turn in t
 what a difference has to exceed).  One JSON line per (batch size, Ta).
 
     python tools/mmin_miss_bench.py [--batch 32] [--ta 100,400] [--replays 50] [--visits 3] [--cpu_steps 1]
+
+--eval_missing times the evaluation under the six missing-modality patterns instead: per Ta a validation
+epoch of --n_val utterances in batches of --batch, the model's pass alone (no EMA pass, no host copy), median of --replays:
+
+  * plain   the full-modality pass (one forward per batch);
+  * fused   the plain pass with MMINMissModule.score_missing behind every forward (the zero-input features are recomputed in
+            every timed pass, as an epoch does);
+  * naive   the plain pass plus six more passes of the unchanged forward over batches masked on the host with MMINMissCollate's
+            arithmetic and uploaded beforehand -- the yardstick, built here only;
+  * kernels erc_resae_latents on the 6 B rows and erc_resae_fwd on the B rows (both networks, as the forward launches it), the
+            recorded calls re-issued.
+
+Each of the four runs in a child process of its own; every child times the plain pass first (``plain_ms``: the spread over the
+children is what a difference has to exceed).  One JSON line per (Ta, what).
 """
 import argparse
 import json
@@ -141,6 +155,76 @@ def cpu_time(B, Ta, steps):
     return statistics.median(times[1:])
 
 
+def eval_missing_child(B, Ta, n_val, what, replays, warmup):
+    """one measurement of --eval_missing (module docstring), in this process"""
+    from erc_amd import capi
+    from erc_amd.mmin_miss import MISSING_TYPES, MMINMissCollate, MMINMissTrainer
+    from erc_amd.synthetic import make_mmin_samples
+    from track_mm.mmin_miss import MMINMissParams
+    tr = MMINMissTrainer(MMINMissParams().from_args(["--eval_missing"]), "cuda:0")
+    tr.model.eval()
+    samples = make_mmin_samples(n_val, "val", seed=7, frames=(Ta, Ta))
+    groups = [samples[i:i + B] for i in range(0, n_val, B)]
+    batches = [tr.prepare_batch(MMINMissCollate(has_miss=False)(g)) for g in groups]
+    C, K = tr.model.n_classes, len(MISSING_TYPES)
+    cm = torch.zeros(K, C, C, dtype=torch.int64, device="cuda:0")
+    sums = torch.zeros(K, dtype=torch.float64, device="cuda:0")
+
+    def plain():
+        for b in batches:
+            tr.to_logits(b)
+
+    def fused():
+        tr.model.begin_missing_pass()
+        for b in batches:
+            tr.to_logits(b)
+            tr.model.score_missing(b["label"], cm, sums)
+    res = {"eval_missing": what, "B": B, "Ta": Ta, "n_val": n_val, "batches": len(batches)}
+    res["plain_ms"] = statistics.median(event_times(plain, replays, warmup))
+    if what == "fused":
+        res["fused_ms"] = statistics.median(event_times(fused, replays, warmup))
+        res["added_ms"] = res["fused_ms"] - res["plain_ms"]
+        res["added_over_plain"] = res["added_ms"] / res["plain_ms"]
+        res["zero_scans_per_pass"] = tr.model.zero_scans // (replays + warmup)
+    elif what == "naive":
+        masked = [[tr.prepare_batch(MMINMissCollate(has_miss=True)([dict(s, missing_type=list(p)) for s in g])) for p in MISSING_TYPES]
+                  for g in groups]
+
+        def naive():
+            for b, six in zip(batches, masked):
+                tr.to_logits(b)
+                for m in six:
+                    tr.to_logits(m)
+        res["naive_ms"] = statistics.median(event_times(naive, replays, warmup))
+        res["added_ms"] = res["naive_ms"] - res["plain_ms"]
+        res["added_over_plain"] = res["added_ms"] / res["plain_ms"]
+    elif what == "kernels":
+        capi.start_recording()
+        tr.to_logits(batches[0])
+        tr.model.score_missing(batches[0]["label"], cm, sums)
+        torch.cuda.synchronize()
+        rec = capi.stop_recording()
+        for name in ("erc_resae_latents", "erc_resae_fwd", "erc_mmin_miss_expand", "erc_mmin_miss_score"):
+            entry = [e for e in rec if e[0] == name][-1]
+            res[name[4:] + "_ms"] = statistics.median(event_times(lambda: capi.replay(entry), replays, warmup))
+        res["latents_rows"], res["fwd_rows"] = K * len(groups[0]), len(groups[0])
+        res["latents_over_fwd"] = res["resae_latents_ms"] / res["resae_fwd_ms"]
+        res["added_launching_calls_per_batch"] = sum(1 for e in rec[[e[0] for e in rec].index("erc_mmin_miss_expand"):] if capi._launches(e[0]))
+    print(json.dumps(res), flush=True)
+
+
+def eval_missing_parent(args):
+    import subprocess
+    for B in (int(v) for v in args.batch.split(",")):
+        for Ta in (int(v) for v in args.ta.split(",")):
+            for what in ("plain", "fused", "naive", "kernels"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--eval_missing_child", what, "--batch", str(B), "--ta", str(Ta),
+                       "--replays", str(args.replays), "--warmup", str(args.warmup), "--n_val", str(args.n_val)]
+                res = subprocess.run(cmd, timeout=600)
+                if res.returncode != 0:      # a child that failed: nothing more is started on the GPU
+                    raise SystemExit("tools/mmin_miss_bench.py --eval_missing: the %s child (Ta=%d) exited with %d" % (what, Ta, res.returncode))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="32")
@@ -149,9 +233,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--visits", type=int, default=3)
     ap.add_argument("--cpu_steps", type=int, default=1)
+    ap.add_argument("--eval_missing", action="store_true", help="time the evaluation under the six missing-modality patterns")
+    ap.add_argument("--eval_missing_child", default=None, choices=("plain", "fused", "naive", "kernels"), help=argparse.SUPPRESS)
+    ap.add_argument("--n_val", type=int, default=64)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/mmin_miss_bench.py times the step on an MI355X; no GPU is visible (there is no CPU fallback)")
+    if args.eval_missing_child:
+        return eval_missing_child(int(args.batch), int(args.ta), args.n_val, args.eval_missing_child, args.replays, args.warmup)
+    if args.eval_missing:
+        return eval_missing_parent(args)
     for B in (int(v) for v in args.batch.split(",")):
         for Ta in (int(v) for v in args.ta.split(",")):
             res = gpu_time(B, Ta, args.replays, args.warmup, args.visits)

@@ -26,6 +26,9 @@ class MMINMissParams(ERCParams):
         self.finetune = False                                                           # :54 (accepted; it has no effect, :149-154)
         # build-specific: keep the loaded pretrained weights instead of re-initialising them as the reference does (:157-158)
         self.pretrain_reinit = True
+        # build-specific: score the validation and test epochs under the six missing-modality patterns as well (the reference
+        # evaluates full-modality only, :368); the default keeps every launch and every printed line as they are
+        self.eval_missing = False
         self.n_train, self.n_val, self.n_test = 256, 64, 64
         self.mmin_frames = (50, 400)
         self.save_dir = None
