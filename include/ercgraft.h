@@ -312,7 +312,7 @@ int erc_bn_lrelu_bwd(const float* x, int ldx, int N, int F, const float* gamma, 
  *   weight (float [C] or NULL): loss = sum w_y nll / sum w_y
  *   out: stats[0] = loss, stats[1] = #(argmax == y), stats[2] = sum of weights; stats must hold >= 256
  *   floats, zero-initialised once by the caller (per-workgroup partials + an arrival counter live there)
- *   dlogits (may be NULL): gradient, same row addressing as logits; rows that
+ *   dlogits (may be NULL): gradient, same row addressing as logits with lddl >= C; rows that
  *     no sample maps to are NOT written (caller zero-fills when row_map != NULL)
  */
 int erc_cross_entropy(const float* logits, int ld, int C, int n_rows, const int32_t* row_map,
