@@ -1370,27 +1370,37 @@ def lstm128_pool_bwd_tcap(jobs, counts, dyn_mask, n_jobs=None):
     _call("erc_lstm128_pool_bwd_tcap", C.addressof(arr), len(jobs) if n_jobs is None else n_jobs, counts, dyn_mask)
 
 
+def lstm128_prefix_max(Hprev, t_rows, out):
+    """out [t_rows, 128]: row t = the max-pool of one sample after t steps, from the Hprev rows of a forward at T = t_rows (ercgraft.h)"""
+    for name, x in (("Hprev", Hprev), ("out", out)):
+        if x is not None and (x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < max(0, t_rows) * 128):
+            raise ErcGraftError("lstm128_prefix_max: %s must be a contiguous float32 tensor of at least %d x 128" % (name, t_rows))
+    _call("erc_lstm128_prefix_max", Hprev, t_rows, out)
+
+
 def mmin_collate_width(modality):
     return int(lib().erc_mmin_collate_width(modality))
 
 
 def mmin_collate(desc, store_audio, store_visual, store_text, store_label, B_cap, T_cap, frames_max, audio, visual, text, label,
-                 counts):
+                 counts, masked=False):
     """``store_*``: the split in HBM (audio [n_frames, 130] ragged, visual [n, Tv, 342], text [n, Tt, 1024], label [n]); ``desc``
-    int32 [3 B_cap] on the device: frames | first frame row | sample index; writes every element of the five outputs"""
+    int32 [3 B_cap] on the device: frames | first frame row | sample index; writes every element of the five outputs.
+    ``masked``: erc_mmin_collate_masked, ``desc`` int32 [4 B_cap] with the slots' keep bits behind the three blocks"""
+    entry = "mmin_collate_masked" if masked else "mmin_collate"
     for name, x, dt in (("desc", desc, torch.int32), ("store_label", store_label, torch.int64), ("label", label, torch.int64),
                         ("counts", counts, torch.int32), ("store_audio", store_audio, torch.float32),
                         ("store_visual", store_visual, torch.float32), ("store_text", store_text, torch.float32),
                         ("audio", audio, torch.float32), ("visual", visual, torch.float32), ("text", text, torch.float32)):
         if x is not None and (x.dtype != dt or not x.is_contiguous()):
-            raise ErcGraftError("mmin_collate: %s must be a contiguous %s tensor" % (name, dt))
+            raise ErcGraftError("%s: %s must be a contiguous %s tensor" % (entry, name, dt))
     n, Tv, Tt = (int(store_visual.shape[0]), int(store_visual.shape[1]), int(store_text.shape[1])) \
         if store_visual is not None and store_text is not None else (0, 0, 0)
-    need = dict(desc=3 * B_cap, audio=B_cap * T_cap * 130, visual=B_cap * Tv * 342, text=B_cap * Tt * 1024, label=B_cap, counts=2)
+    need = dict(desc=(4 if masked else 3) * B_cap, audio=B_cap * T_cap * 130, visual=B_cap * Tv * 342, text=B_cap * Tt * 1024, label=B_cap, counts=2)
     for name, x in (("desc", desc), ("audio", audio), ("visual", visual), ("text", text), ("label", label), ("counts", counts)):
         if x is not None and B_cap > 0 and T_cap > 0 and x.numel() < need[name]:
-            raise ErcGraftError("mmin_collate: %s holds %d elements, B_cap=%d T_cap=%d needs %d" % (name, x.numel(), B_cap, T_cap, need[name]))
-    _call("erc_mmin_collate", desc, store_audio, 0 if store_audio is None else int(store_audio.shape[0]), store_visual, store_text,
+            raise ErcGraftError("%s: %s holds %d elements, B_cap=%d T_cap=%d needs %d" % (entry, name, x.numel(), B_cap, T_cap, need[name]))
+    _call("erc_" + entry, desc, store_audio, 0 if store_audio is None else int(store_audio.shape[0]), store_visual, store_text,
           store_label, n, Tv, Tt, B_cap, T_cap, frames_max, audio, visual, text, label, counts)
 
 
@@ -1531,6 +1541,17 @@ def mmin_miss_expand(feat, ldf, zfeat, patterns, B, out, ldo):
 
 def mmin_miss_score(logits, ld, labels, B, n_cond, Cn, cm, loss_sum):
     _call("erc_mmin_miss_score", logits, ld, labels, B, n_cond, Cn, cm, loss_sum)
+
+
+def mmin_miss_expand_cap(feat, ldf, zaudio, t_rows, zvt, counts, patterns, B_cap, out, ldo):
+    """capacity form: block c at row c * B_cap, a removed modality's columns from zaudio[clamp(counts[1], 1, t_rows - 1)] | zvt"""
+    _call("erc_mmin_miss_expand_cap", feat, ldf, zaudio, t_rows, zvt, counts, None if patterns is None else C.addressof(patterns),
+          0 if patterns is None else len(patterns), B_cap, out, ldo)
+
+
+def mmin_miss_score_cap(logits, ld, labels, B_cap, counts, n_cond, Cn, cm, loss_sum):
+    """capacity form: rows b < clamp(counts[0], 0, B_cap) of every block of B_cap rows"""
+    _call("erc_mmin_miss_score_cap", logits, ld, labels, B_cap, counts, n_cond, Cn, cm, loss_sum)
 
 
 def mse_grad(a, lda, b, ldb, B, n_cols, weight, d, ldd, loss_out):

@@ -261,6 +261,21 @@ __global__ __launch_bounds__(NTH) void lstm128_bwd_kernel(Jobs P, MODE mode) {
     store_chunk((T - 1) % SC);
 }
 
+// The running maximum over the saved hidden rows of ONE sample: thread u owns hidden unit u and walks rows 1 .. t_rows - 1 of
+// Hprev (row t = h_{t-1}; row 0 is the initial state, not a step's output) with the forward's rule -- strict comparison from -2,
+// so row t carries the bits the forward's pool has after t steps.  Loads do not depend on the running value.
+__global__ __launch_bounds__(H) void lstm128_prefix_max_kernel(const float* __restrict__ hprev, const int t_rows, float* __restrict__ out) {
+    const int u = threadIdx.x;
+    out[u] = 0.f;
+    float best = -2.f;      // |h| < 1
+#pragma unroll 8
+    for (int t = 1; t < t_rows; ++t) {
+        const float h = hprev[(int64_t)t * H + u];
+        if (h > best) best = h;
+        out[(int64_t)t * H + u] = best;
+    }
+}
+
 int fill(const char* name, Jobs& P, const ErcLstm128Job* jobs, int n_jobs, bool bwd, int& max_b) {
     ERC_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= MAX_JOBS, "%s: n_jobs=%d outside [1, %d] (or null jobs_host)", name, n_jobs, MAX_JOBS);
     max_b = 0;
@@ -302,6 +317,14 @@ extern "C" int erc_lstm128_pool_bwd(const ErcLstm128Job* jobs_host, int n_jobs, 
     if (int e = fill("lstm128_pool_bwd", P, jobs_host, n_jobs, true, max_b)) return e;
     hipLaunchKernelGGL(lstm128_bwd_kernel<Exact>, dim3(max_b, n_jobs), dim3(NTH), 0, (hipStream_t)stream, P, Exact{});
     ERC_LAUNCH_CHECK("lstm128_pool_bwd");
+    return ERC_OK;
+}
+
+extern "C" int erc_lstm128_prefix_max(const float* Hprev, int t_rows, float* out, void* stream) {
+    ERC_REQUIRE(Hprev && out && Hprev != out, "lstm128_prefix_max: null pointer (or out == Hprev)");
+    ERC_REQUIRE(t_rows >= 2 && t_rows <= 1 << 22, "lstm128_prefix_max: t_rows=%d outside [2, 2^22]", t_rows);
+    hipLaunchKernelGGL(lstm128_prefix_max_kernel, dim3(1), dim3(H), 0, (hipStream_t)stream, Hprev, t_rows, out);
+    ERC_LAUNCH_CHECK("lstm128_prefix_max");
     return ERC_OK;
 }
 

@@ -44,7 +44,10 @@ __device__ __forceinline__ void put_row(f2* __restrict__ dst, const f2* __restri
     }
 }
 
-__global__ __launch_bounds__(NTH) void mmin_collate_kernel(CollateArgs a) {
+// MASKED (erc_mmin_collate_masked): desc has a fourth block of B_cap keep bits (bit 0 visual, bit 1 text, bit 2 audio); a row of a
+// modality whose bit is clear is written as zeros and the store's row is not read.  Labels and counts do not look at the bits.
+template <bool MASKED>
+__device__ __forceinline__ void collate_body(const CollateArgs a) {
     const int lane = threadIdx.x % ERC_WAVE, wave = threadIdx.x / ERC_WAVE;
     const int B_cap = a.B_cap, T_cap = a.T_cap;
     const int64_t rows_a = (int64_t)B_cap * T_cap, rows_v = (int64_t)B_cap * a.Tv, rows_t = (int64_t)B_cap * a.Tt;
@@ -56,14 +59,18 @@ __global__ __launch_bounds__(NTH) void mmin_collate_kernel(CollateArgs a) {
         const int Tseg = seg == 0 ? T_cap : seg == 1 ? a.Tv : a.Tt;
         const int b = (int)(rs / Tseg), t = (int)(rs % Tseg);
         const int frames = min(max(a.desc[b], 0), T_cap);
+        bool drop = false;      // MASKED: the slot's keep bit of this segment's modality is clear
+        if constexpr (MASKED) drop = !((((a.desc[3 * B_cap + b] & 7) >> (seg == 0 ? 2 : seg - 1)) & 1));
         if (seg == 0) {
             const int64_t n = min((int64_t)frames, a.n_frames);
             const int64_t first = min(max((int64_t)a.desc[B_cap + b], (int64_t)0), a.n_frames - n);
             const float* src = t < n ? a.s_audio + (first + t) * DA : nullptr;
+            if constexpr (MASKED) src = drop ? nullptr : src;
             put_row(reinterpret_cast<f2*>(a.audio + rs * DA), reinterpret_cast<const f2*>(src), DA / 2, lane);
         } else {
             const int idx = min(max(a.desc[2 * B_cap + b], 0), a.n_samples - 1);
-            const bool have = frames > 0;
+            bool have = frames > 0;
+            if constexpr (MASKED) have = have && !drop;
             if (seg == 1) {
                 const float* src = have ? a.s_visual + ((int64_t)idx * a.Tv + t) * DV : nullptr;
                 put_row(reinterpret_cast<f2*>(a.visual + rs * DV), reinterpret_cast<const f2*>(src), DV / 2, lane);
@@ -93,29 +100,48 @@ __global__ __launch_bounds__(NTH) void mmin_collate_kernel(CollateArgs a) {
         }
     }
 }
+
+__global__ __launch_bounds__(NTH) void mmin_collate_kernel(CollateArgs a) { collate_body<false>(a); }
+__global__ __launch_bounds__(NTH) void mmin_collate_masked_kernel(CollateArgs a) { collate_body<true>(a); }
 }  // namespace
 
 extern "C" int erc_mmin_collate_width(int modality) { return modality == 0 ? DA : modality == 1 ? DV : modality == 2 ? DT : 0; }
+
+template <bool MASKED>
+static int collate(const char* name, const int32_t* desc, const float* store_audio, int64_t n_frames, const float* store_visual,
+                   const float* store_text, const int64_t* store_label, int n_samples, int Tv, int Tt, int B_cap, int T_cap, int frames_max,
+                   float* audio, float* visual, float* text, int64_t* label, int32_t* counts, void* stream) {
+    ERC_REQUIRE(desc && store_audio && store_visual && store_text && store_label, "%s: null pointer (desc or the store)", name);
+    ERC_REQUIRE(audio && visual && text && label && counts, "%s: null pointer (an output)", name);
+    ERC_REQUIRE(B_cap > 0 && T_cap > 0 && Tv > 0 && Tt > 0, "%s: bad sizes B_cap=%d T_cap=%d Tv=%d Tt=%d", name, B_cap, T_cap, Tv, Tt);
+    ERC_REQUIRE(n_samples > 0 && n_frames > 0, "%s: empty store (n_samples=%d, n_frames=%lld)", name, n_samples, (long long)n_frames);
+    ERC_REQUIRE(frames_max >= 0 && frames_max <= T_cap, "%s: frames=%d > T_cap=%d", name, frames_max, T_cap);
+    ERC_REQUIRE((int64_t)B_cap * T_cap <= (int64_t)1 << 30 && (int64_t)B_cap * (Tv > Tt ? Tv : Tt) <= (int64_t)1 << 30,
+                "%s: B_cap=%d times T_cap=%d, Tv=%d or Tt=%d is beyond 2^30 rows", name, B_cap, T_cap, Tv, Tt);
+    const uintptr_t al = (uintptr_t)store_audio | (uintptr_t)store_visual | (uintptr_t)store_text | (uintptr_t)audio |
+                         (uintptr_t)visual | (uintptr_t)text;
+    ERC_REQUIRE((al & 7) == 0, "%s: a feature buffer is not 8-byte aligned", name);
+    CollateArgs a{desc, store_audio, store_visual, store_text, store_label, audio, visual, text, label, counts,
+                  n_frames, n_samples, B_cap, T_cap, Tv, Tt};
+    const int64_t rows = (int64_t)B_cap * ((int64_t)T_cap + Tv + Tt);
+    const int grid = (int)(rows / WAVES + 1 < 4096 ? rows / WAVES + 1 : 4096);
+    hipLaunchKernelGGL(MASKED ? mmin_collate_masked_kernel : mmin_collate_kernel, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, a);
+    ERC_LAUNCH_CHECK(name);
+    return ERC_OK;
+}
 
 extern "C" int erc_mmin_collate(const int32_t* desc, const float* store_audio, int64_t n_frames, const float* store_visual,
                                 const float* store_text, const int64_t* store_label, int n_samples, int Tv, int Tt, int B_cap,
                                 int T_cap, int frames_max, float* audio, float* visual, float* text, int64_t* label,
                                 int32_t* counts, void* stream) {
-    ERC_REQUIRE(desc && store_audio && store_visual && store_text && store_label, "mmin_collate: null pointer (desc or the store)");
-    ERC_REQUIRE(audio && visual && text && label && counts, "mmin_collate: null pointer (an output)");
-    ERC_REQUIRE(B_cap > 0 && T_cap > 0 && Tv > 0 && Tt > 0, "mmin_collate: bad sizes B_cap=%d T_cap=%d Tv=%d Tt=%d", B_cap, T_cap, Tv, Tt);
-    ERC_REQUIRE(n_samples > 0 && n_frames > 0, "mmin_collate: empty store (n_samples=%d, n_frames=%lld)", n_samples, (long long)n_frames);
-    ERC_REQUIRE(frames_max >= 0 && frames_max <= T_cap, "mmin_collate: frames=%d > T_cap=%d", frames_max, T_cap);
-    ERC_REQUIRE((int64_t)B_cap * T_cap <= (int64_t)1 << 30 && (int64_t)B_cap * (Tv > Tt ? Tv : Tt) <= (int64_t)1 << 30,
-                "mmin_collate: B_cap=%d times T_cap=%d, Tv=%d or Tt=%d is beyond 2^30 rows", B_cap, T_cap, Tv, Tt);
-    const uintptr_t al = (uintptr_t)store_audio | (uintptr_t)store_visual | (uintptr_t)store_text | (uintptr_t)audio |
-                         (uintptr_t)visual | (uintptr_t)text;
-    ERC_REQUIRE((al & 7) == 0, "mmin_collate: a feature buffer is not 8-byte aligned");
-    CollateArgs a{desc, store_audio, store_visual, store_text, store_label, audio, visual, text, label, counts,
-                  n_frames, n_samples, B_cap, T_cap, Tv, Tt};
-    const int64_t rows = (int64_t)B_cap * ((int64_t)T_cap + Tv + Tt);
-    const int grid = (int)(rows / WAVES + 1 < 4096 ? rows / WAVES + 1 : 4096);
-    hipLaunchKernelGGL(mmin_collate_kernel, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, a);
-    ERC_LAUNCH_CHECK("mmin_collate");
-    return ERC_OK;
+    return collate<false>("mmin_collate", desc, store_audio, n_frames, store_visual, store_text, store_label, n_samples, Tv, Tt, B_cap, T_cap,
+                          frames_max, audio, visual, text, label, counts, stream);
+}
+
+extern "C" int erc_mmin_collate_masked(const int32_t* desc, const float* store_audio, int64_t n_frames, const float* store_visual,
+                                       const float* store_text, const int64_t* store_label, int n_samples, int Tv, int Tt, int B_cap,
+                                       int T_cap, int frames_max, float* audio, float* visual, float* text, int64_t* label,
+                                       int32_t* counts, void* stream) {
+    return collate<true>("mmin_collate_masked", desc, store_audio, n_frames, store_visual, store_text, store_label, n_samples, Tv, Tt, B_cap,
+                         T_cap, frames_max, audio, visual, text, label, counts, stream);
 }

@@ -27,10 +27,24 @@ struct Patterns {
     int keep[MAX_COND];      // bit 0: visual kept, bit 1: text kept, bit 2: audio kept (the columns of MISSING_TYPES)
 };
 
+// Capacity form (erc_mmin_miss_expand_cap: one captured step for every batch of a bucket): B is the bucket's B_cap, the audio
+// columns of a removed modality come from row clamp(counts[1], 1, t_rows - 1) of a table of zero-input features per padded
+// length (zfeat = that table), the visual and text columns from zvt [256].
+struct ExpandExact {
+    static constexpr bool CAP = false;
+};
+struct ExpandCap {
+    static constexpr bool CAP = true;
+    const float* zvt;
+    const int32_t* counts;
+    int t_rows;
+};
+
 // one thread per 16 bytes of out; feature blocks: audio 0:128, visual 128:256, text 256:384
+template <class MODE>
 __global__ __launch_bounds__(256) void miss_expand_kernel(const float* __restrict__ feat, const int ldf, const float* __restrict__ zfeat,
                                                           const Patterns pat, const int n_cond, const int B, float* __restrict__ out,
-                                                          const int ldo) {
+                                                          const int ldo, const MODE mode) {
     constexpr int Q = D / 4;      // 16-byte pieces per row
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (int64_t)n_cond * B * Q) return;
@@ -40,16 +54,24 @@ __global__ __launch_bounds__(256) void miss_expand_kernel(const float* __restric
     const int blk = q / (L2 / 4);                            // 0 audio, 1 visual, 2 text
     const int bit = blk == 0 ? 2 : blk - 1;
     const bool keep = (pat.keep[c] >> bit) & 1;
-    const f4 v = keep ? *(const f4*)(feat + (int64_t)b * ldf + 4 * q) : *(const f4*)(zfeat + 4 * q);
+    const float* zsrc = zfeat + 4 * q;
+    if constexpr (MODE::CAP) {
+        const int ta = min(max(mode.counts[1], 1), mode.t_rows - 1);
+        zsrc = blk == 0 ? zfeat + (int64_t)ta * L2 + 4 * q : mode.zvt + (4 * q - L2);
+    }
+    const f4 v = keep ? *(const f4*)(feat + (int64_t)b * ldf + 4 * q) : *(const f4*)zsrc;
     *(f4*)(out + row * ldo + 4 * q) = v;
 }
 
 // workgroup c scores block c of the logits: per row the first index of the maximum (erc_rows_score's rule) and the cross entropy
 // in double; thread t takes rows t, t + 256, .. in order, the threads' sums are added in a fixed tree.  cm block c and
 // loss_sum[c] belong to this workgroup alone: plain read-modify-write, no atomics on global memory.
+// CAP (erc_mmin_miss_score_cap): block c starts at row c * B (B = the bucket's B_cap) and rows b < clamp(counts[0], 0, B) are
+// scored, by the same code in the same order: the bits of the exact form at that B on the same rows.
+template <bool CAP>
 __global__ __launch_bounds__(SCORE_TH) void miss_score_kernel(const float* __restrict__ logits, const int ld, const int64_t* __restrict__ labels,
                                                               const int B, const int C, int64_t* __restrict__ cm,
-                                                              double* __restrict__ loss_sum) {
+                                                              double* __restrict__ loss_sum, const int32_t* __restrict__ counts) {
     __shared__ int s_cm[SCORE_MAXC * SCORE_MAXC];
     __shared__ double s_loss[SCORE_TH];
     __shared__ int s_cnt[SCORE_TH];
@@ -58,7 +80,9 @@ __global__ __launch_bounds__(SCORE_TH) void miss_score_kernel(const float* __res
     __syncthreads();
     double sum = 0.0;
     int cnt = 0;
-    for (int b = tid; b < B; b += SCORE_TH) {
+    int Bdev = B;
+    if constexpr (CAP) Bdev = min(max(counts[0], 0), B);
+    for (int b = tid; b < Bdev; b += SCORE_TH) {
         const float* z = logits + ((int64_t)c * B + b) * ld;
         float mx = z[0];
         for (int k = 1; k < C; ++k) mx = fmaxf(mx, z[k]);
@@ -106,9 +130,34 @@ extern "C" int erc_mmin_miss_expand(const float* feat, int ldf, const float* zfe
         pat.keep[c] = patterns_host[c];
     }
     const int64_t total = (int64_t)n_cond * B * (D / 4);
-    hipLaunchKernelGGL(miss_expand_kernel, dim3(erc_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, feat, ldf, zfeat, pat, n_cond, B,
-                       out, ldo);
+    hipLaunchKernelGGL(miss_expand_kernel<ExpandExact>, dim3(erc_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, feat, ldf, zfeat, pat,
+                       n_cond, B, out, ldo, ExpandExact{});
     ERC_LAUNCH_CHECK("mmin_miss_expand");
+    return ERC_OK;
+}
+
+extern "C" int erc_mmin_miss_expand_cap(const float* feat, int ldf, const float* zaudio, int t_rows, const float* zvt,
+                                        const int32_t* counts, const int32_t* patterns_host, int n_cond, int B_cap, float* out, int ldo,
+                                        void* stream) {
+    ERC_REQUIRE(feat && zaudio && zvt && patterns_host && out, "mmin_miss_expand_cap: null pointer");
+    ERC_REQUIRE(counts, "mmin_miss_expand_cap: null counts");
+    ERC_REQUIRE(t_rows >= 2, "mmin_miss_expand_cap: t_rows=%d: the table has row 0 (unused) and at least row 1", t_rows);
+    ERC_REQUIRE(n_cond >= 1 && n_cond <= MAX_COND && B_cap > 0, "mmin_miss_expand_cap: n_cond=%d (1..%d) B_cap=%d", n_cond, MAX_COND, B_cap);
+    ERC_REQUIRE((int64_t)n_cond * B_cap < ((int64_t)1 << 31), "mmin_miss_expand_cap: n_cond * B_cap = %lld rows", (long long)n_cond * B_cap);
+    ERC_REQUIRE(ldf >= D && ldo >= D && ldf % 4 == 0 && ldo % 4 == 0, "mmin_miss_expand_cap: ldf=%d / ldo=%d below %d or no multiple of 4",
+                ldf, ldo, D);
+    ERC_REQUIRE(aligned16(feat) && aligned16(zaudio) && aligned16(zvt) && aligned16(out),
+                "mmin_miss_expand_cap: feat, zaudio, zvt, out must be 16-byte aligned");
+    Patterns pat{};
+    for (int c = 0; c < n_cond; ++c) {
+        ERC_REQUIRE(patterns_host[c] >= 0 && patterns_host[c] < 8, "mmin_miss_expand_cap: pattern %d = %d outside [0, 8)", c,
+                    patterns_host[c]);
+        pat.keep[c] = patterns_host[c];
+    }
+    const int64_t total = (int64_t)n_cond * B_cap * (D / 4);
+    hipLaunchKernelGGL(miss_expand_kernel<ExpandCap>, dim3(erc_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, feat, ldf, zaudio, pat,
+                       n_cond, B_cap, out, ldo, ExpandCap{zvt, counts, t_rows});
+    ERC_LAUNCH_CHECK("mmin_miss_expand_cap");
     return ERC_OK;
 }
 
@@ -119,7 +168,24 @@ extern "C" int erc_mmin_miss_score(const float* logits, int ld, const int64_t* l
     ERC_REQUIRE(C > 0 && C <= erc_rows_score_max_classes() && C <= SCORE_MAXC && ld >= C, "mmin_miss_score: C=%d ld=%d (C <= %d)", C, ld,
                 SCORE_MAXC);
     ERC_REQUIRE((((uintptr_t)cm | (uintptr_t)loss_sum | (uintptr_t)labels) & 7) == 0, "mmin_miss_score: labels, cm, loss_sum must be 8-byte aligned");
-    hipLaunchKernelGGL(miss_score_kernel, dim3(n_cond), dim3(SCORE_TH), 0, (hipStream_t)stream, logits, ld, labels, B, C, cm, loss_sum);
+    hipLaunchKernelGGL(miss_score_kernel<false>, dim3(n_cond), dim3(SCORE_TH), 0, (hipStream_t)stream, logits, ld, labels, B, C, cm, loss_sum,
+                       (const int32_t*)nullptr);
     ERC_LAUNCH_CHECK("mmin_miss_score");
+    return ERC_OK;
+}
+
+extern "C" int erc_mmin_miss_score_cap(const float* logits, int ld, const int64_t* labels, int B_cap, const int32_t* counts, int n_cond,
+                                       int C, int64_t* cm, double* loss_sum, void* stream) {
+    ERC_REQUIRE(logits && labels && cm && loss_sum, "mmin_miss_score_cap: null pointer");
+    ERC_REQUIRE(counts, "mmin_miss_score_cap: null counts");
+    ERC_REQUIRE(n_cond >= 1 && n_cond <= MAX_COND && B_cap > 0, "mmin_miss_score_cap: n_cond=%d (1..%d) B_cap=%d", n_cond, MAX_COND, B_cap);
+    ERC_REQUIRE((int64_t)n_cond * B_cap < ((int64_t)1 << 31), "mmin_miss_score_cap: n_cond * B_cap = %lld rows", (long long)n_cond * B_cap);
+    ERC_REQUIRE(C > 0 && C <= erc_rows_score_max_classes() && C <= SCORE_MAXC && ld >= C, "mmin_miss_score_cap: C=%d ld=%d (C <= %d)", C, ld,
+                SCORE_MAXC);
+    ERC_REQUIRE((((uintptr_t)cm | (uintptr_t)loss_sum | (uintptr_t)labels) & 7) == 0,
+                "mmin_miss_score_cap: labels, cm, loss_sum must be 8-byte aligned");
+    hipLaunchKernelGGL(miss_score_kernel<true>, dim3(n_cond), dim3(SCORE_TH), 0, (hipStream_t)stream, logits, ld, labels, B_cap, C, cm,
+                       loss_sum, counts);
+    ERC_LAUNCH_CHECK("mmin_miss_score_cap");
     return ERC_OK;
 }

@@ -264,6 +264,25 @@ class MMINDeviceStore:
         return tab.reshape(len(batches), 3 * B_cap), caps
 
 
+class MMINMaskedDeviceStore(MMINDeviceStore):
+    """the training split of ``--module=mmin_base --train_missing``: the descriptor has a fourth block, the slots' keep bits
+    (bit 0 visual, bit 1 text, bit 2 audio: the columns of a MISSING_TYPES row), which erc_mmin_collate_masked reads"""
+
+    DESC_INTS = 4
+
+    def table(self, batches, B_cap, keep=None):
+        """(int32 array [len(batches), 4 B_cap], the batches' T capacities); ``keep``: per batch the samples' keep bits (default:
+        7, everything kept).  The T capacity follows the frames of all samples, kept or not, as the host path pads first"""
+        tab3, caps = super().table(batches, B_cap)
+        tab = np.zeros((len(batches), 4, B_cap), dtype=np.int32)
+        tab[:, :3] = tab3.reshape(len(batches), 3, B_cap)
+        for row, idx, bits in zip(tab, batches, keep if keep is not None else [[7] * len(b) for b in batches]):
+            if len(bits) != len(idx):
+                raise ValueError("%d keep-bit entries for a batch of %d samples" % (len(bits), len(idx)))
+            row[3, :len(idx)] = np.asarray(bits, dtype=np.int32) & 7
+        return tab.reshape(len(batches), 4 * B_cap), caps
+
+
 def index_batches(n, batch_size, shuffle, generator=None):
     """the sample indices of one epoch's batches exactly as ``DataLoader(data, batch_size, shuffle, generator=generator)``
     visits them (it IS a DataLoader, over the indices: same sampler, same draws from ``generator``, a short last batch)"""

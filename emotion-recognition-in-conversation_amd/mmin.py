@@ -27,9 +27,19 @@ erc_lstm128_pool_fwd_tcap / _bwd_tcap and erc_cross_entropy_cap + erc_mm_zero_ta
 ``--capacity_buckets=True`` feeds host-collated batches through trainer.StepGraphs, ``--device_collate --resident`` keeps the
 training split in a datasets.MMINDeviceStore and replays erc_mmin_collate + step + Adam + EMA per 3 B int32
 (``MMINResidentEpochs``), ``--resident_eval`` scores the validation and test epochs on the device (``MMINResidentEval``).
+
+The two baselines of the missing-modality model (opt-in; the masking is MMINMissCollate's, erc_amd/mmin_miss.py):
+``--eval_missing`` also scores the validation and test epochs under the six patterns of ``MISSING_TYPES`` behind every batch's
+unchanged forward -- erc_mmin_miss_expand of the batch's features against the zero-input features | the three classifier GEMMs on
+6 B rows | erc_mmin_miss_score -- with the zero-input audio features of EVERY padded length from one scan over t_max + 1 zero
+frames (erc_lstm128_prefix_max over its saved hidden rows); under ``--resident_eval`` the captured step gains the same route in
+capacity form (erc_mmin_miss_expand_cap, erc_mmin_miss_score_cap).  ``--train_missing`` trains on inputs masked at random as
+``mmin_miss`` trains: the loaders get the ``Missing`` transform and a masking collate, a resident step collates with
+erc_mmin_collate_masked from 4 B int32 (the fourth block: the slots' keep bits, drawn on the host from ``random``).
 """
 import json
 import os
+import random
 import time
 
 import numpy as np
@@ -38,7 +48,7 @@ from torch import nn
 
 from . import capi
 from .capacity import TrainerBase
-from .datasets import MMINDeviceStore, index_batches, mmin_t_cap
+from .datasets import MMINDeviceStore, MMINMaskedDeviceStore, index_batches, mmin_t_cap
 from .engine import FlatParams, GemmPlanner, WorkspaceCache, _world_size, linear_fwd, linear_wgrad
 from .trainer import (ResidentLoop, StepGraphs, classification_report, dynamic_n, epoch_loop_class, fix_seed, print_step_lines,
                       report_from_cm, setup_device, train_epoch_loader)
@@ -48,6 +58,11 @@ AUDIO_DIM, VISUAL_DIM, TEXT_DIM = 130, 342, 1024     # mmin_base.py:86-91: const
 STREAM_TEXT = 0x7E770                                  # dropout stream of the pooled text (erc_dropout_fwd)
 SALT_C0, SALT_C1 = 0xC0 << 32, 0xC1 << 32             # seeds of the two classifier dropouts (the GEMM epilogue has no stream)
 EMA_ALPHA = 0.999                                      # mmin_base.py:99
+MISSING_TYPES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1))     # mmin_miss.py:348-353, columns visual, text, audio
+MODAL_KEYS = ("visual_feature", "text_feature", "audio_feature")                        # mmin_miss.py:354, :332
+# --eval_missing: a pattern's name is the modalities that REMAIN, in the project's a t v letters: "v", "t", "a", "tv", "av", "at"
+MISSING_KEYS = tuple("".join(c for c, i in (("a", 2), ("t", 1), ("v", 0)) if m[i]) for m in MISSING_TYPES)
+MISSING_PATTERNS = capi.mmin_miss_patterns(MISSING_TYPES)      # bit 0 visual, bit 1 text, bit 2 audio kept
 
 
 # parameter holders with the reference's attribute names (state_dict keys); the math is in libercgraft
@@ -244,7 +259,102 @@ class MMINBaseModule(nn.Module):
         capi.cross_entropy_cap(ws["logits"], C, C, B, cnt, None, batch["label"], None, 1.0, None, C, ws["stats"])
         loss_sum.add_(ws["stats"][:1])
         capi.rows_score(ws["logits"], C, B, C, B, cnt, None, batch["label"], cm)
+        ms = batch.get("missing")
+        if ms is not None:      # --eval_missing: the six patterns behind it, against the pass's zero-input table (fixed buffers)
+            m = self._missing_buffers(ws, B)
+            capi.mmin_miss_expand_cap(ws["fused"], EMB, ms["zaudio"], int(ms["zaudio"].shape[0]), ms["zvt"], cnt, MISSING_PATTERNS, B,
+                                      m["x"], EMB)
+            self._classifier_rows(m["x"], EMB, m, len(MISSING_TYPES) * B)
+            capi.mmin_miss_score_cap(m["logits"], C, batch["label"], B, cnt, len(MISSING_TYPES), C, ms["cm"], ms["sums"])
         return ws
+
+    # --------------------------------------------------------------------------------- evaluation under missing modalities
+    zero_scans = 0      # audio zero-input scans so far (tests count them per pass)
+
+    def _zero_encode_ws(self, audio, visual, text):
+        """the encoders on zero inputs of one sample, in workspaces of their own (the batch's workspace and ``_last_ws`` stay)"""
+        if not hasattr(self, "_zero_ws"):
+            self._zero_ws = WorkspaceCache(maxsize=8)
+        batch_ws, self._ws = self._ws, self._zero_ws
+        try:
+            ws, _ = self._encode(audio, visual, text, False)
+        finally:
+            self._ws = batch_ws
+        return ws
+
+    def _zero_encode(self, audio, visual, text):
+        return self._zero_encode_ws(audio, visual, text)["fused"][0]
+
+    def zero_table(self, t_max, Tv, Tt, device, out=None):
+        """dict(zaudio [t_max + 1, 128], zvt [256]): what the encoders make of a sample whose inputs are zero (MMINMissCollate's
+        masking: a missing modality is a zero input that still runs through its encoder).  Row Ta of ``zaudio`` = the audio
+        columns at a padded length of Ta frames, row 0 unused: ONE scan over t_max + 1 zero frames saves h_0 .. h_{t_max - 1}
+        (Hprev[t] = h_{t-1}) and erc_lstm128_prefix_max forms the pool after every number of steps.  ``out``: buffers to fill
+        in place (a captured step reads them: the EMA pass swaps their contents)"""
+        zeros = lambda T, d: torch.zeros(1, T, d, dtype=torch.float32, device=device)
+        if out is None:
+            out = dict(zaudio=torch.zeros(t_max + 1, HID, dtype=torch.float32, device=device),
+                       zvt=torch.zeros(2 * HID, dtype=torch.float32, device=device))
+        if tuple(out["zaudio"].shape) != (t_max + 1, HID) or tuple(out["zvt"].shape) != (2 * HID, ):
+            raise capi.ErcGraftError("%s: zero_table: buffers %s / %s for t_max=%d" % (self.NAME, tuple(out["zaudio"].shape),
+                                                                                      tuple(out["zvt"].shape), t_max))
+        out["zvt"].copy_(self._zero_encode(None, zeros(Tv, self.visual_dim), zeros(Tt, self.text_dim))[HID:])
+        ws = self._zero_encode_ws(zeros(t_max + 1, self.audio_dim), None, None)
+        capi.lstm128_prefix_max(ws["A"]["Hprev"], t_max + 1, out["zaudio"])
+        self.zero_scans += 1
+        return out
+
+    def begin_missing_pass(self, t_max=None):
+        """forget the zero-input features: they are constants of the weights, so a pass over other weights (the EMA copy swapped
+        in, a training step in between) starts with this.  ``t_max``: the longest padded audio length the pass will meet (the
+        table is rebuilt when a longer one comes up)"""
+        self._ztab, self._zrow, self._z_tmax = None, {}, int(t_max or 0)
+
+    def zero_features(self, Ta, Tv, Tt, device):
+        """[384]: the zero-input features at a padded audio length of ``Ta`` frames, from the pass's table"""
+        if not hasattr(self, "_zrow"):
+            self.begin_missing_pass()
+        z = self._zrow.get((Ta, Tv, Tt))
+        if z is None:
+            if self._ztab is None or self._ztab["key"] != (Tv, Tt) or Ta >= int(self._ztab["zaudio"].shape[0]):
+                self._ztab = self.zero_table(max(Ta, self._z_tmax), Tv, Tt, device)
+                self._ztab["key"], self._zrow = (Tv, Tt), {}
+            z = self._zrow[Ta, Tv, Tt] = torch.cat([self._ztab["zaudio"][Ta], self._ztab["zvt"]])
+        return z
+
+    def _missing_buffers(self, ws, B):
+        """the buffers of the 6 B rows behind the forward whose workspace is ``ws`` (they live and die with it)"""
+        if "miss" not in ws:
+            K, dev = len(MISSING_TYPES), ws["fused"].device
+            f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+            ws["miss"] = dict(x=f32(K * B, EMB), z0=f32(K * B, HID), feat=f32(K * B, HID), logits=f32(K * B, self.n_classes))
+        return ws["miss"]
+
+    def _classifier_rows(self, x, k_in, m, rows):
+        """netC in eval mode on ``x`` [rows, k_in] into m["z0"], m["feat"], m["logits"]: three GEMMs, no dropout"""
+        C = self.n_classes
+        for name, xin, k, out, n, act in (("netC.module.0", x, k_in, m["z0"], HID, 1), ("netC.module.3", m["z0"], HID, m["feat"], HID, 1),
+                                          ("netC.fc_out", m["feat"], HID, m["logits"], C, 0)):
+            capi.gemm_f32(xin, k, 0, None, self._w(name + ".weight"), k, 0, None, out, n, rows, n, k, bias=self._w(name + ".bias"), act=act)
+
+    def score_missing(self, labels, cm, loss_sum):
+        """the batch of the forward just run (eval mode), scored under the six patterns of MISSING_TYPES without a second pass
+        over its inputs: its features (``fused`` of that forward) expanded against the zero-input features (1 launch), the
+        classifier on the 6 B rows (3 GEMMs; this model has no autoencoder in between) and erc_mmin_miss_score, which adds the
+        confusion matrices to ``cm`` (int64 [6, C, C]) and the batch-mean cross entropies to ``loss_sum`` (float64 [6]).
+        Nothing is copied to the host; no random draw, no state changes.  -> the logits [6 B, C] (a workspace buffer)"""
+        ws = self._last_ws
+        if ws is None or self.training:
+            raise capi.ErcGraftError("%s: score_missing follows a forward in eval mode" % self.NAME)
+        B, C, K, dev = int(ws["fused"].shape[0]), self.n_classes, len(MISSING_TYPES), ws["fused"].device
+        if tuple(labels.shape) != (B, ) or labels.dtype != torch.int64:
+            raise capi.ErcGraftError("%s: score_missing: labels must be int64 [%d], got %s %s" % (self.NAME, B, labels.dtype, tuple(labels.shape)))
+        z = self.zero_features(ws["A"]["T"], ws["V"]["T"], ws["L"]["T"], dev)
+        m = self._missing_buffers(ws, B)
+        capi.mmin_miss_expand(ws["fused"], EMB, z, MISSING_PATTERNS, B, m["x"], EMB)
+        self._classifier_rows(m["x"], EMB, m, K * B)
+        capi.mmin_miss_score(m["logits"], C, labels, B, K, C, cm, loss_sum)
+        return m["logits"]
 
     # ---------------------------------------------------------------------------------------------------------- backward
     def _classifier_bwd(self, ws, B, xin, k_in, labels, stats):
@@ -362,6 +472,8 @@ class MMINBaseTrainer(TrainerBase):
         self.sched = PlateauLR(params.optim.lr)
         self.accuracy, self.global_steps = 0.0, 0
         self._swap = None
+        self.eval_missing = bool(params.get("eval_missing", False))
+        self.train_missing = bool(params.get("train_missing", False))      # (mmin_miss: refused)
 
     def train_step(self, batch):
         """TrainerBase's step with the EMA step behind the optimizer's (one rank: no gradient all-reduce).  A resident batch
@@ -440,7 +552,10 @@ class MMINBaseTrainer(TrainerBase):
 
     def eval_epoch(self, loader):
         """one pass with the model and one with the EMA model over ``loader``; logits stay on the device, one copy per epoch.
-        -> dict(Lall = sum over batches of the batch-mean CE (meter.sum), Acc, Acc2, C, true, pred)"""
+        -> dict(Lall = sum over batches of the batch-mean CE (meter.sum), Acc, Acc2, C, true, pred).  ``--eval_missing``:
+        ``eval_epoch_missing``"""
+        if self.eval_missing:
+            return self.eval_epoch_missing(loader)
         self.model.eval()
         batches = [self.prepare_batch(b) for b in loader]
         ys = torch.cat([b["label"] for b in batches])
@@ -459,6 +574,43 @@ class MMINBaseTrainer(TrainerBase):
         out.update(Lall=float(losses), Acc=float((host[0] == host[-1]).sum()) / out["C"], true=host[-1].tolist(), pred=host[0].tolist())
         return out
 
+    def eval_epoch_missing(self, loader):
+        """``eval_epoch`` under ``--eval_missing``: the same two passes (the same launches in the same order, so the
+        full-modality figures are the ones without the flag) with the model's ``score_missing`` behind every batch's forward.
+        The dict gains ``missing``: {"v" | "t" | "a" | "tv" | "av" | "at": dict(Lall, Acc, cm [C, C] true x predicted, and
+        under EMA Acc2, cm2)} in MISSING_TYPES' order; the six matrices and sums of both passes reach the host in ONE copy"""
+        self.model.eval()
+        batches = [self.prepare_batch(b) for b in loader]
+        ys = torch.cat([b["label"] for b in batches])
+        t_max = max(int(b["audio_feature"].shape[1]) for b in batches)
+        K, C, n_pass = len(MISSING_TYPES), int(self.model.n_classes), 2 if self.use_ema else 1
+        cm = torch.zeros(n_pass, K, C, C, dtype=torch.int64, device=self.device)
+        sums = torch.zeros(n_pass, K, dtype=torch.float64, device=self.device)
+
+        def run(k):
+            self.model.begin_missing_pass(t_max)
+            out = []
+            for b in batches:
+                out.append(self.to_logits(b).clone())
+                self.model.score_missing(b["label"], cm[k], sums[k])
+            return out
+        logits = run(0)
+        losses = torch.stack([torch.nn.functional.cross_entropy(lg, b["label"]) for lg, b in zip(logits, batches)]).sum()
+        pred = torch.cat(logits).argmax(-1)
+        out = dict(C=int(ys.shape[0]))
+        if self.use_ema:
+            with self.ema_weights():
+                pred2 = torch.cat(run(1)).argmax(-1)
+            host = torch.stack([pred, pred2, ys]).cpu()
+            out["Acc2"] = float((host[1] == host[2]).sum()) / out["C"]
+        else:
+            host = torch.stack([pred, ys]).cpu()
+        self.model.begin_missing_pass()      # the next user of the zero-input features starts from the weights of that time
+        out.update(Lall=float(losses), Acc=float((host[0] == host[-1]).sum()) / out["C"], true=host[-1].tolist(), pred=host[0].tolist())
+        packed = torch.cat([cm.reshape(n_pass, -1).to(torch.float64), sums], 1).cpu()      # counts are exact in float64
+        out["missing"] = missing_dict(packed, C, self.use_ema)
+        return out
+
     def load_pretrained(self, path):
         """``--pretrain_path``: the whole trainer state of a ``mmin_base`` checkpoint"""
         return load(self, path)
@@ -469,7 +621,12 @@ class MMINBaseTrainer(TrainerBase):
 
     @staticmethod
     def make_loaders(params):
-        return make_loaders(params)
+        """``--train_missing``: every training sample gets one of the six patterns at every read (``Missing``) and its batch is
+        masked as MMINMissCollate masks it, without the ``_reverse`` inputs (nothing reads them here)"""
+        if not params.get("train_missing", False):
+            return make_loaders(params)
+        from .mmin_miss import Missing
+        return make_loaders(params, collate=lambda split: mask_collate if split == "train" else mmin_collate, transform=Missing())
 
     def on_eval_end(self, rec):
         """the plateau scheduler on the validation epoch's accumulated loss (mmin_base.py:171-177); -> True when the learning
@@ -497,11 +654,12 @@ CAPACITY_FLAGS = ("capacity_buckets", "device_collate", "resident", "resident_ev
 
 
 def device_collate(batch):
-    """erc_mmin_collate of a resident batch: its descriptor's samples from the store into the bucket's buffers, one launch"""
+    """erc_mmin_collate of a resident batch: its descriptor's samples from the store into the bucket's buffers, one launch
+    (a store whose descriptor carries keep bits, datasets.MMINMaskedDeviceStore: erc_mmin_collate_masked)"""
     st, a = batch["store"], batch["audio_feature"]
     B_cap, T_cap = int(a.shape[0]), int(a.shape[1])
     capi.mmin_collate(batch["desc"], st.audio, st.visual, st.text, st.label, B_cap, T_cap, min(T_cap, st.t_max), a, batch["visual_feature"],
-                      batch["text_feature"], batch["label"], batch["counts"])
+                      batch["text_feature"], batch["label"], batch["counts"], masked=st.DESC_INTS == 4)
 
 
 def state_dict(trainer):
@@ -544,6 +702,32 @@ def mmin_collate(samples):
                 visual_feature=torch.as_tensor(np.stack([s["visual_feature"] for s in samples]), dtype=torch.float32),
                 text_feature=torch.as_tensor(np.stack([s["text_feature"] for s in samples]), dtype=torch.float32),
                 label=torch.tensor([int(s["label"]) for s in samples], dtype=torch.long), name=[s["name"] for s in samples])
+
+
+def mask_collate(samples):
+    """mmin_collate of samples that carry ``missing_type`` (the ``Missing`` transform), every modality x multiplied by its 0 / 1
+    entry as MMINMissCollate(has_miss=True) does (track_mm/mmin_miss.py:328-337); no ``_reverse`` inputs"""
+    data = mmin_collate(samples)
+    missing_type = torch.tensor([s["missing_type"] for s in samples], dtype=torch.long)
+    for i, key in enumerate(MODAL_KEYS):
+        data[key] = data[key] * missing_type[:, i][:, None, None]
+    data["missing_type"] = missing_type
+    return data
+
+
+def missing_dict(packed, C, use_ema):
+    """``eval_epoch``'s ``missing`` entry from the host copy ``packed`` [passes, 6 C C + 6] (per pass: the six confusion matrices,
+    exact in float64, then the six loss sums), in MISSING_TYPES' order"""
+    K = len(MISSING_TYPES)
+    cms = packed[:, :K * C * C].round().to(torch.int64).reshape(-1, K, C, C).numpy()
+    out = {}
+    for i, key in enumerate(MISSING_KEYS):
+        n = max(1, int(cms[0, i].sum()))
+        rec = dict(Lall=float(packed[0, K * C * C + i]), Acc=float(cms[0, i].trace()) / n, cm=cms[0, i])
+        if use_ema:
+            rec.update(Acc2=float(cms[1, i].trace()) / n, cm2=cms[1, i])
+        out[key] = rec
+    return out
 
 
 class _Transformed(torch.utils.data.Dataset):
@@ -600,9 +784,16 @@ class MMINResidentEpochs(ResidentLoop):
         return self.trainer.model._last_ws
 
     def tables(self):
-        """(host int32 table [steps, 3 B], T capacity per step, utterances per step) of the NEXT epoch: draws from the generator"""
+        """(host int32 table [steps, 3 B], T capacity per step, utterances per step) of the NEXT epoch: draws from the generator.
+        ``--train_missing`` (the store's descriptor has keep bits: [steps, 4 B]): one ``random.choice`` over MISSING_TYPES per
+        batch in order and sample in batch order, the stream the default loop's ``Missing`` transform consumes"""
         batches = index_batches(len(self.store), self.B, True, self.gen)
-        table, caps = self.store.table(batches, self.B)
+        if self.store.DESC_INTS == 4:
+            types = [list(t) for t in MISSING_TYPES]
+            keep = [[sum(bit << i for i, bit in enumerate(random.choice(types))) for _ in b] for b in batches]
+            table, caps = self.store.table(batches, self.B, keep)
+        else:
+            table, caps = self.store.table(batches, self.B)
         return table, caps, [len(b) for b in batches]
 
     def epoch(self):
@@ -627,10 +818,24 @@ class MMINResidentEval(ResidentLoop):
         C = self.C = int(trainer.params.n_classes)
         self.cm = torch.zeros(C, C, dtype=torch.int64, device=store.device)
         self.loss_sum = torch.zeros(1, dtype=torch.float64, device=store.device)
-        self.out = torch.zeros(2, C * C + 1, dtype=torch.float64, device=store.device)     # per pass: the matrix (exact in float64) | Lall
+        # --eval_missing: the zero-input table of the pass's weights in FIXED buffers (the captured steps read them; a pass
+        # refills them, as ema_weights swaps the parameters) and the six matrices and sums, which travel with ``out``
+        self.missing = None
+        if getattr(trainer, "eval_missing", False):
+            K, f64 = len(MISSING_TYPES), torch.float64
+            self.missing = dict(zaudio=torch.zeros(self.T + 1, HID, dtype=torch.float32, device=store.device),
+                                zvt=torch.zeros(2 * HID, dtype=torch.float32, device=store.device),
+                                cm=torch.zeros(K, C, C, dtype=torch.int64, device=store.device),
+                                sums=torch.zeros(K, dtype=f64, device=store.device))
+        n_miss = 0 if self.missing is None else len(MISSING_TYPES) * (C * C + 1)
+        # per pass: the matrix (exact in float64) | Lall, then under --eval_missing the six matrices | the six sums
+        self.out = torch.zeros(2, C * C + 1 + n_miss, dtype=torch.float64, device=store.device)
 
     def _batch(self, cap):
-        return self.trainer.resident_batch(self.store, self.cur_desc, self.B, cap)
+        batch = self.trainer.resident_batch(self.store, self.cur_desc, self.B, cap)
+        if self.missing is not None:
+            batch["missing"] = self.missing
+        return batch
 
     def _step(self, batch):
         return self.trainer.resident_eval_step(batch, self.cm, self.loss_sum)
@@ -638,10 +843,18 @@ class MMINResidentEval(ResidentLoop):
     def _pass(self, k):
         self.cm.zero_()
         self.loss_sum.zero_()
+        ms, n = self.missing, self.C * self.C
+        if ms is not None:      # outside the captured steps: built from the weights in place now
+            ms["cm"].zero_()
+            ms["sums"].zero_()
+            self.trainer.model.zero_table(self.T, int(self.store.visual.shape[1]), int(self.store.text.shape[1]), self.store.device, out=ms)
         with dynamic_n(self.trainer.model):
             self._steps(self.table_dev, self.caps)
-        self.out[k, :-1].copy_(self.cm.reshape(-1))
-        self.out[k, -1:].copy_(self.loss_sum)
+        self.out[k, :n].copy_(self.cm.reshape(-1))
+        self.out[k, n:n + 1].copy_(self.loss_sum)
+        if ms is not None:
+            self.out[k, n + 1:n + 1 + ms["cm"].numel()].copy_(ms["cm"].reshape(-1))
+            self.out[k, n + 1 + ms["cm"].numel():].copy_(ms["sums"])
 
     def epoch(self):
         """``eval_epoch``'s dict without the per-sample lists: Lall, Acc, C, cm (host int64 [C, C], true x predicted) and, under
@@ -652,11 +865,13 @@ class MMINResidentEval(ResidentLoop):
             with tr.ema_weights():
                 self._pass(1)
         host = self.out.cpu()
-        cms = host[:, :-1].round().to(torch.int64).reshape(2, C, C)
+        cms = host[:, :C * C].round().to(torch.int64).reshape(2, C, C)
         n = int(cms[0].sum())
-        out = dict(C=n, Lall=float(host[0, -1]), Acc=float(cms[0].diagonal().sum()) / max(1, n), cm=cms[0].numpy())
+        out = dict(C=n, Lall=float(host[0, C * C]), Acc=float(cms[0].diagonal().sum()) / max(1, n), cm=cms[0].numpy())
         if tr.use_ema:
             out.update(Acc2=float(cms[1].diagonal().sum()) / max(1, n), cm2=cms[1].numpy())
+        if self.missing is not None:
+            out["missing"] = missing_dict(host[:2 if tr.use_ema else 1, C * C + 1:], C, tr.use_ema)
         return out
 
 
@@ -693,9 +908,13 @@ class MMINEpochLoop:
                 raise SystemExit("--module=%s: --resident_eval needs --device_collate --resident" % trainer.NAME)
             capture = params.get("graph_capture", True)
             store = lambda loader: MMINDeviceStore(loader.dataset, device)
-            trainer.t_cap = max(int(s["audio_feature"].shape[0]) for s in self.train_loader.dataset)
+            train_data = self.train_loader.dataset
+            if trainer.train_missing:      # (the loader's dataset draws a pattern at every read: the samples are underneath)
+                train_data = train_data.data
+            trainer.t_cap = max(int(s["audio_feature"].shape[0]) for s in train_data)
             if flags["resident"]:
-                self.resident = MMINResidentEpochs(trainer, store(self.train_loader), params.train.batch_size,
+                train_store = (MMINMaskedDeviceStore if trainer.train_missing else MMINDeviceStore)(train_data, device)
+                self.resident = MMINResidentEpochs(trainer, train_store, params.train.batch_size,
                                                    self.train_loader.generator, capture=capture)
             else:
                 self.graphs = StepGraphs(trainer, maxsize=64, capture=capture)
@@ -752,7 +971,7 @@ def epoch_line(params, epoch, utt_per_s, lr, val, test, best_acc, is_best):
             "val": {k: val[k] for k in ("Lall", "Acc", "Acc2") if k in val}, "test": {k: test[k] for k in ("Lall", "Acc", "Acc2") if k in test},
             "report": {k: rep[k] for k in rep if k != "cm"}, "class_names": list(params.class_names), "best_acc": best_acc,
             "is_best": is_best}
-    if "missing" in test:      # --module=mmin_miss --eval_missing: both splits under the six missing-modality patterns
+    if "missing" in test:      # --eval_missing (mmin_base, mmin_miss): both splits under the six missing-modality patterns
         last["missing"] = {split: missing_records(rec["missing"], params.get("confuse_matrix", True))
                            for split, rec in (("val", val), ("test", test))}
     return last

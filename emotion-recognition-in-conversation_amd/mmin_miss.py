@@ -43,17 +43,14 @@ from torch import nn
 
 from . import capi, mmin
 from .engine import WorkspaceCache, _world_size, linear_wgrad
-from .mmin import EMB, HID, MMINBaseModule, MMINBaseTrainer
+from .mmin import EMB, HID, MISSING_KEYS, MISSING_PATTERNS, MISSING_TYPES, MODAL_KEYS, MMINBaseModule, MMINBaseTrainer  # noqa: F401
 
 AE_LAYERS, N_BLOCKS = (256, 128, 64), 5                  # mmin_miss.py:77-78
 LAT = AE_LAYERS[-1] * N_BLOCKS                           # 320: the classifier's input (:82)
 W_MSE, W_CYCLE = 4.0, 2.0                                # :210
 PRETRAINED_SEED_SALT = 0x5EED                            # the pretrained model's dropout counter stream is its own
-MISSING_TYPES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1))     # :348-353, columns visual, text, audio
-MODAL_KEYS = ("visual_feature", "text_feature", "audio_feature")                        # :354, :332
-# --eval_missing: a pattern's name is the modalities that REMAIN, in the project's a t v letters: "v", "t", "a", "tv", "av", "at"
-MISSING_KEYS = tuple("".join(c for c, i in (("a", 2), ("t", 1), ("v", 0)) if m[i]) for m in MISSING_TYPES)
-MISSING_PATTERNS = capi.mmin_miss_patterns(MISSING_TYPES)
+# MISSING_TYPES (:348-353), MODAL_KEYS (:354, :332), MISSING_KEYS and MISSING_PATTERNS: erc_amd/mmin.py (the base model's
+# --eval_missing and --train_missing use them too)
 
 
 class _ResidualAE(nn.Module):
@@ -144,21 +141,11 @@ class MMINMissModule(MMINBaseModule):
         return stats
 
     # --------------------------------------------------------------------------------- evaluation under missing modalities
-    def begin_missing_pass(self):
+    def begin_missing_pass(self, t_max=None):
         """forget the zero-input features: they are constants of the weights, so a pass over other weights (the EMA copy swapped
-        in, a training step in between) starts with this"""
+        in, a training step in between) starts with this (``t_max``: the base model's table; here every audio length has its
+        own scan)"""
         self._zero_feat, self._zero_vt = {}, {}
-
-    def _zero_encode(self, audio, visual, text):
-        """the encoders on zero inputs of one sample, in workspaces of their own (the batch's workspace and ``_last_ws`` stay)"""
-        if not hasattr(self, "_zero_ws"):
-            self._zero_ws = WorkspaceCache(maxsize=8)
-        batch_ws, self._ws = self._ws, self._zero_ws
-        try:
-            ws, _ = self._encode(audio, visual, text, False)
-        finally:
-            self._ws = batch_ws
-        return ws["fused"][0]
 
     def zero_features(self, Ta, Tv, Tt, device):
         """[384]: what the encoders make of a sample whose three inputs are zero (MMINMissCollate's masking: a missing modality is
@@ -250,7 +237,7 @@ def efficiency_init(module):
 
 # ---------------------------------------------------------------------------------------------------------------- training
 class MMINMissTrainer(MMINBaseTrainer):
-    """``--module=mmin_miss`` (mmin_miss.py:110-296).  Evaluation (with ``--eval_missing``: ``eval_epoch`` below), the plateau
+    """``--module=mmin_miss`` (mmin_miss.py:110-296).  Evaluation (with ``--eval_missing``: ``eval_epoch_missing``), the plateau
     scheduler, best / last checkpoints and the epoch loop are MMINBaseTrainer's."""
     NAME = "mmin_miss"
     MODULE = MMINMissModule
@@ -260,6 +247,9 @@ class MMINMissTrainer(MMINBaseTrainer):
         for key, what in (("capacity_buckets", "capacity buckets"), ("resident", "--resident"), ("resident_eval", "--resident_eval")):
             if params.get(key):
                 raise capi.ErcGraftError("--module=mmin_miss: %s is not built (as for --module=mmin_base)" % what)
+        if params.get("train_missing"):
+            raise capi.ErcGraftError("--module=mmin_miss: --train_missing is the augmented baseline of --module=mmin_base; this model's "
+                                     "training is always masked")
         if _world_size() > 1:
             raise capi.ErcGraftError("--module=mmin_miss: data-parallel runs are not built (as for --module=mmin_base)")
         super().__init__(params, device)
@@ -271,7 +261,6 @@ class MMINMissTrainer(MMINBaseTrainer):
         self.finetune = bool(params.get("finetune", False))
         self.reinit = bool(params.get("pretrain_reinit", True))
         self._model_initialised = False
-        self.eval_missing = bool(params.get("eval_missing", False))
         if not params.get("pretrain_path"):      # otherwise the epoch loop's load_pretrained runs it behind the load
             self._efficiency_init()
 
@@ -316,51 +305,6 @@ class MMINMissTrainer(MMINBaseTrainer):
             capi.ema_step(self.ema, self.model.flat.data, self.model.flat.numel, mmin.EMA_ALPHA)
         self.global_steps += 1
         return stats
-
-    def eval_epoch(self, loader):
-        """MMINBaseTrainer.eval_epoch; under ``--eval_missing`` the same two passes (the same launches in the same order, so the
-        full-modality figures are the ones without the flag) with ``MMINMissModule.score_missing`` behind every batch's forward.
-        The dict gains ``missing``: {"v" | "t" | "a" | "tv" | "av" | "at": dict(Lall, Acc, cm [C, C] true x predicted, and
-        under EMA Acc2, cm2)} in MISSING_TYPES' order; the six matrices and sums of both passes reach the host in ONE copy"""
-        if not self.eval_missing:
-            return super().eval_epoch(loader)
-        self.model.eval()
-        batches = [self.prepare_batch(b) for b in loader]
-        ys = torch.cat([b["label"] for b in batches])
-        K, C, n_pass = len(MISSING_TYPES), int(self.model.n_classes), 2 if self.use_ema else 1
-        cm = torch.zeros(n_pass, K, C, C, dtype=torch.int64, device=self.device)
-        sums = torch.zeros(n_pass, K, dtype=torch.float64, device=self.device)
-
-        def run(k):
-            self.model.begin_missing_pass()
-            out = []
-            for b in batches:
-                out.append(self.to_logits(b).clone())
-                self.model.score_missing(b["label"], cm[k], sums[k])
-            return out
-        logits = run(0)
-        losses = torch.stack([torch.nn.functional.cross_entropy(lg, b["label"]) for lg, b in zip(logits, batches)]).sum()
-        pred = torch.cat(logits).argmax(-1)
-        out = dict(C=int(ys.shape[0]))
-        if self.use_ema:
-            with self.ema_weights():
-                pred2 = torch.cat(run(1)).argmax(-1)
-            host = torch.stack([pred, pred2, ys]).cpu()
-            out["Acc2"] = float((host[1] == host[2]).sum()) / out["C"]
-        else:
-            host = torch.stack([pred, ys]).cpu()
-        self.model.begin_missing_pass()      # the next user of the zero-input features starts from the weights of that time
-        out.update(Lall=float(losses), Acc=float((host[0] == host[-1]).sum()) / out["C"], true=host[-1].tolist(), pred=host[0].tolist())
-        packed = torch.cat([cm.reshape(n_pass, -1).to(torch.float64), sums], 1).cpu()      # counts are exact in float64
-        cms = packed[:, :K * C * C].round().to(torch.int64).reshape(n_pass, K, C, C).numpy()
-        out["missing"] = {}
-        for i, key in enumerate(MISSING_KEYS):
-            n = max(1, int(cms[0, i].sum()))
-            rec = dict(Lall=float(packed[0, K * C * C + i]), Acc=float(cms[0, i].trace()) / n, cm=cms[0, i])
-            if self.use_ema:
-                rec.update(Acc2=float(cms[1, i].trace()) / n, cm2=cms[1, i])
-            out["missing"][key] = rec
-        return out
 
     @staticmethod
     def make_loaders(params):

@@ -1598,6 +1598,14 @@ int erc_lstm128_pool_bwd(const ErcLstm128Job* jobs_host, int n_jobs, void* strea
  * (backward) a dGX that is not 16-byte aligned.  A repeated launch is bit-identical. */
 int erc_lstm128_pool_fwd_tcap(const ErcLstm128Job* jobs_host, int n_jobs, const int32_t* counts, int dyn_mask, void* stream);
 int erc_lstm128_pool_bwd_tcap(const ErcLstm128Job* jobs_host, int n_jobs, const int32_t* counts, int dyn_mask, void* stream);
+/* The max-pool of ONE sample after every number of steps, from the Hprev rows a forward at T = t_rows saved for it (row t =
+ * h_{t-1}, row 0 = the initial state): out [t_rows, 128] dense, out[t] = max(out[t-1], Hprev[t]) per column for t >= 1 under the
+ * forward's rule (strict comparison, the first step attaining the maximum stays), so out[t] carries the bits of `pool` of
+ * erc_lstm128_pool_fwd at T = t on the same first t rows of GX; out[0] = 0 (no step has run: unused).  With an all-zero input of
+ * t_max + 1 steps this is the table of zero-input audio features per padded length 1 .. t_max (erc_mmin_miss_expand_cap's
+ * zaudio).  One small launch; it writes out alone and a repeated launch gives the same bits.  ERC_E_ARG before any launch: null
+ * pointer, out == Hprev, t_rows < 2. */
+int erc_lstm128_prefix_max(const float* Hprev, int t_rows, float* out, void* stream);
 
 /* Device collate of an MMIN batch (MMINBaseCollate, mmin_base.py:224-251) from a split that lives in device memory, one launch.
  *   store   store_audio [n_frames, 130]: the frames of all utterances, one ragged matrix; store_visual [n_samples, Tv, 342];
@@ -1618,6 +1626,18 @@ int erc_mmin_collate(const int32_t* desc, const float* store_audio, int64_t n_fr
                      const float* store_text, const int64_t* store_label, int n_samples, int Tv, int Tt, int B_cap,
                      int T_cap, int frames_max, float* audio, float* visual, float* text, int64_t* label,
                      int32_t* counts, void* stream);
+/* erc_mmin_collate of a batch whose samples are masked as MMINMissCollate(has_miss=True) masks them (track_mm/mmin_miss.py:328-337;
+ * the augmented baseline, --module=mmin_base --train_missing).  The same contract word for word -- every element of the five
+ * outputs is written, the clamps run on the device, 8-byte accesses, no waiting between workgroups, the same refusals -- with
+ *   desc    [4 B_cap] int32: frames | first frame row | sample index | keep bits of every slot; bit 0 = visual kept, bit 1 =
+ *           text kept, bit 2 = audio kept (the columns of a MISSING_TYPES row); the bits are masked to 3 on the device.
+ * A row of a modality whose keep bit is clear is written as zeros and the store's row is not read.  label and counts do not look
+ * at the bits: counts[1] stays the longest utterance of all non-empty slots, kept or not (the host path pads first and multiplies
+ * afterwards).  The host path writes x * 0, which is -0.0 for a negative x; this launch writes +0.0. */
+int erc_mmin_collate_masked(const int32_t* desc, const float* store_audio, int64_t n_frames, const float* store_visual,
+                            const float* store_text, const int64_t* store_label, int n_samples, int Tv, int Tt, int B_cap,
+                            int T_cap, int frames_max, float* audio, float* visual, float* text, int64_t* label,
+                            int32_t* counts, void* stream);
 
 /* erc_textcnn_pool_fwd / _bwd replace TextCNN's three conv blocks (mmin_models.py:15-17,24-37: Conv2d(1, 128, (k, D)) for
  * k = 3, 4, 5, ReLU, F.max_pool1d over the T - k + 1 windows, the results side by side) and their autograd; the dropout and the
@@ -1726,7 +1746,8 @@ int erc_mmin_miss_combine(const float* dx0, const float* dx1, const float* dcyc,
                           float* stats, void* stream);
 
 /* Evaluation under missing modalities (the patterns of track_mm/mmin_miss.py:345-360, masked as MMINMissCollate masks a training
- * batch, track_mm/mmin_miss.py:328-337; the reference evaluates full-modality only).  A masked modality is a zero input that
+ * batch, track_mm/mmin_miss.py:328-337; the reference evaluates full-modality only), for --module=mmin_miss (the autoencoder's
+ * latents in between, erc_resae_latents) and for --module=mmin_base (the classifier reads the 384 features).  A masked modality is a zero input that
  * still runs through its encoder, so its 128 feature columns are one row of constants of the weights (audio: and of the padded
  * length): the features of a batch under a pattern are a column-block selection.
  *
@@ -1749,6 +1770,23 @@ int erc_mmin_miss_expand(const float* feat, int ldf, const float* zfeat, const i
                          float* out, int ldo, void* stream);
 int erc_mmin_miss_score(const float* logits, int ld, const int64_t* labels, int B, int n_cond, int C, int64_t* cm,
                         double* loss_sum, void* stream);
+/* The CAPACITY forms of the two (one captured step for every batch of a bucket; --module=mmin_base --resident_eval
+ * --eval_missing), counts = {B, Ta} int32 on the device (erc_mmin_collate writes it).
+ *
+ * erc_mmin_miss_expand_cap: erc_mmin_miss_expand over the bucket's B_cap rows, block c at row c * B_cap, where the columns of a
+ *   removed modality come from zaudio [t_rows, 128] row clamp(counts[1], 1, t_rows - 1) (audio: the zero-input features per padded
+ *   length, erc_lstm128_prefix_max) and from zvt [256] (visual | text).  All n_cond * B_cap rows are written; rows at or beyond
+ *   counts[0] hold finite values (feat's own rows there) that nobody reads.  16-byte accesses; refused as erc_mmin_miss_expand
+ *   refuses (zaudio and zvt must be 16-byte aligned), and a null counts or t_rows < 2 gives ERC_E_ARG before any launch.
+ * erc_mmin_miss_score_cap: erc_mmin_miss_score over rows b < Bdev = clamp(counts[0], 0, B_cap) of every block (block c starts at
+ *   row c * B_cap); labels [B_cap].  Rows at or beyond Bdev are neither read nor counted; Bdev == 0 adds nothing (and forms no
+ *   NaN).  The same kernel in another mode: cm and loss_sum carry the bits of erc_mmin_miss_score at B = Bdev on the same rows.
+ *   One workgroup per block, no atomics on global memory, the sum in double in a fixed order.  Refused as erc_mmin_miss_score
+ *   refuses, and for a null counts. */
+int erc_mmin_miss_expand_cap(const float* feat, int ldf, const float* zaudio, int t_rows, const float* zvt, const int32_t* counts,
+                             const int32_t* patterns_host, int n_cond, int B_cap, float* out, int ldo, void* stream);
+int erc_mmin_miss_score_cap(const float* logits, int ld, const int64_t* labels, int B_cap, const int32_t* counts, int n_cond, int C,
+                            int64_t* cm, double* loss_sum, void* stream);
 
 /* ------------------------------------------------------------------------
  * Launch chain: a captured step replayed as PLAIN kernel launches from native code.

@@ -26,7 +26,7 @@ call, as tools/bcrnn_bench.py counts its ``launches_per_step`` and DESIGN.md sta
 ``kernel_launches_per_eager_step`` take a stream and enqueue work (bc-RNN: 19), the others are host-side queries.  After
 the runs of a config the parent prints one ratio line per pair of modes that both ran (medians of their last runs).
 ``--repo DIR`` times another checkout's package; ``--set KEY=VALUE`` overrides a flag of the preset; ``--collate_on_device``
-adds --device_collate to the modes that lack it.
+adds --device_collate to the modes that lack it; ``--eval_missing`` / ``--train_missing`` set the MMIN modules' flags of that name.
 
 ``--steps`` (trainers with capacity buckets) times, in one more child per config, the replayed step on a bucket's static
 buffers against an exact-shape graph of the same first batch, and reports the workspace bytes of both, the node capacities
@@ -278,6 +278,8 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="override a flag of the preset (repeatable)")
     ap.add_argument("--collate_on_device", action="store_true", help="add --device_collate to the modes that do not have it")
+    ap.add_argument("--eval_missing", action="store_true", help="mmin_base / mmin_miss: --set eval_missing=True (six more patterns per evaluation)")
+    ap.add_argument("--train_missing", action="store_true", help="mmin_base: --set train_missing=True (the augmented baseline's masked training)")
     ap.add_argument("--steps", action="store_true", help="also time one replayed step, bucket against exact shape")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repo", default=REPO, help="the checkout whose package is timed")
@@ -285,6 +287,7 @@ def main(argv=None):
     ap.add_argument("--child", action="store_true", help="run the one (config, mode) given in this process")
     a = ap.parse_args(argv)
     a.repo = os.path.abspath(a.repo)
+    a.set = a.set + [k + "=True" for k in ("eval_missing", "train_missing") if getattr(a, k)]
     if a.module not in PRESETS:
         raise SystemExit("--module=%s has no preset; known: %s" % (a.module, ", ".join(sorted(PRESETS))))
     if a.child:

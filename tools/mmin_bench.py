@@ -7,12 +7,21 @@ the baseline.  One JSON line per (batch size, Ta).
 
     python tools/mmin_bench.py [--batch 32] [--ta 100,400] [--replays 50] [--cpu_steps 1]
 
+    python tools/mmin_bench.py --eval_missing [--batch 32] [--ta 100,400] [--repeats 20]
+
+``--eval_missing`` times a validation epoch of 64 utterances (two passes: model and EMA) with a host clock around work that ends
+in a device synchronise, the variants alternating inside one process: the plain pass (the code path without the flag), the pass
+with the fused scoring behind every forward, and the naive route (the plain pass plus six more over host-masked batches); then
+the same epoch under ``--resident_eval`` with and without the flag, each in a child process of its own (a captured step binds to
+its trainer); then erc_mmin_collate_masked beside erc_mmin_collate on one bucket of B slots (device events).
+
 Whole epochs (training + validation + test, in every loop form) are timed by tools/epoch_bench.py --module=mmin_base.
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -96,14 +105,134 @@ def cpu_time(B, Ta, steps):
     return statistics.median(times[1:])
 
 
+# ------------------------------------------------------------------------------------------------------------ --eval_missing
+N_VAL = 64
+
+
+def _eval_trainer(B, *flags):
+    from erc_amd.mmin import MMINBaseTrainer
+    from track_mm.mmin_base import MMINBaseParams
+    p = MMINBaseParams().from_args(["--val.batch_size=%d" % B, "--train.batch_size=%d" % B, "--test.batch_size=%d" % B] + list(flags))
+    tr = MMINBaseTrainer(p, "cuda:0")
+    tr.ema.mul_(0.5)           # the EMA pass computes with weights of its own
+    return tr
+
+
+def _val_samples(Ta):
+    from erc_amd.synthetic import make_mmin_samples
+    return make_mmin_samples(N_VAL, "val", seed=11, frames=(Ta, Ta))
+
+
+def _wall_ms(fns, repeats, warmup):
+    """median wall time of every variant, the variants alternating; each call ends in a device synchronise"""
+    times = [[] for _ in fns]
+    for r in range(warmup + repeats):
+        for i, fn in enumerate(fns):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if r >= warmup:
+                times[i].append((time.perf_counter() - t0) * 1e3)
+    return [statistics.median(t) for t in times], [min(t) for t in times], [max(t) for t in times]
+
+
+def eval_missing_default_loop(B, Ta, repeats, warmup):
+    from torch.utils.data import DataLoader
+    from erc_amd import capi
+    from erc_amd.mmin import MISSING_TYPES, MODAL_KEYS, mmin_collate
+    plain, fused = _eval_trainer(B), _eval_trainer(B, "--eval_missing")
+    loader = DataLoader(_val_samples(Ta), batch_size=B, shuffle=False, collate_fn=mmin_collate)
+    batches = [plain.prepare_batch(b) for b in loader]
+    masked = [[dict(b, **{key: b[key] * m[i] for i, key in enumerate(MODAL_KEYS)}) for m in MISSING_TYPES] for b in batches]
+
+    def naive():
+        plain.eval_epoch(loader)
+        for k in (0, 1):
+            with (plain.ema_weights() if k else _null()):
+                logits = [plain.to_logits(mb).clone() for six in masked for mb in six]
+        torch.stack([lg.argmax(-1) for lg in logits]).cpu()
+    capi.start_recording()
+    fused.eval_epoch(loader)
+    rec = capi.stop_recording()
+    names = [e[0] for e in rec]
+    med, lo, hi = _wall_ms([lambda: plain.eval_epoch(loader), lambda: fused.eval_epoch(loader), naive], repeats, warmup)
+    return {"eval_missing": "default_loop", "B": B, "Ta": Ta, "n_val": N_VAL, "plain_ms": med[0], "fused_ms": med[1], "naive_ms": med[2],
+            "plain_min_max_ms": [lo[0], hi[0]], "fused_min_max_ms": [lo[1], hi[1]], "naive_min_max_ms": [lo[2], hi[2]],
+            "fused_over_plain": med[1] / med[0], "naive_over_fused": med[2] / med[1],
+            "zero_scans_per_epoch": names.count("erc_lstm128_prefix_max"), "launching_calls_per_epoch": sum(1 for n in names if capi._launches(n))}
+
+
+def _null():
+    import contextlib
+    return contextlib.nullcontext()
+
+
+def eval_missing_resident_child(B, Ta, repeats, warmup, with_flag):
+    from erc_amd.datasets import MMINDeviceStore
+    from erc_amd.mmin import MMINResidentEval
+    flags = ["--device_collate", "--resident", "--resident_eval"] + (["--eval_missing"] if with_flag else [])
+    tr = _eval_trainer(B, *flags)
+    ev = MMINResidentEval(tr, MMINDeviceStore(_val_samples(Ta), "cuda:0"), B)
+    med, lo, hi = _wall_ms([ev.epoch], repeats, warmup)
+    return {"eval_missing": "resident_eval", "with_flag": with_flag, "B": B, "Ta": Ta, "n_val": N_VAL, "epoch_ms": med[0],
+            "min_max_ms": [lo[0], hi[0]], "graph_replays": ev.replays, "graphs_captured": ev.captures}
+
+
+def collate_masked_times(B, T_cap, replays, warmup):
+    from erc_amd import capi
+    from erc_amd.datasets import MMINMaskedDeviceStore
+    from erc_amd.mmin import MMINBaseTrainer
+    from erc_amd.synthetic import make_mmin_samples
+    from track_mm.mmin_base import MMINBaseParams
+    tr = MMINBaseTrainer(MMINBaseParams().from_args(["--train.batch_size=%d" % B]), "cuda:0")
+    store = MMINMaskedDeviceStore(make_mmin_samples(B, "train", seed=7, frames=(T_cap, T_cap)), "cuda:0")
+    bits = [[(1, 2, 4, 3, 5, 6)[i % 6] for i in range(B)]]
+    table, _ = store.table([list(range(B))], B, bits)
+    d4 = torch.from_numpy(table[0]).to("cuda:0")
+    d3 = d4[:3 * B].contiguous()
+    out = tr.make_bucket(B, T_cap, int(store.visual.shape[1]), int(store.text.shape[1]))
+    call = lambda desc, masked: capi.mmin_collate(desc, store.audio, store.visual, store.text, store.label, B, T_cap, T_cap, out["audio_feature"],
+                                                  out["visual_feature"], out["text_feature"], out["label"], out["counts"], masked=masked)
+    t3 = event_times(lambda: call(d3, False), replays, warmup)
+    t4 = event_times(lambda: call(d4, True), replays, warmup)
+    written = sum(out[k].numel() * 4 for k in ("audio_feature", "visual_feature", "text_feature"))
+    return {"eval_missing": "collate", "B": B, "T_cap": T_cap, "mmin_collate_ms": statistics.median(t3),
+            "mmin_collate_masked_ms": statistics.median(t4), "bytes_written": written}
+
+
+def eval_missing_main(args):
+    if args.child:
+        B, Ta = int(args.batch), int(args.ta)
+        print(json.dumps(eval_missing_resident_child(B, Ta, args.repeats, args.warmup, args.child == "resident_missing")), flush=True)
+        return
+    for B in (int(v) for v in args.batch.split(",")):
+        for Ta in (int(v) for v in args.ta.split(",")):
+            print(json.dumps(eval_missing_default_loop(B, Ta, args.repeats, args.warmup)), flush=True)
+            for child in ("resident_plain", "resident_missing"):      # a fresh process each: a captured step binds to its trainer
+                cmd = [sys.executable, os.path.abspath(__file__), "--eval_missing", "--child=" + child, "--batch=%d" % B, "--ta=%d" % Ta,
+                       "--repeats=%d" % args.repeats, "--warmup=%d" % args.warmup]
+                res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+                if res.returncode != 0:
+                    raise SystemExit("child %s failed: %s" % (child, res.stderr[-2000:]))
+                print(res.stdout.strip().splitlines()[-1], flush=True)
+        for T_cap in (128, 400):
+            print(json.dumps(collate_masked_times(B, T_cap, args.replays, args.warmup)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--eval_missing", action="store_true", help="time a validation epoch under --eval_missing and the masked collate")
+    ap.add_argument("--repeats", type=int, default=20, help="--eval_missing: timed epochs per variant")
+    ap.add_argument("--child", default="", help="--eval_missing: (internal) resident_plain | resident_missing, one process each")
     ap.add_argument("--batch", default="32")
     ap.add_argument("--ta", default="100,400")
     ap.add_argument("--replays", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--cpu_steps", type=int, default=1)
     args = ap.parse_args()
+    if args.eval_missing:
+        return eval_missing_main(args)
     for B in (int(v) for v in args.batch.split(",")):
         for Ta in (int(v) for v in args.ta.split(",")):
             res = gpu_time(B, Ta, args.replays, args.warmup)

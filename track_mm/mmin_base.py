@@ -19,6 +19,11 @@ class MMINBaseParams(ERCParams):
         self.ema = True                                                                 # :45
         self.sche_type, self.warmup_epochs = "cos", 0                                   # :47-48 (declared, never read)
         self.pretrain_path = None                                                       # :49
+        # build-specific: the two baselines of the missing-modality model (the reference has neither flag).  eval_missing: the
+        # validation and test epochs are also scored under the six missing-modality patterns; train_missing: every training
+        # sample is masked at random as --module=mmin_miss masks it.  The defaults keep every launch and printed line as they are
+        self.eval_missing = False
+        self.train_missing = False
         # build-specific: the synthetic splits (no .h5 features and no h5py here) and the assumed ComParE frame-count range
         self.n_train, self.n_val, self.n_test = 256, 64, 64
         self.mmin_frames = (50, 400)
